@@ -8,9 +8,12 @@ k=1, Adam.  A step = zero_grad -> fused backbone forward over the three task bat
 sum_t w_t * loss_t.mean() -> backward -> (gradient all-reduce) -> Adam, inputs resident in HBM.
 One process per GPU (torchrun env), weak scaling: per-GPU work is fixed.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with ``roofline`` (dominant kernel,
-HIP-event timings taken by the library on the launch stream) and ``cpu_baseline`` (the CPU oracle
-timed on the host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+exactly --steps steps once and reports; --dump-outputs DIR also writes what the last timed step
+computed.  --full adds the legs beyond the headline: ``roofline`` (dominant kernel, HIP-event timings
+taken by the library on the launch stream), ``cpu_baseline`` (the CPU oracle timed on the host cores
+on a bounded sample of the same workload), ``f32`` (the step in reference precision) and the timed
+block repeated to --min-timed-s.
 """
 from __future__ import annotations
 
@@ -166,6 +169,26 @@ def cpu_baseline(sds, names, dev, weights, sample_batch=None, budget_s=20.0, ego
             "sample": f"{n or 1} step(s){' after 1 warm-up' if n else ' (the first one)'} of the same step on "
                       f"{b0.num_graphs} of the {dev[t0_].num_graphs} sequences per task ({len(batches)} task(s) x T="
                       f"{b0.x.shape[0] // b0.num_graphs}), fp32 torch CPU oracle, {cores} threads, {dt * 1e3:.0f} ms/step"}
+
+
+DUMP_PARAMS = 1 << 22  # parameters written by --dump-outputs: a fixed seeded sample of this many (16 MB as f32)
+
+
+def dump_outputs(out_dir, total, vectors, flat_p) -> None:
+    """``--dump-outputs``: what the last timed step handed its caller -- the objective (``loss_total``, f64) and the per-task
+    loss vectors (``loss_<task>``) -- and the parameters its Adam update left (``params_sample``: the values at a fixed,
+    seeded, sorted sample of DUMP_PARAMS flat indices; all of them when there are fewer), as .npy files (f32 but the objective)."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "loss_total.npy", np.asarray(total.detach().double().cpu().numpy(), dtype=np.float64))
+    for t, v in sorted(vectors.items()):
+        np.save(out / f"loss_{t}.npy", v.detach().float().cpu().numpy())
+    p = flat_p.detach()
+    if p.numel() > DUMP_PARAMS:
+        idx = torch.randperm(p.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAMS].sort().values
+        p = p[idx.to(p.device)]
+    np.save(out / "params_sample.npy", p.float().cpu().numpy())
 
 
 # library profiler name -> kernel symbol (substring) in rocprofv3 output
@@ -354,15 +377,27 @@ def parse_args(argv=None):
     ap.add_argument("--no-f32-leg", action="store_true",
                     help="skip the short reference-precision (--compute f32) measurement added to the JSON line at N = 1")
     ap.add_argument("--f32-steps", type=int, default=50, help="timed steps of the reference-precision leg")
-    ap.add_argument("--min-timed-s", type=float, default=0.5,
-                    help="repeat the timed K-step block until at least this much stepping has been timed; the median block is reported")
-    ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel table (stderr)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the legs beyond the headline: roofline (per-kernel timers), cpu_baseline, the f32 leg, and "
+                         "the K-step block repeated to --min-timed-s; a plain run times exactly --steps steps once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (loss total, "
+                         "per-task loss vectors, a fixed seeded sample of the updated parameters)")
+    ap.add_argument("--min-timed-s", type=float, default=None,
+                    help="repeat the timed K-step block until at least this much stepping has been timed; the median block is "
+                         "reported (default 0.5 with --full, else 0: one block)")
+    ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel table (stderr; with --full)")
     ap.add_argument("--stamps", action="store_true",
                     help="development: capture one-lane wall-clock stamps at the phase boundaries of the step and print the "
                          "phase table of the last replay (stderr); each stamp costs ~2 us of the step")
     ap.add_argument("--no-grouped-heads", action="store_true", help="A/B: one projection chain per task instead of grouped launches")
     ap.add_argument("--no-wgrad-grouping", action="store_true", help="A/B: every weight gradient as its own (split-K) launch")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the K steps, report
+        args.no_cpu_baseline = args.no_roofline = args.no_f32_leg = True
+    if args.min_timed_s is None:
+        args.min_timed_s = 0.5 if args.full else 0.0
+    return args
 
 
 def spawn_plan(n: int, argv, port: int = None):
@@ -457,9 +492,11 @@ def one_graph_probe(args, argv, rank: int, world: int):
         time.sleep(0.25)
 
 
-def measure(args, rank, world, device, steps, warmup, want_roofline=True, want_cpu=True, min_timed_s=0.0, group=None):
+def measure(args, rank, world, device, steps, warmup, want_roofline=True, want_cpu=True, min_timed_s=0.0, group=None,
+            dump_dir=None):
     """Build the workload in ``args.compute`` mode, capture / warm up, time ``steps`` steps (barrier + synchronize on both
-    sides, MAX over ranks) and take the roofline / CPU-baseline legs.  Returns a dict of results."""
+    sides, MAX over ranks), write the last timed step's outputs to ``dump_dir`` (rank 0) and take the roofline / CPU-baseline
+    legs.  Returns a dict of results."""
     from egopack_amd import dist as edist
     from egopack_amd import engine, ops
     from egopack_amd.optim import FlatAdam
@@ -530,7 +567,7 @@ def measure(args, rank, world, device, steps, warmup, want_roofline=True, want_c
     step.one_graph_exchange = getattr(args, "exchange_graph", "staged") == "one"  # ('auto' was resolved by main(): probe)
 
     def eager_step():
-        step.step(dev, fused_merged)
+        return step.step(dev, fused_merged)
 
     if args.feature_store and fused_merged is not None and torch.is_tensor(fused_merged.x):
         from egopack_amd import feature_store as FS
@@ -600,15 +637,18 @@ def measure(args, rank, world, device, steps, warmup, want_roofline=True, want_c
     for _ in range(warmup):
         run()
 
+    last = {}
+
     def timed_block():
         """EXACTLY ``steps`` steps between barrier + synchronize on both sides: milliseconds per step of this rank."""
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            run()
+            out = run()
         torch.cuda.synchronize()
         barrier()
+        last["out"] = out
         return (time.perf_counter() - t0) * 1e3 / steps
 
     def over_ranks(v, op):
@@ -634,6 +674,8 @@ def measure(args, rank, world, device, steps, warmup, want_roofline=True, want_c
     # ``steps`` of the JSON line stays K (the contract's block length); ``steps_timed`` = K x blocks is what was really timed
     timing = {"timed_s": sum(blocks) * steps * 1e-3, "timed_blocks": len(blocks), "steps_timed": steps * len(blocks),
               "block_ms_min": srt[0], "block_ms_max": srt[-1]}
+    if dump_dir is not None and rank == 0:  # (before any leg below steps the model again)
+        dump_outputs(dump_dir, *(step._static_out if capture != "eager" else last["out"]), opt.flat_p)
 
     # N ranks: what the gradient exchange costs the step BEYOND what backward hides -- the same steps with the collectives
     # left out of the exchange path (conversion, stream hand-offs, per-chunk Adam all still run: GradSync.skip_collectives)
@@ -808,7 +850,8 @@ def main(argv=None):
         from egopack_amd import data as _D
         _D.HEAVY_IN_LAUNCH_DEGREE = 0
 
-    res = measure(args, rank, world, device, args.steps, args.warmup, min_timed_s=args.min_timed_s, group=data_group)
+    res = measure(args, rank, world, device, args.steps, args.warmup, min_timed_s=args.min_timed_s, group=data_group,
+                  dump_dir=None if args.probe_child else args.dump_outputs)
     ms = res["ms"]
     if args.probe_child:
         # a pre-flight child of --exchange-graph auto: the one-graph step captured, replayed and (N > 1) re-captured for the

@@ -273,3 +273,36 @@ def test_main_egopack_on_the_device_resident_feature_store(tmp_path):
     ego = torch.load(tmp_path / "EGO_egopack_oscc" / "checkpoint.pth", weights_only=False)
     assert "graphone" in ego and all(torch.isfinite(v).all() for v in ego["graphone"].values() if v.is_floating_point())
     assert all(torch.isfinite(v).all() for v in ego["temporal_graph"].values() if v.is_floating_point())
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """``bench.py`` without --full: ONE block of exactly --steps timed steps, none of the --full legs in the result line; with
+    --dump-outputs, two runs with the same arguments write the same arrays (seeded inputs, parameters, dropout streams), in
+    the captured and in the eager mode."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import numpy as np
+    bench = Path(__file__).resolve().parents[1] / "bench.py"
+    small = ["--batch", "8", "--T", "8", "--hidden", "128", "--trn-hidden", "128", "--steps", "5", "--warmup", "2"]
+    dumps = {}
+    for tag, mode in (("g1", "graph"), ("g2", "graph"), ("e1", "eager"), ("e2", "eager")):
+        r = subprocess.run([sys.executable, str(bench), *small, "--mode", mode, "--dump-outputs", str(tmp_path / tag)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-4000:]
+        out = json.loads(r.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 5 and out["steps_timed"] == 5 and out["timed_blocks"] == 1 and out["ms_per_step"] > 0
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["f32"] is None
+        assert out["config"]["capture"] == ("one graph" if mode == "graph" else "eager"), out["config"]
+        dumps[tag] = {p.name: np.load(p) for p in sorted((tmp_path / tag).iterdir())}
+    names = ["loss_ar.npy", "loss_lta.npy", "loss_pnr.npy", "loss_total.npy", "params_sample.npy"]
+    for a, b in (("g1", "g2"), ("e1", "e2")):
+        assert sorted(dumps[a]) == names and sorted(dumps[b]) == names
+        for n in names:
+            assert dumps[a][n].dtype == (np.float64 if n == "loss_total.npy" else np.float32)
+            assert np.isfinite(dumps[a][n]).all() and np.array_equal(dumps[a][n], dumps[b][n]), n

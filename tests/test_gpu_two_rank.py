@@ -37,7 +37,7 @@ def test_bench_runs_two_ranks_through_the_staged_graphs():
     timing protocol and the per-kernel leg complete on every rank (a rank 0 taking its eager profiling steps alone used to
     wait for its peers for ever), and rank 0's JSON line is the last line of stdout."""
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--one-gpu-gloo", "--steps", "4", "--warmup", "2",
-                        "--strict-capture"], capture_output=True, text=True, timeout=900)
+                        "--strict-capture", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     last = r.stdout.strip().splitlines()[-1]
     out = json.loads(last)

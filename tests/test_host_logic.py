@@ -311,6 +311,38 @@ def test_bench_gpus_n_spawns_n_ranks_and_propagates_failure():
     assert '"metric"' not in r.stdout
 
 
+def test_bench_plain_run_takes_only_the_headline_and_full_keeps_the_legs():
+    """A plain ``bench.py`` run times exactly --steps steps once and takes no other leg; ``--full`` takes the roofline,
+    CPU-baseline and f32 legs and the repeated timed blocks, each still switchable off on its own."""
+    import bench
+    plain = bench.parse_args(["--steps", "7"])
+    assert not plain.full and plain.steps == 7 and plain.min_timed_s == 0.0 and plain.dump_outputs is None
+    assert plain.no_roofline and plain.no_cpu_baseline and plain.no_f32_leg
+    full = bench.parse_args(["--full"])
+    assert full.min_timed_s == 0.5 and not (full.no_roofline or full.no_cpu_baseline or full.no_f32_leg)
+    some = bench.parse_args(["--full", "--no-roofline", "--min-timed-s", "0", "--dump-outputs", "out"])
+    assert some.no_roofline and not some.no_cpu_baseline and some.min_timed_s == 0.0 and some.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_writes_f32_f64_and_a_fixed_parameter_sample(tmp_path):
+    """``bench.dump_outputs``: the objective as f64, the loss vectors as f32, and the parameters as a fixed, seeded sample when
+    they outnumber DUMP_PARAMS (the same indices every run), in full otherwise."""
+    import numpy as np
+    import bench
+    flat = torch.arange(bench.DUMP_PARAMS + 1000, dtype=torch.float32)
+    vectors = {"ar": torch.rand(6), "pnr": torch.rand(6, dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, torch.tensor(2.5), vectors, flat)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["loss_ar.npy", "loss_pnr.npy", "loss_total.npy", "params_sample.npy"]
+    assert np.load(tmp_path / "a" / "loss_total.npy").dtype == np.float64 and float(np.load(tmp_path / "a" / "loss_total.npy")) == 2.5
+    assert np.load(tmp_path / "a" / "loss_pnr.npy").dtype == np.float32
+    s = np.load(tmp_path / "a" / "params_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_PARAMS,) and np.all(np.diff(s) > 0)  # sorted distinct indices
+    assert np.array_equal(s, np.load(tmp_path / "b" / "params_sample.npy"))
+    bench.dump_outputs(tmp_path / "c", torch.tensor(2.5), {}, flat[:10])
+    assert np.array_equal(np.load(tmp_path / "c" / "params_sample.npy"), flat[:10].numpy())
+
+
 # ---- whole-batch builders of the live loaders (VERDICT r2 #6) --------------------------------------------------------------
 def _same_fields(a, b, skip=()):
     from egopack_amd import engine as E

@@ -6,7 +6,7 @@ TAG=${1:-r01}; shift || true
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 3 --no-cpu-baseline --no-f32-leg $*"
+ARGS="--full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-leg $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 bench.py $ARGS > "$OUT/bench_stats.log" 2>&1
 echo "stats rc=$?"
 PARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-f32-leg --mode eager $*"

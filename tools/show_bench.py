@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pretty-print a bench.py log produced with --kernel-table (table on stderr + JSON line on stdout)."""
+"""Pretty-print a bench.py log produced with --full --kernel-table (table on stderr + JSON line on stdout)."""
 import json
 import sys
 
