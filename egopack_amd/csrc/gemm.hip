@@ -55,7 +55,10 @@ struct GemmArgs {
     int group_m;      // pipelined kernel: tile rows per group of the XCD-local tile order (see tile_of)
     float* dbias;     // fused bias gradient: dbias[m] += sum_k op(A)[m, k]  (transA pipelined kernel only)
     float* ws_bias;   // [splitk][M] partial row sums when splitk > 1
-    int rows_epilogue;  // 4-wave pipelined variants: write the tile out through LDS in whole rows (development knob, default 1)
+    // 4-wave pipelined variants: write the tile out through LDS in whole rows.  Always 1 now (the direct epilogue's knob is
+    // retired).  The field and its test stay: the build without them (and without the spread branch of gemm_pipe_group_kernel)
+    // measured 0.2-0.7 % slower in the median step time, inside the spread of repeats but in most pairs (HISTORY 13)
+    int rows_epilogue;
     // per-segment sums of the RESULT for the graph-mode LayerNorm that consumes it (egk_gemm_desc.st_*), rows epilogue only
     int st_mode, st_nseg;
     const int* st_seg_ptr;
@@ -726,7 +729,7 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
     // NI = MFMA row fragments per wave: 4 -> 128-row tiles; 3 -> 96-row tiles (row-major A only), for outputs whose
     // 128-row tiling leaves the CUs unevenly loaded (6144 x 1024: 384 tiles = 1.5 per CU; 512 tiles of 96 x 128 = 2)
     // MB = 2 with NI = 3: 192 x 128 tiles, 8 waves as 4 x 2 (48 x 64 each) -- 6144 x 1024 outputs are exactly 256 of them, one
-    // per CU, at 40 KiB per K tile for 1.5 x the flops of the 128 x 128 tile's 32 KiB.  Measured (tools/round6/r192_bench.py): alone
+    // per CU, at 40 KiB per K tile for 1.5 x the flops of the 128 x 128 tile's 32 KiB.  Measured (round 6, HISTORY.md): alone
     // it runs at the 96-row tiles' rate (20.9 against 19.6 us at K = 1024, 59.5 against 59.2 at K = 4608), in the step 1.340 against
     // 1.365 ms.  Built beside it and NOT kept: a 4-stage ring (every byte of LDS: 20.7 us, the step 1.345) and waves 4-7 staggered by
     // half a K tile against their SIMD partners (fragments held across the barrier: 23.7 us, 256 registers + spills, the step 1.45).
@@ -1106,17 +1109,16 @@ __global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW) void gemm_pipe_kernel
 
 // Grouped launch: up to MAX_GROUPS independent contractions of the SAME layout / element types / tile variant in one
 // launch (the projection heads of the task batches: same shapes, different rows of the backbone output, different
-// weights).  blockIdx.y = problem, blockIdx.x = its tile id; gridDim.x is the largest tile count rounded up to a
-// multiple of 8, so that blockIdx.x & 7 is still the XCD the hardware deals the workgroup to (linear id = y * gridDim.x
-// + x) and every problem keeps its XCD-local tile order.  Workgroups beyond a problem's tile count leave at once.
-// XCD-packed placement (``packed``, 1-D grid): the tiles of ALL problems form one list, problem after problem, and XCD x (linear
+// weights).  XCD-packed placement (``packed``, 1-D grid): the tiles of ALL problems form one list, problem after problem, and XCD x (linear
 // workgroup id mod 8) takes a CONSECUTIVE run of it -- so an XCD works on one problem (at most two) at a time and its L2 sees
 // that problem's operand strips once, instead of every XCD pulling the strips of every problem: six H x H weight gradients
 // fetched 450 MB (8 XCDs x 6 problems x ~6 strips of 1.5 MB) for 151 MB of operands; packed, 8 x ~14 strips = ~170 MB.
+// Every launch is packed now (the spread placement's knob is retired).  The spread branch of the kernel -- blockIdx.y = problem,
+// blockIdx.x = its tile id -- stays, for the reason given at GemmArgs::rows_epilogue.
 constexpr int MAX_GROUPS = 8;
 struct GemmGroup {
     GemmArgs p[MAX_GROUPS];
-    int packed, count, total;  // packed placement: number of problems, total tile count
+    int packed, count, total;  // packed placement (always 1): number of problems, total tile count
 };
 template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 = false, int LW = 0>
 __global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW) void gemm_pipe_group_kernel(const GemmGroup gg) {
@@ -1633,18 +1635,10 @@ using namespace egk;
 static int g_use_pipe = 1;
 // fixed cost of the reduce launch behind a split-K contraction in the bf16 cost model below, in microseconds.  3.5 is the
 // stand-alone fit; inside a captured step every extra launch also pays a boundary on its queue (a one-lane kernel lasts ~4.7 us
-// in a replay) -- development knob egk_gemm_set_pipeline(400 + tenths of a microsecond).
-static double g_reduce_fixed_us = 3.5;
-static int g_group_tt_pad_kb = 0;   // development knob (egk_gemm_set_pipeline(600 + KiB)): extra dynamic LDS of queued weight-gradient groups
-static int g_wg2_rows64 = 0;        // development knob (egk_gemm_set_pipeline(500 / 501)): variant 12 inside the policy off / on
-static int g_group_m_override = 0;  // development knob (egk_gemm_set_pipeline(100 + group_m); 100 = policy)
-static int g_rows_epilogue = 1;     // development knob (egk_gemm_set_pipeline(200 / 201): direct / row-contiguous epilogue)
-static int g_group_packed = 1;      // development knob (egk_gemm_set_pipeline(300 / 301): spread / XCD-packed placement of grouped launches)
-static int g_row_affinity = 1;      // development knob (egk_gemm_set_pipeline(950 / 951)): XCD x owns a contiguous eighth of the tile rows off / on
-static int g_group_r192 = 1;        // development knob (egk_gemm_set_pipeline(860 / 861)): the 192 x 128 tile for one-round row-major-A groups off / on
-static int g_r192_loaders = 1;      // development knob (egk_gemm_set_pipeline(870 / 871)): the 192 x 128 tile with four loader waves (variant 19) off / on
-static int g_tt_tall = 1;           // development knob (egk_gemm_set_pipeline(850 / 851)): 256 x 128 tiles for weight-gradient groups that leave the second workgroup slot of many CUs empty, off / on
-static int g_r192 = 1;              // development knob (egk_gemm_set_pipeline(900 / 901)): 192 x 128 tiles (variant 16) inside the policy off / on
+// in a replay).
+static constexpr double REDUCE_FIXED_US = 3.5;
+static int g_r192_loaders = 1;  // egk_gemm_set_pipeline(870 / 871): the 192 x 128 tile with four loader waves (variant 19) off / on
+static int g_tt_tall = 1;       // egk_gemm_set_pipeline(850 / 851): 256 x 128 tiles for weight-gradient groups that leave the second workgroup slot of many CUs empty, off / on
 static bool g_lds_attr_set = false;
 template <int NS, bool TA, bool TB, int KG, int MB = 1>
 static void set_lds_attr() {
@@ -1696,26 +1690,17 @@ static void ensure_lds_attr() {
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
     g_lds_attr_set = true;
 }
-// development knob (A/B runs in one process): 0 routes every contraction through the generic kernel
+// A/B runs in one process and the tests' forced variants: 0 routes every contraction through the generic kernel; 850 / 851 and
+// 870 / 871 switch one policy choice (g_tt_tall, g_r192_loaders).  Any other code outside 0 .. 19 changes nothing and returns -1.
 extern "C" int egk_gemm_set_pipeline(int32_t on) {
     const int prev = g_use_pipe;
-    if (on >= 950) { g_row_affinity = on - 950; return prev; }
-    if (on >= 900) { g_r192 = on - 900; return prev; }
-    if (on >= 870) { g_r192_loaders = on - 870; return prev; }
-    if (on >= 860) { g_group_r192 = on - 860; return prev; }
-    if (on >= 850) { g_tt_tall = on - 850; return prev; }
-    if (on >= 700) return prev;  // (700 / 80x: knobs of variants that no longer exist)
-    if (on >= 600) { g_group_tt_pad_kb = on - 600; return prev; }
-    if (on >= 500) { g_wg2_rows64 = on - 500; return prev; }
-    if (on >= 400) { g_reduce_fixed_us = (on - 400) * 0.1; return prev; }
-    if (on >= 300) { g_group_packed = on - 300; return prev; }
-    if (on >= 200) { g_rows_epilogue = on - 200; return prev; }
-    if (on >= 100) { g_group_m_override = on - 100; return prev; }
+    if (on == 870 || on == 871) { g_r192_loaders = on - 870; return prev; }
+    if (on == 850 || on == 851) { g_tt_tall = on - 850; return prev; }
+    if (on < 0 || on >= 20) return -1;
     // 0 generic kernel only; 1 default policy; 2 always 3-stage; 3 always 2-stage; 4 always 4-stage (all 128 x 128,
     // one wave group); 5 always two wave groups; 6 always the 256 x 128 tile (2-stage); 7 always the 256 x 256 tile (no fused
     // bias gradient: falls back to 3 with one); 8 / 11 the 96 x 128 / 64 x 128 tile where legal (row-major A); 16 the 192 x 128
-    // tile (8 waves, 3-stage ring) where legal (row-major A, no split-K); 900 / 901: variant 16 inside the policy off / on;
-    // 950 / 951: XCD x owns a contiguous eighth of the tile rows (row-major A) off / on
+    // tile (8 waves, 3-stage ring) where legal (row-major A, no split-K)
     g_use_pipe = on;
     return prev;
 }
@@ -1757,7 +1742,7 @@ extern "C" int egk_gemm_splitk(int32_t M, int32_t N, int32_t K, int32_t compute)
     int best = 1;
     double best_cost = 6.5 + 0.45 * nkt;
     for (int s = 2; s <= 16 && tiles * s <= 256 && nkt / s >= 2; s *= 2) {
-        const double cost = 6.5 + 0.45 * cdiv(nkt, s) + g_reduce_fixed_us + 1.5 * s * mn;
+        const double cost = 6.5 + 0.45 * cdiv(nkt, s) + REDUCE_FIXED_US + 1.5 * s * mn;
         if (cost < best_cost - 0.5) { best_cost = cost; best = s; }
     }
     return best;
@@ -1865,7 +1850,7 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
     g.tiles_m = cdiv(g.M, BM); g.tiles_n = cdiv(g.N, BN);
     g.dbias = nullptr; g.ws_bias = nullptr;
     g.group_m = 1;
-    g.rows_epilogue = g_rows_epilogue;
+    g.rows_epilogue = 1;
     g.st_mode = d->st_mode; g.st_nseg = d->st_nseg; g.st_seg_ptr = d->st_seg_ptr; g.st_ws = (double*)d->st_ws;
     g.st_x = d->st_x; g.st_ldx = d->st_ldx; g.st_stats = d->st_stats; g.st_w = d->st_w; g.st_b = d->st_b; g.st_slope = d->st_slope;
     if (d->st_mode) {
@@ -1934,17 +1919,13 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
                     const long long cur = variant == 8 ? ((t96 + 255) / 256) * 28 : ((t128 + 255) / 256) * 32;
                     // (ONE round only: 8192 x 1024 -- 344 tiles, two rounds of which the second is a third full -- measured 32.6 us
                     //  against 22.3 on 128-row tiles; BASELINE config 5's 16384 rows 3.08 against 2.92 ms per step)
-                    if (g_r192 && t192 > 192 && t192 <= 256 && 40 < cur) variant = 16;
+                    if (t192 > 192 && t192 <= 256 && 40 < cur) variant = 16;
                     // (several rounds of this tile with its loader waves -- 16384 x 1024: 688 tiles, 2.7 rounds -- measured 2.938 -> 2.901 ms
                     //  for BASELINE config 5 on one box and 2.93 -> 3.03 on two others: one round only)
                 } else if (t64 <= 256 && t64 > t128) {
                     // at most 128 tiles: 64-row tiles put one 4-wave workgroup on twice as many CUs instead of one
                     // 8-wave (two wave groups) workgroup on half of them (2048 x 1024 x 1024: 10.6 vs 12.4 us)
                     variant = 11;
-                    // ... and BOTH where the epilogue needs no finished tile in one wave group (no LayerNorm statistics, no row
-                    // gather): 64-row tiles on every CU, two wave groups per workgroup walking alternate K tiles -- the lone
-                    // 4-wave workgroup of (11) leaves its CU's DMA / LDS / matrix phases unoverlapped
-                    if (g_wg2_rows64 && !d->st_mode && nkt_slab >= 8) variant = 12;
                 }
             }
             // large outputs with a long K walk: 256 x 256 tiles, one 8-wave workgroup per CU, when whole tiles fill at least
@@ -1959,7 +1940,7 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
             // ... and 192 x 256 tiles (row-major A) where THEY fill their rounds and the 256-row tiles do not: 6144 x 4096 is 384
             // tiles of 256 rows (1.5 rounds: the makespan of two) but 512 of 192 rows (two whole rounds of 3/4 the height)
             const long long t192 = (long long)cdiv(g.M, 192) * cdiv(g.N, 256);
-            // (tools/round5/pp_bench.py, us: 6144 x 4096 x 4608 199 vs 211-263 on 128-row tiles, x 4096 180 vs 190, the dX form 185 vs
+            // (round 5, HISTORY.md; us: 6144 x 4096 x 4608 199 vs 211-263 on 128-row tiles, x 4096 180 vs 190, the dX form 185 vs
             //  190, 6144 x 4096 x 1024 63.3 vs 66.7; 6144 x 1024 outputs are 128 such tiles and stay on 96-row tiles)
             if (variant != 7 && !d->transA && g.splitk == 1 && !g.dbias && g.M % 192 == 0 && g.N % 256 == 0 && t192 >= 192 && K >= 1024 &&
                 10 * t192 >= 9 * 256 * ((t192 + 255) / 256))
@@ -1999,8 +1980,7 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
             // rows will be read, by workgroups of the SAME XCD, i.e. through that XCD's own L2 instead of across the fabric
             // (tools/exp/xcd_affinity.hip: 4.0-4.4 us against 8.3-11.2 us for a 12.6 MB hand-off).  Every XCD then streams the whole
             // B operand (weights: 2-9 MB, shared by its 32 workgroups K tile by K tile).
-            if (g_row_affinity && !d->transA && g.splitk == 1 && g.tiles_m % 8 == 0) g.group_m = g.tiles_m / 8;
-            if (g_group_m_override > 0) g.group_m = g_group_m_override < g.tiles_m ? g_group_m_override : g.tiles_m;
+            if (!d->transA && g.splitk == 1 && g.tiles_m % 8 == 0) g.group_m = g.tiles_m / 8;
         }
 
         // segment statistics in the epilogue: the 4-wave variants that write their tile out through LDS in whole rows, unsplit,
@@ -2079,7 +2059,7 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
             int gm = 1;
             while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
             g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
-            if (g_row_affinity && !d->transA && g.splitk == 1 && g.tiles_m % 8 == 0) g.group_m = g.tiles_m / 8;  // (as for the bf16 kernel)
+            if (!d->transA && g.splitk == 1 && g.tiles_m % 8 == 0) g.group_m = g.tiles_m / 8;  // (as for the bf16 kernel)
         }
         const bool st_ok = g.splitk == 1 && epilogue_rows_ok(g) && d->st_min_seg_rows >= (r96 ? 96 : 128) &&
                            (d->st_mode != 2 || (aligned16(d->st_x) && d->st_ldx % 4 == 0 && aligned16(d->st_w) && aligned16(d->st_b)));
@@ -2188,7 +2168,7 @@ static int fill_group_args(const egk_gemm_desc* d, GemmArgs& g) {
     g.splitk = 1;
     g.ws = nullptr;
     g.dbias = d->dbias; g.ws_bias = nullptr;
-    g.rows_epilogue = g_rows_epilogue;
+    g.rows_epilogue = 1;
     g.st_mode = 0; g.st_nseg = 0; g.st_seg_ptr = nullptr; g.st_ws = nullptr; g.st_x = nullptr; g.st_ldx = 0;
     g.st_stats = nullptr; g.st_w = nullptr; g.st_b = nullptr; g.st_slope = 0.f;
     EGK_REQUIRE(d->st_mode == 0, "egk_gemm_grouped: no segment statistics in a grouped launch");
@@ -2273,48 +2253,38 @@ extern "C" int egk_gemm_grouped(egk_stream_t stream, const egk_gemm_desc* descs,
     // than half fills the chip and 128- / 96-row tiles would take more than one (the projection heads of three task batches:
     // 64 + 2048 + 2048 rows = 184 tiles against 264 / 360)
     // (not for the three-product groups of the precise pass: BASELINE config 4 2.113 -> 2.124 ms with them)
-    if (!ta && !f16 && !any_extra && g_r192 && g_r192_loaders && g_group_r192 && t192 > 128 && t192 <= 256 && t128 > 256 && min_nkt >= 8) variant = 16;
+    if (!ta && !f16 && !any_extra && g_r192_loaders && t192 > 128 && t192 <= 256 && t128 > 256 && min_nkt >= 8) variant = 16;
     if (g_use_pipe == 3 || g_use_pipe == 5) variant = g_use_pipe;
     if (g_use_pipe == 13 && ta && tb) variant = 13;
     if ((g_use_pipe == 8 || g_use_pipe == 11) && !ta) variant = g_use_pipe;
     if (f16) variant = 3;  // (one instantiation: 128 x 128 tiles, one wave group)
-    int max_wg = 0, total = 0;
+    int total = 0;
     for (int i = 0; i < count; ++i) {
         GemmArgs& g = gg.p[i];
         g.tiles_m = variant == 8 ? cdiv(g.M, 96) : variant == 11 ? cdiv(g.M, 64) : variant == 13 ? cdiv(g.M, 256) : variant == 16 ? cdiv(g.M, 192) : cdiv(g.M, BM);
         g.tiles_n = cdiv(g.N, BN);
         total += g.tiles_m * g.tiles_n;
     }
-    const bool packed = g_group_packed != 0;
     for (int i = 0; i < count; ++i) {
         GemmArgs& g = gg.p[i];
         const int tiles = g.tiles_m * g.tiles_n;
-        // near-square patches of what ONE XCD works on: its share of this problem (spread placement) or of the whole launch
-        int per_xcd = packed ? cdiv(total, 8) : cdiv(tiles, 8), gm = 1;
+        // near-square patches of what ONE XCD works on: its share of the whole launch
+        int per_xcd = cdiv(total, 8), gm = 1;
         if (per_xcd > tiles) per_xcd = tiles;
         while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
         g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
-        max_wg = tiles > max_wg ? tiles : max_wg;
     }
     for (int i = count; i < MAX_GROUPS; ++i) gg.p[i] = gg.p[0];
-    gg.packed = packed ? 1 : 0; gg.count = count; gg.total = total;
-    const dim3 pgrid = packed ? dim3((total + 7) / 8 * 8) : dim3((max_wg + 7) / 8 * 8, count);
+    gg.packed = 1; gg.count = count; gg.total = total;
+    const dim3 pgrid((total + 7) / 8 * 8);
     const dim3 pblock(NTHREADS);
     const int layout = ta ? (tb ? 2 : 3) : (tb ? 1 : 0);
     EGK_REQUIRE(!(ta && !tb), "egk_gemm_grouped: the tn layout is not instantiated");
 #define EGK_PIPE_G(TA, TB)                                                                                                  \
     do {                                                                                                                    \
         if (variant == 5) hipLaunchKernelGGL((gemm_pipe_group_kernel<2, TA, TB, 2, 1>), pgrid, dim3(2 * NTHREADS), 4 * 32768, s, gg); \
-        else hipLaunchKernelGGL((gemm_pipe_group_kernel<2, TA, TB, 1, 1>), pgrid, pblock, 2 * 32768 + pad, s, gg);          \
+        else hipLaunchKernelGGL((gemm_pipe_group_kernel<2, TA, TB, 1, 1>), pgrid, pblock, 2 * 32768, s, gg);                \
     } while (0)
-    // (experiment) a weight-gradient group that runs BESIDE the backward chain may be held to one workgroup per CU by asking for
-    // more LDS than half a CU has: the chain's launches then always find registers and LDS on every CU
-    int pad = 0;
-    if (ta && tb && g_group_tt_pad_kb > 0) {
-        bool side = true;
-        for (int i = 0; i < count; ++i) side = side && gg.p[i].N <= 1024;
-        if (side) pad = g_group_tt_pad_kb * 1024;
-    }
     {
         ProfScope prof(KID_GEMM_BF16_GROUP_NN + layout, s, flops, bytes);  // (layout 0 nn, 1 nt, 2 tt; the tall weight-gradient tile included)
         if (f16) {

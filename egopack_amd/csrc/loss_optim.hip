@@ -457,10 +457,6 @@ static inline int row_grid(int rows) {
 
 using namespace egk;
 
-static int g_zero_fill_blocks = 0;  // development knob: egk_tune(5, workgroups); 0 = default
-static int g_adam_blocks = 0;       // development knob: egk_tune(6, workgroups); 0 = default
-namespace egk { void set_zero_fill_blocks(int n) { g_zero_fill_blocks = n; } }
-namespace egk { void set_adam_blocks(int n) { g_adam_blocks = n; } }
 
 extern "C" {
 
@@ -717,9 +713,9 @@ int egk_zero_fill(egk_stream_t stream, void* p, int64_t bytes) {
     const long long blocks = (n16 + 255) / 256;
     // A GENTLE fill: the captured step clears the gradient buffer beside its forward pass, with ~0.4 ms to spare -- at full
     // rate (4096 workgroups, 5 TB/s) the 100 MB burst doubled the HBM-bound row kernel it ran beside (positional-encoding add
-    // 7.2 -> 15.7 us, profiles/r05_c3_replay_timeline.txt at 141 us); egk_tune(5, n) sets the workgroup cap.
+    // 7.2 -> 15.7 us, profiles/r05_c3_replay_timeline.txt at 141 us): at most 64 workgroups.
     // Same box, three alternating rounds of the headline step: 4096 workgroups 1.407-1.417 ms, 192: 1.399-1.413, 64: 1.401-1.408
-    const long long cap = g_zero_fill_blocks > 0 ? g_zero_fill_blocks : 64;
+    const long long cap = 64;
     hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)(blocks > cap ? cap : blocks)), dim3(256), 0, s, (uint4*)p, n16);
     return check_launch("egk_zero_fill");
 }
@@ -787,7 +783,7 @@ int egk_adam_step_bump(egk_stream_t stream, float* p, const void* g, int32_t g_d
     // ahead again: headline 1.365-1.379 against 1.374-1.386 ms, config 4 2.180-2.182 against 2.191-2.206, Hp = 4096 2.722 against
     // 2.751 (narrower is clearly worse: 1024 workgroups 1.405-1.414, 512 1.447)
     const long long want = (n / 4 + 255) / 256;
-    const long long cap = g_adam_blocks > 0 ? g_adam_blocks : 32768;
+    const long long cap = 32768;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
     EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL(adam_kernel<T>, dim3(grid), dim3(256), 0, s, p, (const T*)g, m, v,
                                                (long long)n, hyper, beta1, beta2, eps, weight_decay, (bf16_t*)bf16_shadow,

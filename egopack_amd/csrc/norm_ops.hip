@@ -1024,18 +1024,18 @@ __global__ __launch_bounds__(256) void rowdot_reduce_kernel(const float* __restr
 }
 
 static inline int nv_for(int cols) { return cols <= 256 ? 1 : cols <= 1024 ? 4 : cols <= 4096 ? 16 : 0; }
-// development knobs (egk_tune 1 / 2).  Streaming kernels: three workgroups per CU -- every wave re-reads the f32 affine rows
+// Workgroup caps of the row kernels.  Streaming kernels: three workgroups per CU -- every wave re-reads the f32 affine rows
 // (8 KB against a 2 KB bf16 row) and, in the graph LayerNorm, re-reduces the statistics partials, so a wave should walk
 // >= 2 rows; in-step A/B of the headline workload, 200 steps x 3 rounds: 2048 -> 1.637, 512 -> 1.626, 768 -> 1.612 ms
-static int g_cap_partial = 512, g_cap_wide = 768;
+constexpr int CAP_PARTIAL = 512, CAP_WIDE = 768;
 extern int g_graph_rows_v2;  // (graph_ops.hip)
 static inline int row_grid(int rows) {  // kernels that emit per-workgroup partial rows: two workgroups per CU
     int g = cdiv(rows, WPB);
-    return g < 1 ? 1 : (g > g_cap_partial ? g_cap_partial : g);
+    return g < 1 ? 1 : (g > CAP_PARTIAL ? CAP_PARTIAL : g);
 }
 static inline int row_grid_wide(int rows) {  // pure streaming row kernels
     int g = cdiv(rows, WPB);
-    return g < 1 ? 1 : (g > g_cap_wide ? g_cap_wide : g);
+    return g < 1 ? 1 : (g > CAP_WIDE ? CAP_WIDE : g);
 }
 
 // ---- two-logit classifier + cross entropy over FEW rows (the OSCC head: one row per sequence), loss AND gradients in one launch --
@@ -1186,7 +1186,7 @@ using namespace egk;
         case 3: { constexpr int NVW = 3; __VA_ARGS__; } break;     \
         default: { constexpr int NVW = 4; __VA_ARGS__; } break;    \
     }
-static int g_wide_rows = 1;  // development knob (egk_tune 7): 0 = the one-wave-per-row kernels for every width
+static int g_wide_rows = 1;  // egk_tune 7 (tests: the reference): 0 = the one-wave-per-row kernels for every width
 static inline bool wide_rows_ok(int cols, const void* in, const void* out, const float* w, const float* b, const uint8_t* mask, int dtype) {
     auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     (void)dtype;
@@ -1196,13 +1196,10 @@ static inline bool wide_rows_ok(int cols, const void* in, const void* out, const
 
 extern "C" {
 
-// development knob: 1 = workgroup cap of the row kernels that emit per-workgroup partials, 2 = cap of the streaming ones
+// the tests' references: 3 = the rows1024.h graph-row kernels on / off, 7 = the workgroup-per-row LayerNorm kernels on / off;
+// any other key changes nothing and returns -1
 int egk_tune(int32_t key, int32_t value) {
-    if (key == 1) { const int p = g_cap_partial; g_cap_partial = value; return p; }
-    if (key == 2) { const int p = g_cap_wide; g_cap_wide = value; return p; }
     if (key == 3) { const int p = g_graph_rows_v2; g_graph_rows_v2 = value; return p; }  // graph_ops.hip: the rows1024.h kernels
-    if (key == 5) { ::egk::set_zero_fill_blocks(value); return 0; }  // loss_optim.hip: workgroups of egk_zero_fill (0 = default)
-    if (key == 6) { ::egk::set_adam_blocks(value); return 0; }       // loss_optim.hip: workgroup cap of the Adam launch (0 = default)
     if (key == 7) { const int p = g_wide_rows; g_wide_rows = value; return p; }  // the workgroup-per-row LayerNorm kernels on / off
     return -1;
 }

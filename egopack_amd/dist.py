@@ -62,7 +62,7 @@ def init_single_rank_group(backend: str = "nccl") -> None:
 def quiesce_before_capture(group=None, settle_s: float = 1.0) -> None:
     """Let the RCCL process group's WATCHDOG retire every collective issued so far before a hipGraph capture starts.
 
-    Root cause of the round-3 driver abort (reproduced 3 times in 9 on fresh boxes, tools/round4/repro_abort.sh; the C++ trace is
+    Root cause of the round-3 driver abort (reproduced 3 times in 9 on fresh boxes, HISTORY.md; the C++ trace is
     in profiles/r04_abort_root_cause.txt): ProcessGroupNCCL's watchdog thread keeps a copy of every EAGERLY issued collective
     and polls its end event (hipEventQuery) every ~100 ms until it has completed.  ``capture(warmup=...)`` issues eager steps
     -- with their collectives -- and starts capturing right behind them; when a capture that contains collectives then takes
@@ -133,12 +133,6 @@ class GradSync:
         self._side = None
         self._g16 = None
         self._inflight = []
-        # region-wise exchange (start / finish_and_step): every chunk's Adam slice may be issued behind its collective on the
-        # communication stream, beside the backward stages that follow (a region's parameters are not read again by them).
-        # OPT-IN (EGK_ENABLE=adam_behind_collective or the attribute): the Adam writes (f32 parameters, bf16 shadows) then run
-        # concurrently with the remaining backward graphs, and that ordering has never executed against real RCCL peers --
-        # the default issues every slice after the last stage, behind its collective's event
-        self.adam_behind_collective = switches.enabled("adam_behind_collective")
         self.hyper_ready = False  # set by a caller that has prepared the step's Adam constants itself (a captured exchange)
 
     def quiesce(self) -> None:
@@ -256,14 +250,9 @@ class GradSync:
             self._side.wait_event(ready)
             with torch.cuda.stream(self._side):
                 all_reduce_sum_(src[b:e], self.group)
-                # the Adam slice of the chunk right behind its collective, on the communication stream: the parameters of a
-                # region are not read again by the backward stages that follow it (heads: used in stage A only; SAGE stack:
-                # not by the temporal pooling's backward), so the update runs beside those stages instead of after them
-                if self.adam_behind_collective:
-                    opt.launch(src, b, e)
                 ev = torch.cuda.Event()
                 ev.record(self._side)
-            self._inflight.append({"b": b, "e": e, "ev": ev, "src": src, "stepped": self.adam_behind_collective})
+            self._inflight.append({"b": b, "e": e, "ev": ev, "src": src, "stepped": False})
 
     def step_started_chunks(self, opt, stream) -> None:
         """The Adam slice of every chunk started so far and not stepped yet, on ``stream``, each behind its collective: the

@@ -12,7 +12,6 @@
 """
 from __future__ import annotations
 
-import os
 import queue
 import threading
 from typing import Dict, Mapping, Optional, Sequence
@@ -183,7 +182,7 @@ class StagedBatches:
         # (``StepBase.gathers_inputs``) the feature block is no longer gathered here
         self.step = step
         # steps staged ahead by the staging thread (0: staged inline, right behind the consumer's launch of the step before)
-        self.depth = (2 if switches.enabled("staging_thread") else 0) if depth is None else int(depth)
+        self.depth = 2 if depth is None else int(depth)
         # ONE copy stream per device for the life of the process: the caching allocator keeps a pool per stream, so a fresh
         # stream per epoch stranded every epoch's staging blocks in a pool nobody allocates from again (reserved memory grew
         # by ~130 MB per epoch of the headline workload while the allocated bytes stayed flat)
@@ -194,8 +193,7 @@ class StagedBatches:
             if self.copy_stream is None:
                 # (a priority stream: the runtime keeps hardware queues per priority level, so the staging launches do not sit in a
                 #  queue behind a branch of the replayed graph that is waiting for its dependencies)
-                prio = int(switches.value("staging_priority", -1)) if switches.enabled("staging_priority") else 0
-                self.copy_stream = _COPY_STREAMS[key] = torch.cuda.Stream(device=device, priority=prio)
+                self.copy_stream = _COPY_STREAMS[key] = torch.cuda.Stream(device=device, priority=-1)
 
     def _stage(self, host):
         live = {t: b for t, b in host.items() if b is not None}
@@ -539,7 +537,7 @@ class StepBase:
         """H x H weight-gradient problems per grouped launch.  Eight problems are 512 tiles = two whole rounds of the chip (16.4 us per
         problem at 6144 rows against 20 for six = 1.5 rounds), but such a launch holds EVERY CU for both rounds and the backward chain's
         launches wait behind it: worth it while the K walk is short.  Measured, 6 against 8 on one box, alternating
-        (tools/round6/wgrad_count_ab*.sh): fused three-task step at 6144 rows 1.308 -> 1.287 ms (its 8-rank dry run 1.360 -> 1.317,
+        (round 6, HISTORY.md): fused three-task step at 6144 rows 1.308 -> 1.287 ms (its 8-rank dry run 1.360 -> 1.317,
         sharded 1.282 -> 1.247), four tasks at 8192 rows 1.636 -> 1.644, at 16384 rows 2.945 -> 3.013, one task at 2048 rows
         0.837 -> 0.847 -- so: eight for a fused multi-task pass of fewer than 8192 rows, else the module default (six)."""
         if self.wgrad_group_count is not None:
@@ -583,11 +581,6 @@ class StepBase:
             forced = switches.override(name)
             if forced is not None:
                 setattr(self, name, forced)
-        if not switches.enabled("grouped_heads"):
-            self.grouped_heads = False
-        self._fused_loss = switches.enabled("fused_loss")
-        if not switches.enabled("ln_fusion"):
-            ops._ln_fusion["on"] = False
 
     # ---- backbone ------------------------------------------------------------------------------------
     def features(self, batches: Mapping[str, Data], merged: Optional[Data] = None) -> Dict[str, torch.Tensor]:
@@ -983,7 +976,6 @@ class StepBase:
     # one set runs, the next batch is copied into the other on a stream of its own (behind the event that ends the last replay that
     # read that set, and behind the staging of the batch).  The two graphs share everything else -- parameters, optimizer state,
     # gradient buffer, dropout offset word, loss accumulators -- and run one after the other on the training stream.
-    double_buffered_inputs = None  # None: switches.enabled("double_buffered_inputs") for one-rank steps whose optimizer is in the graph
     gathers_inputs = False  # set once the step gathers the store rows into its own input buffers (see _input_slot)
 
     def _slot_of_capture(self, blob, static_b, static_m) -> dict:
@@ -993,10 +985,8 @@ class StepBase:
     def _select_slot(self, slot) -> None:
         self._graph, self._static_out, self._static_in = slot["graph"], slot["out"], slot["static_in"]
 
-    def _double_buffer_ok(self) -> bool:
-        on = self.double_buffered_inputs
-        on = switches.enabled("double_buffered_inputs") if on is None else bool(on)
-        return bool(on and getattr(self, "_fuse_adam", False) and not isinstance(self._graph, list))
+    def _double_buffer_ok(self) -> bool:  # (one-rank steps whose optimizer is in the graph)
+        return bool(getattr(self, "_fuse_adam", False) and not isinstance(self._graph, list))
 
     def _input_slot(self, st, ref, batches, merged) -> dict:
         """The set of input buffers this step's replay reads, holding this step's batch (see above)."""
@@ -1016,7 +1006,7 @@ class StepBase:
         side = cur
         if len(slots) > 1:
             if not hasattr(self, "_input_stream"):
-                self._input_stream = torch.cuda.Stream(priority=-1 if switches.enabled("staging_priority") else 0)
+                self._input_stream = torch.cuda.Stream(priority=-1)
             side = self._input_stream
             ready = getattr(ref, "ready", None)
             if ready is not None:
@@ -1042,7 +1032,7 @@ class StepBase:
                     elif merged is None:
                         dst.x.copy_(b.x, non_blocking=True)
                     dst._struct_key = getattr(b, "_struct_key", 0)
-        if len(slots) > 1 and store is not None and switches.enabled("step_gathers_inputs"):
+        if len(slots) > 1 and store is not None:
             self.gathers_inputs = True  # (from now on a StagedBatches that feeds this step leaves the gathers to it)
         if side is not cur:
             for v in (ref.dev, getattr(merged, "x", None), *(getattr(b, "x", None) for b in batches.values() if b is not None)):
@@ -1125,34 +1115,25 @@ class StepBase:
                 ops.stamp("step_start")
                 # the gradient buffer is cleared BESIDE the forward pass (nothing writes a gradient before the first backward
                 # launch): 100 MB of memset off the chain's head; joined in _join_zero() before backward starts
-                hyper_here = fuse_adam and switches.enabled("hyper_in_graph")
+                hyper_here = fuse_adam
                 self._hyper_in_graph = hyper_here
-                if not switches.enabled("zero_stream"):
-                    opt.zero_flat_grads()
-                    if hyper_here:
-                        opt.prepare_hyper(in_capture=True)
-                else:
-                    if not hasattr(self, "_zero_stream"):
-                        self._zero_stream = torch.cuda.Stream()
+                if not hasattr(self, "_zero_stream"):
+                    self._zero_stream = torch.cuda.Stream()
 
-                    def issue_zero(ev):  # (behind the forward pass's first launch: see ops.defer_after_next_launch)
-                        self._zero_stream.wait_event(ev)
-                        with torch.cuda.stream(self._zero_stream):
-                            opt.zero_flat_grads()
-                            if hyper_here:  # the step's Adam constants: one thread, beside the forward pass
-                                opt.prepare_hyper(in_capture=True)
-                    if not switches.enabled("zero_deferred"):
-                        issue_zero(torch.cuda.current_stream().record_event())
-                    else:
-                        ops.defer_after_next_launch(issue_zero)
-                    self._zero_pending = True
+                def issue_zero(ev):  # (behind the forward pass's first launch: see ops.defer_after_next_launch)
+                    self._zero_stream.wait_event(ev)
+                    with torch.cuda.stream(self._zero_stream):
+                        opt.zero_flat_grads()
+                        if hyper_here:  # the step's Adam constants: one thread, beside the forward pass
+                            opt.prepare_hyper(in_capture=True)
+                ops.defer_after_next_launch(issue_zero)
+                self._zero_pending = True
                 self._rng_in_graph = False
                 if self.input_hook is not None:
                     self.input_hook()
                 if early is None and not fuse_adam:
                     self._install_tail(self._tail_only_plan(live))
                 if early is not None:
-                    early["rng"] = switches.enabled("rng_in_graph") and switches.enabled("rng_early")
                     ops.set_last_wgrad_hook(early["param"], early["hook"], pre=self._join_gradient_branches)
                     ops.set_graphone_backward_hook(early.get("graphone_hook"))
                     if early["tail"]:
@@ -1169,7 +1150,7 @@ class StepBase:
                 # dropout launch of the step is done when the optimizer starts): replay k draws the masks of offset base + k * stride
                 # without a separate launch in front of every replay -- and without a launch of its own: it rides in an optimizer
                 # launch (egk_adam_step_bump)
-                rng_here = switches.enabled("rng_in_graph") and not (early is not None and early.get("rng_done"))
+                rng_here = not (early is not None and early.get("rng_done"))
                 bump = (ops.rng_device_offset(opt.flat_p.device), ops.RNG_DEVICE_STRIDE) if rng_here else None
                 if fuse_adam:
                     if early is not None and early["fired"]:
@@ -1185,10 +1166,9 @@ class StepBase:
                         opt.launch(bump=bump)
                         bump = None
                     ops.stamp("adam_done")
-                if switches.enabled("rng_in_graph"):
-                    if bump is not None:
-                        ops.advance_rng_device(opt.flat_p.device)
-                    self._rng_in_graph = True
+                if bump is not None:
+                    ops.advance_rng_device(opt.flat_p.device)
+                self._rng_in_graph = True
         finally:
             ops.set_last_wgrad_hook(None, None)
             ops.set_graphone_backward_hook(None)
@@ -1216,7 +1196,7 @@ class StepBase:
         tp = getattr(self.model, "temporal_pooling", None)
         first = getattr(tp, "proj", [None])[0] if tp is not None else None
         if (first is None or not hasattr(opt, "region_of") or not getattr(opt, "materialised", False) or not (self.fused or len(live) == 1)
-                or not switches.enabled("tail_group") or not self.headwise_backward_ok()
+                or not self.headwise_backward_ok()
                 or first.weight.numel() >= 512 * 128 * 128):  # (a wide first linear's weight gradient stays a launch of its own)
             return None
         params = [p for p in tp.parameters() if p.requires_grad]
@@ -1261,7 +1241,7 @@ class StepBase:
         #  runs beside it; Hp = 4096 step 2.785-2.796 -> 2.770-2.772 ms.  At Hp = 1024 (288 tiles) the pooling's three weight
         #  gradients are one grouped launch, 123 against 120 + 66 us.)
         tail = None
-        if switches.enabled("tail_group") and first.weight.numel() < 512 * 128 * 128:
+        if first.weight.numel() < 512 * 128 * 128:
             tail = region([p for p in tp.parameters() if p.requires_grad])
         reg = tail or region([p for p in (getattr(first, "weight", None), getattr(first, "bias", None)) if p is not None])
         if reg is None:
@@ -1285,14 +1265,13 @@ class StepBase:
                 with torch.cuda.stream(plan["stream"]):
                     # the dropout offset word moves on here, beside the last weight gradient (every dropout launch of the step
                     # is long done), INSIDE the first optimizer launch: no launch of its own
-                    bump = (ops.rng_device_offset(opt.flat_p.device), ops.RNG_DEVICE_STRIDE) if plan.get("rng") else None
+                    bump = (ops.rng_device_offset(opt.flat_p.device), ops.RNG_DEVICE_STRIDE)
                     for a, b in _minus([(0, lo), (hi, total)], plan.get("done", ())):  # (``done``: slices stepped earlier in the step)
                         opt.launch(None, a, b, bump=bump)
                         bump = None
                     if bump is not None:  # (no slice left to step here: the word still moves on)
                         ops.advance_rng_device(opt.flat_p.device)
-            if plan.get("rng"):
-                plan["rng_done"] = True  # (every dropout launch of the step has been issued: this is backward's end)
+            plan["rng_done"] = True  # (every dropout launch of the step has been issued: this is backward's end)
             ops.defer_after_next_launch(issue)
             plan["fired"] = True
         plan["hook"] = hook
@@ -1355,8 +1334,8 @@ class StepBase:
         prev_d = ops.set_deferred_forks(self.deferred_forks)
         sync.begin_step()
         sync.hyper_ready = True
-        self._handoff = switches.enabled("wgrad_handoff")
-        prev_h = ops.set_wgrad_handoff(self._handoff)
+        self._handoff = True
+        prev_h = ops.set_wgrad_handoff(True)
         store_prev = self._grad_store_begin()  # (single-writer gradient slots are stored: the collectives read final values either way)
         try:
             with torch.cuda.graph(g, stream=ops.unexcluded_stream(), capture_error_mode=CAPTURE_MODE):
@@ -1388,7 +1367,7 @@ class StepBase:
                 fired = []
 
                 def early_adam_hook():
-                    if fired or not switches.enabled("exchange_early_adam"):
+                    if fired:
                         return
                     fired.append(True)
                     if not hasattr(self, "_adam_stream"):
@@ -1408,9 +1387,8 @@ class StepBase:
                 self._exchange_region(regions[2])
                 sync.finish_and_step(opt)
                 ops.stamp("adam_done")
-                if switches.enabled("rng_in_graph"):
-                    ops.advance_rng_device(opt.flat_p.device)
-                    self._rng_in_graph = True
+                ops.advance_rng_device(opt.flat_p.device)
+                self._rng_in_graph = True
         finally:
             self._handoff = False
             ops.set_wgrad_handoff(prev_h)
@@ -1447,18 +1425,15 @@ class StepBase:
             with torch.cuda.graph(gs[0], stream=cap, capture_error_mode=CAPTURE_MODE):
                 # the gradient buffer is cleared BESIDE the forward pass, as in the one-rank capture (a fork and a join inside
                 # the first graph; _stage_a joins it before the heads' backward writes the first gradient)
-                if not switches.enabled("zero_stream"):
-                    opt.zero_flat_grads()
-                else:
-                    if not hasattr(self, "_zero_stream"):
-                        self._zero_stream = torch.cuda.Stream()
+                if not hasattr(self, "_zero_stream"):
+                    self._zero_stream = torch.cuda.Stream()
 
-                    def issue_zero(ev):
-                        self._zero_stream.wait_event(ev)
-                        with torch.cuda.stream(self._zero_stream):
-                            opt.zero_flat_grads()
-                    ops.defer_after_next_launch(issue_zero)
-                    self._zero_pending = True
+                def issue_zero(ev):
+                    self._zero_stream.wait_event(ev)
+                    with torch.cuda.stream(self._zero_stream):
+                        opt.zero_flat_grads()
+                ops.defer_after_next_launch(issue_zero)
+                self._zero_pending = True
                 if self.input_hook is not None:
                     self.input_hook()
                 total, vectors = self._stage_a(batches, merged)
@@ -1549,23 +1524,17 @@ class MTLStep(StepBase):
 
     def _one_pass_head_ok(self, t: str) -> bool:
         from .criterion import BCEWithLogitsNone
-        return (self.one_pass_heads and hasattr(self.tasks[t], "fused_head_loss") and type(self.criteria[t]) is BCEWithLogitsNone
-                and switches.enabled("rowdot_head"))
+        return self.one_pass_heads and hasattr(self.tasks[t], "fused_head_loss") and type(self.criteria[t]) is BCEWithLogitsNone
 
     def _one_pass_oscc_ok(self, t: str) -> bool:
         """The OSCC head (max pool -> 2-logit classifier -> cross entropy, one loss element per SEQUENCE) as pool + one launch
         (ops.linear2_ce): its eleven short launches sat on the critical path of the 4-task step between forward and backward."""
         from .criterion import CrossEntropyNone
         return (t == "oscc" and self.one_pass_heads and hasattr(self.tasks[t], "fused_head_loss")
-                and type(self.criteria[t]) is CrossEntropyNone and getattr(self, "_fused_loss", True)
-                and switches.enabled("rowdot_head") and switches.enabled("oscc_one_pass"))
-
-    grouped_classifiers = True
+                and type(self.criteria[t]) is CrossEntropyNone and switches.enabled("oscc_one_pass"))
 
     def _banked_tasks(self, order, proj_leaves):
         """Tasks whose multi-head classifier banks can share grouped launches (ops.grouped_classifier_banks): at least two."""
-        if not self.grouped_classifiers or not switches.enabled("grouped_classifiers"):
-            return []
         cand = []
         for t in order:
             task = self.tasks[t]
@@ -1634,7 +1603,7 @@ class MTLStep(StepBase):
             # AR / LTA: one loss element per node, back-propagated below with the constant w_t / numel -- known before the
             # loss is computed, so the cross entropy emits its gradient in the same launch (ops.loss_seed)
             # (the loss vector has one element per NODE, so the seed divides by the full node count also for a compacted head)
-            n_loss = n_full[t] if (t in ("ar", "lta", "pnr") and getattr(self, "_fused_loss", True)) else 0
+            n_loss = n_full[t] if t in ("ar", "lta", "pnr") else 0
             oscc_one = self._one_pass_oscc_ok(t) and batches[t].y.dim() == 1
             if oscc_one:
                 n_loss = int(batches[t].y.numel())  # one loss element per sequence
@@ -1677,21 +1646,19 @@ class MTLStep(StepBase):
         def banked_chain():
             views = [self.tasks[t].classifiers[0][1].weight._egk_bank_views for t in banked]
             n_loss = {t: n_full[t] for t in banked}  # (one loss element per NODE: a compacted head's seed divides by the full count)
-            all_logits = ops.grouped_classifier_banks([proj_leaves[t] for t in banked], views,
-                                                      fused_loss=getattr(self, "_fused_loss", True))
+            all_logits = ops.grouped_classifier_banks([proj_leaves[t] for t in banked], views, fused_loss=True)
             vs, gs = [], []
             multi = None
-            if getattr(self, "_fused_loss", True) and switches.enabled("ce_multi"):
-                # the cross entropies of the banked tasks as ONE launch (each writes its own loss vector and gradient operand)
-                sel = [self.criteria[t].select(logits, labels[t]) for t, logits in zip(banked, all_logits)]
-                if len({s_[2] for s_ in sel}) == 1:
-                    multi = ops.cross_entropy_multi([(s_[0], s_[1]) for s_ in sel], [self.weights[t] / n_loss[t] for t in banked],
-                                                    sel[0][2])
+            # the cross entropies of the banked tasks as ONE launch (each writes its own loss vector and gradient operand)
+            sel = [self.criteria[t].select(logits, labels[t]) for t, logits in zip(banked, all_logits)]
+            if len({s_[2] for s_ in sel}) == 1:
+                multi = ops.cross_entropy_multi([(s_[0], s_[1]) for s_ in sel], [self.weights[t] / n_loss[t] for t in banked],
+                                                sel[0][2])
             for i, (t, logits) in enumerate(zip(banked, all_logits)):
                 if multi is not None:
                     v = multi[i]
                 else:
-                    with ops.loss_seed(self.weights[t] / n_loss[t] if getattr(self, "_fused_loss", True) else None):
+                    with ops.loss_seed(self.weights[t] / n_loss[t]):
                         v = self.criteria[t](logits, labels[t])
                 if v.numel() != proj_leaves[t].shape[0]:
                     raise RuntimeError(f"head {t}: {v.numel()} loss elements for {proj_leaves[t].shape[0]} rows")
@@ -1722,7 +1689,7 @@ class MTLStep(StepBase):
             # backward and the backbone's
             src = {t: compact_v.get(t, v) for t, v in vectors.items()}
             cnt = {t: (n_full[t] if t in compact_v else None) for t in vectors}
-            if not switches.enabled("objective_rider") or not src:
+            if not src:
                 total = self._objective(src, cnt)
                 self._ride_loss_sums(src)
             else:
@@ -1736,14 +1703,14 @@ class MTLStep(StepBase):
                                (total, *[src[t] for t in order if t in src]))
         return total, vectors, leaves
 
-    compact_heads = True  # heads on the labelled rows only (data.live_label_rows); EGK_DISABLE=compact_heads: every row
+    compact_heads = True  # heads on the labelled rows only (data.live_label_rows); False: every row
 
     def _compact_head_ok(self, t: str, d, leaf) -> bool:
         """Task ``t``'s head runs on its labelled rows: a multi-head cross-entropy head (MetricSelectorWrapper over
         CrossEntropyNone with ignore_index -1: the row's loss and gradient are exactly zero when every head's label is -1),
         no active dropout in the head (its masks are drawn by row position), the batch built by data.collate with its
         ``live_*`` index arrays on the features' device."""
-        if not self.compact_heads or not switches.enabled("compact_heads") or t not in ("ar", "lta"):
+        if not self.compact_heads or t not in ("ar", "lta"):
             return False
         idx = getattr(d, "live_idx", None)
         if idx is None or getattr(d, "live_inv", None) is None or getattr(d, "live_y", None) is None:
@@ -1774,11 +1741,10 @@ class MTLStep(StepBase):
         self._join_zero()
         total, vectors, leaves = self._heads_forward_backward(feats)
         ops.stamp("heads_done")
-        if switches.enabled("heads_flush"):
-            # the heads' parked weight gradients (classifier banks, projections) go out as one launch NOW, beside the first
-            # links of the backbone's dX chain; left parked, the backbone's first weight gradient would flush nine problems
-            # as 8 + 1
-            ops.flush_wgrad(in_backward=False, force=True)
+        # the heads' parked weight gradients (classifier banks, projections) go out as one launch NOW, beside the first
+        # links of the backbone's dX chain; left parked, the backbone's first weight gradient would flush nine problems
+        # as 8 + 1
+        ops.flush_wgrad(in_backward=False, force=True)
         order = [t for t in feats if leaves[t].grad is not None]
         torch.autograd.backward([feats[t] for t in order], [leaves[t].grad for t in order])
         return total, vectors
@@ -1886,7 +1852,6 @@ class EgoPackStep(StepBase):
     # + auxiliary projections, no gradient -- the reference detaches these features (main_egopack.py:53).  The GraphONE stages
     # consume the same values (rounded to the activation type).
     precise_search = True
-    precise_stream = True  # the precise pass on its own stream beside the training pass's forward (False: in line, A/B)
     # Adam over everything but the temporal pooling's slots beside the step's last weight-gradient launch (StepBase._early_adam_plan):
     # the step is ONE backward() call whose last node is the first TRN linear -- every other node has been issued by then, on
     # the backward stream or on the branch streams below, which the optimizer slice waits for.  Config 4: 55 M parameters,
@@ -1894,16 +1859,16 @@ class EgoPackStep(StepBase):
     early_adam = True
 
     def _early_adam_ok(self) -> bool:
-        return bool(self.early_adam and self.backprop and switches.enabled("early_adam"))
+        return bool(self.early_adam and self.backprop)
 
     def _gradient_branch_streams(self):
         return [*getattr(self.graphone, "_task_streams", ()), *getattr(self, "_head_streams", ())]
 
     def _early_adam_plan(self, live):
-        """+ GraphONE's own slice (EGK_DISABLE=graphone_adam: off): its stage parameters (half of the step's parameters in config
+        """+ GraphONE's own slice (``graphone_adam`` off: none): its stage parameters (half of the step's parameters in config
         4) have their final gradients when the grouped GraphONE backward returns (ops.set_graphone_backward_hook) -- Adam over
         that slice then runs beside the backbone's backward instead of in the step's tail.  Round 4: the tail shrank from 275 to
-        114 us and the backbone's backward grew by as much (2.746-2.751 against 2.72-2.80 ms, tools/round4/c4_g1adam_ab.sh: the
+        114 us and the backbone's backward grew by as much (2.746-2.751 against 2.72-2.80 ms, HISTORY.md: the
         memory-bound launch slows the chain it runs beside) -- opt-in then.  Round 5, with the searches grouped and the precise pass
         first: 2.42-2.45 against 2.475-2.478 ms (three alternating rounds): the default.  Elementwise, the same update bit for bit
         (tests/test_gpu_configs.py::test_config4_graphone_optimizer_slice_is_the_same_update)."""
@@ -1974,8 +1939,8 @@ class EgoPackStep(StepBase):
     def _one_pass_ok(self, batches, merged) -> bool:
         """ONE backbone pass per step (ops.dual_record / dual_replay) applies: a single task batch with bf16 features, gradients
         through the backbone, no active dropout in it (the keep masks of the two passes would have to be shared), statistics
-        local to the rank.  EGK_DISABLE=one_pass: the two-pass step of rounds 3-5."""
-        if not (self.one_pass and self.backprop) or not switches.enabled("one_pass") or not switches.enabled("one_pass"):
+        local to the rank.  ``one_pass`` off: the two-pass step of rounds 3-5."""
+        if not (self.one_pass and self.backprop) or not switches.enabled("one_pass"):
             return False
         live = [batches[t] for t in self.enabled if batches.get(t) is not None]
         if len(live) != 1 or isinstance(live[0].x, (list, tuple)) or live[0].x.dtype != torch.bfloat16 or ops.graph_ln_exchange_on():
@@ -1993,8 +1958,6 @@ class EgoPackStep(StepBase):
         the precise features only, so they start when that pass ends -- not behind the join with the training pass's forward chain,
         which (created second) ends later: profiles/r05_c4_replay_timeline.txt vs r05b: the searches 907 -> 7xx us."""
         self.graphone.drop_searched()
-        if not switches.enabled("search_ahead"):
-            return
         for d in precise.values():
             self.graphone.search_ahead(d)
 
@@ -2007,15 +1970,13 @@ class EgoPackStep(StepBase):
             with torch.no_grad():
                 # f32 out of the projections' last contraction: the nearest-prototype search (an index op) ranks the f32
                 # accumulators in every compute mode; GraphONE brings them to the activation type for its stages
-                grouped = None
-                if switches.enabled("grouped_aux"):
-                    grouped = ops.grouped_projection_infer(ops.to_act(feat), [self.tasks[t].net for t in others], out_f32=True)
+                grouped = ops.grouped_projection_infer(ops.to_act(feat), [self.tasks[t].net for t in others], out_f32=True)
                 aux_in = (dict(zip(others, grouped)) if grouped is not None
                           else {t: self.tasks[t].forward_features(feat, out_f32=True) for t in others})
         aux, closest = self.graphone.interact(aux_in)
         ops.stamp("stages_done")
         if (primary == "oscc" and getattr(task, "loss_func", None) == "ce" and hasattr(task, "fused_head_loss") and data.y.dim() == 1
-                and switches.enabled("oscc_one_pass") and switches.enabled("rowdot_head")):
+                and switches.enabled("oscc_one_pass")):
             # the four 2-logit classifiers (primary + one per auxiliary task) behind their max pools, the logit fusion, the loss and
             # every gradient as ONE launch: the objective is sum_t w_t mean(loss_t), so the loss vector's backward seed is the
             # constant w / B (ops.loss_seed) -- ~35 short launches of the contraction path otherwise
@@ -2037,10 +1998,9 @@ class EgoPackStep(StepBase):
         self.graphone.train()
         snap = ops.rng_snapshot()
         precise, side = {}, None
-        tape, gate_ev = None, {}
+        tape = None
         first = next((b for b in batches.values() if b is not None), None)
-        on_side = (self._precise_on() and self.precise_stream and first is not None and first.pos.is_cuda
-                   and switches.enabled("precise_stream"))
+        on_side = self._precise_on() and first is not None and first.pos.is_cuda
         # Which chain is CREATED first keeps the launch queue under capture: the precise pass IS the step's critical chain and goes
         # first (2.529-2.549 against 2.565-2.586 ms with the training pass's forward chain created first, four alternating rounds).
         if self._precise_on():
@@ -2053,17 +2013,9 @@ class EgoPackStep(StepBase):
                     ops.exclude_wgrad_streams([self._precise_side])
                 side = self._precise_side
                 side.wait_stream(main)
-                gate = os.environ.get("EGK_TRAIN_AFTER", "")  # (development: the training pass starts behind this phase of the precise pass)
-                gate_ev = {}
-                if gate:
-                    ops.phase_callbacks({gate: lambda: gate_ev.setdefault("ev", side.record_event())})
                 tape = [] if self._one_pass_ok(batches, merged) else None
                 with torch.cuda.stream(side):
-                    try:
-                        precise = self.precise_aux_features(batches, merged, rng_snap=snap, tape=tape)
-                    finally:
-                        if gate:
-                            ops.phase_callbacks(None)
+                    precise = self.precise_aux_features(batches, merged, rng_snap=snap, tape=tape)
                     ops.stamp("precise_done")
                     self._search_ahead(precise)
                     ops.stamp("search_done")
@@ -2071,10 +2023,6 @@ class EgoPackStep(StepBase):
                 precise = self.precise_aux_features(batches, merged, rng_snap=snap)
         import contextlib
         # (the two passes draw the same dropout offsets: same keep masks when the backbone is in train mode)
-        if side is not None and switches.debug("serial_precise"):  # (measurement: the two passes one after the other)
-            torch.cuda.current_stream().wait_stream(side)
-        if side is not None and gate_ev.get("ev") is not None:
-            torch.cuda.current_stream().wait_event(gate_ev["ev"])
         tape = tape if side is not None else None
         if tape:
             # ONE backbone pass: the training graph is built from the precise pass's taped results (ops.dual_replay) -- its nodes
@@ -2092,7 +2040,7 @@ class EgoPackStep(StepBase):
         # the primary projection heads need nothing of the precise pass: issued BEFORE the join with its stream, so that they run
         # beside its tail instead of behind it (profiles/r04_c4_replay_timeline.txt: 896-990 us, 95 us in which nothing else ran)
         f_prim = {}
-        if side is not None and len(feats) == 1 and switches.enabled("primary_early"):
+        if side is not None and len(feats) == 1:
             f_prim = {t: self.tasks[t].forward_features(f) for t, f in feats.items()}
         ops.stamp("train_fwd_done")
         if side is not None:

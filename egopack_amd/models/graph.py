@@ -18,7 +18,7 @@ import logging
 import torch
 import torch.nn as nn
 
-from .. import ops, switches
+from .. import ops
 from ..data import build_csr
 from .layers import Dropout, GraphLayerNorm, Linear, PositionalEncoding, SAGEConv
 
@@ -92,9 +92,6 @@ class Graph(torch.nn.Module):
             except Exception:
                 pass
         pr = getattr(data, "pos_range", None)  # (min, max) of the positions, known on the host for collated batches
-        import os
-        if not switches.enabled("pe_table"):
-            pr = None
         h = self.positional_encoding.add_to(x, data.pos, tuple(pr) if pr is not None else None)
         # the graph LayerNorm's per-segment sums ride on the epilogue of the contraction that produces its input (forward:
         # the SAGE layer's last contraction; backward: the dX contraction of whatever consumes its output) when the shortest

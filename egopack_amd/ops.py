@@ -20,7 +20,6 @@ Every op is polymorphic in the activation element type: it follows the dtype of 
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import torch
@@ -157,7 +156,7 @@ def _stream():
 # other pays a cross-queue hand-off.  A backward pass naturally issues the forked weight gradient first, so the dX CHAIN
 # was the child that hopped, at every fork (tools/exp/fork_order.py: 12 links with a forked weight-gradient launch each,
 # 601 us per replay side-launch-first, 500 us chain-first).
-_deferred = {"items": [], "busy": False, "on": switches.enabled("fork_order")}
+_deferred = {"items": [], "busy": False, "on": True}
 
 
 def set_deferred_forks(on: bool) -> bool:
@@ -165,7 +164,7 @@ def set_deferred_forks(on: bool) -> bool:
     queued is dropped: a step ends with ``join_wgrad`` (which drains the queue), so something is left only when the step
     was abandoned by an exception -- its launches must not surface in the next step."""
     prev = _deferred["on"]
-    _deferred["on"] = bool(on) and switches.enabled("fork_order")
+    _deferred["on"] = bool(on)
     _deferred["items"] = []
     return prev
 
@@ -361,7 +360,7 @@ def to_act(x: torch.Tensor, lazy: bool = False) -> torch.Tensor:
     the result straight to a contraction (the temporal pooling's first Linear).  In the three-product mode a bf16 input IS the
     high half of its widening and has no low half, so that contraction never reads the widened f32 values: the f32 tensor is then
     only allocated, and written when anything else asks for its pointer (``_p`` / ``_c`` / ``_rm``) -- 15 us and 38 MB at the head
-    of the precise pass of BASELINE config 4 (EGK_DISABLE=x3_lazy_input: always written)."""
+    of the precise pass of BASELINE config 4 (``x3_lazy_input`` off: always written)."""
     want = _state["act"]
     if x.dtype == want:
         return x
@@ -641,13 +640,12 @@ def _gemm_with_stats(args, kw, stats):
     lib = _lib.load()
     d = _gemm_desc(*args, stats=stats, **kw)
     blocks = lib.egk_gemm_stats_blocks(C.byref(d))
-    if blocks > 0 and d.n_extra and switches.enabled("x3_stats_split"):
+    if blocks > 0 and d.n_extra:
         # a three-product contraction (six K sources for a SAGE layer's two-source launch: K = 6144 at H = 1024) of a batch
         # that fills half the chip: the statistics epilogue needs the finished tile, i.e. NO split-K -- 87 us for 2048 x 1024
         # on one workgroup per CU.  When the policy would cut the walk, the cut launch + its reduce + the LayerNorm's own
         # statistics pass are the cheaper chain (the precise pass of the EgoPack step sits on the step's critical path):
-        # config 4 3.70 -> 3.65 ms.  ON BY DEFAULT since late round 4 (EGK_DISABLE=x3_stats_split turns it off; DESIGN 10.8,
-        # profiles/r04_switches.txt): it was opt-in until the block-wise parity test of the OSCC head stated its input gradient "up
+        # config 4 3.70 -> 3.65 ms (HISTORY.md).  It was opt-in until the block-wise parity test of the OSCC head stated its input gradient "up
         # to near-ties of the max pool" -- the other summation order moves the auxiliary features by 1e-6 and with them WHICH one to
         # three near-tie pairs the draw contains (1.7e-3 .. 6.5e-3 over all rows, 1.66e-3 over the rows no tie touches).
         if lib.egk_gemm_splitk(d.M, d.N, _desc_k(d), d.compute) > 1:
@@ -796,7 +794,7 @@ def _wgrad_launch(in_place: bool, tensors, launch, in_backward: bool = True):
     stream of the current stream; ``tensors`` are the temporaries it reads (kept alive for that stream).
     ``in_backward`` False: called from ``join_wgrad`` itself (possibly after backward has returned): no end-of-backward
     callback is installed, the caller joins right away."""
-    if not (_wgrad["enabled"] and in_place and tensors and tensors[0].is_cuda) or _wq_sched["mode"] == "inline":
+    if not (_wgrad["enabled"] and in_place and tensors and tensors[0].is_cuda):
         launch()
         return
     main = torch.cuda.current_stream()
@@ -835,53 +833,25 @@ _wq = {"on": False, "items": [], "tiles": 0, "hold": [], "extra": [], "riders": 
 # step: 4 / 5 / 6 / 7 / 8 -> 1.558 / 1.60 / 1.538 / 1.60 / 1.595 ms (three alternating rounds of 200 steps; 12 H x H weight
 # gradients = two full launches of six).  Before the dX chain kept its hardware queue at the forks (defer_after_next_launch)
 # six measured WORSE than four (1.75 vs 1.68): the chain was the child that paid the queue hand-off behind every larger
-# launch.  EGK_WGRAD_COUNT is a development knob (the library takes up to 8 per launch).
-WGRAD_GROUP_COUNT = int(os.environ.get("EGK_WGRAD_COUNT", "6"))
+# launch.  The library takes up to 8 per launch.
+# Issued as soon as a group is full, on the side stream, beside whatever the dX chain does next.  Measured against issuing them on
+# the backward stream itself (1.598-1.604 ms) and against issuing them right before a backward row kernel and joining behind it
+# (1.774-1.782) in round 4: free-running groups 1.474-1.477 ms (HISTORY.md).
+WGRAD_GROUP_COUNT = 6
 WGRAD_GROUP_TILES = 64 * WGRAD_GROUP_COUNT
-F32_WGRAD_GROUP_COUNT = int(os.environ.get("EGK_F32_WGRAD_COUNT", "8"))  # (development knob, as EGK_WGRAD_COUNT)
-
-
-# WHEN parked weight gradients are issued (development knob EGK_WGRAD_SCHED, A/B of the backward schedule):
-#   free   (default) a full group goes to the side stream as soon as it is full and runs beside whatever the dX chain does next
-#   rows   what is parked is issued right before a backward ROW kernel (graph / row LayerNorm backward) and JOINED behind it:
-#          the matrix-bound weight gradients then overlap the memory-bound row kernels only, never the chain's contractions
-#          (two matrix-bound launches side by side each slow down by more than they overlap: VERDICT r3 timeline, a 38 us dX
-#          contraction took 132 us beside a 184 us grouped weight-gradient launch)
-#   inline every group is issued on the backward stream itself (no side stream at all)
-# Measured (round 4, headline step, same box, three alternating rounds): free 1.474-1.477 ms, inline 1.598-1.604, rows
-# 1.774-1.782 -- letting the weight gradients run beside WHATEVER the chain does is worth 125 us against serialising them, and
-# a join behind every row kernel stalls the chain for the length of each group.
-_wq_sched = {"mode": os.environ.get("EGK_WGRAD_SCHED", "free")}
-
-
-def _rows_fork() -> bool:
-    """'rows' schedule: called right before a backward row kernel is launched on the backward stream."""
-    if _wq_sched["mode"] != "rows" or not (_wq["on"] and _wgrad["enabled"]) or not (_wq["items"] or _wq["extra"]) or _on_excluded_stream():
-        return False
-    flush_wgrad()  # (issued behind the row kernel's own launch: defer_after_next_launch)
-    return True
-
-
-def _rows_join(forked: bool) -> None:
-    if not forked:
-        return
-    drain_deferred(all_streams=False)
-    main = torch.cuda.current_stream()
-    side = wgrad_side_stream(main)
-    if side is not None:
-        main.wait_stream(side)
+F32_WGRAD_GROUP_COUNT = 8
 
 
 def set_wgrad_grouping(on, count: Optional[int] = None):
     """Switch the parking queue (engine: at the start and the end of every step); returns the previous setting (hand it back to
-    restore).  ``count``: bf16 problems per grouped launch for this step (None: WGRAD_GROUP_COUNT; EGK_WGRAD_COUNT overrides).
+    restore).  ``count``: bf16 problems per grouped launch for this step (None: WGRAD_GROUP_COUNT).
     Whatever is still parked is dropped: a step ends with ``join_wgrad`` (which issues it), so something is left only when the step
     was abandoned by an exception -- its weight gradients must not be accumulated by the next step."""
     prev = (_wq["on"], _wq.get("count"))
     if isinstance(on, tuple):
         on, count = on
     _wq["on"] = bool(on)
-    _wq["count"] = None if (count is None or "EGK_WGRAD_COUNT" in os.environ) else int(count)
+    _wq["count"] = None if count is None else int(count)
     _wq["items"], _wq["hold"], _wq["extra"], _wq["tiles"], _wq["riders"] = [], [], [], 0, []
     return prev
 
@@ -902,7 +872,7 @@ def _wgrad_groupable(M, N, A, lda, B, ldb, K, compute=None) -> bool:
         return False
     if A.dtype == torch.bfloat16:
         ok = K % 64 == 0 and lda % 8 == 0 and ldb % 8 == 0
-    elif A.dtype == torch.float32 and compute == F32 and switches.enabled("f32_wgrad_groups"):
+    elif A.dtype == torch.float32 and compute == F32:
         ok = K % 32 == 0 and lda % 4 == 0 and ldb % 4 == 0  # exact-f32 problems: the grouped f32 kernel (egk_gemm_grouped)
     else:
         return False
@@ -984,32 +954,6 @@ def _launch_reductions(reds):
             "egk_ln_bwd_reduce_multi")
 
 
-# (experiment) a grouped weight-gradient launch holds every CU for the length of its K walk (6144 rows: 90-130 us) and a launch of
-# the backward chain that arrives meanwhile waits for its workgroups to retire (a 43 us dX contraction took 135 us).
-# EGK_WGRAD_KCHUNKS = n issues the group as n launches over consecutive K ranges, each accumulating into the gradient slots.
-WGRAD_KCHUNKS = int(os.environ.get("EGK_WGRAD_KCHUNKS", "1"))
-
-
-def _k_pieces(chunk):
-    """``chunk`` (parked (args, kw) weight-gradient problems) cut into WGRAD_KCHUNKS lists over consecutive K ranges, or None."""
-    n = WGRAD_KCHUNKS
-    if n <= 1:
-        return None
-    K = chunk[0][0][6]
-    for a, kw in chunk:
-        if not (kw.get("transA") and kw.get("transB") and kw.get("accumulate") and a[6] == K and a[2].dim() == 2 and a[4].dim() == 2
-                and a[2].shape[0] == K and a[4].shape[0] == K and kw.get("K2", 0) in (0, None)):
-            return None
-    step = (K // n + 63) // 64 * 64
-    if step < 512:
-        return None
-    out = []
-    for k0 in range(0, K, step):
-        k1 = min(K, k0 + step)
-        out.append([((a[0], a[1], a[2][k0:k1], a[3], a[4][k0:k1], a[5], k1 - k0, a[7], a[8]), kw) for a, kw in chunk])
-    return out
-
-
 def flush_wgrad(in_backward: bool = True, force: bool = False):
     """Issue what is parked.  On an excluded (task-head) stream nothing is issued -- unless ``force``: the engine's own
     calls from the backward stream (end of a step's backward, the last-weight-gradient hook) must never leave parked work
@@ -1031,11 +975,7 @@ def flush_wgrad(in_backward: bool = True, force: bool = False):
         for i in range(0, len(items), 8):
             chunk = items[i:i + 8]
             stamp("wgrad_group", seq=True)
-            pieces = _k_pieces(chunk) if len(chunk) > 1 else None
-            if pieces is not None:
-                for piece in pieces:
-                    gemm_grouped(piece, four_wave=len(piece) <= 4 and switches.enabled("wg4"))
-            elif len(chunk) == 1:
+            if len(chunk) == 1:
                 gemm(*chunk[0][0], **chunk[0][1])
             else:
                 # beside the dX chain a group runs on 4-WAVE workgroups also when it has <= 256 tiles (alone the 8-wave
@@ -1043,7 +983,7 @@ def flush_wgrad(in_backward: bool = True, force: bool = False):
                 # 2 x 208 VGPRs of every SIMD of its CU and the chain's row kernels (96-193 VGPRs) wait for it to leave --
                 # a 13 us row-LayerNorm backward took 82 us behind such a launch; 4 waves leave 304.  Step 1.511 -> 1.498 ms
                 # (six alternating runs of 300 steps, every pair)
-                gemm_grouped(chunk, four_wave=len(chunk) <= 4 and switches.enabled("wg4"))
+                gemm_grouped(chunk, four_wave=len(chunk) <= 4)
         if extra:
             _launch_reductions(extra)
         stamp("wgrad_flush_end", seq=True)
@@ -1111,7 +1051,7 @@ def _ln_reduce_on_side(slot_w, slot_b, x) -> bool:
     return (main.device.index, main.cuda_stream) not in _wgrad["exclude"]
 
 
-_wgrad_ln = {"side": True}  # development knob
+_wgrad_ln = {"side": True}  # (bench.py --ln-reduce-inline: False)
 
 
 def join_wgrad(force: bool = False):
@@ -1186,7 +1126,7 @@ def _match(g: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 # roundings of the precise activations, the forward VALUES are the precise ones.  Nodes: _Linear, _RowLN, _PEAdd, _SageMean, _GraphLN
 # (what models.Graph.forward with a TRN pooling issues); the sequences of the two passes must agree node by node (checked).
 _dual = {"tape": None, "replay": None}
-_slab_defer = {"on": switches.enabled("slab_defer")}  # the precise pass's split contractions without reduce launches
+_slab_defer = {"on": True}  # the precise pass's split contractions without reduce launches
 
 
 class dual_record:
@@ -1502,9 +1442,6 @@ def classifier_bank(x, anchor, views, compute=None):
     return outs
 
 
-_banks_ride = {"on": switches.enabled("banks_ride")}  # development knob
-
-
 class _GroupedBanks(torch.autograd.Function):
     """The classifier banks of several task heads (same feature width, own rows, own weights) as ONE grouped contraction
     forward and ONE grouped dX contraction backward -- the multi-head classifiers of the AR and LTA tasks
@@ -1550,7 +1487,7 @@ class _GroupedBanks(torch.autograd.Function):
         for w_args, w_kw, hold in parked:
             # parked WITHOUT a join of their own: the projection heads' backward, which follows in the same step, takes them
             # along in its first grouped weight-gradient launch (one launch and one end-of-backward join fewer in the chain)
-            if not _wgrad_defer(w_args, w_kw, hold, park_on_excluded=True, park_only=_banks_ride["on"]):
+            if not _wgrad_defer(w_args, w_kw, hold, park_on_excluded=True, park_only=True):
                 _wgrad_launch(True, hold, lambda a=w_args, kw=w_kw: gemm(*a, **kw))
         return (None, None, None, None, *dxs)
 
@@ -1733,16 +1670,15 @@ class _GroupedProjection(torch.autograd.Function):
         da = torch.empty_like(a)
         gemm_grouped([((rows[g], H1, dfs[g], dfs[g].stride(0), W2o[g], H1, H2, da[ptr[g]:ptr[g + 1]], H1),
                        dict(transB=True, compute=cmp)) for g in range(G)])
-        proj_park = switches.enabled("proj_park")
         dw2 = [((H2, H1, dfs[g], dfs[g].stride(0), a[ptr[g]:ptr[g + 1]], H1, rows[g], slots[g][4], H1),
                 dict(transA=True, transB=True, accumulate=True, compute=cmp, dbias=slots[g][5])) for g in range(G)]
-        proj_park = proj_park and all(_wgrad_groupable(*pa[:7]) for pa, _ in dw2)  # (the parking queue must be on and take them)
+        proj_park = all(_wgrad_groupable(*pa[:7]) for pa, _ in dw2)  # (the parking queue must be on and take them)
         if proj_park:
             for g, (pa, pk) in enumerate(dw2):
                 if not _wgrad_defer(pa, pk, (dfs[g], a), park_on_excluded=True, park_only=True):
                     raise RuntimeError("grouped_projection: a weight gradient announced as parkable was refused")
         else:
-            riders = _take_parked(8 - G) if _banks_ride["on"] else []  # (the classifier banks' weight gradients, parked by their backward)
+            riders = _take_parked(8 - G)  # (the classifier banks' weight gradients, parked by their backward)
             _wgrad_launch(True, (a, *dfs), lambda: gemm_grouped(riders + dw2))
         dh1 = torch.empty_like(h1)
         grid = lib.egk_rowln_bwd_ws_rows(max(rows))
@@ -1803,8 +1739,6 @@ def grouped_projection_infer(x, nets, out_f32: bool = False):
     x3 = x.dtype == torch.float32 and _state["compute"] == X3 and _x3["cache"] is not None and out_f32
     if not (2 <= G <= 8) or x.dim() != 2 or not x.is_cuda or not (x.dtype == torch.bfloat16 or x3) or x.shape[0] == 0:
         return None
-    if x3 and not switches.enabled("x3_grouped_aux"):
-        return None
     dims = None
     for net in nets:
         if len(net) != 5 or (net[0].p > 0 and net[0].training):
@@ -1831,8 +1765,8 @@ def grouped_projection_infer(x, nets, out_f32: bool = False):
                       for g, net in enumerate(nets)])
         lw, lb = [_f32c(net[2].weight) for net in nets], [_f32c(net[2].bias) for net in nets]
         row_ptr = (C.c_int32 * (G + 1))(*[g * M for g in range(G + 1)])
-        # the LayerNorm launch also stores the halves of its result (egk_tee_split_next; EGK_DISABLE=group_ln_tee: a split launch)
-        halves = _tee_arm(a) if switches.enabled("group_ln_tee") else None
+        # the LayerNorm launch also stores the halves of its result (egk_tee_split_next)
+        halves = _tee_arm(a)
         _ck(lib.egk_rowln_group_fwd(_stream(), _p(h1), _ptr_array(lw), _ptr_array(lb), row_ptr, G, _p(a), _p(mean), _p(rstd), H1,
                                     float(nets[0][2].eps), 1, _dt(h1)), "egk_rowln_group_fwd")
         hi, lo = halves if halves is not None else _split_rows(a, G * M, H1, H1)  # the groups' row blocks are registered as split
@@ -2156,10 +2090,8 @@ class _RowLN(torch.autograd.Function):
             # dw / db feed nothing but the optimizer: their reduction goes to the weight-gradient side stream, from a
             # workspace of its own (the shared one may be rewritten by the next launch of this stream)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            forked = _rows_fork()
             _ck(lib.egk_rowln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(mean), _p(rstd), _p(mask), _p(dx), None, None,
                                   _p(ws), rows, cols, int(ctx.relu), ctx.p, _dt(x)), "egk_rowln_bwd")
-            _rows_join(forked)
             if _wq["on"] and _wgrad["enabled"]:
                 _wgrad_defer_reduce(ws, dw, db, rows, cols, 0)
             else:
@@ -2211,7 +2143,7 @@ def _ln_bwd_stats_launch(lnctx, args, kw, dy_out):
     lnctx["bwd"] = (got[0], got[1], dy_out.data_ptr()) if got else None
 
 
-_ln_fusion = {"on": True}  # development knob: False = every graph LayerNorm runs its own statistics passes
+_ln_fusion = {"on": True}  # False = every graph LayerNorm runs its own statistics passes (tests: the reference)
 
 # Exact cross-rank statistics (data parallelism): the reference is one process, its graph-mode LayerNorm sees the whole
 # batch (models/graph.py:43); with the batch sharded over ranks the default is per-rank statistics (every replica is the
@@ -2327,10 +2259,8 @@ class _GraphLN(torch.autograd.Function):
         if pre is not None and pre[2] == dy.data_ptr():
             # the segment sums came with the contraction that produced dy: ONE pass (dx + the dw / db partial rows)
             ws_col = torch.empty(lib.egk_rowln_bwd_ws_rows(rows) * 2 * cols, dtype=torch.float32, device=x.device)
-            forked = _rows_fork()
             _ck(lib.egk_graphln_bwd_apply(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(stats), _p(dx), _p(seg_ptr), n_seg, rows,
                                           cols, ctx.eps, ctx.slope, _p(pre[0]), pre[1], _p(ws_col), _dt(x)), "egk_graphln_bwd_apply")
-            _rows_join(forked)
             if _ln_reduce_on_side(slot_w, slot_b, x):
                 if _wq["on"] and _wgrad["enabled"]:
                     _wgrad_defer_reduce(ws_col, dw, db, rows, cols, 0)
@@ -2468,7 +2398,7 @@ def _csr_gather(x, rowptr, col, wgt, gate, out, heavy=None, heavy_mode=0, band=N
     ws = workspace(lib.egk_csr_heavy_ws_bytes(nh, cols), x.device) if nh and not heavy_mode else None
     # (the split tee: only when every row is finished inside the gather launch itself)
     tee = _tee_arm(out) if (wgt is None and gate is None and (nh == 0 or heavy_mode)) else None
-    if band is not None and wgt is None and gate is None and _banded["on"]:
+    if band is not None and wgt is None and gate is None:
         # forward mean aggregation: rows whose neighbours are {i - 1, i, i + 1} need no index fetch (data.band_codes)
         _ck(lib.egk_csr_gather_banded(_stream(), _p(x), _p(rowptr), _p(col), _p(band), _p(out), rows, cols, _dt(x),
                                       _p(heavy) if nh else None, nh, _p(ws) if ws is not None else None, int(heavy_mode)),
@@ -2479,8 +2409,6 @@ def _csr_gather(x, rowptr, col, wgt, gate, out, heavy=None, heavy_mode=0, band=N
                            _p(heavy) if nh else None, nh, _p(ws) if ws is not None else None, int(heavy_mode)), "egk_csr_gather")
     _tee_done(out, tee)
 
-
-_banded = {"on": switches.enabled("banded_gather")}  # development knob
 
 
 class _CSRMean(torch.autograd.Function):
@@ -2802,8 +2730,7 @@ def segment_max_multi(xs, ptr):
     them), the pools one by one otherwise."""
     xs = list(xs)
     x0 = xs[0]
-    if (2 <= len(xs) <= 4 and x0.is_cuda and all(x.shape == x0.shape and x.dtype == x0.dtype and x.dim() == 2 for x in xs)
-            and switches.enabled("segmax_multi")):
+    if 2 <= len(xs) <= 4 and x0.is_cuda and all(x.shape == x0.shape and x.dtype == x0.dtype and x.dim() == 2 for x in xs):
         return list(_SegMaxMulti.apply(ptr, *xs))
     return [segment_max(x, ptr) for x in xs]
 
@@ -3162,7 +3089,7 @@ class _RowDotCE2Multi(torch.autograd.Function):
                                          _dt(fs[0])), "egk_rowdot_ce2_multi")
         in_slots = all((dw is None or sw is not None) for dw, sw in zip(dws, slots_w)) and all(
             (db is None or sb is not None) for db, sb in zip(dbs, slots_b))
-        if in_slots and any(d is not None for d in (*dws, *dbs)) and switches.enabled("ce2_cols_ride"):
+        if in_slots and any(d is not None for d in (*dws, *dbs)):
             # the classifiers' gradients feed nothing on the chain and land in the optimizer's slots: their launch (27 us on the
             # critical chain of BASELINE config 4 between the head and backward) rides with the next flush of the parked weight
             # gradients (``park_rider``: at once when nothing can be parked)
@@ -3501,8 +3428,8 @@ def row_sq_norm(x):
 
 # The one-product search (egk_topk_window): per bank the bf16 operand hi(P) and the largest rounding residual ratio of its rows,
 # kept while (address, shape, version) stand -- the banks are frozen (graphONE.py:48) unless GraphONE is built with freeze=False.
-_window_search = {"on": switches.enabled("window_search")}
-_window_f16 = {"on": switches.enabled("window_f16")}  # the grouped search's screen on the f16 matrix instructions
+_window_search = {"on": True}
+_window_f16 = {"on": True}  # the grouped search's screen on the f16 matrix instructions
 _window_bank_cache = {}
 _window_stats = {"cand": None}  # development / tests: an int32 [N] tensor here receives the candidates per row of the next search
 
@@ -3606,8 +3533,7 @@ def nearest_prototypes_grouped_ok(feats, banks, k, distance_func: str = "cosine"
         return False
     f0, b0 = feats[0], banks[0]
     if (f0.dtype != torch.float32 or not f0.is_cuda or any(f.shape != f0.shape for f in feats)
-            or any(b.dtype != torch.float32 or b.shape != b0.shape or not b.is_contiguous() for b in banks)
-            or not switches.enabled("grouped_search")):
+            or any(b.dtype != torch.float32 or b.shape != b0.shape or not b.is_contiguous() for b in banks)):
         return False
     base = rows_of_one_buffer(feats)
     return base is not None and _window_search_ok(f0.shape[0], b0.shape[0], f0.shape[1], k, base, b0)
@@ -3625,9 +3551,9 @@ def nearest_prototypes_grouped(feats, banks, k, bank_norms):
     K = banks[0].shape[0]
     # the screen's product from IEEE-half roundings (f16 matrix instructions: 11 significand bits, a window ~8 x narrower than
     # bf16's -- the prototype banks of a trained model put 30-90 prototypes inside the bf16 window of a row); values beyond the
-    # half range make that row's window unbounded (slow, never wrong).  EGK_DISABLE=window_f16: the bf16 screen.
+    # half range make that row's window unbounded (slow, never wrong).  ``_window_f16`` off: the bf16 screen.
     f16 = _window_f16["on"]
-    if base.is_contiguous() and H % 4 == 0 and switches.enabled("search_prep"):
+    if base.is_contiguous() and H % 4 == 0:
         # row norms, the bf16 rounding and the half rounding in ONE pass over the rows (egk_row_inv_norm_cast: the bits of the three)
         f_norm = torch.empty(G * N, dtype=torch.float32, device=base.device)
         hi = torch.empty((G * N, H), dtype=torch.bfloat16, device=base.device)
@@ -3718,14 +3644,6 @@ def stamps_enable(device="cuda", slots: int = 256):
 def stamp(name: str, seq: bool = False):
     """``seq``: the name gets a running index per step (reset by stamp("step_start")): stamps inside autograd nodes that
     run once per layer."""
-    cb = _stamps.get("callbacks")
-    if cb:
-        k = _stamps.setdefault("cb_seq", {}).get(name, 0) if seq else None
-        if seq:
-            _stamps["cb_seq"][name] = k + 1
-        fn = cb.get(f"{name}[{k}]" if seq else name)
-        if fn is not None:
-            fn()
     buf = _stamps["buf"]
     if buf is None:
         return
@@ -3742,13 +3660,6 @@ def stamp(name: str, seq: bool = False):
         names.append(name)
         idx = len(names) - 1
     _ck(_lib.load().egk_stamp(_stream(), _p(buf), idx), "egk_stamp")
-
-
-def phase_callbacks(callbacks) -> None:
-    """``{phase name: fn}`` (or None): ``fn()`` runs where the forward / backward code marks that phase with ``stamp(name)`` -- the
-    engine records stream events at phases of one pass to order another pass behind them.  Sequence counters restart here."""
-    _stamps["callbacks"] = dict(callbacks) if callbacks else None
-    _stamps["cb_seq"] = {}
 
 
 def stamps_read():

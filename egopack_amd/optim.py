@@ -15,7 +15,7 @@ from typing import Iterable, List
 
 import torch
 
-from . import _lib, switches
+from . import _lib
 from .ops import _ck, _p, _stream
 
 
@@ -247,8 +247,8 @@ class FlatAdam(torch.optim.Optimizer):
     # Once the low halves exist the Adam launch keeps them: it writes bf16(p - bf16(p)) of the slice it updates beside the bf16
     # shadow (+ 2 B per parameter on a 30 B pass), so the precise pass at the head of the NEXT step finds them fresh instead of
     # splitting the backbone's 17 M parameters in a launch of its own at the head of the step's critical chain (38 us in BASELINE
-    # config 4, profiles/r04_c4_replay_timeline.txt at 118 us).  EGK_DISABLE=adam_lo: the round-4 behaviour.
-    adam_writes_lo = switches.enabled("adam_lo")
+    # config 4, profiles/r04_c4_replay_timeline.txt at 118 us).  False: the round-4 behaviour (tests: the reference).
+    adam_writes_lo = True
 
     def _lo_is_fresh(self, off: int, n: int) -> bool:
         # (fresh ranges may have been cut by partial updates: a slot is fresh when the union of the ranges covers it)

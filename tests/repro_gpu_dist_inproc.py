@@ -1,5 +1,5 @@
 """ROUND-3 LAYOUT, kept to reproduce the round-3 driver abort (NOT collected by default: run it explicitly, after
-tests/test_gpu_blockwise.py and tests/test_gpu_configs.py in ONE pytest process -- tools/round4/repro_abort.sh).  The process group lives
+tests/test_gpu_blockwise.py and tests/test_gpu_configs.py in ONE pytest process -- HISTORY.md, round 4).  The process group lives
 in the pytest process here; the product no longer swallows a failed one-graph capture, so the exception that used to precede
 the abort is now reported.
 

@@ -500,7 +500,7 @@ def test_config4_graphone_optimizer_slice_is_the_same_update(monkeypatch):
 def test_config4_one_pass_step_tracks_the_two_pass_step(monkeypatch):
     """The one-pass EgoPack step (bf16 training graph built from the precise pass's taped results, ops.dual_record / dual_replay),
     eager and captured, against the captured two-pass step after four optimizer steps from the same parameters: the three differ by
-    bf16-level gradient noise only (tools/round5/c4_eager_vs_captured.py: the eager and the captured step of EITHER variant differ
+    bf16-level gradient noise only (HISTORY.md, round 5: the eager and the captured step of EITHER variant differ
     by as much -- Adam's normalised update turns a last-bit difference of a near-zero gradient into a step of lr)."""
     from egopack_amd import ops
     monkeypatch.delenv("EGK_DISABLE", raising=False)

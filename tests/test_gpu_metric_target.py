@@ -109,7 +109,7 @@ def test_bf16_training_tracks_f32_where_the_metrics_are_not_saturated(tmp_path):
     """The same three runs at an operating point where the target CAN fail (round-4 review: the first point's f32 metrics sit at
     0.98-1.0, where every training mode lands within 0.1): weaker class / event codes per task (signal 0.25 for AR and LTA, 0.13
     for OSCC, 0.10 for PNR) and four epochs leave the f32 run at verbs 0.85 / 0.69, nouns 0.19 / 0.14, OSCC accuracy 0.71, PNR
-    AUROC 0.85 (tools/round5/metric_sweep.py) -- half-learned tasks, on the steep part of their learning curves, where a training
+    AUROC 0.85 (HISTORY.md, round 5: a sweep of main_temporal) -- half-learned tasks, on the steep part of their learning curves, where a training
     mode that lags shows up as tenths of a point.  Same assertion: every reported figure of the bf16 runs within 0.1 of the f32
     run; the deltas are on record in gpurun_out/metric_target_unsaturated.json (profiles/r05_metric_target_unsaturated.json)."""
     if not torch.cuda.is_available():

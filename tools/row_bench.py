@@ -11,16 +11,10 @@ from egopack_amd import ops
 dev = "cuda"
 N, H = 6144, 1024
 dt = torch.bfloat16 if (len(sys.argv) < 2 or sys.argv[1] == "bf16") else torch.float32
-if len(sys.argv) > 3:  # row_bench.py bf16 <cap_partial> <cap_wide>
+if len(sys.argv) > 2:  # row_bench.py bf16 0: the generic row kernels (egk_tune 3)
     from egopack_amd import _lib
-    _lib.load().egk_tune(1, int(sys.argv[2]))
-    _lib.load().egk_tune(2, int(sys.argv[3]))
-    print("caps", sys.argv[2], sys.argv[3])
-import os
-if os.environ.get("EGK_ROWS_V2") is not None:  # EGK_ROWS_V2=0: the generic row kernels (egk_tune 3)
-    from egopack_amd import _lib
-    _lib.load().egk_tune(3, int(os.environ["EGK_ROWS_V2"]))
-    print("rows v2", os.environ["EGK_ROWS_V2"])
+    _lib.load().egk_tune(3, int(sys.argv[2]))
+    print("rows v2", sys.argv[2])
 x = torch.randn(N, H, device=dev).to(dt)
 g = torch.randn(N, H, device=dev).to(dt)
 w, b = torch.randn(H, device=dev), torch.randn(H, device=dev)
