@@ -192,6 +192,10 @@ SIGNATURES = {
     "egk_zero_fill_ranges": (C.c_int, [vp, vp, vp, vp, i32]),
     "egk_adam_step_bump": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, f32, f32, f32, f32, vp, vp, vp, i64]),
     "egk_adam_hyper": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp]),
+    "egk_grad_sumsq_slots": (C.c_int, [i64]),
+    "egk_grad_sumsq": (C.c_int, [vp, vp, i32, i64, vp, i32]),
+    "egk_grad_norm_finalize": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp]),
+    "egk_adam_step_gated": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, f32, f32, f32, f32, vp, vp, vp, i64, vp]),
 }
 
 

@@ -432,16 +432,117 @@ __device__ __forceinline__ void adam_span(float* __restrict__ p, const GT* __res
     }
 }
 
-template <typename GT>  // GT: element type of the gradient buffer (f32, or bf16 after a compressed all-reduce)
+template <typename GT, bool GATED>  // GT: element type of the gradient buffer (f32, or bf16 after a compressed all-reduce)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long long n, const float* __restrict__ hyper,
                                                    float b1, float b2, float eps, float wd, bf16_t* __restrict__ shadow,
-                                                   bf16_t* __restrict__ shadow_lo, long long* __restrict__ bump_word, long long bump) {
+                                                   bf16_t* __restrict__ shadow_lo, long long* __restrict__ bump_word, long long bump,
+                                                   const int* __restrict__ gate) {
     // (egk_adam_step_bump: a device-side counter that moves on once per step -- the Philox offset word of the step's dropout
     //  launches -- rides in this launch instead of costing one of its own)
     if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
+    // (egk_adam_step_gated: the step's gate word, written by egk_grad_norm_finalize -- 0 = the gradient norm was not finite, the
+    //  step is skipped: one wave-uniform load, nothing of p / m / v / the bf16 copies is touched; the offset word above still moved)
+    if (GATED && *gate == 0) return;
     const AdamConsts ac{hyper[0] / hyper[1], hyper[2], hyper[3], b1, b2, eps, wd};
     adam_span(p, g, m, v, n, ac, shadow, shadow_lo, blockIdx.x, gridDim.x);
+}
+
+// ---- global gradient norm (clipping inside the step) ---------------------------------------------------------------------
+// Sum of squares of n gradient elements: 16-byte loads, grid-stride, products and sums in f64 (the product of two f32 or bf16
+// values is exact in f64), ONE f64 partial per workgroup stored to partials[blockIdx.x].  The grid is a function of n alone
+// (sumsq_grid) and every partial has one writer: no atomics, the same bits on every launch over the same data.
+constexpr int SUMSQ_THREADS = 256;
+constexpr long long SUMSQ_PER_WG = 16384;  // elements per workgroup until the grid reaches its cap
+constexpr int SUMSQ_MAX_WG = 1024;
+static inline int sumsq_grid(long long n) {
+    const long long b = (n + SUMSQ_PER_WG - 1) / SUMSQ_PER_WG;
+    return (int)(b < 1 ? 1 : b > SUMSQ_MAX_WG ? SUMSQ_MAX_WG : b);
+}
+
+__device__ __forceinline__ double sumsq16(const float* __restrict__ g) {
+    const float4 v = *reinterpret_cast<const float4*>(g);
+    return ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
+}
+__device__ __forceinline__ double sumsq16(const bf16_t* __restrict__ g) {
+    const uint4 r = *reinterpret_cast<const uint4*>(g);
+    const unsigned w[4] = {r.x, r.y, r.z, r.w};
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double a = (double)__uint_as_float(w[k] << 16), b = (double)__uint_as_float(w[k] & 0xffff0000u);
+        s += a * a + b * b;
+    }
+    return s;
+}
+
+template <typename GT>
+__global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_kernel(const GT* __restrict__ g, long long n, double* __restrict__ partials) {
+    constexpr int V = 16 / (int)sizeof(GT);  // elements per 16-byte load
+    __shared__ double part[SUMSQ_THREADS / 64];
+    const long long stride = (long long)gridDim.x * SUMSQ_THREADS * V;
+    const long long nv = n / V * V;
+    double a0 = 0.0, a1 = 0.0;
+    long long i = ((long long)blockIdx.x * SUMSQ_THREADS + threadIdx.x) * V;
+    for (; i + stride < nv; i += 2 * stride) {  // two loads in flight per thread
+        const double s0 = sumsq16(g + i), s1 = sumsq16(g + i + stride);
+        a0 += s0;
+        a1 += s1;
+    }
+    if (i < nv) a0 += sumsq16(g + i);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long j = nv; j < n; ++j) {  // (a ragged end of fewer than V elements)
+            const double x = (double)ld1t(g + j);
+            a1 += x * x;
+        }
+    const double s = wave_sum(a0 + a1);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// Device-side statistics of the clipped steps since the last reset (f64 words, FlatAdam.grad_norm_stats reads them)
+enum { GN_STEPS = 0, GN_SUM, GN_MAX, GN_CLIPPED, GN_SKIPPED, GN_LAST, GN_WORDS };
+
+// One workgroup: the partials added in a fixed order (thread t: slots t, t + 256, ... ; then a fixed tree), norm = grad_scale *
+// sqrt(sum) -- the norm of the AVERAGED gradient on N ranks -- and torch.nn.utils.clip_grad_norm_'s arithmetic in f32:
+// coef = min(1, max_norm / (norm + 1e-6)); hyper[3] = grad_scale * coef, EXACTLY grad_scale when coef clamps to 1.  A norm that
+// is not finite closes the gate (the step's Adam launches leave everything untouched) and takes the step back out of t_dev.
+__global__ __launch_bounds__(SUMSQ_THREADS) void grad_norm_finalize_kernel(const double* __restrict__ partials, int n_slots,
+                                                                           const float* __restrict__ src, float max_norm,
+                                                                           float* __restrict__ hyper, long long* __restrict__ t_dev,
+                                                                           int* __restrict__ gate, double* __restrict__ stats) {
+    __shared__ double part[SUMSQ_THREADS];
+    double s = 0.0;
+    for (int k = threadIdx.x; k < n_slots; k += SUMSQ_THREADS) s += partials[k];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = SUMSQ_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+        const float gs = src[1];
+        const float norm = (float)((double)gs * sqrt(part[0]));
+        const bool finite = norm - norm == 0.f;  // (false for inf and NaN)
+        stats[GN_STEPS] += 1.0;
+        stats[GN_LAST] = (double)norm;
+        if (finite) {
+            const float coef = max_norm / (norm + 1e-6f);
+            const bool clip = coef < 1.f;
+            hyper[3] = clip ? gs * coef : gs;
+            *gate = 1;
+            stats[GN_SUM] += (double)norm;
+            if ((double)norm > stats[GN_MAX]) stats[GN_MAX] = (double)norm;
+            if (clip) stats[GN_CLIPPED] += 1.0;
+        } else {
+            hyper[3] = gs;
+            *gate = 0;
+            *t_dev -= 1;  // (egk_adam_hyper counted this step: it does not happen)
+            stats[GN_SKIPPED] += 1.0;
+        }
+    }
 }
 
 static inline unsigned ew_grid(long long n, int per_thread) {
@@ -769,6 +870,13 @@ int egk_adam_step(egk_stream_t stream, float* p, const void* g, int32_t g_dtype,
 int egk_adam_step_bump(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
                        const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
                        void* bf16_lo_shadow, int64_t* bump_word, int64_t bump) {
+    return egk_adam_step_gated(stream, p, g, g_dtype, m, v, n, hyper, beta1, beta2, eps, weight_decay, bf16_shadow, bf16_lo_shadow,
+                               bump_word, bump, nullptr);
+}
+
+int egk_adam_step_gated(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
+                        const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
+                        void* bf16_lo_shadow, int64_t* bump_word, int64_t bump, const int32_t* gate) {
     EGK_REQUIRE(p && g && m && v && hyper, "egk_adam_step: null pointer");
     EGK_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
                 "egk_adam_step: buffers must be 16-byte aligned");
@@ -785,9 +893,39 @@ int egk_adam_step_bump(egk_stream_t stream, float* p, const void* g, int32_t g_d
     const long long want = (n / 4 + 255) / 256;
     const long long cap = 32768;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
-    EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL(adam_kernel<T>, dim3(grid), dim3(256), 0, s, p, (const T*)g, m, v,
-                                               (long long)n, hyper, beta1, beta2, eps, weight_decay, (bf16_t*)bf16_shadow,
-                                               (bf16_t*)bf16_lo_shadow, (long long*)bump_word, (long long)bump));
+    if (gate)
+        EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL((adam_kernel<T, true>), dim3(grid), dim3(256), 0, s, p, (const T*)g, m, v,
+                                                   (long long)n, hyper, beta1, beta2, eps, weight_decay, (bf16_t*)bf16_shadow,
+                                                   (bf16_t*)bf16_lo_shadow, (long long*)bump_word, (long long)bump, (const int*)gate));
+    else
+        EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL((adam_kernel<T, false>), dim3(grid), dim3(256), 0, s, p, (const T*)g, m, v,
+                                                   (long long)n, hyper, beta1, beta2, eps, weight_decay, (bf16_t*)bf16_shadow,
+                                                   (bf16_t*)bf16_lo_shadow, (long long*)bump_word, (long long)bump, (const int*)nullptr));
     return check_launch("egk_adam_step");
+}
+
+int egk_grad_sumsq_slots(int64_t n) { return n > 0 ? sumsq_grid((long long)n) : 0; }
+
+int egk_grad_sumsq(egk_stream_t stream, const void* g, int32_t g_dtype, int64_t n, double* partials, int32_t n_slots) {
+    EGK_REQUIRE(g && partials, "egk_grad_sumsq: null pointer");
+    EGK_REQUIRE(((uintptr_t)g & 15) == 0, "egk_grad_sumsq: the gradient slice must be 16-byte aligned");
+    EGK_REQUIRE(((uintptr_t)partials & 7) == 0, "egk_grad_sumsq: the partial sums must be 8-byte aligned");
+    EGK_REQUIRE(n > 0, "egk_grad_sumsq: n >= 1 (got %lld)", (long long)n);
+    const int grid = sumsq_grid((long long)n);
+    EGK_REQUIRE(n_slots == grid, "egk_grad_sumsq: %lld elements write %d partial sums (egk_grad_sumsq_slots), the caller gave %d slots",
+                (long long)n, grid, (int)n_slots);
+    hipStream_t s = (hipStream_t)stream;
+    EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL(grad_sumsq_kernel<T>, dim3(grid), dim3(SUMSQ_THREADS), 0, s, (const T*)g, (long long)n, partials));
+    return check_launch("egk_grad_sumsq");
+}
+
+int egk_grad_norm_finalize(egk_stream_t stream, const double* partials, int32_t n_slots, const float* src, float max_norm,
+                           float* hyper, int64_t* t_dev, int32_t* gate, double* stats) {
+    EGK_REQUIRE(partials && src && hyper && t_dev && gate && stats, "egk_grad_norm_finalize: null pointer");
+    EGK_REQUIRE(n_slots >= 1, "egk_grad_norm_finalize: at least one partial sum (got %d)", (int)n_slots);
+    EGK_REQUIRE(max_norm > 0.f, "egk_grad_norm_finalize: max_norm > 0 (got %g)", (double)max_norm);
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, partials, (int)n_slots, src,
+                       max_norm, hyper, (long long*)t_dev, (int*)gate, stats);
+    return check_launch("egk_grad_norm_finalize");
 }
 }

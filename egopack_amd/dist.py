@@ -262,19 +262,37 @@ class GradSync:
             if not c["stepped"]:
                 stream.wait_event(c["ev"])
                 with torch.cuda.stream(stream):
-                    if "shard" in c:
+                    if getattr(opt, "clipping", False):
+                        # (gradient clipping: no Adam slice before the norm of the WHOLE reduced gradient exists -- the chunk's
+                        #  partial sums are taken here instead, finish_and_step finalizes and steps)
+                        if not c.get("normed"):
+                            opt.norm_partials(c["src"], c["b"], c["e"])
+                    elif "shard" in c:
                         self._step_shard(opt, c)
                     else:
                         opt.launch(c["src"], c["b"], c["e"])
                     ev = torch.cuda.Event()
                     ev.record(stream)
-                c["ev"], c["stepped"] = ev, True
+                if getattr(opt, "clipping", False):
+                    c["ev"], c["normed"] = ev, True
+                else:
+                    c["ev"], c["stepped"] = ev, True
 
     def finish_and_step(self, opt) -> None:
         """Adam launch per exchanged chunk, in the order the chunks were started, each behind its collective."""
         main = torch.cuda.current_stream(opt.flat_g.device) if opt.flat_g.is_cuda else None
         covered = 0
         regions = []
+        if getattr(opt, "clipping", False):
+            # partial sums over the REDUCED chunks (what Adam reads: f32, or the bf16 copy), each behind its collective; finalize behind
+            # the last one.  Every rank sums the same values in the same order: the same norm, coefficient and gate everywhere.
+            for c in self._inflight:
+                if c["ev"] is not None:
+                    main.wait_event(c["ev"])
+                    c["ev"] = None
+                if not c.get("normed"):
+                    opt.norm_partials(c["src"], c["b"], c["e"])
+            opt.norm_finalize()
         for c in self._inflight:
             if c["ev"] is not None:
                 main.wait_event(c["ev"])
@@ -318,7 +336,14 @@ class GradSync:
     # bf16 operand copies of the slices other ranks stepped.  Elementwise the same update on the same summed gradient: parameters
     # equal to all-reduce + full Adam bit for bit (tests/test_dist_gloo.py); the moments of a slice live on the rank that steps it
     # (``gather_moments`` before a checkpoint).
+    def _refuse_clipping(self, opt) -> None:
+        if getattr(opt, "clipping", False):
+            raise RuntimeError("gradient clipping (FlatAdam max_grad_norm / grad_clip_norm) does not combine with the sharded update "
+                               "(sharded_update): each rank holds 1 / world of the reduced gradient, the global norm would need a "
+                               "collective of its own in front of every Adam slice -- use the all-reduce exchange (the default)")
+
     def _start_sharded(self, opt, lo, hi, after=()) -> None:
+        self._refuse_clipping(opt)
         flat_g = opt.flat_g
         gpu = flat_g.is_cuda
         compress = self.compress == "bf16" and gpu
@@ -401,6 +426,7 @@ class GradSync:
 
     # ---- sharded update of the WHOLE buffer in one piece (one-piece backward: reduce_and_step) -------------------------------------
     def _sharded_step(self, opt) -> None:
+        self._refuse_clipping(opt)
         flat_g, n = opt.flat_g, opt.flat_g.numel()
         per, lo, hi, body = self.shard_bounds(n)
         real = dist.get_world_size(self.group) if dist.is_initialized() else 1
@@ -569,8 +595,15 @@ class GradSync:
             done.append(ev)
         opt.grad_scale = 1.0 / self.world
         opt.prepare_hyper()
+        if getattr(opt, "clipping", False):  # (the norm of the whole reduced gradient first: no Adam launch beside the later collectives)
+            for (b, e), ev in zip(bounds, done):
+                main.wait_event(ev)
+                opt.norm_partials(src, b, e)
+            opt.norm_finalize()
+            done = [None] * len(bounds)
         for (b, e), ev in zip(bounds, done):
-            main.wait_event(ev)
+            if ev is not None:
+                main.wait_event(ev)
             opt.launch(src, b, e)
         opt.step_count += 1
 

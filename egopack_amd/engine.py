@@ -682,6 +682,29 @@ class StepBase:
             cnt.clear()
         return out
 
+    # ---- global-norm gradient clipping (optim.FlatAdam max_grad_norm) ------------------------------------------------------------------
+    # The norm's partial sums are taken piece by piece as backward finishes the pieces of the flat gradient, on the stream and at the
+    # points where the unclipped step starts its early Adam slices (GraphONE's slice beside the backbone's backward, everything but the
+    # temporal pooling beside the step's last weight-gradient group); only the pooling's partial sums, the one-workgroup finalize and
+    # ONE Adam launch over the whole buffer are left behind backward: no Adam launch may start before the coefficient exists.  The
+    # eager step sums the same pieces in the same order (``_clip_pieces``), so eager and replayed steps report the same bits.
+    def _clip_on(self) -> bool:
+        return bool(getattr(self.optimizer, "clipping", False))
+
+    def grad_norm_stats(self, reset: bool = True) -> dict:
+        """Gradient-norm statistics of the steps since the last reset (optim.FlatAdam.grad_norm_stats; one synchronisation)."""
+        return self.optimizer.grad_norm_stats(reset)
+
+    def _clip_pieces(self, live, plan=None):
+        """[lo, hi) pieces of the flat gradient in the order a one-rank step sums them."""
+        opt = self.optimizer
+        total = opt.flat_p.numel()
+        plan = self._early_adam_plan(live) if plan is None else plan
+        if plan is None:
+            return [(0, total)]
+        first = [plan["graphone_region"]] if plan.get("graphone_region") else []
+        return first + _minus([(0, plan["lo"]), (plan["hi"], total)], first) + [(plan["lo"], plan["hi"])]
+
     def _objective(self, vectors, counts=None):
         order = [t for t in self.enabled if t in vectors]
         return ops.weighted_mean_sum([vectors[t] for t in order], [self.weights[t] for t in order],
@@ -712,6 +735,7 @@ class StepBase:
         return scope()
 
     def forward_backward(self, batches, merged=None):
+        self._live_last = [t for t in self.enabled if batches.get(t) is not None]
         self.optimizer.zero_grad()
         if self.input_hook is not None:
             self.input_hook()
@@ -886,6 +910,8 @@ class StepBase:
             else:
                 self.sync.reduce_and_step(opt)  # chunked: Adam of chunk i overlaps the collectives of the later chunks
         else:
+            if self._clip_on():
+                opt.norm_regions = self._clip_pieces(getattr(self, "_live_last", list(self.enabled)))
             opt.step()
 
     # ---- training loop entry: eager for the first steps, then the captured step on static-shape batches -------------
@@ -1106,6 +1132,9 @@ class StepBase:
         prev_g = ops.set_wgrad_grouping(self.wgrad_grouping, self._wgrad_count(batches, merged))
         prev_d = ops.set_deferred_forks(self.deferred_forks)
         early = self._early_adam_plan(live) if fuse_adam else None
+        clip = fuse_adam and self._clip_on()
+        if clip and early is not None:
+            early["clip"], early["normed"] = True, []  # (its hooks take partial sums of the norm where they would start Adam slices)
         # gradient slots with one writer per step (learnt from the eager steps above, FlatAdam.learn_begin) are stored, not cleared +
         # accumulated: the step's buffer clear shrinks to what is still added into (EGK_DISABLE=grad_store); also when the
         # optimizer follows a gradient exchange outside the graph
@@ -1152,7 +1181,19 @@ class StepBase:
                 # launch (egk_adam_step_bump)
                 rng_here = not (early is not None and early.get("rng_done"))
                 bump = (ops.rng_device_offset(opt.flat_p.device), ops.RNG_DEVICE_STRIDE) if rng_here else None
-                if fuse_adam:
+                if clip:
+                    # every Adam launch waits for the norm: the pieces summed beside backward are joined, the rest (the temporal
+                    # pooling, final only now) is summed here, then finalize and ONE Adam launch behind its gate
+                    if early is not None and (early["fired"] or early.get("done")):
+                        torch.cuda.current_stream().wait_stream(early["stream"])
+                    for a, b in _minus([(0, opt.flat_p.numel())], early["normed"] if early is not None else ()):
+                        opt.norm_partials(None, a, b)
+                    opt.norm_finalize()
+                    ops.stamp("norm_done")
+                    opt.launch(bump=bump)
+                    bump = None
+                    ops.stamp("adam_done")
+                elif fuse_adam:
                     if early is not None and early["fired"]:
                         torch.cuda.current_stream().wait_stream(early["stream"])
                         opt.launch(None, early["lo"], early["hi"], bump=bump if early["hi"] > early["lo"] else None)
@@ -1263,6 +1304,11 @@ class StepBase:
                 if side is not None:
                     plan["stream"].wait_stream(side)
                 with torch.cuda.stream(plan["stream"]):
+                    if plan.get("clip"):  # (clipping: no Adam before the norm exists -- this piece's partial sums instead)
+                        for a, b in _minus([(0, lo), (hi, total)], plan.get("done", ())):
+                            opt.norm_partials(None, a, b)
+                            plan["normed"].append((a, b))
+                        return
                     # the dropout offset word moves on here, beside the last weight gradient (every dropout launch of the step
                     # is long done), INSIDE the first optimizer launch: no launch of its own
                     bump = (ops.rng_device_offset(opt.flat_p.device), ops.RNG_DEVICE_STRIDE)
@@ -1271,7 +1317,7 @@ class StepBase:
                         bump = None
                     if bump is not None:  # (no slice left to step here: the word still moves on)
                         ops.advance_rng_device(opt.flat_p.device)
-            plan["rng_done"] = True  # (every dropout launch of the step has been issued: this is backward's end)
+            plan["rng_done"] = not plan.get("clip")  # (every dropout launch of the step has been issued: this is backward's end)
             ops.defer_after_next_launch(issue)
             plan["fired"] = True
         plan["hook"] = hook
@@ -1884,6 +1930,7 @@ class EgoPackStep(StepBase):
         if not (g1 > g0 and g0 % 8 == 0 and g1 % 8 == 0 and sum(n for _, n in slots) == g1 - g0 and (g1 <= plan["lo"] or g0 >= plan["hi"])):
             return plan
         plan["done"] = []
+        plan["graphone_region"] = (g0, g1)
 
         def graphone_done():
             if plan["fired"] or plan["done"]:
@@ -1897,7 +1944,11 @@ class EgoPackStep(StepBase):
                 if side is not None:
                     plan["stream"].wait_stream(side)
                 with torch.cuda.stream(plan["stream"]):
-                    opt.launch(None, g0, g1)
+                    if plan.get("clip"):
+                        opt.norm_partials(None, g0, g1)
+                        plan["normed"].append((g0, g1))
+                    else:
+                        opt.launch(None, g0, g1)
             ops.defer_after_next_launch(issue)
             plan["done"].append((g0, g1))
         plan["graphone_hook"] = graphone_done

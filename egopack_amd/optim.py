@@ -35,8 +35,12 @@ def _minus_ranges(ranges, lo, hi):
 
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, max_grad_norm=None):
+        """``max_grad_norm`` (None or 0: off): clip the global L2 norm of the gradient to it before every update --
+        torch.nn.utils.clip_grad_norm_'s arithmetic, computed on the device inside the step (see ``norm_partials``)."""
         params = [p for p in params]
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"FlatAdam: max_grad_norm must be None, 0 (off) or positive, got {max_grad_norm!r}")
         if len({id(p) for p in params}) != len(params):  # the reference passes some parameters twice
             seen, uniq = set(), []
             for p in params:
@@ -55,6 +59,9 @@ class FlatAdam(torch.optim.Optimizer):
         self._moment_views = {}     # id(param) -> (m view, v view) once materialised
         self._slot_of = {}          # id(param) -> (first element, slot length) in the flat buffers
         self._pending_state = None  # a state dict loaded before the flat buffers exist
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
+        self.norm_regions = None    # [lo, hi) pieces the eager ``step`` takes the norm's partial sums over (None: one piece)
+        self._norm_cursor = 0       # partial-sum slots written since the last ``norm_finalize``
 
     # -- construction of the flat buffers (first step, once the set of live gradients is known) -------
     def _materialise(self):
@@ -106,6 +113,8 @@ class FlatAdam(torch.optim.Optimizer):
         self._hyper_src = torch.zeros(2, dtype=torch.float32, device=dev)  # {lr, grad_scale}: uploaded when they change
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)        # optimizer steps taken (device-side counter)
         self._src_host, self._t_mirror = None, 0
+        if self.clipping:
+            self._norm_buffers()
         if self._pending_state is not None:
             self._apply_state(self._pending_state)
             self._pending_state = None
@@ -178,7 +187,7 @@ class FlatAdam(torch.optim.Optimizer):
         for i, p in enumerate(group["params"]):
             mv = self._moment_views.get(id(p))
             if mv is not None:
-                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": mv[0].detach().clone(),
+                state[i] = {"step": torch.tensor(float(self._steps_taken())), "exp_avg": mv[0].detach().clone(),
                             "exp_avg_sq": mv[1].detach().clone()}
         if self._pending_state is not None and not state:
             return self._pending_state
@@ -335,6 +344,7 @@ class FlatAdam(torch.optim.Optimizer):
         recorded into a graph -- the caller has called ``sync_hyper_source`` before the capture and calls
         ``note_captured_step`` after every replay."""
         b1, b2 = self.param_groups[0]["betas"]
+        self._norm_cursor, self._norm_covered = 0, 0  # (a step abandoned between its partial sums and its finalize leaves nothing behind)
         if not in_capture:
             self.sync_hyper_source()
         _ck(_lib.load().egk_adam_hyper(_stream(), _p(self._hyper_src), _p(self._t_dev), float(b1), float(b2), _p(self._hyper)),
@@ -423,6 +433,81 @@ class FlatAdam(torch.optim.Optimizer):
             _ck(_lib.load().egk_zero_fill_ranges(_stream(), _p(self.flat_g), bg, ln, len(part)), "egk_zero_fill_ranges")
         return True
 
+    # -- global-norm gradient clipping (max_grad_norm) -------------------------------------------------------------------------------
+    # torch.nn.utils.clip_grad_norm_ needs the norm on the host and a scaling pass over the gradient between backward and the
+    # optimizer.  Here both stay on the device: ``norm_partials`` sums the squares of a piece of the gradient buffer (f64, one partial
+    # per workgroup, one writer each -- no atomics, the same bits every time) as soon as backward has finished that piece,
+    # ``norm_finalize`` adds the partials, writes grad_scale * min(1, max_norm / (norm + 1e-6)) into the grad_scale word every Adam
+    # launch multiplies the gradient by, and keeps the statistics ``grad_norm_stats`` reads once per epoch.  A norm that is not
+    # finite closes the gate word the step's Adam launches check: the step is skipped (parameters, moments, bf16 copies and the
+    # device step counter as before it) -- where torch would write NaN into every weight.
+    NORM_SLOTS = 1 << 16  # partial sums per step (1 .. 1024 per piece)
+
+    @property
+    def clipping(self) -> bool:
+        return self.max_grad_norm > 0.0
+
+    def _norm_buffers(self) -> None:
+        """Partial sums, statistics and the gate word (built with the flat buffers; on first use when ``max_grad_norm`` was set later)."""
+        if getattr(self, "_gate", None) is None:
+            dev = self.flat_p.device
+            self._norm_partials = torch.zeros(self.NORM_SLOTS, dtype=torch.float64, device=dev)
+            self._norm_stats = torch.zeros(6, dtype=torch.float64, device=dev)
+            self._gate = torch.ones(1, dtype=torch.int32, device=dev)
+
+    def _steps_taken(self) -> int:
+        """Optimizer steps taken.  With clipping on, skipped steps make the host's count an upper bound: the device counter is
+        the truth (one synchronisation, when a checkpoint is written), and the host's count follows it."""
+        if self.clipping and self.materialised and self._t_mirror == self.step_count:
+            self.step_count = self._t_mirror = int(self._t_dev.item())
+        return self.step_count
+
+    def norm_partials(self, grads=None, lo: int = 0, hi=None) -> None:
+        """Partial sums of squares of ``grads[lo:hi]`` (default: the f32 flat gradient; dist.GradSync hands in what Adam will read)
+        into the next free slots (capturable).  Every element of the buffer must be covered exactly once before ``norm_finalize``;
+        the order of the calls fixes the order of the sum."""
+        if not self.clipping:
+            raise RuntimeError("FlatAdam.norm_partials(): built without max_grad_norm")
+        grads = self.flat_g if grads is None else grads
+        hi = self.flat_p.numel() if hi is None else hi
+        if hi <= lo:
+            return
+        lib = _lib.load()
+        self._norm_buffers()
+        k = int(lib.egk_grad_sumsq_slots(hi - lo))
+        if self._norm_cursor + k > self.NORM_SLOTS:
+            raise RuntimeError(f"FlatAdam.norm_partials(): more than {self.NORM_SLOTS} partial sums in one step")
+        _ck(lib.egk_grad_sumsq(_stream(), _p(grads[lo:hi]), 1 if grads.dtype == torch.bfloat16 else 0, hi - lo,
+                               _p(self._norm_partials[self._norm_cursor:]), k), "egk_grad_sumsq")
+        self._norm_cursor += k
+        self._norm_covered = getattr(self, "_norm_covered", 0) + (hi - lo)
+
+    def norm_finalize(self) -> None:
+        """Norm, clip coefficient (into the grad_scale word of the step constants), gate and statistics from the partial sums taken
+        since the last call (capturable; behind ``prepare_hyper`` and every ``norm_partials`` of the step, in front of its Adam launches)."""
+        covered, self._norm_covered = getattr(self, "_norm_covered", 0), 0
+        count, self._norm_cursor = self._norm_cursor, 0
+        if covered != self.flat_p.numel():
+            raise RuntimeError(f"FlatAdam.norm_finalize(): the partial sums cover {covered} of {self.flat_p.numel()} gradient elements")
+        _ck(_lib.load().egk_grad_norm_finalize(_stream(), _p(self._norm_partials), count, _p(self._hyper_src), self.max_grad_norm,
+                                               _p(self._hyper), _p(self._t_dev), _p(self._gate), _p(self._norm_stats)),
+            "egk_grad_norm_finalize")
+
+    def grad_norm_stats(self, reset: bool = True) -> dict:
+        """{"steps", "mean_norm", "max_norm", "clipped", "skipped", "last_norm"} over the steps since the last reset (one device
+        synchronisation).  The norm is that of the gradient Adam steps on (averaged over the ranks); mean and largest are taken
+        over the steps whose norm was finite, ``skipped`` counts the others."""
+        if not self.clipping:
+            raise RuntimeError("FlatAdam.grad_norm_stats(): built without max_grad_norm")
+        live = self.materialised and getattr(self, "_gate", None) is not None
+        vals = self._norm_stats.tolist() if live else [0.0] * 6
+        steps, skipped = int(vals[0]), int(vals[4])
+        out = {"steps": steps, "mean_norm": vals[1] / max(steps - skipped, 1), "max_norm": vals[2], "clipped": int(vals[3]),
+               "skipped": skipped, "last_norm": vals[5]}
+        if reset and live:
+            self._norm_stats.zero_()
+        return out
+
     def launch(self, grads=None, lo: int = 0, hi=None, bump=None):
         """The kernel launch alone (capturable).  ``grads``: the buffer to read gradients from (default the f32
         flat buffer; dist.GradSync hands in its bf16 copy after a compressed all-reduce).  ``[lo, hi)``: element range
@@ -441,6 +526,15 @@ class FlatAdam(torch.optim.Optimizer):
             self._lo_fresh = _minus_ranges(self._lo_fresh, lo, hi) + [(lo, hi)]
         elif self._lo_fresh:
             self._lo_fresh = []  # (the parameters move: every low half is stale)
+        if self.clipping:  # (behind ``norm_finalize``: its coefficient is in the step constants, its gate decides whether the step happens)
+            self._norm_buffers()
+            _ck(_lib.load().egk_adam_step_gated(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
+                                                _p(self.flat_m[sl]), _p(self.flat_v[sl]), hi - lo, _p(self._hyper), b1, b2,
+                                                g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
+                                                _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0,
+                                                _p(self._gate)),
+                "egk_adam_step_gated")
+            return
         if bump is not None or lo16 is not None:
             _ck(_lib.load().egk_adam_step_bump(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
                                                _p(self.flat_m[sl]), _p(self.flat_v[sl]), hi - lo, _p(self._hyper), b1, b2,
@@ -458,5 +552,9 @@ class FlatAdam(torch.optim.Optimizer):
         if not self.materialised:
             self._materialise()
         self.prepare_hyper()
+        if self.clipping:
+            for lo, hi in (self.norm_regions or [(0, self.flat_p.numel())]):
+                self.norm_partials(grads, lo, hi)
+            self.norm_finalize()
         self.launch(grads)
         self.step_count += 1

@@ -150,7 +150,17 @@ def build_optimizer(cfg, params):
     target = ocfg.pop("_target_")
     if target != "torch.optim.Adam":
         raise ValueError(f"optimizer {target}: only torch.optim.Adam is on the hot path")
-    return FlatAdam(params, **ocfg)
+    # (``grad_clip_norm`` sits beside ``optimizer:``, not inside it: that block is handed to Hydra's instantiate by the reference)
+    return FlatAdam(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0))
+
+
+def log_grad_norms(logger, epoch: int, step) -> None:
+    """With gradient clipping on: the epoch's gradient-norm figures, next to the task losses (nothing otherwise)."""
+    if not getattr(step.optimizer, "clipping", False):
+        return
+    st = step.grad_norm_stats()
+    logger.info("epoch %d: gradient norm mean %.9g, largest %.9g, clipped %d of %d steps (max norm %g), skipped %d (norm not finite)",
+                epoch, st["mean_norm"], st["max_norm"], st["clipped"], st["steps"], step.optimizer.max_grad_norm, st["skipped"])
 
 
 def build_scheduler(cfg, optimizer):

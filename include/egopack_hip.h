@@ -669,6 +669,25 @@ int egk_adam_step_bump(egk_stream_t s, float* p, const void* g, int32_t g_dtype,
  * torch.optim.Adam's bias corrections are).  One thread; a node of the captured step, so that a graph replay needs no
  * host -> device copy in front of it and the step count advances with the replays.  src: device float[2]. */
 int egk_adam_hyper(egk_stream_t s, const float* src, int64_t* t_dev, double beta1, double beta2, float* hyper);
+/* ---- global-norm gradient clipping inside the step  (torch.nn.utils.clip_grad_norm_, L2) ----
+ * Sum of squares of n gradient elements (g_dtype as egk_adam_step: the norm is taken over what Adam reads): products and sums in
+ * f64, partials[b] = the sum of workgroup b for b < egk_grad_sumsq_slots(n) -- a function of n alone, 1 .. 1024, 0 for n <= 0;
+ * n_slots must be that number.  One writer per partial, no atomics: the same bits on every launch over the same data.
+ * g: 16-byte aligned (the slots of the flat layout are multiples of 8 elements). */
+int egk_grad_sumsq_slots(int64_t n);
+int egk_grad_sumsq(egk_stream_t s, const void* g, int32_t g_dtype, int64_t n, double* partials, int32_t n_slots);
+/* One workgroup: sum = partials[0 .. n_slots) added in a fixed order (f64); norm = src[1] * sqrt(sum) rounded to f32 (src: the
+ * {lr, grad_scale} source of egk_adam_hyper -- on N ranks the norm of the AVERAGED gradient); coef = min(1, max_norm / (norm + 1e-6))
+ * in f32; hyper[3] = grad_scale * coef, exactly grad_scale when coef clamps to 1; *gate = 1.  A norm that is not finite is a SKIPPED
+ * step: *gate = 0, *t_dev -= 1 (egk_adam_hyper had counted it), hyper[3] = grad_scale.  stats: device double[6] since the caller
+ * last cleared them = {steps, sum of the finite norms, largest finite norm, clipped steps, skipped steps, last norm}. */
+int egk_grad_norm_finalize(egk_stream_t s, const double* partials, int32_t n_slots, const float* src, float max_norm, float* hyper,
+                           int64_t* t_dev, int32_t* gate, double* stats);
+/* egk_adam_step_bump behind a gate word (device int32, written by egk_grad_norm_finalize; NULL: no gate): when *gate == 0 the
+ * launch leaves p, m, v and both bf16 copies untouched -- *bump_word still moves on. */
+int egk_adam_step_gated(egk_stream_t s, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
+                        const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
+                        void* bf16_lo_shadow, int64_t* bump_word, int64_t bump, const int32_t* gate);
 
 /* ---- the step objective in one launch each way  main_temporal.py:99-128 (torch.stack([w * l.mean() ...]).sum()) ----
  * out[0] = sum_k coefs[k] * sum(xs[k][0..ns[k])), terms added in k order (count <= 8; xs / ns / coefs are HOST arrays);

@@ -39,6 +39,8 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
     order = ("ar", "lta", "oscc", "pnr")
     it = 0
     step.loss_sums()  # (clears the per-task loss sums: they accumulate inside the step, on the device, until the epoch ends)
+    if step.optimizer.clipping:
+        step.grad_norm_stats()  # (and the gradient-norm statistics of grad_clip_norm)
     hosts = (dict(zip(order, batch)) for batch in multiloader([loaders[t] for t in order], [weights[t] for t in order]))
     # batch i + 1 is built and copied to the device (staging thread, copy stream) while step i runs
     mark = None  # (iteration, wall clock, sequences so far) once the eager steps and the capture are behind: steady-state rate
@@ -58,6 +60,7 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
                     it - mark[0], mark[0], torch.cuda.memory_allocated() / 2 ** 20, torch.cuda.memory_reserved() / 2 ** 20)
     logger.info("epoch %d: %d iterations, train loss %s", epoch, it,
                 {t: round(s_ / max(n_, 1), 4) for t, (s_, n_) in step.loss_sums().items() if n_})
+    T.log_grad_norms(logger, epoch, step)
     lc = getattr(step, "loop_counts", None)
     if lc is not None:  # how many steps replayed the captured graph and how many ran eagerly (shape changes, warm-up)
         logger.info("epoch %d: %d steps replayed the captured step, %d ran eagerly", epoch, lc["replayed"], lc["eager"])
