@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "../../include/egopack_hip.h"
 
 namespace egk {
@@ -18,6 +20,21 @@ void set_error(const char* fmt, ...);
             return EGK_EINVAL;               \
         }                                    \
     } while (0)
+
+// ---- alignment of the row kernels' operands ----------------------------------------------------------------------------------
+// The one-wave-per-row kernels access rows whose width is a multiple of 4 columns FOUR ELEMENTS AT A TIME (16 bytes of f32, 8 bytes
+// of bf16, 4 mask / arg bytes) and decide that from the width alone, never from the pointers.  Rows are ``cols`` elements apart, so
+// an aligned base pointer makes every row aligned; a launcher refuses anything else on the host, before it launches.  (The flat
+// layout of the optimizer, the row ranges of merged activation buffers and torch's allocations are all aligned by construction.)
+inline bool aligned_to(unsigned bytes, std::initializer_list<const void*> ps) {  // (null pointers: optional arguments)
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) return false;
+    return true;
+}
+inline unsigned vec_bytes(int dtype) { return dtype == EGK_BF16 ? 8u : 16u; }  // four elements of an activation matrix
+#define EGK_REQUIRE_VEC_ALIGNED(what, cond)                                                                                      \
+    EGK_REQUIRE(cond, "%s: unaligned pointer -- rows of a multiple of 4 columns are accessed 4 elements at a time: f32 matrices and " \
+                      "vectors must be 16-byte aligned, bf16 matrices 8-byte, masks / arg bytes 4-byte", what)
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -577,7 +577,7 @@ __global__ __launch_bounds__(256) void csr_heavy_partial_kernel(const T* __restr
                     a.x += w[u] * v[u].x; a.y += w[u] * v[u].y; a.z += w[u] * v[u].z; a.w += w[u] * v[u].w;
                 }
         }
-        if (c0 + 4 <= cols) *reinterpret_cast<float4*>(wrow + c0) = a;
+        if (vec && c0 + 4 <= cols) *reinterpret_cast<float4*>(wrow + c0) = a;  // (cols % 4 != 0: partial rows are not 16-byte aligned)
         else {
             const float t[4] = {a.x, a.y, a.z, a.w};
             for (int q = 0; q < 4 && c0 + q < cols; ++q) wrow[c0 + q] = t[q];
@@ -1475,6 +1475,13 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const S* __restrict__ 
     }
 }
 
+// f32 -> bf16, round to nearest even, computed on the bits of the f32 value (NaN stays a quiet NaN, overflow rounds to inf)
+__device__ __forceinline__ bf16_t bf16_rne_bits(float f) {
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40u);
+    return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
 // out[i, :] = table[lo[i], :] where lo[i] == hi[i] (a copy), else (float)((1 - w[i]) * table[lo[i], :] + w[i] * table[hi[i], :])
 // evaluated in double with separately rounded products and sum -- numpy's
 //     (1 - frac)[:, None] * low + frac[:, None] * high  ->  torch.from_numpy(...).float()
@@ -1497,7 +1504,12 @@ __global__ __launch_bounds__(256) void gather_lerp_rows_kernel(const S* __restri
             const double wb = w[row], wa = 1.0 - wb;
             for (int c = lane; c < cols; c += 64) {
                 const double x = va ? (double)ld1t(ta + c) : 0.0, y = vb ? (double)ld1t(tb + c) : 0.0;
-                st1t(o + c, (float)__dadd_rn(__dmul_rn(wa, x), __dmul_rn(wb, y)));
+                const float r = (float)__dadd_rn(__dmul_rn(wa, x), __dmul_rn(wb, y));
+                // A bf16 output is the bf16 rounding of THIS f32 value (numpy's double result, ``.float()``, then the cast): rounded
+                // on the bits of r, because a plain (__bf16)(float)double is compiled into ONE f64 -> bf16 rounding, which differs
+                // wherever r is a bf16 tie (about one element in 2^16; tests/test_gpu_bounds.py gather_rows compares exactly)
+                if constexpr (sizeof(D) == 2) o[c] = bf16_rne_bits(r);
+                else o[c] = r;
             }
         }
     }
@@ -1605,6 +1617,11 @@ int egk_gather_rows(egk_stream_t stream, const void* table, int32_t table_dtype,
                     const int64_t* idx, void* out, int32_t out_dtype, int64_t n, int32_t cols) {
     EGK_REQUIRE(table && idx && out, "egk_gather_rows: null pointer");
     EGK_REQUIRE(cols >= 1 && ld >= cols, "egk_gather_rows: bad row width / leading dimension");
+    {   // the kernel copies 16 bytes of a table row per lane when the row width and the row stride are whole 16-byte groups
+        const int V = table_dtype == EGK_BF16 ? 8 : 4;
+        EGK_REQUIRE(cols % V || ld % V || aligned_to(16, {table, out}),
+                    "egk_gather_rows: unaligned pointer -- rows of whole 16-byte groups are copied 16 bytes at a time: table and out must be 16-byte aligned");
+    }
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const long long blocks = (n + WPB - 1) / WPB;
@@ -1648,6 +1665,7 @@ int egk_pe_add(egk_stream_t stream, const void* x, const int64_t* pos, const flo
                int32_t cols, int32_t dtype) {
     EGK_REQUIRE(x && pos && freq && y, "egk_pe_add: null pointer");
     EGK_REQUIRE((cols & 1) == 0, "egk_pe_add: odd channel count");
+    EGK_REQUIRE_VEC_ALIGNED("egk_pe_add", (cols & 3) || aligned_to(vec_bytes(dtype), {x, y}));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_PE_ADD, s, 0, (dtype == EGK_BF16 ? 4.0 : 8.0) * rows * cols);
@@ -1672,6 +1690,7 @@ int egk_pe_add_table(egk_stream_t stream, const void* x, const int64_t* pos, con
                      int32_t n_pos, void* y, int32_t rows, int32_t cols, int32_t dtype) {
     EGK_REQUIRE(x && pos && freq && table && y && n_pos >= 1, "egk_pe_add_table: null pointer");
     EGK_REQUIRE((cols & 1) == 0, "egk_pe_add_table: odd channel count");
+    EGK_REQUIRE_VEC_ALIGNED("egk_pe_add_table", (cols & 3) || (aligned_to(vec_bytes(dtype), {x, y}) && aligned_to(16, {table})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_PE_ADD, s, 0, (dtype == EGK_BF16 ? 4.0 : 8.0) * rows * cols);
@@ -1701,6 +1720,7 @@ static int csr_gather_impl(egk_stream_t stream, const void* x, const int32_t* ro
     EGK_REQUIRE(x && rowptr && out, "egk_csr_gather: null pointer");
     EGK_REQUIRE(!band || !wgt, "egk_csr_gather_banded: the neighbour codes describe the unweighted (mean) orientation only");
     EGK_REQUIRE(n_heavy == 0 || (heavy_rows && (ws || heavy_mode == 1)), "egk_csr_gather: heavy rows need their list and a workspace");
+    EGK_REQUIRE_VEC_ALIGNED("egk_csr_gather", (cols & 3) || (aligned_to(vec_bytes(dtype), {x, out, relu_gate}) && aligned_to(16, {ws})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_CSR_GATHER, s, 0, (dtype == EGK_BF16 ? 0.5 : 1.0) * (relu_gate ? 12.0 : 8.0) * rows * cols);
@@ -1796,6 +1816,7 @@ int egk_gather_max_fwd(egk_stream_t stream, const void* f, const float* bank, co
                        int32_t rows, int32_t cols, int32_t k, int32_t dtype) {
     EGK_REQUIRE(f && bank && nn && m && arg, "egk_gather_max_fwd: null pointer");
     EGK_REQUIRE(k >= 0 && k < 255, "egk_gather_max_fwd: k out of range");
+    EGK_REQUIRE_VEC_ALIGNED("egk_gather_max_fwd", (cols & 3) || (aligned_to(vec_bytes(dtype), {f, m}) && aligned_to(16, {bank}) && aligned_to(4, {arg})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_GATHER_MAX_FWD, s, 0, (4.0 * (k + 2) + 1.0) * rows * cols);
@@ -1815,6 +1836,7 @@ int egk_gather_max_fwd(egk_stream_t stream, const void* f, const float* bank, co
 int egk_gather_max_bwd(egk_stream_t stream, const void* dm, const uint8_t* arg, void* df, int32_t rows, int32_t cols,
                        int32_t k, int32_t accumulate, int32_t dtype) {
     EGK_REQUIRE(dm && arg && df, "egk_gather_max_bwd: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_gather_max_bwd", aligned_to(vec_bytes(dtype), {dm, df}) && aligned_to(4, {arg}));  // (a flat walk: whatever the width)
     const long long n = (long long)rows * cols;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1902,6 +1924,7 @@ int egk_segment_max_multi_bwd(egk_stream_t stream, const void* const* douts, con
 
 int egk_row_inv_norm(egk_stream_t stream, const void* x, float* inv_norm, int32_t rows, int32_t cols, int32_t dtype) {
     EGK_REQUIRE(x && inv_norm, "egk_row_inv_norm: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_row_inv_norm", (cols & 3) || aligned_to(vec_bytes(dtype), {x}));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_ROW_INV_NORM, s, 0, 4.0 * rows * cols);
@@ -1924,6 +1947,7 @@ int egk_row_inv_norm_cast(egk_stream_t stream, const float* x, float* inv_norm, 
 
 int egk_row_sq_norm(egk_stream_t stream, const void* x, float* sq_norm, int32_t rows, int32_t cols, int32_t dtype) {
     EGK_REQUIRE(x && sq_norm, "egk_row_sq_norm: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_row_sq_norm", (cols & 3) || aligned_to(vec_bytes(dtype), {x}));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_ROW_INV_NORM, s, 0, 4.0 * rows * cols);
@@ -2057,6 +2081,7 @@ int egk_segment_sum_rows_f64(egk_stream_t stream, const void* x, const int32_t* 
                              const int64_t* seg_label, double* bank, int64_t* count, int32_t n_seg, int32_t cols,
                              int64_t n_labels, int32_t dtype) {
     EGK_REQUIRE(x && order && seg_ptr && seg_label && bank, "egk_segment_sum_rows_f64: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_segment_sum_rows_f64", (cols & 3) || aligned_to(vec_bytes(dtype), {x}));
     if (n_seg == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_SCATTER_ADD_F64, s, 0, 4.0 * n_seg * cols + 16.0 * n_seg * cols);
@@ -2070,6 +2095,7 @@ int egk_gather_max_bank_grad(egk_stream_t stream, const void* dm, const uint8_t*
                              const int32_t* t_edge, float* dbank, int32_t K, int32_t cols, int32_t k, int32_t dtype) {
     EGK_REQUIRE(dm && arg && t_rowptr && t_edge && dbank, "egk_gather_max_bank_grad: null pointer");
     EGK_REQUIRE(k >= 1 && k < 255, "egk_gather_max_bank_grad: k out of range");
+    EGK_REQUIRE_VEC_ALIGNED("egk_gather_max_bank_grad", (cols & 3) || aligned_to(vec_bytes(dtype), {dm}));
     if (K == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(KID_GATHER_MAX_BWD, s, 0, 8.0 * K * cols);

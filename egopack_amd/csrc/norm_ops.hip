@@ -1217,6 +1217,7 @@ int egk_colsum_ws_len(int32_t M, int32_t N) { return colsum_chunks(M, N) * N; }
 int egk_colsum(egk_stream_t stream, const void* x, int64_t ldx, int32_t M, int32_t N, float* out, int32_t accumulate,
                float* ws, int32_t dtype) {
     EGK_REQUIRE(x && out && ws, "egk_colsum: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_colsum", (N & 3) || aligned_to(16, {ws}));  // (x has its own predicate below; the partial rows are stored 16 bytes at a time)
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int chunks = colsum_chunks(M, N);
@@ -1236,6 +1237,7 @@ int egk_rowln_fwd(egk_stream_t stream, const void* x, const float* w, const floa
     EGK_REQUIRE(x && w && b && y && mean && rstd, "egk_rowln_fwd: null pointer");
     EGK_REQUIRE(p == 0.f || mask, "egk_rowln_fwd: dropout needs a mask buffer");
     EGK_REQUIRE(p >= 0.f && p < 1.f, "egk_rowln_fwd: p out of range");
+    EGK_REQUIRE_VEC_ALIGNED("egk_rowln_fwd", (cols & 3) || (aligned_to(vec_bytes(dtype), {x, y}) && aligned_to(16, {w, b}) && aligned_to(4, {mask})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
@@ -1259,12 +1261,13 @@ int egk_rowln_fwd(egk_stream_t stream, const void* x, const float* w, const floa
 int egk_rowln_bwd_ws_rows(int32_t rows) { return row_grid(rows); }
 
 static int fill_ln_groups(const char* what, RowLNGroups& G, const float* const* w, const float* const* b, const int32_t* row_ptr,
-                          int32_t n_groups, int& max_rows) {
+                          int32_t n_groups, int& max_rows, int cols) {
     EGK_REQUIRE(w && b && row_ptr && n_groups >= 1 && n_groups <= LN_MAX_GROUPS, "%s: 1 .. %d row ranges", what, LN_MAX_GROUPS);
     max_rows = 0;
     for (int g = 0; g < LN_MAX_GROUPS; ++g) {
         const int k = g < n_groups ? g : n_groups - 1;
         EGK_REQUIRE(w[k] && b[k], "%s: null parameter pointer", what);
+        EGK_REQUIRE_VEC_ALIGNED(what, (cols & 3) || aligned_to(16, {w[k], b[k]}));
         G.w[g] = w[k]; G.b[g] = b[k];
     }
     for (int g = 0; g <= LN_MAX_GROUPS; ++g) G.row0[g] = row_ptr[g <= n_groups ? g : n_groups];
@@ -1279,9 +1282,10 @@ int egk_rowln_group_fwd(egk_stream_t stream, const void* x, const float* const* 
                         int32_t n_groups, void* y, float* mean, float* rstd, int32_t cols, float eps, int32_t relu,
                         int32_t dtype) {
     EGK_REQUIRE(x && y && mean && rstd, "egk_rowln_group_fwd: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_rowln_group_fwd", (cols & 3) || aligned_to(vec_bytes(dtype), {x, y}));
     RowLNGroups G;
     int max_rows;
-    const int rc = fill_ln_groups("egk_rowln_group_fwd", G, w, b, row_ptr, n_groups, max_rows);
+    const int rc = fill_ln_groups("egk_rowln_group_fwd", G, w, b, row_ptr, n_groups, max_rows, cols);
     if (rc) return rc;
     if (max_rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1301,9 +1305,10 @@ int egk_rowln_group_bwd(egk_stream_t stream, const void* dy, const void* x, cons
                         const int32_t* row_ptr, int32_t n_groups, const float* mean, const float* rstd, void* dx, float* ws,
                         int32_t cols, int32_t relu, int32_t dtype) {
     EGK_REQUIRE(dy && x && mean && rstd && dx && ws, "egk_rowln_group_bwd: null pointer");
+    EGK_REQUIRE_VEC_ALIGNED("egk_rowln_group_bwd", (cols & 3) || aligned_to(vec_bytes(dtype), {dy, x, dx}));
     RowLNGroups G;
     int max_rows;
-    const int rc = fill_ln_groups("egk_rowln_group_bwd", G, w, b, row_ptr, n_groups, max_rows);
+    const int rc = fill_ln_groups("egk_rowln_group_bwd", G, w, b, row_ptr, n_groups, max_rows, cols);
     if (rc) return rc;
     if (max_rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1320,6 +1325,7 @@ int egk_rowln_bwd(egk_stream_t stream, const void* dy, const void* x, const floa
                   int32_t cols, int32_t relu, float p, int32_t dtype) {
     EGK_REQUIRE(dy && x && w && b && mean && rstd && dx && ws, "egk_rowln_bwd: null pointer");  // (dw = db = NULL: see egk_ln_bwd_reduce)
     EGK_REQUIRE(p == 0.f || mask, "egk_rowln_bwd: dropout needs the mask");
+    EGK_REQUIRE_VEC_ALIGNED("egk_rowln_bwd", (cols & 3) || (aligned_to(vec_bytes(dtype), {dy, x, dx}) && aligned_to(16, {w, b}) && aligned_to(4, {mask})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int grid = row_grid(rows);
@@ -1392,6 +1398,7 @@ int egk_graphln_fwd(egk_stream_t stream, const void* x, const float* w, const fl
                     int32_t dtype) {
     EGK_REQUIRE(x && w && b && y && stats && seg_ptr && ws, "egk_graphln_fwd: null pointer");
     EGK_REQUIRE(n_seg >= 1 && n_seg <= MAXSEG, "egk_graphln_fwd: n_seg must be in [1,%d]", MAXSEG);
+    EGK_REQUIRE_VEC_ALIGNED("egk_graphln_fwd", (cols & 3) || (aligned_to(vec_bytes(dtype), {x, y}) && aligned_to(16, {w, b})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int grid = row_grid(rows);
@@ -1424,6 +1431,7 @@ int egk_graphln_fwd_apply(egk_stream_t stream, const void* x, const float* w, co
                           const void* partials, int32_t n_partials, int32_t dtype) {
     EGK_REQUIRE(x && w && b && y && stats && seg_ptr && partials, "egk_graphln_fwd_apply: null pointer");
     EGK_REQUIRE(n_seg >= 1 && n_seg <= MAXSEG && n_partials >= 1, "egk_graphln_fwd_apply: bad segment / partial count");
+    EGK_REQUIRE_VEC_ALIGNED("egk_graphln_fwd_apply", (cols & 3) || (aligned_to(vec_bytes(dtype), {x, y}) && aligned_to(16, {w, b})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
@@ -1444,6 +1452,7 @@ int egk_graphln_bwd_apply(egk_stream_t stream, const void* dy, const void* x, co
                           const void* partials, int32_t n_partials, float* ws_col, int32_t dtype) {
     EGK_REQUIRE(dy && x && w && b && stats && dx && seg_ptr && partials && ws_col, "egk_graphln_bwd_apply: null pointer");
     EGK_REQUIRE(n_seg >= 1 && n_seg <= MAXSEG && n_partials >= 1, "egk_graphln_bwd_apply: bad segment / partial count");
+    EGK_REQUIRE_VEC_ALIGNED("egk_graphln_bwd_apply", (cols & 3) || (aligned_to(vec_bytes(dtype), {dy, x, dx}) && aligned_to(16, {w, b})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
@@ -1465,6 +1474,7 @@ int egk_graphln_stats(egk_stream_t stream, const void* x, const int32_t* seg_ptr
                       void* partials, int32_t dtype) {
     EGK_REQUIRE(x && seg_ptr && partials, "egk_graphln_stats: null pointer");
     EGK_REQUIRE(n_seg >= 1 && n_seg <= MAXSEG, "egk_graphln_stats: n_seg must be in [1,%d]", MAXSEG);
+    EGK_REQUIRE_VEC_ALIGNED("egk_graphln_stats", (cols & 3) || aligned_to(vec_bytes(dtype), {x}));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
@@ -1478,6 +1488,7 @@ int egk_graphln_bwd_stats(egk_stream_t stream, const void* dy, const void* x, co
                           const int32_t* seg_ptr, int32_t n_seg, int32_t rows, int32_t cols, float slope, void* ws, int32_t dtype) {
     EGK_REQUIRE(dy && x && w && b && stats && seg_ptr && ws, "egk_graphln_bwd_stats: null pointer");
     EGK_REQUIRE(n_seg >= 1 && n_seg <= MAXSEG, "egk_graphln_bwd_stats: n_seg must be in [1,%d]", MAXSEG);
+    EGK_REQUIRE_VEC_ALIGNED("egk_graphln_bwd_stats", (cols & 3) || (aligned_to(vec_bytes(dtype), {dy, x}) && aligned_to(16, {w, b})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int grid = row_grid(rows);
@@ -1496,6 +1507,7 @@ int egk_graphln_bwd_finish(egk_stream_t stream, const void* dy, const void* x, c
                            float eps, float slope, const void* partials, int32_t n_partials, const void* ws, int32_t dtype) {
     EGK_REQUIRE(dy && x && w && b && stats && dx && seg_ptr && partials && ws, "egk_graphln_bwd_finish: null pointer");
     EGK_REQUIRE(n_seg >= 1 && n_seg <= MAXSEG && n_partials >= 1, "egk_graphln_bwd_finish: bad segment / partial count");
+    EGK_REQUIRE_VEC_ALIGNED("egk_graphln_bwd_finish", (cols & 3) || (aligned_to(vec_bytes(dtype), {dy, x, dx}) && aligned_to(16, {w, b})));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int grid = row_grid(rows);
@@ -1534,6 +1546,7 @@ int egk_rowdot_bce(egk_stream_t stream, const void* f, const void* w, const floa
                    float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, int32_t dtype) {
     EGK_REQUIRE(f && w && y && logits && loss, "egk_rowdot_bce: null pointer");
     EGK_REQUIRE(!df || ws, "egk_rowdot_bce: gradients need the partial-row workspace");
+    EGK_REQUIRE_VEC_ALIGNED("egk_rowdot_bce", (cols & 3) || aligned_to(vec_bytes(dtype), {f, w, df}));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
@@ -1566,6 +1579,7 @@ int egk_rowdot_ce2_multi(egk_stream_t stream, int32_t n_src, const void* const* 
         S.dw[k] = (in && dw) ? dw[k] : nullptr;
         S.db[k] = (in && db) ? db[k] : nullptr;
         EGK_REQUIRE(!in || (S.f[k] && S.w[k]), "egk_rowdot_ce2_multi: null source");
+        EGK_REQUIRE_VEC_ALIGNED("egk_rowdot_ce2_multi", (cols & 3) || aligned_to(vec_bytes(dtype), {S.f[k], S.w[k], S.df[k]}));
         want = want || S.df[k] || S.dw[k] || S.db[k];
         want_w = want_w || S.dw[k] || S.db[k];
     }

@@ -9,6 +9,16 @@
  *   - return value: 0 = ok, negative = EGK_E* argument error, positive = hipError_t;
  *     egk_last_error() returns a thread-local message.  No exception crosses the ABI.
  *   - all matrices are row-major; "ld*" = leading dimension in ELEMENTS.
+ *   - a launch touches only what its arguments name: the [rows, cols] window of every matrix (never the pad columns of a wider
+ *     leading dimension), the n elements of every vector, and of a workspace exactly what its query function reports
+ *     (tests/test_gpu_bounds.py holds every entry point to this with guard bands around every argument).
+ *   - alignment (CHECKED on the host, EGK_EINVAL before anything is launched): the row kernels without a leading-dimension
+ *     argument -- egk_rowln_*, egk_graphln_*, egk_rowdot_*, egk_pe_add*, egk_csr_gather*, egk_gather_max_*, egk_row_inv_norm,
+ *     egk_row_sq_norm, egk_segment_sum_rows_f64 -- access rows of a multiple of 4 columns four elements at a time: their
+ *     matrices must then be aligned to four elements (16 bytes f32, 8 bytes bf16), their f32 parameter vectors / tables / banks
+ *     to 16 bytes, mask and arg bytes to 4.  Rows of any other width are accessed element by element (no requirement).
+ *     egk_gather_max_bwd walks its [rows, cols] arrays flat: the requirement holds whatever the width.  egk_colsum: ws 16-byte
+ *     aligned when N % 4 == 0.  egk_gather_rows: table and out 16-byte aligned when cols and ld are whole 16-byte groups.
  *
  * Each entry point names the reference interface it replaces (path:line relative to the
  * reference repository sapeirone/EgoPack).  The reference has no FFI of its own (it is pure
@@ -714,7 +724,7 @@ int egk_gather_rows(egk_stream_t s, const void* table, int32_t table_dtype, int6
 /* interpolating variant (PNR key-frame sampling data/ego4d_oscc.py:258-275, LTA 'avg' forecast nodes ego4d_fho.py:388-394):
  * out[i, :] = table[lo[i], :] where lo[i] == hi[i], else (float)((1 - w[i]) * table[lo[i], :] + w[i] * table[hi[i], :]) in
  * double with separately rounded products and sum (numpy's evaluation, then ``.float()``); an index < 0 or >= table_rows
- * stands for an all-zero row. */
+ * stands for an all-zero row.  A bf16 output is the bf16 rounding of THAT f32 value (two roundings, as ``.float().bfloat16()``). */
 int egk_gather_lerp_rows(egk_stream_t s, const void* table, int32_t table_dtype, int64_t ld, int64_t table_rows,
                          const int64_t* lo, const int64_t* hi, const double* w, void* out, int32_t out_dtype, int64_t n,
                          int32_t cols);
