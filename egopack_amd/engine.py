@@ -12,6 +12,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import queue
 import threading
 from typing import Dict, Mapping, Optional, Sequence
@@ -530,6 +531,7 @@ class StepBase:
     ``(total, vectors, extra)``."""
 
     order: Sequence[str] = TASK_ORDER
+    headwise_backward = False  # (MTLStep: the heads' backward inside their stream contexts, the backbone's as a call of its own)
     wgrad_grouping_default = True
     wgrad_group_count = None  # bf16 weight-gradient problems per grouped launch (None: _wgrad_count's policy)
 
@@ -559,12 +561,38 @@ class StepBase:
         self.optimizer, self.fused, self.sync = optimizer, fused_backbone, sync
         self.enabled = [t for t in self.order if self.weights.get(t, 0) > 0 and t in self.tasks]
         self.parallel_heads = parallel_heads
-        self._head_streams = []
-        self._graph = None
-        self._static_out = None
-        self._static_in = None
-        self._fuse_adam = True
-        self._stage_state, self._cuts = None, []
+        # ---- everything a step object holds besides its configuration, at its idle value ----
+        # streams of its own, created on first use (a step may be built before its device is chosen): ``_own_stream``
+        self._head_streams = []     # one per task head (``_run_heads``)
+        self.max_head_streams = None  # cap on them (None: one per head)
+        self._zero_stream = None    # clears the gradient buffer beside a captured forward pass (``_fork_grad_clear``)
+        self._adam_stream = None    # optimizer slices beside the step's last weight gradient (``_early_adam_plan``)
+        self._input_stream = None   # fills the idle set of input buffers (``_input_slot``)
+        # the captured step
+        self._graph = None          # the hipGraph (staged: a list of three)
+        self._static_out = None     # (objective, loss vectors) the graph writes
+        self._static_in = None      # everything the graph reads, kept alive
+        self._fuse_adam = True      # the optimizer is inside the graph
+        self._graph_has_exchange = False  # ... and so are the gradient exchange's collectives
+        self._graph_adam_lo = False  # the captured Adam launches write the low halves of the weights
+        self._hyper_in_graph = False  # the graph computes the step's Adam constants itself
+        self._rng_in_graph = False  # the graph moves the dropout offset word on itself
+        self._grad_store_off = False  # a capture with stored gradient slots failed its check: every slot is cleared + accumulated
+        self._grad_store_slots = 0  # gradient slots the last capture stored instead
+        self.capture_notes = []     # what a capture fell back from (empty: nothing)
+        # the step being issued
+        self._stage_state, self._cuts = None, []  # the staged backward's leaves between its stages
+        self._zero_pending = False  # the gradient clear is forked and not yet joined (``_join_zero``)
+        self._handoff = False       # the weight-gradient side streams are handed to the gradient exchange (``_issuing``)
+        self._live_last = list(self.enabled)  # tasks with a batch in the last one-piece eager step
+        self._grad_one = None       # the persistent 1.0 the objective's backward starts from
+        # running loss sums (``loss_sums``)
+        self._loss_acc = self._loss_scratch = None
+        self._loss_counts = {}
+        # the training loop (``train_step``)
+        self._steps_seen = 0
+        self.loop_counts = {"replayed": 0, "eager": 0}  # per training loop; the entry points log and reset it per epoch
+        self._train_static = None   # the static batches of the captured step and its sets of input buffers
         # optional launch(es) in front of every step, inside the captured graph too: e.g. the feature-store gather that
         # materialises the step's input block from its index matrix (feature_store.FeatureStore.gather(idx, out=buffer))
         self.input_hook = None
@@ -584,7 +612,7 @@ class StepBase:
 
     # ---- backbone ------------------------------------------------------------------------------------
     def features(self, batches: Mapping[str, Data], merged: Optional[Data] = None) -> Dict[str, torch.Tensor]:
-        live = [t for t in self.enabled if batches.get(t) is not None]
+        live = self._live(batches)
         if self.fused and len(live) > 1:
             if merged is None:
                 merged = merge_batches([batches[t] for t in live])
@@ -608,7 +636,7 @@ class StepBase:
             main = torch.cuda.current_stream()
             fork = torch.cuda.Event()
             fork.record(main)
-            n_streams = min(len(feats), getattr(self, "max_head_streams", len(feats)))
+            n_streams = min(len(feats), self.max_head_streams or len(feats))
             while len(self._head_streams) < n_streams:
                 self._head_streams.append(torch.cuda.Stream())
                 ops.exclude_wgrad_streams(self._head_streams[-1:])
@@ -635,11 +663,21 @@ class StepBase:
         opt = self.optimizer
         return bool(getattr(opt, "adam_writes_lo", False) and getattr(opt, "flat_w16lo", None) is not None)
 
+    def _own_stream(self, name: str, **kw) -> torch.cuda.Stream:
+        """The step's stream ``self.<name>`` (declared None in ``_init_base``), created on first use."""
+        st = getattr(self, name)
+        if st is None:
+            st = torch.cuda.Stream(**kw)
+            setattr(self, name, st)
+        return st
+
+    def _branch_streams(self):
+        """The step's own head / task / side streams: backward work on them keeps its weight-gradient launches."""
+        return list(self._head_streams)
+
     def _scope_streams(self) -> None:
         """This step's own head / task / side streams are the excluded ones from here on (ops.scope_excluded_streams)."""
-        g1 = getattr(self, "graphone", None)
-        ops.scope_excluded_streams([*getattr(self, "_head_streams", ()), *(getattr(g1, "_task_streams", ()) if g1 is not None else ()),
-                                    getattr(self, "_precise_side", None)])
+        ops.scope_excluded_streams(self._branch_streams())
 
     # ---- running per-task loss sums (what a training loop logs per epoch: reference main_temporal.py:129-134) -----------------------
     # The reference keeps them with ``.item()`` per step; kept as ``sum()`` + ``add_`` launches between two replays of the captured
@@ -647,7 +685,7 @@ class StepBase:
     # slot per enabled task, added to by the objective's launch (or a one-workgroup launch of their own) beside the parked weight
     # gradients; the host only counts elements.  ``loss_sums()`` reads (and clears) them: one synchronisation per epoch.
     def _loss_acc_for(self, device):
-        acc = getattr(self, "_loss_acc", None)
+        acc = self._loss_acc
         if acc is None or acc.device != device:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("the loss accumulators must exist before a capture (run one eager step, or loss_sums(), first)")
@@ -666,14 +704,13 @@ class StepBase:
                        tuple(src.values()))
 
     def _count_losses(self, vectors) -> None:
-        cnt = self.__dict__.setdefault("_loss_counts", {})
+        cnt = self._loss_counts
         for t, v in vectors.items():
             cnt[t] = cnt.get(t, 0) + int(v.numel())
 
     def loss_sums(self, reset: bool = True) -> Dict[str, tuple]:
         """{task: (sum of its per-element losses, elements)} over the steps since the last reset (one device synchronisation)."""
-        acc = getattr(self, "_loss_acc", None)
-        cnt = self.__dict__.setdefault("_loss_counts", {})
+        acc, cnt = self._loss_acc, self._loss_counts
         vals = acc.tolist() if acc is not None else [0.0] * len(self.enabled)
         out = {t: (float(vals[k]), int(cnt.get(t, 0))) for k, t in enumerate(self.enabled)}
         if reset:
@@ -722,38 +759,60 @@ class StepBase:
     def _exact_ln_on(self) -> bool:
         return bool(self.exact_graph_ln and self.sync is not None and self.sync.world > 1)
 
+    @contextlib.contextmanager
     def _ln_exchange_scope(self):
-        import contextlib
+        prev = ops.set_graph_ln_exchange(self.sync.sum_small) if self._exact_ln_on() else ops.set_graph_ln_exchange(None)
+        try:
+            yield
+        finally:
+            ops.set_graph_ln_exchange(prev)
 
-        @contextlib.contextmanager
-        def scope():
-            prev = ops.set_graph_ln_exchange(self.sync.sum_small) if self._exact_ln_on() else ops.set_graph_ln_exchange(None)
-            try:
+    def _live(self, batches):
+        """The enabled tasks that have a batch in this step, in the step's order."""
+        return [t for t in self.enabled if batches.get(t) is not None]
+
+    # ---- the one way into issuing a step: eager (one piece, staged) and captured (one rank, exchange graph, staged graphs) ----------
+    # ops.step_schedule keeps three rules for every one of them: nothing parked or deferred survives a step that was abandoned by an
+    # exception, no hook outlives its step, and the settings of whoever issued before come back.
+    @contextlib.contextmanager
+    def _issuing(self, batches, merged, *, handoff: bool = False, store: bool = False):
+        """Issue one step inside: this step's streams are the excluded ones, the weight-gradient / fork scheduler of ``ops`` runs
+        with this step's settings.  ``handoff``: the side streams are handed to the gradient exchange at the end of every backward
+        stage (``_exchange_region``) instead of joined.  ``store`` (captures): gradient slots learnt to have one writer per step
+        (``_learn_single_writers``) are stored, not cleared + accumulated -- the provider is installed for the body (not at all:
+        switched off, or nothing learnt), ``zero_flat_grads`` leaves those slots out meanwhile, and the optimizer checks at the end
+        that every slot left uncleared was written exactly once (EGK_DISABLE=grad_store)."""
+        opt = self.optimizer
+        self._scope_streams()
+        prev_handoff, stored, ok = self._handoff, None, False
+        try:
+            with ops.step_schedule(self.wgrad_side_streams, self.wgrad_grouping, self._wgrad_count(batches, merged), self.deferred_forks,
+                                   handoff):
+                self._handoff = handoff
+                if store and not self._grad_store_off and hasattr(opt, "store_begin") and switches.enabled("grad_store"):
+                    provider = opt.store_begin()
+                    if provider is not None:
+                        stored = (ops.set_grad_slot_provider(provider),)
                 yield
-            finally:
-                ops.set_graph_ln_exchange(prev)
-        return scope()
+            ok = True
+        finally:
+            self._handoff = prev_handoff
+            if stored is not None:
+                ops.set_grad_slot_provider(stored[0])
+                opt.store_end(ok=ok)
+                self._grad_store_slots = len(opt.store_slots)
 
     def forward_backward(self, batches, merged=None):
-        self._live_last = [t for t in self.enabled if batches.get(t) is not None]
+        self._live_last = self._live(batches)
         self.optimizer.zero_grad()
         if self.input_hook is not None:
             self.input_hook()
-        self._scope_streams()
-        prev = ops.set_wgrad_side_streams(self.wgrad_side_streams)
-        prev_g = ops.set_wgrad_grouping(self.wgrad_grouping, self._wgrad_count(batches, merged))
-        prev_d = ops.set_deferred_forks(self.deferred_forks)
-        try:
+        with self._issuing(batches, merged):
             # (eagerly issued steps end with the same grouped tail launch as captured ones: same tile variants, same bits)
-            self._install_tail(self._tail_only_plan([t for t in self.enabled if batches.get(t) is not None]))
+            self._install_tail(self._tail_only_plan(self._live(batches)))
             with self._ln_exchange_scope():
                 total, vectors = self._backward_pass(batches, merged)
             ops.join_wgrad(force=True)
-        finally:
-            ops.set_last_wgrad_hook(None, None)
-            ops.set_wgrad_side_streams(prev)
-            ops.set_wgrad_grouping(prev_g)
-            ops.set_deferred_forks(prev_d)
         return total, vectors
 
     def step(self, batches: Mapping[str, Data], merged: Optional[Data] = None):
@@ -772,45 +831,38 @@ class StepBase:
     # Learnt from the EAGER steps of every execution structure (one-piece and staged), applied to every CAPTURE (one rank, the
     # staged graphs of the N-rank step, the one-graph exchange): the gradient exchange reads the flat buffer region by region
     # once backward has finished it -- whether a slot was cleared and added into or stored makes no difference to what it reads.
+    @contextlib.contextmanager
     def _learn_single_writers(self):
-        import contextlib
         opt = self.optimizer
+        learn = (getattr(opt, "materialised", False) and hasattr(opt, "learn_begin") and not torch.cuda.is_current_stream_capturing()
+                 and switches.enabled("grad_store"))
+        prev = ops.set_grad_slot_provider(opt.learn_begin()) if learn else None  # (which gradient slots have ONE writer per step)
+        try:
+            yield
+        finally:
+            if learn:
+                ops.set_grad_slot_provider(prev)
+                opt.learn_end()
 
-        @contextlib.contextmanager
-        def scope():
-            learn = (getattr(opt, "materialised", False) and hasattr(opt, "learn_begin") and not torch.cuda.is_current_stream_capturing()
-                     and switches.enabled("grad_store"))
-            prev = ops.set_grad_slot_provider(opt.learn_begin()) if learn else None  # (which gradient slots have ONE writer per step)
-            try:
-                yield
-            finally:
-                if learn:
-                    ops.set_grad_slot_provider(prev)
-                    opt.learn_end()
-        return scope()
+    def _fork_grad_clear(self, hyper: bool) -> None:
+        """Captured steps clear the gradient buffer BESIDE the forward pass (nothing writes a gradient before the first backward
+        launch): 100 MB of memset off the chain's head, forked behind the forward pass's first launch (ops.defer_after_next_launch)
+        and joined by ``_join_zero`` before backward starts.  ``hyper``: the step's Adam constants (one thread, from the device-side
+        step counter) ride along."""
+        opt, side = self.optimizer, self._own_stream("_zero_stream")
 
-    def _grad_store_begin(self):
-        """Install the 'store' provider for a capture (None: off / nothing learnt); ``zero_flat_grads`` leaves the stored slots out
-        until ``_grad_store_end``."""
-        opt = self.optimizer
-        if getattr(self, "_grad_store_off", False) or not hasattr(opt, "store_begin") or not switches.enabled("grad_store"):
-            return None
-        prov = opt.store_begin()
-        if prov is None:
-            return None
-        return (ops.set_grad_slot_provider(prov),)
-
-    def _grad_store_end(self, prev) -> None:
-        if prev is not None:
-            import sys
-            ops.set_grad_slot_provider(prev[0])
-            self.optimizer.store_end(ok=sys.exc_info()[0] is None)  # (checks that every slot left uncleared was written exactly once)
-            self._grad_store_slots = len(self.optimizer.store_slots)
+        def issue_zero(ev):
+            side.wait_event(ev)
+            with torch.cuda.stream(side):
+                opt.zero_flat_grads()
+                if hyper:
+                    opt.prepare_hyper(in_capture=True)
+        ops.defer_after_next_launch(issue_zero)
+        self._zero_pending = True
 
     def _join_zero(self):
-        """Captured steps clear the gradient buffer on a side stream beside the forward pass: wait for it before the first
-        launch that writes a gradient."""
-        if getattr(self, "_zero_pending", False):
+        """Wait for the gradient clear forked by ``_fork_grad_clear`` before the first launch that writes a gradient."""
+        if self._zero_pending:
             ops.drain_deferred()
             torch.cuda.current_stream().wait_stream(self._zero_stream)
             self._zero_pending = False
@@ -822,7 +874,7 @@ class StepBase:
         self._join_zero()
         # (the seed of the objective's backward is a persistent 1.0: ``backward()`` without it fills a fresh tensor with a torch
         #  kernel on the chain, between the loss and the first backward launch)
-        one = getattr(self, "_grad_one", None)
+        one = self._grad_one
         if one is None or one.device != total.device or one.dtype != total.dtype:
             one = self._grad_one = torch.ones((), dtype=total.dtype, device=total.device)
         total.backward(gradient=one)
@@ -851,12 +903,12 @@ class StepBase:
         if self.sync is not None and self.sync.world > 1:
             # (handoff: the region's weight gradients may still be running on their side streams -- the communication stream
             #  waits for them, the backward stream goes straight on with the next stage)
-            after = ops.take_wgrad_streams() if getattr(self, "_handoff", False) else ()
+            after = ops.take_wgrad_streams() if self._handoff else ()
             self.sync.start(self.optimizer, *region, after=after)
 
     def _stage_join(self):
         """End of a backward stage: the stage's gradients are complete once the weight-gradient side streams are joined."""
-        if not getattr(self, "_handoff", False):
+        if not self._handoff:
             ops.join_wgrad(force=True)
 
     def _finish_staged(self):
@@ -872,12 +924,8 @@ class StepBase:
         self.optimizer.zero_grad()
         if self.input_hook is not None:
             self.input_hook()
-        self._scope_streams()
-        prev = ops.set_wgrad_side_streams(self.wgrad_side_streams)
-        prev_g = ops.set_wgrad_grouping(self.wgrad_grouping, self._wgrad_count(batches, merged))
-        prev_d = ops.set_deferred_forks(self.deferred_forks)
-        try:
-            self._install_tail(self._tail_only_plan([t for t in self.enabled if batches.get(t) is not None]))
+        with self._issuing(batches, merged):
+            self._install_tail(self._tail_only_plan(self._live(batches)))
             with self._ln_exchange_scope(), self._learn_single_writers():
                 total, vectors = self._stage_a(batches, merged)
                 self._exchange_region(regions[0])
@@ -885,11 +933,6 @@ class StepBase:
                 self._exchange_region(regions[1])
                 self._stage_c()
                 self._exchange_region(regions[2])
-        finally:
-            ops.set_last_wgrad_hook(None, None)
-            ops.set_wgrad_side_streams(prev)
-            ops.set_wgrad_grouping(prev_g)
-            ops.set_deferred_forks(prev_d)
         self._finish_staged()
         return total.detach(), {t: v.detach() for t, v in vectors.items()}
 
@@ -911,7 +954,7 @@ class StepBase:
                 self.sync.reduce_and_step(opt)  # chunked: Adam of chunk i overlaps the collectives of the later chunks
         else:
             if self._clip_on():
-                opt.norm_regions = self._clip_pieces(getattr(self, "_live_last", list(self.enabled)))
+                opt.norm_regions = self._clip_pieces(self._live_last)
             opt.step()
 
     # ---- training loop entry: eager for the first steps, then the captured step on static-shape batches -------------
@@ -929,10 +972,8 @@ class StepBase:
         from Python.  Anything else (different shapes, several ranks with an eager exchange path, ``use_graph`` off) takes
         the eager step.  Returns what ``step`` returns; after a replay the loss vectors are the graph's static outputs,
         valid until the next call.  ``loop_counts`` tallies replayed vs eager steps."""
-        self._steps_seen = getattr(self, "_steps_seen", 0) + 1
-        if not hasattr(self, "loop_counts"):
-            self.loop_counts = {"replayed": 0, "eager": 0}  # per training loop; the entry points log and reset it per epoch
-        st = getattr(self, "_train_static", None)
+        self._steps_seen += 1
+        st = self._train_static
         ref = _shared_blob(batches, merged)
         if not (ref is not None and st is not None and self.use_graph and st.get("gsig") == ref.gsig and len(st.get("slots", ())) > 1
                 and st["xkey"] == _feature_key(batches, merged)):
@@ -944,7 +985,7 @@ class StepBase:
                 or (self._exact_ln_on() and not self._one_graph_exchange_ok())):
             self.loop_counts["eager"] += 1
             return self.step(batches, merged)
-        if self.fused and len([t for t in self.enabled if batches.get(t) is not None]) > 1 and merged is None:
+        if self.fused and len(self._live(batches)) > 1 and merged is None:
             self.loop_counts["eager"] += 1
             return self.step(batches, merged)  # (the caller did not stage a merged batch: nothing static to replay on)
         # batches out of ONE packed transfer (data.to_device_packed) with the layout the static buffers were built from: one
@@ -1005,14 +1046,14 @@ class StepBase:
     gathers_inputs = False  # set once the step gathers the store rows into its own input buffers (see _input_slot)
 
     def _slot_of_capture(self, blob, static_b, static_m) -> dict:
-        return {"graph": self._graph, "out": self._static_out, "static_in": getattr(self, "_static_in", None), "blob": blob,
+        return {"graph": self._graph, "out": self._static_out, "static_in": self._static_in, "blob": blob,
                 "batches": static_b, "merged": static_m, "done": None}
 
     def _select_slot(self, slot) -> None:
         self._graph, self._static_out, self._static_in = slot["graph"], slot["out"], slot["static_in"]
 
     def _double_buffer_ok(self) -> bool:  # (one-rank steps whose optimizer is in the graph)
-        return bool(getattr(self, "_fuse_adam", False) and not isinstance(self._graph, list))
+        return bool(self._fuse_adam and not isinstance(self._graph, list))
 
     def _input_slot(self, st, ref, batches, merged) -> dict:
         """The set of input buffers this step's replay reads, holding this step's batch (see above)."""
@@ -1031,9 +1072,7 @@ class StepBase:
         slot = slots[k]
         side = cur
         if len(slots) > 1:
-            if not hasattr(self, "_input_stream"):
-                self._input_stream = torch.cuda.Stream(priority=-1)
-            side = self._input_stream
+            side = self._own_stream("_input_stream", priority=-1)
             ready = getattr(ref, "ready", None)
             if ready is not None:
                 side.wait_event(ready)  # (the staging of this batch: engine.StagedBatches)
@@ -1072,7 +1111,7 @@ class StepBase:
         """Capture forward+backward(+Adam if no gradient exchange) for THESE device tensors (static
         shapes and addresses: refill them in place between replays).
 
-        The stored gradient slots (``_grad_store_begin``) are whatever the last EAGER step learnt; when the captured batches
+        The stored gradient slots (``_issuing``) are whatever the last EAGER step learnt; when the captured batches
         write them differently (another live-task set: MTL loaders of unequal length, per-task backbone passes) the provider or
         its end-of-capture check raises -- the capture is then taken once more with every slot cleared and accumulated, and
         ``capture_notes`` says so: a slower step, never a crash of the training loop and never a wrong gradient."""
@@ -1080,13 +1119,13 @@ class StepBase:
             try:
                 return self._capture_once(batches, merged, warmup)
             except RuntimeError as e:
-                if not str(e).startswith("grad_store:") or getattr(self, "_grad_store_off", False):
+                if not str(e).startswith("grad_store:") or self._grad_store_off:
                     raise
                 if self.sync is not None and self.sync.world > 1 and self._one_graph_exchange_ok():
                     raise  # (a failed capture that holds collectives is not retried in this process: see one_graph_exchange)
                 torch.cuda.synchronize()
                 self._grad_store_off = True
-                self.capture_notes = [*getattr(self, "capture_notes", []), f"stored gradient slots off for this step ({e})"]
+                self.capture_notes = [*self.capture_notes, f"stored gradient slots off for this step ({e})"]
                 return self._capture_once(batches, merged, 0)
 
     def _capture_once(self, batches, merged, warmup):
@@ -1095,7 +1134,7 @@ class StepBase:
         if self._exact_ln_on() and not self._one_graph_exchange_ok():
             raise RuntimeError("exact_graph_ln sums the graph-LayerNorm statistics over the ranks inside the step: this process "
                                "group's collectives cannot be captured in a hipGraph -- use step() / train_step() (eager) in this mode")
-        live = [t for t in self.enabled if batches.get(t) is not None]
+        live = self._live(batches)
         if self.fused and len(live) > 1 and merged is None:  # index work must stay outside the capture
             merged = merge_batches([batches[t] for t in live]).to(batches[live[0]].pos.device)
         if warmup > 0 or not getattr(opt, "materialised", True):
@@ -1127,36 +1166,18 @@ class StepBase:
         opt.sync_hyper_source()  # (the step constants are computed inside the graph from a device-side step counter)
         ops.rng_device_offset(opt.flat_p.device)  # (the dropout offset word exists BEFORE the capture: created inside, its fill is a node)
         self._hyper_in_graph = False
-        self._scope_streams()
-        prev = ops.set_wgrad_side_streams(self.wgrad_side_streams)
-        prev_g = ops.set_wgrad_grouping(self.wgrad_grouping, self._wgrad_count(batches, merged))
-        prev_d = ops.set_deferred_forks(self.deferred_forks)
-        early = self._early_adam_plan(live) if fuse_adam else None
-        clip = fuse_adam and self._clip_on()
-        if clip and early is not None:
-            early["clip"], early["normed"] = True, []  # (its hooks take partial sums of the norm where they would start Adam slices)
         # gradient slots with one writer per step (learnt from the eager steps above, FlatAdam.learn_begin) are stored, not cleared +
-        # accumulated: the step's buffer clear shrinks to what is still added into (EGK_DISABLE=grad_store); also when the
-        # optimizer follows a gradient exchange outside the graph
-        store_prev = self._grad_store_begin()
-        try:
+        # accumulated (``store``): the step's buffer clear shrinks to what is still added into; also when the optimizer follows a
+        # gradient exchange outside the graph
+        with self._issuing(batches, merged, store=True):
+            early = self._early_adam_plan(live) if fuse_adam else None
+            clip = fuse_adam and self._clip_on()
+            if clip and early is not None:
+                early["clip"], early["normed"] = True, []  # (its hooks take partial sums of the norm where they would start Adam slices)
             with torch.cuda.graph(g, stream=ops.unexcluded_stream(), capture_error_mode=CAPTURE_MODE):
                 ops.stamp("step_start")
-                # the gradient buffer is cleared BESIDE the forward pass (nothing writes a gradient before the first backward
-                # launch): 100 MB of memset off the chain's head; joined in _join_zero() before backward starts
-                hyper_here = fuse_adam
-                self._hyper_in_graph = hyper_here
-                if not hasattr(self, "_zero_stream"):
-                    self._zero_stream = torch.cuda.Stream()
-
-                def issue_zero(ev):  # (behind the forward pass's first launch: see ops.defer_after_next_launch)
-                    self._zero_stream.wait_event(ev)
-                    with torch.cuda.stream(self._zero_stream):
-                        opt.zero_flat_grads()
-                        if hyper_here:  # the step's Adam constants: one thread, beside the forward pass
-                            opt.prepare_hyper(in_capture=True)
-                ops.defer_after_next_launch(issue_zero)
-                self._zero_pending = True
+                self._hyper_in_graph = fuse_adam
+                self._fork_grad_clear(hyper=fuse_adam)  # (with the step's Adam constants when the optimizer is in the graph)
                 self._rng_in_graph = False
                 if self.input_hook is not None:
                     self.input_hook()
@@ -1210,13 +1231,6 @@ class StepBase:
                 if bump is not None:
                     ops.advance_rng_device(opt.flat_p.device)
                 self._rng_in_graph = True
-        finally:
-            ops.set_last_wgrad_hook(None, None)
-            ops.set_graphone_backward_hook(None)
-            ops.set_wgrad_side_streams(prev)
-            ops.set_wgrad_grouping(prev_g)
-            ops.set_deferred_forks(prev_d)
-            self._grad_store_end(store_prev)
         self._graph, self._static_out, self._fuse_adam = g, (total, vectors), fuse_adam
         self._graph_adam_lo = bool(fuse_adam and self._adam_keeps_lo())  # (the captured Adam launches write the low halves)
         # the graph holds raw addresses: keep every tensor it reads alive for as long as the graph exists
@@ -1248,7 +1262,7 @@ class StepBase:
         return first.weight, lo, hi
 
     def headwise_backward_ok(self) -> bool:
-        return bool(getattr(self, "headwise_backward", False))
+        return bool(self.headwise_backward)
 
     def _install_tail(self, plan, hook=None) -> None:
         if plan is None:
@@ -1288,9 +1302,7 @@ class StepBase:
         if reg is None:
             return None
         lo, hi = reg
-        if not hasattr(self, "_adam_stream"):
-            self._adam_stream = torch.cuda.Stream()
-        plan = {"param": first.weight, "lo": lo, "hi": hi, "stream": self._adam_stream, "fired": False, "tail": tail is not None}
+        plan = {"param": first.weight, "lo": lo, "hi": hi, "stream": self._own_stream("_adam_stream"), "fired": False, "tail": tail is not None}
         def hook():
             if plan["fired"]:
                 return
@@ -1368,67 +1380,51 @@ class StepBase:
     def _capture_exchange_graph(self, batches, merged):
         opt, sync = self.optimizer, self.sync
         regions = self._stage_regions()
-        live = [t for t in self.enabled if batches.get(t) is not None]
+        live = self._live(batches)
         g = torch.cuda.CUDAGraph()
         opt.grad_scale = 1.0 / sync.world
         opt.sync_hyper_source()
         self._hyper_in_graph = True
         count = opt.step_count
-        self._scope_streams()
-        prev = ops.set_wgrad_side_streams(self.wgrad_side_streams)
-        prev_g = ops.set_wgrad_grouping(self.wgrad_grouping, self._wgrad_count(batches, merged))
-        prev_d = ops.set_deferred_forks(self.deferred_forks)
         sync.begin_step()
         sync.hyper_ready = True
-        self._handoff = True
-        prev_h = ops.set_wgrad_handoff(True)
-        store_prev = self._grad_store_begin()  # (single-writer gradient slots are stored: the collectives read final values either way)
         try:
-            with torch.cuda.graph(g, stream=ops.unexcluded_stream(), capture_error_mode=CAPTURE_MODE):
+            # (handoff: every stage's side streams go to its region's collectives; single-writer gradient slots are stored: the
+            #  collectives read final values either way)
+            with (self._issuing(batches, merged, handoff=True, store=True),
+                  torch.cuda.graph(g, stream=ops.unexcluded_stream(), capture_error_mode=CAPTURE_MODE)):
+                ops.stamp("step_start")
                 # (the gradient buffer is cleared beside the forward pass, as in the one-rank capture: joined by _join_zero()
                 #  before the heads' backward writes the first gradient)
-                if not hasattr(self, "_zero_stream"):
-                    self._zero_stream = torch.cuda.Stream()
-
-                def issue_zero(ev):
-                    self._zero_stream.wait_event(ev)
-                    with torch.cuda.stream(self._zero_stream):
-                        opt.zero_flat_grads()
-                        opt.prepare_hyper(in_capture=True)  # (the step's Adam constants, from the device-side step counter)
-                ops.stamp("step_start")
-                ops.defer_after_next_launch(issue_zero)
-                self._zero_pending = True
+                self._fork_grad_clear(hyper=True)
                 self._rng_in_graph = False
                 if self.input_hook is not None:
                     self.input_hook()
-                ln_scope = self._ln_exchange_scope()  # (exact cross-rank graph-LN statistics: their collectives are captured too)
-                ln_scope.__enter__()
-                total, vectors = self._stage_a(batches, merged)
-                self._join_zero()
-                ops.stamp("heads_done")
-                self._exchange_region(regions[0])
-                # beside the step's LAST weight-gradient launch (the grouped tail of the temporal pooling): the Adam slices of
-                # the regions exchanged by then, each behind its collective -- what the one-rank capture does with its early
-                # Adam launch; only the pooling's own slices are left for the end of the step
-                fired = []
+                with self._ln_exchange_scope():  # (exact cross-rank graph-LN statistics: their collectives are captured too)
+                    total, vectors = self._stage_a(batches, merged)
+                    self._join_zero()
+                    ops.stamp("heads_done")
+                    self._exchange_region(regions[0])
+                    # beside the step's LAST weight-gradient launch (the grouped tail of the temporal pooling): the Adam slices of
+                    # the regions exchanged by then, each behind its collective -- what the one-rank capture does with its early
+                    # Adam launch; only the pooling's own slices are left for the end of the step
+                    fired = []
 
-                def early_adam_hook():
-                    if fired:
-                        return
-                    fired.append(True)
-                    if not hasattr(self, "_adam_stream"):
-                        self._adam_stream = torch.cuda.Stream()
+                    def early_adam_hook():
+                        if fired:
+                            return
+                        fired.append(True)
+                        side = self._own_stream("_adam_stream")
 
-                    def issue(ev):
-                        self._adam_stream.wait_event(ev)
-                        sync.step_started_chunks(opt, self._adam_stream)
-                    ops.defer_after_next_launch(issue)
-                self._install_tail(self._tail_only_plan(live), early_adam_hook if self._early_adam_ok() else None)
-                self._stage_b()
-                ops.stamp("stack_done")
-                self._exchange_region(regions[1])
-                self._stage_c()
-                ln_scope.__exit__(None, None, None)
+                        def issue(ev):
+                            side.wait_event(ev)
+                            sync.step_started_chunks(opt, side)
+                        ops.defer_after_next_launch(issue)
+                    self._install_tail(self._tail_only_plan(live), early_adam_hook if self._early_adam_ok() else None)
+                    self._stage_b()
+                    ops.stamp("stack_done")
+                    self._exchange_region(regions[1])
+                    self._stage_c()
                 ops.stamp("backward_done")
                 self._exchange_region(regions[2])
                 sync.finish_and_step(opt)
@@ -1436,16 +1432,9 @@ class StepBase:
                 ops.advance_rng_device(opt.flat_p.device)
                 self._rng_in_graph = True
         finally:
-            self._handoff = False
-            ops.set_wgrad_handoff(prev_h)
             sync.hyper_ready = False
             sync.begin_step()
             opt.step_count = count  # (finish_and_step counted the capture; replay() counts the steps that run)
-            ops.set_last_wgrad_hook(None, None)
-            ops.set_wgrad_side_streams(prev)
-            ops.set_wgrad_grouping(prev_g)
-            ops.set_deferred_forks(prev_d)
-            self._grad_store_end(store_prev)
         self._graph, self._static_out, self._fuse_adam = g, (total, vectors), True
         self._graph_adam_lo = self._adam_keeps_lo()  # (every chunk's captured Adam launch writes the low halves of its slice)
         self._graph_has_exchange = True
@@ -1457,29 +1446,16 @@ class StepBase:
         self._graph_has_exchange = False
         if self._one_graph_exchange_ok():
             return self._capture_exchange_graph(batches, merged)  # (an exception ends the attempt: see one_graph_exchange)
-        opt = self.optimizer
         gs = [torch.cuda.CUDAGraph() for _ in range(3)]
         self._rng_in_graph = False  # (no staged graph advances the Philox offset word: replay() does, also after a one-piece capture)
-        self._scope_streams()
-        prev = ops.set_wgrad_side_streams(self.wgrad_side_streams)
-        prev_g = ops.set_wgrad_grouping(self.wgrad_grouping, self._wgrad_count(batches, merged))
-        prev_d = ops.set_deferred_forks(self.deferred_forks)
-        store_prev = self._grad_store_begin()  # (one provider over the three captures: every learnt slot is written in exactly one of them)
-        try:
-            live = [t for t in self.enabled if batches.get(t) is not None]
+        # (``store``: one provider over the three captures -- every learnt slot is written in exactly one of them)
+        with self._issuing(batches, merged, store=True):
+            live = self._live(batches)
             cap = ops.unexcluded_stream()  # (one capture stream for the three graphs, never a registered head / task stream)
             with torch.cuda.graph(gs[0], stream=cap, capture_error_mode=CAPTURE_MODE):
                 # the gradient buffer is cleared BESIDE the forward pass, as in the one-rank capture (a fork and a join inside
                 # the first graph; _stage_a joins it before the heads' backward writes the first gradient)
-                if not hasattr(self, "_zero_stream"):
-                    self._zero_stream = torch.cuda.Stream()
-
-                def issue_zero(ev):
-                    self._zero_stream.wait_event(ev)
-                    with torch.cuda.stream(self._zero_stream):
-                        opt.zero_flat_grads()
-                ops.defer_after_next_launch(issue_zero)
-                self._zero_pending = True
+                self._fork_grad_clear(hyper=False)
                 if self.input_hook is not None:
                     self.input_hook()
                 total, vectors = self._stage_a(batches, merged)
@@ -1490,12 +1466,6 @@ class StepBase:
                 self._stage_b()
             with torch.cuda.graph(gs[2], pool=pool, stream=cap, capture_error_mode=CAPTURE_MODE):
                 self._stage_c()
-        finally:
-            ops.set_last_wgrad_hook(None, None)
-            ops.set_wgrad_side_streams(prev)
-            ops.set_wgrad_grouping(prev_g)
-            ops.set_deferred_forks(prev_d)
-            self._grad_store_end(store_prev)
         self._graph, self._static_out, self._fuse_adam = gs, (total, vectors), False
         self._static_in = (batches, merged, self._stage_state, self._cuts)  # everything the graphs read stays alive
         return gs
@@ -1504,7 +1474,7 @@ class StepBase:
         """One training step from the captured graph(s)."""
         self._count_losses(self._static_out[1])
         opt = self.optimizer
-        if not getattr(self, "_rng_in_graph", False):
+        if not self._rng_in_graph:
             ops.advance_rng_device(opt.flat_p.device)
         if isinstance(self._graph, list):
             regions = self._stage_regions()
@@ -1516,7 +1486,7 @@ class StepBase:
             self._finish_staged()
             return self._static_out[0]
         if self._fuse_adam:
-            if getattr(self, "_hyper_in_graph", False):
+            if self._hyper_in_graph:
                 opt.sync_hyper_source()  # (host -> device only when lr / grad_scale changed or the step count was set)
                 self._graph.replay()
                 opt.note_captured_step()
@@ -1527,7 +1497,7 @@ class StepBase:
             # the graph's Adam launch moved flat_p on the DEVICE without opt.launch() running on the host: every low half a
             # 'bf16x3' contraction marked fresh before this replay (validation's precise pass between two epochs) is stale now --
             # unless the captured Adam launches write the low halves themselves: then ALL of them are fresh behind a replay
-            if getattr(self, "_graph_adam_lo", False):
+            if self._graph_adam_lo:
                 opt._lo_fresh = [(0, opt.flat_p.numel())]
             else:
                 opt.invalidate_lo_shadows()
@@ -1545,6 +1515,8 @@ class MTLStep(StepBase):
                  parallel_heads: bool = True):
         self._init_base(model, tasks, weights, optimizer, fused_backbone, sync, parallel_heads)
         self.criteria = dict(criteria)
+        self._head_batches = None  # the batches of the step being issued, for the heads (``_heads_forward_backward``)
+        self._coef_grads = {}      # per task the constant its head's backward starts from (w_t / numel), filled once
 
     def _head(self, t: str, feat, d):
         task = self.tasks[t]
@@ -1602,8 +1574,6 @@ class MTLStep(StepBase):
         constant w_t / numel(v_t) -- the value the one-call backward of the objective hands it, bit for bit."""
         leaves = {t: f.detach().requires_grad_(True) for t, f in feats.items()}
         batches = self._head_batches
-        if not hasattr(self, "_coef_grads"):
-            self._coef_grads = {}
         order = list(leaves)
         nets = [self.tasks[t].net for t in order]
         # Row compaction (exact): the heads are row-wise and a node whose labels are all ``ignore_index`` has loss 0 and gradient 0
@@ -1881,6 +1851,7 @@ class EgoPackStep(StepBase):
         self._init_base(model, tasks, weights, optimizer, fused_backbone, sync, parallel_heads)
         self.graphone = graphone
         self.backprop, self.train_mode = backprop_temporal_graph, temporal_graph_train_mode
+        self._precise_side = None  # the stream of the precise pass beside the training pass's forward, created on first use (``losses``)
         # Tasks that are not trained here only lend their projection heads to the detached auxiliary features (reference
         # main_egopack.py:53: ``.detach()``): their parameters never receive a gradient and the reference's Adam skips them
         # (grad is None).  They are marked frozen, which changes no result and lets the operand copies of their weights (bf16
@@ -1907,8 +1878,11 @@ class EgoPackStep(StepBase):
     def _early_adam_ok(self) -> bool:
         return bool(self.early_adam and self.backprop)
 
+    def _branch_streams(self):
+        return [*self._head_streams, *getattr(self.graphone, "_task_streams", ()), self._precise_side]
+
     def _gradient_branch_streams(self):
-        return [*getattr(self.graphone, "_task_streams", ()), *getattr(self, "_head_streams", ())]
+        return [*getattr(self.graphone, "_task_streams", ()), *self._head_streams]
 
     def _early_adam_plan(self, live):
         """+ GraphONE's own slice (``graphone_adam`` off: none): its stage parameters (half of the step's parameters in config
@@ -1965,7 +1939,7 @@ class EgoPackStep(StepBase):
         """{primary: {aux task: f32 [N, H]}}: the auxiliary projections of every enabled task batch from the 'bf16x3' pass.
         ``tape`` (a list): the backbone's nodes leave their results in it (ops.dual_record) for the one-pass step."""
         opt = self.optimizer
-        live = [t for t in self.enabled if batches.get(t) is not None]
+        live = self._live(batches)
         with ops.precise_scope(), ops.rng_replay(ops.rng_snapshot() if rng_snap is None else rng_snap):
             if getattr(opt, "materialised", False):
                 opt.refresh_lo_shadows(list(self.model.parameters()))  # the backbone's low halves: one launch
@@ -1993,7 +1967,7 @@ class EgoPackStep(StepBase):
         local to the rank.  ``one_pass`` off: the two-pass step of rounds 3-5."""
         if not (self.one_pass and self.backprop) or not switches.enabled("one_pass"):
             return False
-        live = [batches[t] for t in self.enabled if batches.get(t) is not None]
+        live = [batches[t] for t in self._live(batches)]
         if len(live) != 1 or isinstance(live[0].x, (list, tuple)) or live[0].x.dtype != torch.bfloat16 or ops.graph_ln_exchange_on():
             return False
         if ops.get_compute() != "bf16" or getattr(self.model, "stage_cut", None) is not None:
@@ -2059,9 +2033,8 @@ class EgoPackStep(StepBase):
                 # the precise pass is a chain of ~50 launches over the same few thousand rows as the training pass's forward:
                 # forked onto its own stream, the two chains run side by side (each alone leaves most of the chip idle)
                 main = torch.cuda.current_stream()
-                if getattr(self, "_precise_side", None) is None:
-                    self._precise_side = torch.cuda.Stream()  # (a high-priority stream: 5.05-5.26 against 2.53-2.55 ms in the captured step)
-                    ops.exclude_wgrad_streams([self._precise_side])
+                if self._precise_side is None:  # (a high-priority stream: 5.05-5.26 against 2.53-2.55 ms in the captured step)
+                    ops.exclude_wgrad_streams([self._own_stream("_precise_side")])
                 side = self._precise_side
                 side.wait_stream(main)
                 tape = [] if self._one_pass_ok(batches, merged) else None
@@ -2072,7 +2045,6 @@ class EgoPackStep(StepBase):
                     ops.stamp("search_done")
             else:
                 precise = self.precise_aux_features(batches, merged, rng_snap=snap)
-        import contextlib
         # (the two passes draw the same dropout offsets: same keep masks when the backbone is in train mode)
         tape = tape if side is not None else None
         if tape:

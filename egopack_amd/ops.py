@@ -19,6 +19,7 @@ Every op is polymorphic in the activation element type: it follows the dtype of 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -156,17 +157,8 @@ def _stream():
 # other pays a cross-queue hand-off.  A backward pass naturally issues the forked weight gradient first, so the dX CHAIN
 # was the child that hopped, at every fork (tools/exp/fork_order.py: 12 links with a forked weight-gradient launch each,
 # 601 us per replay side-launch-first, 500 us chain-first).
+# ``on``: switched per step (``step_schedule``).
 _deferred = {"items": [], "busy": False, "on": True}
-
-
-def set_deferred_forks(on: bool) -> bool:
-    """Switch the late issue of forked launches (engine: per step class); returns the previous setting.  Anything still
-    queued is dropped: a step ends with ``join_wgrad`` (which drains the queue), so something is left only when the step
-    was abandoned by an exception -- its launches must not surface in the next step."""
-    prev = _deferred["on"]
-    _deferred["on"] = bool(on)
-    _deferred["items"] = []
-    return prev
 
 
 def defer_after_next_launch(fn) -> None:
@@ -451,7 +443,7 @@ def _gemm_desc(M, N, A1, lda1, B1, ldb1, K1, out, ldc, *, A2=None, lda2=0, B2=No
     d.dbias = _p(dbias)
     d.ws, d.ws_bytes = None, 0
     # A dW-form launch that accumulates into a parameter's slot of the flat gradient buffer STORES instead when the step installed a
-    # provider that says this launch is the slot's only writer in this step (engine.StepBase._grad_store_begin, optim.FlatAdam.store_begin);
+    # provider that says this launch is the slot's only writer in this step (engine.StepBase._issuing, optim.FlatAdam.store_begin);
     # ``slot_final`` False: several launches add up this gradient -- the provider is not asked
     prov = _slot_provider["provider"]
     if (prov is not None and slot_final and transA and transB and accumulate and compute == BF16 and bias is None and residual is None and act == 0
@@ -751,8 +743,11 @@ def _grad_slot(param: Optional[torch.Tensor]):
 # every side stream with the stream that called backward() before the gradients can be consumed.
 # Off by default: measured on MI355X it gains 3-4 % on the multi-task steps (M = 6144 backbone rows, heads on their
 # own streams) and loses 3-5 % on single-task steps (M = 2048: every launch is already a partial-chip launch);
-# egopack_amd.engine turns it on for steps with more than one enabled task.
-_wgrad = {"enabled": False, "streams": {}, "pending": [], "queued": False, "exclude": set()}
+# egopack_amd.engine turns it on for steps with more than one enabled task (``step_schedule``).
+# ``handoff``: while on, the end of a backward() call does NOT make the backward stream wait for the side streams: the engine takes
+# them over with ``take_wgrad_streams`` and orders its gradient exchange behind them instead, so the next backward stage's dX chain
+# starts beside the weight gradients of the stage before.
+_wgrad = {"enabled": False, "streams": {}, "pending": [], "queued": False, "exclude": set(), "handoff": False}
 
 
 def exclude_wgrad_streams(streams) -> None:
@@ -781,12 +776,6 @@ def unexcluded_stream() -> torch.cuda.Stream:
             return st
         keep.append(st)
     return keep[-1]
-
-
-def set_wgrad_side_streams(on: bool) -> bool:
-    prev = _wgrad["enabled"]
-    _wgrad["enabled"] = bool(on)
-    return prev
 
 
 def _wgrad_launch(in_place: bool, tensors, launch, in_backward: bool = True):
@@ -827,7 +816,8 @@ def _wgrad_launch(in_place: bool, tensors, launch, in_backward: bool = True):
 # step, all competing with the dX chain for the CUs).  With the queue on, such launches are PARKED (operands kept alive)
 # and issued SIX AT A TIME as one grouped launch on the side stream: 384 workgroups, no slabs, no reduce launch, a sixth
 # of the forks.  ``flush_wgrad`` issues what is parked (fewer than four at the end of backward).
-_wq = {"on": False, "items": [], "tiles": 0, "hold": [], "extra": [], "riders": []}
+# ``count``: bf16 problems per grouped launch for the step being issued (None: WGRAD_GROUP_COUNT).
+_wq = {"on": False, "count": None, "items": [], "tiles": 0, "hold": [], "extra": [], "riders": []}
 # Six per launch: alone, six H x H problems in one launch of two 4-wave workgroups per CU run at 900 TF/s against 740 for
 # four on one 8-wave workgroup per CU (tools/gemm_group_bench.py: x4 70 us, x6 85 us, x8 133 us at K = 6144).  Inside the
 # step: 4 / 5 / 6 / 7 / 8 -> 1.558 / 1.60 / 1.538 / 1.60 / 1.595 ms (three alternating rounds of 200 steps; 12 H x H weight
@@ -842,20 +832,6 @@ WGRAD_GROUP_TILES = 64 * WGRAD_GROUP_COUNT
 F32_WGRAD_GROUP_COUNT = 8
 
 
-def set_wgrad_grouping(on, count: Optional[int] = None):
-    """Switch the parking queue (engine: at the start and the end of every step); returns the previous setting (hand it back to
-    restore).  ``count``: bf16 problems per grouped launch for this step (None: WGRAD_GROUP_COUNT).
-    Whatever is still parked is dropped: a step ends with ``join_wgrad`` (which issues it), so something is left only when the step
-    was abandoned by an exception -- its weight gradients must not be accumulated by the next step."""
-    prev = (_wq["on"], _wq.get("count"))
-    if isinstance(on, tuple):
-        on, count = on
-    _wq["on"] = bool(on)
-    _wq["count"] = None if count is None else int(count)
-    _wq["items"], _wq["hold"], _wq["extra"], _wq["tiles"], _wq["riders"] = [], [], [], 0, []
-    return prev
-
-
 def park_rider(fn, hold=()) -> None:
     """``fn()`` -- a launch that feeds nothing on the backward chain (a reported vector, say) -- rides with the next flush of the
     parked weight gradients: issued on their side stream, in front of the grouped launch.  Run at once when nothing can be parked
@@ -863,7 +839,7 @@ def park_rider(fn, hold=()) -> None:
     if not (_wq["on"] and _wgrad["enabled"]) or _on_excluded_stream():
         fn()
         return
-    _wq.setdefault("riders", []).append(fn)
+    _wq["riders"].append(fn)
     _wq["hold"].extend(t for t in hold if t is not None)
 
 
@@ -901,7 +877,7 @@ def _wgrad_defer(args, kw, tensors, park_on_excluded: bool = False, park_only: b
         return True
     # exact-f32 problems are matrix-pipe bound: a launch lasts as long as the workgroups on its fullest CU, so EIGHT H x H
     # problems (512 tiles = two per CU everywhere) where the bf16 launches take six
-    count = F32_WGRAD_GROUP_COUNT if A.dtype == torch.float32 else (_wq.get("count") or WGRAD_GROUP_COUNT)
+    count = F32_WGRAD_GROUP_COUNT if A.dtype == torch.float32 else (_wq["count"] or WGRAD_GROUP_COUNT)
     if len(_wq["items"]) >= count or _wq["tiles"] >= 64 * count:
         flush_wgrad()
     # (no end-of-backward join is scheduled for a parked problem: whoever switched the queue on -- engine.StepBase -- ends the
@@ -959,7 +935,7 @@ def flush_wgrad(in_backward: bool = True, force: bool = False):
     calls from the backward stream (end of a step's backward, the last-weight-gradient hook) must never leave parked work
     behind, whatever stream handle the backward stream happens to have (a capture stream may alias a pooled handle that an
     earlier step registered as excluded)."""
-    items, hold, extra, riders = _wq["items"], _wq["hold"], _wq["extra"], _wq.get("riders") or []
+    items, hold, extra, riders = _wq["items"], _wq["hold"], _wq["extra"], _wq["riders"]
     if (not items and not extra and not riders) or (_on_excluded_stream() and not force):  # (a head stream never issues what others parked)
         return
     _wq["items"], _wq["hold"], _wq["extra"], _wq["tiles"], _wq["riders"] = [], [], [], 0, []
@@ -990,7 +966,7 @@ def flush_wgrad(in_backward: bool = True, force: bool = False):
     _wgrad_launch(True, hold, launch, in_backward)
 
 
-_last_wgrad = {"param": None, "hook": None, "inline": True, "tail": None, "leaked": False}
+_last_wgrad = {"param": None, "hook": None, "pre": None, "inline": True, "tail": None, "leaked": False}
 
 
 def set_last_wgrad_tail(lo_ptr: int, hi_ptr: int) -> None:
@@ -1058,7 +1034,7 @@ def join_wgrad(force: bool = False):
     """The current stream waits for every weight-gradient side stream with work in flight (call after backward,
     before the gradients are read: optimizer step, gradient exchange, or the end of a hipGraph capture).  ``force``: the
     caller IS the step's backward stream (see flush_wgrad)."""
-    if _wgrad.get("handoff") and not force:
+    if _wgrad["handoff"] and not force:
         return  # (end-of-backward callback while the engine hands the side streams to its exchange: take_wgrad_streams)
     flush_wgrad(in_backward=False, force=force)
     drain_deferred()
@@ -1067,15 +1043,6 @@ def join_wgrad(force: bool = False):
         cur.wait_stream(side)
     _wgrad["pending"].clear()
     _wgrad["queued"] = False
-
-
-def set_wgrad_handoff(on: bool) -> bool:
-    """While on, the end of a backward() call does NOT make the backward stream wait for the weight-gradient side streams:
-    the engine takes them over with ``take_wgrad_streams`` and orders its gradient exchange behind them instead, so the next
-    backward stage's dX chain starts beside the weight gradients of the stage before.  Returns the previous setting."""
-    prev = bool(_wgrad.get("handoff"))
-    _wgrad["handoff"] = bool(on)
-    return prev
 
 
 def take_wgrad_streams() -> list:
@@ -1087,6 +1054,31 @@ def take_wgrad_streams() -> list:
     _wgrad["pending"].clear()
     _wgrad["queued"] = False
     return streams
+
+
+@contextlib.contextmanager
+def step_schedule(side_streams: bool, grouping: bool, count: Optional[int] = None, deferred_forks: bool = True, handoff: bool = False):
+    """The scheduler's settings for ONE step being issued (egopack_amd.engine: every eager step and every capture runs inside one):
+    weight gradients on side streams, the parking queue with ``count`` bf16 problems per grouped launch (None: WGRAD_GROUP_COUNT),
+    the late issue of forked launches, the hand-over of the side streams to a gradient exchange.
+    Entering and leaving both drop whatever is parked or deferred: a step ends with ``join_wgrad`` (which issues it), so something
+    is left only when a step was abandoned by an exception -- its launches must not surface in, and its weight gradients must not
+    be accumulated by, the next step.  Leaving -- normally or through an exception -- also clears the hooks a step installs while
+    it runs (``set_last_wgrad_hook`` with its ``pre`` and tail range, ``set_graphone_backward_hook``): no hook outlives its step.
+    Scopes nest: the inner one hands the outer one's settings back."""
+    def install(enabled, on, per_launch, late, hand):
+        _wgrad["enabled"], _wgrad["handoff"] = bool(enabled), bool(hand)
+        _wq["on"], _wq["count"] = bool(on), None if per_launch is None else int(per_launch)
+        _wq["items"], _wq["hold"], _wq["extra"], _wq["tiles"], _wq["riders"] = [], [], [], 0, []
+        _deferred["on"], _deferred["items"] = bool(late), []
+    prev = (_wgrad["enabled"], _wq["on"], _wq["count"], _deferred["on"], _wgrad["handoff"])
+    install(side_streams, grouping, count, deferred_forks, handoff)
+    try:
+        yield
+    finally:
+        set_last_wgrad_hook(None, None)
+        set_graphone_backward_hook(None)
+        install(*prev)
 
 
 def _operand_rows(g: torch.Tensor, dtype: torch.dtype, pad_cols: int = 0) -> torch.Tensor:
@@ -1299,7 +1291,7 @@ class _Linear(torch.autograd.Function):
             last = Wp is _last_wgrad["param"] and _last_wgrad["hook"] is not None
             tail_items, tail_extra = [], []
             if last:
-                if _last_wgrad.get("pre") is not None:
+                if _last_wgrad["pre"] is not None:
                     _last_wgrad["pre"]()
                 tail_items, tail_extra = _take_tail_items()  # (issued below; the argument tuples keep their operands alive)
                 flush_wgrad(force=True)  # (the hook starts the optimizer on every other slot: their gradients must be issued)

@@ -631,6 +631,66 @@ def test_dual_replay_refuses_a_tape_that_was_not_consumed():
     assert ops._dual["replay"] is None
 
 
+def test_step_schedule_installs_its_settings_and_leaves_nothing_behind():
+    """ops.step_schedule (every step of the engine is issued inside one): the four settings hold inside and come back on the way
+    out, a nested scope hands the outer one's settings back, and whichever way the scope is left -- normally or by an exception
+    in the body -- nothing parked or deferred and no hook survives it."""
+    import pytest
+    from egopack_amd import ops
+
+    def settings():
+        return ops._wgrad["enabled"], ops._wq["on"], ops._wq["count"], ops._deferred["on"], ops._wgrad["handoff"]
+
+    def assert_clean():
+        assert all(ops._wq[k] == [] for k in ("items", "hold", "extra", "riders")) and ops._wq["tiles"] == 0
+        assert ops._deferred["items"] == []
+        assert ops._last_wgrad["param"] is None and ops._last_wgrad["hook"] is None and ops._last_wgrad["pre"] is None
+        assert ops._last_wgrad["tail"] is None and ops._g1_hook["fn"] is None
+
+    def litter():  # (what a step leaves when it is abandoned half-way)
+        ops._wq["items"].append((("args",), {}))
+        ops._wq["hold"].append(torch.zeros(1))
+        ops._wq["extra"].append(("reduction",))
+        ops._wq["riders"].append(lambda: None)
+        ops._wq["tiles"] += 3
+        ops._deferred["items"].append(((0, 0), None, lambda ev: None))
+        ops.set_last_wgrad_hook(torch.zeros(1), lambda: None, pre=lambda: None)
+        ops.set_last_wgrad_tail(64, 128)
+        ops.set_graphone_backward_hook(lambda: None)
+
+    for key in ("count", "riders"):  # every key is in the literal that creates its dict: no .get / .setdefault fallbacks
+        assert key in ops._wq
+    assert "handoff" in ops._wgrad and "pre" in ops._last_wgrad
+    idle = settings()
+    # 1. chosen settings inside, the previous ones afterwards
+    with ops.step_schedule(True, True, 8, False, True):
+        assert settings() == (True, True, 8, False, True)
+        assert_clean()
+        with ops.step_schedule(False, True, None, True):  # nested: the outer scope's settings come back
+            assert settings() == (False, True, None, True, False)
+        assert settings() == (True, True, 8, False, True)
+    assert settings() == idle
+    assert_clean()
+    # 2. left through an exception, with work parked / deferred and hooks installed inside
+    with pytest.raises(ValueError):
+        with ops.step_schedule(True, True, 6, True, False):
+            litter()
+            assert ops._wq["items"] and ops._wq["riders"] and ops._deferred["items"] and ops._last_wgrad["tail"] == (64, 128)
+            raise ValueError("abandoned")
+    assert settings() == idle
+    assert_clean()
+    # ... and the same litter is dropped on a normal exit, and on the way IN (left by whoever issued outside a scope)
+    with ops.step_schedule(True, False):
+        litter()
+    assert settings() == idle
+    assert_clean()
+    ops._wq["items"].append((("args",), {}))
+    ops._deferred["items"].append(((0, 0), None, lambda ev: None))
+    with ops.step_schedule(True, True):
+        assert ops._wq["items"] == [] and ops._deferred["items"] == []
+    assert_clean()
+
+
 def test_fast_key_sees_the_labelled_row_set_of_a_compacted_head():
     """two AR batches with the same graph structure, feature shape and label shape but another labelled-row set
     (a sequence whose centre labels are all -1) differ in what a capture bakes in (the strided row view, the padded height of
