@@ -19,6 +19,7 @@ import torch  # noqa: F401
 HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["EGK_LIB_PATH"]) if os.environ.get("EGK_LIB_PATH") else HERE / "libegopack_hip.so"  # (env: development A/B of two builds)
 HEADER = HERE.parent / "include" / "egopack_hip.h"
+OPTIM_HEADER = HERE.parent / "include" / "egopack_optim.h"  # included by egopack_hip.h; its symbols: OPTIM_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -82,6 +83,15 @@ class CETask(C.Structure):
     _fields_ = [("logits", vp * 4), ("ld", i64 * 4), ("C", i32 * 4), ("pad", i32 * 4), ("dcol", i64 * 4), ("n_heads", i32),
                 ("y", vp), ("y_stride", i64), ("loss", vp), ("dlogits", vp), ("ldd", i64), ("rows", i32), ("gscale", f32)]
 
+
+class OptimDesc(C.Structure):
+    """struct egk_optim_desc (include/egopack_optim.h)."""
+    _fields_ = [("rule", i32), ("g_dtype", i32), ("n", i64), ("p", vp), ("g", vp), ("state0", vp), ("state1", vp), ("hyper", vp),
+                ("t_dev", vp), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", f32), ("weight_decay", f32), ("momentum", f32), ("dampening", f32),
+                ("nesterov", i32), ("bf16_shadow", vp), ("bf16_lo_shadow", vp), ("bump_word", vp), ("bump", i64), ("gate", vp)]
+
+
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
 
 # name -> (restype, argtypes); mirrors include/egopack_hip.h one to one
 SIGNATURES = {
@@ -199,11 +209,26 @@ SIGNATURES = {
 }
 
 
-def header_symbols() -> list:
-    """Every function name declared in include/egopack_hip.h."""
-    text = HEADER.read_text()
+# ... and include/egopack_optim.h, the header egopack_hip.h includes (its own table: the ledgers of the two headers are separate)
+OPTIM_SIGNATURES = {
+    "egk_optim_step": (C.c_int, [vp, C.POINTER(OptimDesc)]),
+}
+
+
+def _declared(header: Path) -> list:
+    text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(egk_[a-z0-9_]+)\s*\(", text)))
+
+
+def header_symbols() -> list:
+    """Every function name declared in include/egopack_hip.h."""
+    return _declared(HEADER)
+
+
+def optim_header_symbols() -> list:
+    """Every function name declared in include/egopack_optim.h."""
+    return _declared(OPTIM_HEADER)
 
 
 _lib = None
@@ -219,7 +244,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m egopack_amd.build` "
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -39,7 +39,7 @@ def _stale(target: Path, deps) -> bool:
 def build_library(force: bool = False, verbose: bool = False) -> Path:
     hipcc = _hipcc()
     OBJ.mkdir(parents=True, exist_ok=True)
-    headers = list(CSRC.glob("*.h")) + [HERE.parent / "include" / "egopack_hip.h"]
+    headers = list(CSRC.glob("*.h")) + sorted((HERE.parent / "include").glob("*.h"))
     jobs = []
     for src in sources():
         obj = OBJ / (src.stem + ".o")

@@ -103,6 +103,7 @@ enum KernelId {
     KID_AXPBY,
     KID_SUM_SCALE,
     KID_ADAM,
+    KID_OPTIM,             // egk_optim_step: the update rules behind one launch interface (optim_rules.hip)
     KID_COUNT
 };
 

@@ -1,0 +1,178 @@
+// The update rules of the flat-buffer optimizer behind one launch interface (include/egopack_optim.h): Adam, AdamW and SGD, the
+// single-tensor formulas of torch 2.10.  ONE kernel family in the shape of adam_span / adam_kernel (loss_optim.hip): 16-byte
+// accesses on p, g and the state, a scalar tail for n % 4, the bf16 copy and the low half of the stored p, the offset word moved on
+// by workgroup 0, one wave-uniform load of the gate.  No atomics; every element has one writer.
+#include "common.h"
+
+namespace egk {
+
+// what a kernel of the family does per element; the rule codes of the ABI map onto these (SGD: by its momentum)
+enum { K_ADAM = 0, K_ADAMW, K_SGD, K_SGD_MOMENTUM };
+template <int KIND> struct StateCount { static constexpr int value = KIND == K_SGD ? 0 : KIND == K_SGD_MOMENTUM ? 1 : 2; };
+
+struct OptimConsts {
+    AdamConsts adam;    // (K_ADAM: adam_update itself, the shipped kernel's bits; K_ADAMW: its step, bc2s, gs, b2, eps; wd through ``decay``)
+    float lr, decay;    // decay = 1 - lr * wd
+    float omb1, omb2;   // K_ADAMW: 1 - beta1, 1 - beta2 taken in double, rounded once (torch hands its kernels these scalars)
+    float wd, gs, mu, damp1;  // damp1 = 1 - dampening
+    bool first, nesterov;     // first: no momentum buffer yet (*t_dev == 1)
+};
+
+template <int KIND>
+__device__ __forceinline__ void optim_update(float& p, float g, float& a, float& b, const OptimConsts& c) {
+#pragma clang fp contract(off)  // (no fused multiply-adds: as adam_update)
+    if constexpr (KIND == K_ADAM) {
+        adam_update(p, g, a, b, c.adam);
+    } else if constexpr (KIND == K_ADAMW) {
+        p = p * c.decay;                                      // param.mul_(1 - lr * weight_decay)
+        const float gg = g * c.gs;
+        a = a + (gg - a) * c.omb1;                            // exp_avg.lerp_(grad, 1 - beta1)
+        b = b * c.adam.b2 + c.omb2 * gg * gg;                 // mul_(beta2).addcmul_(g, g, 1 - beta2)
+        const float denom = sqrtf(b) / c.adam.bc2s + c.adam.eps;
+        p = p - c.adam.step * (a / denom);
+    } else {
+        const float gg = g * c.gs + c.wd * p;                 // grad.add(param, alpha=weight_decay)
+        float step = gg;
+        if constexpr (KIND == K_SGD_MOMENTUM) {
+            a = c.first ? gg : c.mu * a + c.damp1 * gg;       // buf = clone(grad) | buf.mul_(momentum).add_(grad, alpha=1 - dampening)
+            step = c.nesterov ? gg + c.mu * a : a;            // grad.add(buf, alpha=momentum) | buf
+        }
+        p = p - c.lr * step;                                  // param.add_(grad, alpha=-lr)
+    }
+}
+
+// the elements [0, n) of one span, grid-stride over ``nblk`` workgroups
+template <int KIND, typename GT>
+__device__ __forceinline__ void optim_span(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                                           long long n, const OptimConsts& c, bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
+                                           int blk, int nblk) {
+    constexpr int NS = StateCount<KIND>::value;
+    for (long long i = ((long long)blk * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)nblk * blockDim.x * 4) {
+        if (i + 4 <= n) {
+            float4 pv = *reinterpret_cast<float4*>(p + i);
+            const float4 gv = ld4t(g + i, 0, 4, true);
+            float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
+            if constexpr (NS >= 1) av = *reinterpret_cast<float4*>(s0 + i);
+            if constexpr (NS >= 2) bv = *reinterpret_cast<float4*>(s1 + i);
+            float* pp = &pv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) optim_update<KIND>(pp[t], gp[t], ap[t], bp[t], c);
+            *reinterpret_cast<float4*>(p + i) = pv;
+            if constexpr (NS >= 1) *reinterpret_cast<float4*>(s0 + i) = av;
+            if constexpr (NS >= 2) *reinterpret_cast<float4*>(s1 + i) = bv;
+            if (shadow) st4t(shadow + i, 0, 4, true, pv);
+            if (shadow_lo) {  // bf16(p - bf16(p)): egk_split_bf16's bits
+                const float lo4[4] = {pp[0] - bf2f(f2bf(pp[0])), pp[1] - bf2f(f2bf(pp[1])), pp[2] - bf2f(f2bf(pp[2])), pp[3] - bf2f(f2bf(pp[3]))};
+                st4t(shadow_lo + i, 0, 4, true, make_float4(lo4[0], lo4[1], lo4[2], lo4[3]));
+            }
+        } else {
+            for (long long j = i; j < n; ++j) {
+                float a = 0.f, b = 0.f;
+                if constexpr (NS >= 1) a = s0[j];
+                if constexpr (NS >= 2) b = s1[j];
+                optim_update<KIND>(p[j], ld1t(g + j), a, b, c);
+                if constexpr (NS >= 1) s0[j] = a;
+                if constexpr (NS >= 2) s1[j] = b;
+                if (shadow) shadow[j] = f2bf(p[j]);
+                if (shadow_lo) shadow_lo[j] = f2bf(p[j] - bf2f(f2bf(p[j])));
+            }
+        }
+    }
+}
+
+struct OptimHyper {  // the host's scalars of a launch
+    float b1, b2, omb1, omb2, eps, wd, mu, damp1;
+    int nesterov;
+};
+
+template <int KIND, typename GT, bool GATED>  // GT: element type of the gradient buffer (f32, or bf16 after a compressed all-reduce)
+__global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0,
+                                                    float* __restrict__ s1, long long n, const float* __restrict__ hyper,
+                                                    const long long* __restrict__ t_dev, const OptimHyper h, bf16_t* __restrict__ shadow,
+                                                    bf16_t* __restrict__ shadow_lo, long long* __restrict__ bump_word, long long bump,
+                                                    const int* __restrict__ gate) {
+    // (the step's dropout offset word moves on inside this launch, whether the step happens or not: adam_kernel)
+    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
+    // (a closed gate -- the gradient norm was not finite -- skips the step: one wave-uniform load, nothing else is touched)
+    if (GATED && *gate == 0) return;
+    OptimConsts c;
+    {
+#pragma clang fp contract(off)
+        const float lr = hyper[0];
+        c.adam = AdamConsts{lr / hyper[1], hyper[2], hyper[3], h.b1, h.b2, h.eps, h.wd};
+        c.lr = lr;
+        c.decay = (float)(1.0 - (double)lr * (double)h.wd);  // (torch takes 1 - lr * weight_decay in double and rounds it once)
+        c.wd = h.wd;
+        c.gs = hyper[3];
+        c.omb1 = h.omb1;
+        c.omb2 = h.omb2;
+        c.mu = h.mu;
+        c.damp1 = h.damp1;
+        c.nesterov = h.nesterov != 0;
+        c.first = KIND == K_SGD_MOMENTUM ? *t_dev == 1 : false;  // (egk_adam_hyper has counted this step)
+    }
+    optim_span<KIND, GT>(p, g, s0, s1, n, c, shadow, shadow_lo, blockIdx.x, gridDim.x);
+}
+
+template <int KIND, typename GT>
+static void optim_launch(hipStream_t s, unsigned grid, const egk_optim_desc& d, const OptimHyper& h) {
+    if (d.gate)
+        hipLaunchKernelGGL((optim_kernel<KIND, GT, true>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
+                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
+                           (long long*)d.bump_word, (long long)d.bump, (const int*)d.gate);
+    else
+        hipLaunchKernelGGL((optim_kernel<KIND, GT, false>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
+                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
+                           (long long*)d.bump_word, (long long)d.bump, (const int*)nullptr);
+}
+
+}  // namespace egk
+
+using namespace egk;
+
+extern "C" int egk_optim_step(egk_stream_t stream, const egk_optim_desc* d) {
+    EGK_REQUIRE(d, "egk_optim_step: null descriptor");
+    EGK_REQUIRE(d->rule == EGK_OPT_ADAM || d->rule == EGK_OPT_ADAMW || d->rule == EGK_OPT_SGD,
+                "egk_optim_step: unknown rule %d (EGK_OPT_ADAM = 0, EGK_OPT_ADAMW = 1, EGK_OPT_SGD = 2)", (int)d->rule);
+    EGK_REQUIRE(d->g_dtype == EGK_F32 || d->g_dtype == EGK_BF16, "egk_optim_step: unknown gradient dtype %d", (int)d->g_dtype);
+    EGK_REQUIRE(d->p && d->g && d->hyper, "egk_optim_step: null pointer");
+    EGK_REQUIRE(d->n >= 0, "egk_optim_step: n >= 0 (got %lld)", (long long)d->n);
+    const bool sgd = d->rule == EGK_OPT_SGD;
+    const int kind = !sgd ? (d->rule == EGK_OPT_ADAM ? K_ADAM : K_ADAMW) : d->momentum != 0.f ? K_SGD_MOMENTUM : K_SGD;
+    if (kind == K_ADAM || kind == K_ADAMW)
+        EGK_REQUIRE(d->state0 && d->state1, "egk_optim_step: missing state pointer -- Adam and AdamW need state0 (exp_avg) and state1 (exp_avg_sq)");
+    if (kind == K_SGD_MOMENTUM)
+        EGK_REQUIRE(d->state0 && d->t_dev, "egk_optim_step: missing state pointer -- SGD with momentum needs state0 (the momentum buffer) "
+                                           "and t_dev (the step counter)");
+    if (sgd) {
+        EGK_REQUIRE(d->momentum >= 0.f, "egk_optim_step: momentum >= 0 (got %g)", (double)d->momentum);
+        EGK_REQUIRE(!d->nesterov || (d->momentum > 0.f && d->dampening == 0.f),
+                    "egk_optim_step: nesterov momentum requires a momentum and zero dampening");
+    }
+    // (state the rule does not have is neither checked nor handed to the kernel)
+    egk_optim_desc a = *d;
+    if (kind == K_SGD) a.state0 = nullptr;
+    if (kind == K_SGD || kind == K_SGD_MOMENTUM) a.state1 = nullptr;
+    EGK_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.state0 | (uintptr_t)a.state1) & 15) == 0,
+                "egk_optim_step: buffers must be 16-byte aligned");
+    EGK_REQUIRE(((uintptr_t)a.bf16_shadow & 7) == 0, "egk_optim_step: shadow must be 8-byte aligned");
+    EGK_REQUIRE(((uintptr_t)a.bf16_lo_shadow & 7) == 0, "egk_optim_step: low-half shadow must be 8-byte aligned");
+    if (a.n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    // bytes per parameter: p read + written, each state buffer read + written, the gradient read, the bf16 copies written
+    const double state_bytes = kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0;
+    ProfScope prof(KID_OPTIM, s, 0, (8.0 + state_bytes + (a.g_dtype == EGK_BF16 ? 2.0 : 4.0) + (a.bf16_shadow ? 2.0 : 0.0) +
+                                    (a.bf16_lo_shadow ? 2.0 : 0.0)) * (double)a.n);
+    // the grid of egk_adam_step*: one 1024-element group per workgroup up to 32768 of them (measured there)
+    const long long want = (a.n / 4 + 255) / 256;
+    const long long cap = 32768;
+    const unsigned grid = (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
+    const OptimHyper h{(float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), a.eps, a.weight_decay, a.momentum, (float)(1.0 - (double)a.dampening), a.nesterov ? 1 : 0};
+    switch (kind) {
+        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_ADAM, T>(s, grid, a, h))); break;
+        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_ADAMW, T>(s, grid, a, h))); break;
+        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_SGD, T>(s, grid, a, h))); break;
+        default: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_SGD_MOMENTUM, T>(s, grid, a, h))); break;
+    }
+    return check_launch("egk_optim_step");
+}

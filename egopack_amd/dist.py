@@ -494,21 +494,31 @@ class GradSync:
         opt._moments_sharded = self.world > 1 and per > 0  # (FlatAdam.state_dict refuses until gather_moments has run)
         opt._shard_regions = [(0, n)]
 
+    @staticmethod
+    def _state_buffers(opt) -> list:
+        """The optimizer's flat state buffers: two (Adam, AdamW), one (SGD with momentum) or none -- ``opt.state_buffers()``;
+        an optimizer without the accessor is read by its ``flat_m`` / ``flat_v`` attributes."""
+        fn = getattr(opt, "state_buffers", None)
+        if fn is not None:
+            return list(fn())
+        return [b for b in (getattr(opt, "flat_m", None), getattr(opt, "flat_v", None)) if b is not None]
+
     def gather_moments(self, opt) -> None:
-        """Sharded update: all-gather every rank's slice of the Adam moments so that each rank holds the full flat_m / flat_v
+        """Sharded update: all-gather every rank's slice of the optimizer's state buffers so that each rank holds them in full
         -- what a checkpoint must contain (a resumed run may use another world size or the all-reduce path).  A COLLECTIVE:
         every rank calls it (the entry points do, before rank 0 saves).  The slices of the other ranks are overwritten by the
         next sharded step's bookkeeping only in the sense that this rank never reads them: the gathered values stay valid
         until the next step."""
         if not getattr(opt, "_moments_sharded", False):
             return
-        if getattr(opt, "flat_m", None) is None:
+        bufs = self._state_buffers(opt)
+        if not bufs:  # (no flat buffers yet, or a rule without state: nothing is sharded)
             opt._moments_sharded = False
             return
-        n = opt.flat_m.numel()
+        n = bufs[0].numel()
         regions = getattr(opt, "_shard_regions", None) or [(0, n)]
         if len(regions) > 1 or regions[0] != (0, n):
-            return self._gather_moments_regions(opt, regions)
+            return self._gather_moments_regions(opt, regions, bufs)
         per, lo, hi, body = self.shard_bounds(n)
         real = dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
         if not per and real == self.world:
@@ -525,8 +535,8 @@ class GradSync:
             warnings.warn("GradSync.gather_moments: the sharded Adam moments cannot be gathered on this group "
                           f"(group size {real}, sharded for {self.world}); a checkpoint would hold partial moments")
             return
-        native = opt.flat_m.is_cuda and dist.get_backend(self.group) == "nccl"
-        for buf in (opt.flat_m, opt.flat_v):
+        native = bufs[0].is_cuda and dist.get_backend(self.group) == "nccl"
+        for buf in bufs:
             if native:
                 dist.all_gather_into_tensor(buf[:body], buf[lo:hi].clone(), group=self.group)
             else:
@@ -537,19 +547,19 @@ class GradSync:
                     buf[r * per:(r + 1) * per].copy_(part)
         opt._moments_sharded = False
 
-    def _gather_moments_regions(self, opt, regions) -> None:
+    def _gather_moments_regions(self, opt, regions, bufs) -> None:
         real = dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
         if real != self.world:
             import warnings
             warnings.warn("GradSync.gather_moments: the sharded Adam moments cannot be gathered on this group "
                           f"(group size {real}, sharded for {self.world}); a checkpoint would hold partial moments")
             return
-        native = opt.flat_m.is_cuda and dist.get_backend(self.group) == "nccl"
+        native = bufs[0].is_cuda and dist.get_backend(self.group) == "nccl"
         for lo, hi in regions:
             per, a, b, body = self.shard_bounds(hi - lo, lo)
             if not per:
                 continue
-            for buf in (opt.flat_m, opt.flat_v):
+            for buf in bufs:
                 if native:
                     dist.all_gather_into_tensor(buf[lo:body], buf[a:b].clone(), group=self.group)
                 else:

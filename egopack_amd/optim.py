@@ -1,4 +1,4 @@
-"""Flat-buffer Adam: torch.optim.Adam semantics (L2 weight decay) in ONE kernel launch.
+"""Flat-buffer optimizers: torch.optim.Adam (L2 weight decay), torch.optim.AdamW and torch.optim.SGD semantics in ONE kernel launch.
 
 All trainable parameters that actually receive gradients are re-homed as views of one contiguous
 fp32 buffer (``flat_p``); their ``.grad`` are views of ``flat_g``.  The backward kernels accumulate
@@ -7,7 +7,13 @@ is one ``egk_adam_step`` launch and the data-parallel gradient exchange all-redu
 same buffer (dist.GradSync).  Mirrors ``_target_: torch.optim.Adam`` of configs/defaults.yaml:17-20.
 
 Parameters whose gradient is None after the first backward (disabled tasks, detached aux heads,
-frozen prototypes) are left alone, exactly as torch.optim.Adam skips ``grad is None``."""
+frozen prototypes) are left alone, exactly as torch.optim.Adam skips ``grad is None``.
+
+``FlatOptimizer`` holds everything that is not the update rule: the flat buffers, the bank ordering, the stored gradient
+slots, the bf16 copies and low halves, the device-side step constants, clipping, ``launch(grads, lo, hi, bump)``.  A rule
+(``FlatAdam``, ``FlatAdamW``, ``FlatSGD``) names its per-parameter state -- two buffers, one or none, in torch's
+state-dict names -- and issues its launch: ``FlatAdam`` through the egk_adam_step* entry points, the others through
+egk_optim_step (include/egopack_optim.h)."""
 from __future__ import annotations
 
 import math
@@ -33,14 +39,27 @@ def _minus_ranges(ranges, lo, hi):
     return out
 
 
-class FlatAdam(torch.optim.Optimizer):
-    def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, max_grad_norm=None):
-        """``max_grad_norm`` (None or 0: off): clip the global L2 norm of the gradient to it before every update --
+_STATE_NAMES = {frozenset(("exp_avg", "exp_avg_sq")): "Adam / AdamW state (exp_avg, exp_avg_sq)",
+                frozenset(("momentum_buffer",)): "SGD state with momentum (momentum_buffer)",
+                frozenset(): "no per-parameter buffers (SGD without momentum)"}
+
+
+def _refuse_unbuilt(name: str, amsgrad, maximize) -> None:
+    """``amsgrad`` / ``maximize`` have no kernel; foreach / fused / capturable / differentiable are execution hints without
+    arithmetic and are accepted."""
+    for key, val in (("amsgrad", amsgrad), ("maximize", maximize)):
+        if val:
+            raise ValueError(f"{name}: {key}=True is not built (the flat-buffer kernels implement the plain rule only)")
+
+
+class FlatOptimizer(torch.optim.Optimizer):
+    def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None):
+        """``state_keys``: torch's state-dict names of the rule's per-parameter buffers, in the order of ``state_buffers()``.
+        ``max_grad_norm`` (None or 0: off): clip the global L2 norm of the gradient to it before every update --
         torch.nn.utils.clip_grad_norm_'s arithmetic, computed on the device inside the step (see ``norm_partials``)."""
         params = [p for p in params]
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
-            raise ValueError(f"FlatAdam: max_grad_norm must be None, 0 (off) or positive, got {max_grad_norm!r}")
+            raise ValueError(f"{type(self).__name__}: max_grad_norm must be None, 0 (off) or positive, got {max_grad_norm!r}")
         if len({id(p) for p in params}) != len(params):  # the reference passes some parameters twice
             seen, uniq = set(), []
             for p in params:
@@ -48,15 +67,17 @@ class FlatAdam(torch.optim.Optimizer):
                     seen.add(id(p))
                     uniq.append(p)
             params = uniq
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.flat_p = self.flat_g = self.flat_m = self.flat_v = self.flat_w16 = None
+        super().__init__(params, defaults)
+        self.flat_p = self.flat_g = self.flat_w16 = None
+        self._state_keys = tuple(state_keys)
+        self._state_bufs: List[torch.Tensor] = []  # one flat f32 buffer per state key
         self.active: List[torch.Tensor] = []
         self.step_count = 0
         self.grad_scale = 1.0
         self._hyper = None
         self.flat_w16lo = None      # bf16 LOW halves of the parameters (p - bf16(p)), built on demand: ensure_lo_shadows
         self._lo_fresh = []         # [lo, hi) ranges of flat_w16lo that match flat_p (cleared by every write to flat_p)
-        self._moment_views = {}     # id(param) -> (m view, v view) once materialised
+        self._moment_views = {}     # id(param) -> one view per state buffer once materialised
         self._slot_of = {}          # id(param) -> (first element, slot length) in the flat buffers
         self._pending_state = None  # a state dict loaded before the flat buffers exist
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
@@ -68,13 +89,13 @@ class FlatAdam(torch.optim.Optimizer):
         group = self.param_groups[0]
         live = [p for p in group["params"] if p.requires_grad and p.grad is not None]
         if not live:
-            raise RuntimeError("FlatAdam.step(): no parameter has a gradient")
+            raise RuntimeError(f"{type(self).__name__}.step(): no parameter has a gradient")
         dev = live[0].device
         if dev.type != "cuda":
-            raise RuntimeError("FlatAdam needs parameters on a ROCm device (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} needs parameters on a ROCm device (no CPU fallback)")
         # slots aligned to 16 bytes in the bf16 shadow (32 B in f32).  A matrix whose row count is not a multiple of
         # 64 (the classifier layers: 478, 115, 2 ... rows) gets its slot padded to whole 64-row blocks: the padding
-        # stays zero under Adam (zero gradient, zero moments, zero weight), and the padded bf16 copy is the K-major
+        # stays zero under every rule (zero gradient, zero state, zero weight), and the padded bf16 copy is the K-major
         # operand of the layer's dX contraction on the pipelined kernel (ops._Linear.backward).
         def slot(p):
             if p.dim() == 2 and p.shape[0] % 64:
@@ -87,8 +108,7 @@ class FlatAdam(torch.optim.Optimizer):
         total = sum(sizes)
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._state_bufs = [torch.zeros(total, dtype=torch.float32, device=dev) for _ in self._state_keys]
         self.flat_w16 = torch.zeros(total, dtype=torch.bfloat16, device=dev)  # bf16 operand copies of the weights
         off = 0
         with torch.no_grad():
@@ -99,7 +119,7 @@ class FlatAdam(torch.optim.Optimizer):
                 p.data = self.flat_p[off:off + n].view(p.shape)
                 p.grad = self.flat_g[off:off + n].view(p.shape)
                 p._egk_shadow = self.flat_w16[off:off + n].view(p.shape)
-                self._moment_views[id(p)] = (self.flat_m[off:off + n].view(p.shape), self.flat_v[off:off + n].view(p.shape))
+                self._moment_views[id(p)] = tuple(b[off:off + n].view(p.shape) for b in self._state_bufs)
                 self._slot_of[id(p)] = (off, sz)
                 p._egk_lo_init = self.ensure_lo_shadows
                 if p.dim() == 2 and p.shape[0] % 64 and p.shape[1] % 8 == 0:
@@ -174,21 +194,27 @@ class FlatAdam(torch.optim.Optimizer):
             return (0, 0)
         return (min(o for o, _ in slots), max(o + n for o, n in slots))
 
-    # -- checkpointing: the layout of torch.optim.Adam's state dict (per-parameter exp_avg / exp_avg_sq / step) -----
+    def state_buffers(self) -> List[torch.Tensor]:
+        """The rule's flat state buffers (Adam, AdamW: exp_avg, exp_avg_sq; SGD with momentum: the momentum buffer; SGD without:
+        none), each laid out like ``flat_p``; empty before the flat buffers exist."""
+        return list(self._state_bufs)
+
+    # -- checkpointing: the layout of the torch class's state dict (per-parameter ``step`` + the rule's buffers) -----
     def state_dict(self):
-        """``{"state": {index: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]}`` with parameter indices
-        in constructor order -- loadable by torch.optim.Adam over the same parameter list and vice versa."""
+        """``{"state": {index: {"step", *state keys}}, "param_groups": [...]}`` with parameter indices in constructor order --
+        loadable by the torch class of the rule over the same parameter list and vice versa.  (torch.optim.SGD keeps no
+        ``step``; the entry is harmless to it and tells a resumed run that its first step has happened.)"""
         if getattr(self, "_moments_sharded", False):
-            raise RuntimeError("FlatAdam.state_dict(): the moments are sharded over the ranks (dist.GradSync shard_update: every rank "
-                               "holds its own 1 / world slice, zeros elsewhere) -- call GradSync.gather_moments(optimizer) on "
-                               "EVERY rank before saving")
+            raise RuntimeError(f"{type(self).__name__}.state_dict(): the moments are sharded over the ranks (dist.GradSync shard_update: "
+                               "every rank holds its own 1 / world slice, zeros elsewhere) -- call GradSync.gather_moments(optimizer) "
+                               "on EVERY rank before saving")
         group = self.param_groups[0]
         state = {}
         for i, p in enumerate(group["params"]):
             mv = self._moment_views.get(id(p))
             if mv is not None:
-                state[i] = {"step": torch.tensor(float(self._steps_taken())), "exp_avg": mv[0].detach().clone(),
-                            "exp_avg_sq": mv[1].detach().clone()}
+                state[i] = {"step": torch.tensor(float(self._steps_taken())),
+                            **{k: v.detach().clone() for k, v in zip(self._state_keys, mv)}}
         if self._pending_state is not None and not state:
             return self._pending_state
         pg = {k: v for k, v in group.items() if k != "params"}
@@ -196,10 +222,11 @@ class FlatAdam(torch.optim.Optimizer):
         return {"state": state, "param_groups": [pg]}
 
     def load_state_dict(self, state_dict):
-        """Hyper-parameters now; moments now if the flat buffers exist, otherwise when the first step builds them."""
+        """Hyper-parameters now; the state now if the flat buffers exist, otherwise when the first step builds them."""
+        self._check_state_rule(state_dict)
         pg = state_dict["param_groups"][0]
         for k, v in pg.items():
-            if k != "params" and k in self.param_groups[0]:
+            if k not in ("params", *self._fixed_keys) and k in self.param_groups[0]:
                 self.param_groups[0][k] = v
         if self.materialised:
             self._apply_state(state_dict)
@@ -207,7 +234,7 @@ class FlatAdam(torch.optim.Optimizer):
             self._pending_state = {"state": {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                                              for i, st in state_dict["state"].items()},
                                    "param_groups": state_dict["param_groups"]}
-            steps = [float(s["step"]) for s in state_dict["state"].values() if "step" in s]
+            steps = [self._entry_steps(s) for s in state_dict["state"].values()]
             self.step_count = int(max(steps)) if steps else 0
             # The parameters with saved moments ARE the live set of the run that wrote the state: build the flat buffers
             # now, so that the first step after a resume runs on the layout (bf16 operand copies, classifier banks) every
@@ -220,6 +247,27 @@ class FlatAdam(torch.optim.Optimizer):
                         p.grad = torch.zeros_like(p)
                 self._materialise()
 
+    # keys of a parameter group that select the kernel (the rule itself, the number of state buffers): a loaded state leaves them
+    _fixed_keys = ()
+
+    @staticmethod
+    def _entry_steps(st) -> float:
+        """Steps a per-parameter state entry stands for; a torch.optim.SGD entry (a buffer, no ``step``) counts as one."""
+        if "step" in st:
+            return float(st["step"])
+        return 1.0 if any(v is not None for v in st.values()) else 0.0
+
+    def _check_state_rule(self, state_dict) -> None:
+        """A state of another rule is refused by name, before anything is changed."""
+        if not state_dict["state"]:
+            return
+        held = frozenset(k for st in state_dict["state"].values() for k, v in st.items() if k != "step" and v is not None)
+        want = frozenset(self._state_keys)
+        if held != want:
+            name = lambda keys: _STATE_NAMES.get(keys, "per-parameter state (" + ", ".join(sorted(keys)) + ")")
+            raise RuntimeError(f"{type(self).__name__}.load_state_dict(): the checkpoint holds {name(held)}, the configured optimizer "
+                               f"is {type(self).__name__} and keeps {name(want)}")
+
     def _apply_state(self, state_dict):
         params = self.param_groups[0]["params"]
         steps = []
@@ -228,9 +276,9 @@ class FlatAdam(torch.optim.Optimizer):
                 mv = self._moment_views.get(id(params[int(i)]))
                 if mv is None:
                     continue  # saved for a parameter that receives no gradient in this run
-                mv[0].copy_(st["exp_avg"])
-                mv[1].copy_(st["exp_avg_sq"])
-                steps.append(float(st["step"]))
+                for k, view in zip(self._state_keys, mv):
+                    view.copy_(st[k])
+                steps.append(self._entry_steps(st))
         if steps:
             self.step_count = int(max(steps))
 
@@ -343,7 +391,7 @@ class FlatAdam(torch.optim.Optimizer):
         """The constants of the NEXT step (t = step_count + 1), on the current stream.  ``in_capture``: the launch is being
         recorded into a graph -- the caller has called ``sync_hyper_source`` before the capture and calls
         ``note_captured_step`` after every replay."""
-        b1, b2 = self.param_groups[0]["betas"]
+        b1, b2 = self.param_groups[0].get("betas", (0.0, 0.0))  # (a rule without betas: both bias corrections come out as 1)
         self._norm_cursor, self._norm_covered = 0, 0  # (a step abandoned between its partial sums and its finalize leaves nothing behind)
         if not in_capture:
             self.sync_hyper_source()
@@ -467,7 +515,7 @@ class FlatAdam(torch.optim.Optimizer):
         into the next free slots (capturable).  Every element of the buffer must be covered exactly once before ``norm_finalize``;
         the order of the calls fixes the order of the sum."""
         if not self.clipping:
-            raise RuntimeError("FlatAdam.norm_partials(): built without max_grad_norm")
+            raise RuntimeError(f"{type(self).__name__}.norm_partials(): built without max_grad_norm")
         grads = self.flat_g if grads is None else grads
         hi = self.flat_p.numel() if hi is None else hi
         if hi <= lo:
@@ -476,7 +524,7 @@ class FlatAdam(torch.optim.Optimizer):
         self._norm_buffers()
         k = int(lib.egk_grad_sumsq_slots(hi - lo))
         if self._norm_cursor + k > self.NORM_SLOTS:
-            raise RuntimeError(f"FlatAdam.norm_partials(): more than {self.NORM_SLOTS} partial sums in one step")
+            raise RuntimeError(f"{type(self).__name__}.norm_partials(): more than {self.NORM_SLOTS} partial sums in one step")
         _ck(lib.egk_grad_sumsq(_stream(), _p(grads[lo:hi]), 1 if grads.dtype == torch.bfloat16 else 0, hi - lo,
                                _p(self._norm_partials[self._norm_cursor:]), k), "egk_grad_sumsq")
         self._norm_cursor += k
@@ -488,7 +536,7 @@ class FlatAdam(torch.optim.Optimizer):
         covered, self._norm_covered = getattr(self, "_norm_covered", 0), 0
         count, self._norm_cursor = self._norm_cursor, 0
         if covered != self.flat_p.numel():
-            raise RuntimeError(f"FlatAdam.norm_finalize(): the partial sums cover {covered} of {self.flat_p.numel()} gradient elements")
+            raise RuntimeError(f"{type(self).__name__}.norm_finalize(): the partial sums cover {covered} of {self.flat_p.numel()} gradient elements")
         _ck(_lib.load().egk_grad_norm_finalize(_stream(), _p(self._norm_partials), count, _p(self._hyper_src), self.max_grad_norm,
                                                _p(self._hyper), _p(self._t_dev), _p(self._gate), _p(self._norm_stats)),
             "egk_grad_norm_finalize")
@@ -498,7 +546,7 @@ class FlatAdam(torch.optim.Optimizer):
         synchronisation).  The norm is that of the gradient Adam steps on (averaged over the ranks); mean and largest are taken
         over the steps whose norm was finite, ``skipped`` counts the others."""
         if not self.clipping:
-            raise RuntimeError("FlatAdam.grad_norm_stats(): built without max_grad_norm")
+            raise RuntimeError(f"{type(self).__name__}.grad_norm_stats(): built without max_grad_norm")
         live = self.materialised and getattr(self, "_gate", None) is not None
         vals = self._norm_stats.tolist() if live else [0.0] * 6
         steps, skipped = int(vals[0]), int(vals[4])
@@ -512,9 +560,7 @@ class FlatAdam(torch.optim.Optimizer):
         """The kernel launch alone (capturable).  ``grads``: the buffer to read gradients from (default the f32
         flat buffer; dist.GradSync hands in its bf16 copy after a compressed all-reduce).  ``[lo, hi)``: element range
         of the flat buffers to update (multiples of 8; the pipelined gradient exchange steps chunk by chunk).
-        ``bump`` = (int64 device word, stride): the word moves on by ``stride`` inside this launch (egk_adam_step_bump)."""
-        g = self.param_groups[0]
-        b1, b2 = g["betas"]
+        ``bump`` = (int64 device word, stride): the word moves on by ``stride`` inside this launch."""
         grads = self.flat_g if grads is None else grads
         hi = self.flat_p.numel() if hi is None else hi
         if hi <= lo:
@@ -528,24 +574,28 @@ class FlatAdam(torch.optim.Optimizer):
             self._lo_fresh = []  # (the parameters move: every low half is stale)
         if self.clipping:  # (behind ``norm_finalize``: its coefficient is in the step constants, its gate decides whether the step happens)
             self._norm_buffers()
-            _ck(_lib.load().egk_adam_step_gated(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
-                                                _p(self.flat_m[sl]), _p(self.flat_v[sl]), hi - lo, _p(self._hyper), b1, b2,
-                                                g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
-                                                _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0,
-                                                _p(self._gate)),
-                "egk_adam_step_gated")
-            return
-        if bump is not None or lo16 is not None:
-            _ck(_lib.load().egk_adam_step_bump(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
-                                               _p(self.flat_m[sl]), _p(self.flat_v[sl]), hi - lo, _p(self._hyper), b1, b2,
-                                               g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
-                                               _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0),
-                "egk_adam_step_bump")
-            return
-        _ck(_lib.load().egk_adam_step(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
-                                      _p(self.flat_m[sl]), _p(self.flat_v[sl]), hi - lo, _p(self._hyper), b1, b2,
-                                      g["eps"], g["weight_decay"], _p(self.flat_w16[sl])),
-            "egk_adam_step")
+        self._launch_rule(sl, grads, lo16, bump, self._gate if self.clipping else None)
+
+    def _launch_rule(self, sl, grads, lo16, bump, gate) -> None:
+        """The rule's launch over the slice ``sl`` of the flat buffers."""
+        raise NotImplementedError
+
+    def _optim_step(self, rule: int, sl, grads, lo16, bump, gate, **scalars) -> None:
+        """One egk_optim_step launch (include/egopack_optim.h); ``scalars``: the descriptor's beta1 .. nesterov."""
+        d = _lib.OptimDesc()
+        d.rule, d.g_dtype, d.n = rule, 1 if grads.dtype == torch.bfloat16 else 0, sl.stop - sl.start
+        d.p, d.g, d.hyper, d.t_dev = self.flat_p[sl].data_ptr(), grads[sl].data_ptr(), self._hyper.data_ptr(), self._t_dev.data_ptr()
+        for name, buf in zip(("state0", "state1"), self._state_bufs):
+            setattr(d, name, buf[sl].data_ptr())
+        for name, val in scalars.items():
+            setattr(d, name, val)
+        d.bf16_shadow = self.flat_w16[sl].data_ptr()
+        d.bf16_lo_shadow = lo16.data_ptr() if lo16 is not None else None
+        if bump is not None:
+            d.bump_word, d.bump = bump[0].data_ptr(), int(bump[1])
+        d.gate = gate.data_ptr() if gate is not None else None
+        import ctypes as C
+        _ck(_lib.load().egk_optim_step(_stream(), C.byref(d)), "egk_optim_step")
 
     @torch.no_grad()
     def step(self, closure=None, grads=None):
@@ -558,3 +608,103 @@ class FlatAdam(torch.optim.Optimizer):
             self.norm_finalize()
         self.launch(grads)
         self.step_count += 1
+
+
+class FlatAdam(FlatOptimizer):
+    """torch.optim.Adam (L2 weight decay) through the egk_adam_step* entry points; ``decoupled_weight_decay=True``: AdamW's rule
+    (``p *= 1 - lr * wd`` in front of Adam's update on the bare gradient) through egk_optim_step."""
+
+    def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, max_grad_norm=None, *, decoupled_weight_decay: bool = False, amsgrad: bool = False,
+                 maximize: bool = False, foreach=None, fused=None, capturable: bool = False, differentiable: bool = False):
+        _refuse_unbuilt(type(self).__name__, amsgrad, maximize)
+        if not 0.0 <= lr:  # (torch.optim.Adam's checks and messages)
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        if self.decoupled_weight_decay:  # (what torch.optim.Adam needs to read the saved group as AdamW's; plain Adam's group as it was)
+            defaults["decoupled_weight_decay"] = True
+        super().__init__(params, defaults, state_keys=("exp_avg", "exp_avg_sq"), max_grad_norm=max_grad_norm)
+
+    _fixed_keys = ("decoupled_weight_decay",)
+
+    # (bench.py and the tests read the moments by these names)
+    @property
+    def flat_m(self):
+        return self._state_bufs[0] if self._state_bufs else None
+
+    @property
+    def flat_v(self):
+        return self._state_bufs[1] if self._state_bufs else None
+
+    def _launch_rule(self, sl, grads, lo16, bump, gate) -> None:
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        n = sl.stop - sl.start
+        if self.decoupled_weight_decay:
+            self._optim_step(_lib.OPT_ADAMW, sl, grads, lo16, bump, gate, beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"])
+            return
+        if gate is not None:
+            _ck(_lib.load().egk_adam_step_gated(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
+                                                _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
+                                                g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
+                                                _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0,
+                                                _p(gate)),
+                "egk_adam_step_gated")
+            return
+        if bump is not None or lo16 is not None:
+            _ck(_lib.load().egk_adam_step_bump(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
+                                               _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
+                                               g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
+                                               _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0),
+                "egk_adam_step_bump")
+            return
+        _ck(_lib.load().egk_adam_step(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
+                                      _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
+                                      g["eps"], g["weight_decay"], _p(self.flat_w16[sl])),
+            "egk_adam_step")
+
+
+
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW: ``FlatAdam(decoupled_weight_decay=True)`` with AdamW's default ``weight_decay`` of 0.01."""
+
+    def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, max_grad_norm=None, **hints):
+        hints.pop("decoupled_weight_decay", None)  # (the class IS the flag)
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, decoupled_weight_decay=True, **hints)
+
+
+class FlatSGD(FlatOptimizer):
+    """torch.optim.SGD: weight decay, momentum, dampening, nesterov.  With momentum one state buffer (``momentum_buffer``), none
+    without; the first step that happens stores the gradient as the buffer (the kernel reads the device step counter)."""
+
+    def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm=None, *, maximize: bool = False, foreach=None,
+                 fused=None, capturable: bool = False, differentiable: bool = False):
+        _refuse_unbuilt(type(self).__name__, False, maximize)
+        if lr < 0.0:  # (torch.optim.SGD's checks and messages)
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov))
+        super().__init__(params, defaults, state_keys=("momentum_buffer",) if momentum != 0 else (), max_grad_norm=max_grad_norm)
+
+    _fixed_keys = ("momentum",)  # (zero or not decides whether there is a buffer: the constructor's value stands)
+
+    def _launch_rule(self, sl, grads, lo16, bump, gate) -> None:
+        g = self.param_groups[0]
+        self._optim_step(_lib.OPT_SGD, sl, grads, lo16, bump, gate, weight_decay=g["weight_decay"], momentum=g["momentum"],
+                         dampening=g["dampening"], nesterov=int(bool(g["nesterov"])))

@@ -13,7 +13,7 @@ from . import data as D
 from . import ops
 from .config import Cfg, compose, instantiate
 from .criterion import BCEWithLogitsNone, CrossEntropyNone, MetricSelectorWrapper
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatAdamW, FlatSGD
 
 logger = logging.getLogger("egopack")
 TASKS = ("ar", "oscc", "lta", "pnr")
@@ -144,14 +144,22 @@ def build_criteria(dsets):
             "oscc": CrossEntropyNone(), "pnr": BCEWithLogitsNone()}
 
 
+OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
+
+
 def build_optimizer(cfg, params):
-    """``_target_: torch.optim.Adam`` of the config is served by the flat-buffer Adam (same arithmetic)."""
+    """``_target_: torch.optim.Adam | AdamW | SGD`` of the config is served by the flat-buffer optimizer of the same rule (same
+    arithmetic, same keyword arguments); ``torch.optim.Adam`` with ``decoupled_weight_decay: true`` is AdamW's rule."""
     ocfg = dict(cfg.optimizer)
     target = ocfg.pop("_target_")
-    if target != "torch.optim.Adam":
-        raise ValueError(f"optimizer {target}: only torch.optim.Adam is on the hot path")
+    if target not in OPTIMIZERS:
+        raise ValueError(f"optimizer {target}: the flat-buffer kernels serve {', '.join(OPTIMIZERS)}")
+    cls = OPTIMIZERS[target]
+    if cls is FlatAdam and ocfg.pop("decoupled_weight_decay", False):
+        cls = FlatAdamW
+        ocfg.setdefault("weight_decay", 0.0)  # (torch.optim.Adam's default, not AdamW's)
     # (``grad_clip_norm`` sits beside ``optimizer:``, not inside it: that block is handed to Hydra's instantiate by the reference)
-    return FlatAdam(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0))
+    return cls(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0))
 
 
 def log_grad_norms(logger, epoch: int, step) -> None:

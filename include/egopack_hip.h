@@ -742,4 +742,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 #ifdef __cplusplus
 }
 #endif
+
+/* the update rules of the flat-buffer optimizer behind one launch interface (egk_optim_step) */
+#include "egopack_optim.h"
+
 #endif /* EGOPACK_HIP_H */
