@@ -2063,6 +2063,7 @@ class _RowLN(torch.autograd.Function):
         ctx.save_for_backward(x, wc, bc, mean, rstd, mask)
         if _mask_tap["on"] and mask is not None:
             _mask_tap["masks"].append(mask)
+            _mask_tap["launches"].append(("rows", seed, off, rows, cols))
         return y
 
     @staticmethod
@@ -2096,21 +2097,25 @@ class _RowLN(torch.autograd.Function):
         return dx, (None if slot_w is not None else dw), (None if slot_b is not None else db), None, None, None, None
 
 
-_mask_tap = {"on": False, "masks": []}
+_mask_tap = {"on": False, "masks": [], "launches": []}
 
 
 class tap_dropout_masks:
     """``with ops.tap_dropout_masks() as masks:`` -- the keep masks (uint8, 1 = keep) of every fused LayerNorm + dropout launch
     issued inside, in issue order: tests hand them to the oracle (``oracle.path.trn_pooling(masks=...)``) so that a step with
-    active dropout can be compared element by element."""
+    active dropout can be compared element by element.  ``tap.launches`` (``tap = ops.tap_dropout_masks()``; ``with tap as
+    masks:``) records what every dropout launch issued inside was given, one tuple per launch in issue order:
+    ``("rows", seed, host offset, rows, cols)`` for a fused LayerNorm + dropout launch (``launches`` filtered by ``"rows"`` lines up
+    with ``masks``), ``("flat", seed, host offset, 1, n)`` for a ``dropout`` launch.  Read-only: nothing reads it back."""
 
     def __enter__(self):
-        self.prev = (_mask_tap["on"], _mask_tap["masks"])
-        _mask_tap["on"], _mask_tap["masks"] = True, []
+        self.prev = (_mask_tap["on"], _mask_tap["masks"], _mask_tap["launches"])
+        _mask_tap["on"], _mask_tap["masks"], _mask_tap["launches"] = True, [], []
+        self.launches = _mask_tap["launches"]
         return _mask_tap["masks"]
 
     def __exit__(self, *a):
-        _mask_tap["on"], _mask_tap["masks"] = self.prev
+        _mask_tap["on"], _mask_tap["masks"], _mask_tap["launches"] = self.prev
 
 
 def row_layernorm(x, w, b, eps=1e-5, relu=False, p=0.0, training=False):
@@ -3188,6 +3193,8 @@ class _Dropout(torch.autograd.Function):
                                         _p(rng_device_offset(x.device)), _dt(x)), "egk_dropout_fwd")
         ctx.p = p
         ctx.save_for_backward(mask)
+        if _mask_tap["on"]:
+            _mask_tap["launches"].append(("flat", seed, off, 1, x.numel()))
         return y
 
     @staticmethod
