@@ -20,6 +20,7 @@ HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["EGK_LIB_PATH"]) if os.environ.get("EGK_LIB_PATH") else HERE / "libegopack_hip.so"  # (env: development A/B of two builds)
 HEADER = HERE.parent / "include" / "egopack_hip.h"
 OPTIM_HEADER = HERE.parent / "include" / "egopack_optim.h"  # included by egopack_hip.h; its symbols: OPTIM_SIGNATURES
+OPTIM_GROUPS_HEADER = HERE.parent / "include" / "egopack_optim_groups.h"  # likewise; its symbols: OPTIM_GROUPS_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -89,6 +90,11 @@ class OptimDesc(C.Structure):
     _fields_ = [("rule", i32), ("g_dtype", i32), ("n", i64), ("p", vp), ("g", vp), ("state0", vp), ("state1", vp), ("hyper", vp),
                 ("t_dev", vp), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", f32), ("weight_decay", f32), ("momentum", f32), ("dampening", f32),
                 ("nesterov", i32), ("bf16_shadow", vp), ("bf16_lo_shadow", vp), ("bump_word", vp), ("bump", i64), ("gate", vp)]
+
+
+class OptimGroups(C.Structure):
+    """struct egk_optim_groups (include/egopack_optim_groups.h)."""
+    _fields_ = [("base", i64), ("n_seg", i32), ("n_groups", i32), ("seg_begin", vp), ("seg_group", vp), ("group_hyper", vp)]
 
 
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
@@ -215,6 +221,12 @@ OPTIM_SIGNATURES = {
 }
 
 
+# ... and include/egopack_optim_groups.h (the third ledger: tests/test_param_groups_cpu.py over tests/test_gpu_bounds_param_groups.py)
+OPTIM_GROUPS_SIGNATURES = {
+    "egk_optim_step_groups": (C.c_int, [vp, C.POINTER(OptimDesc), C.POINTER(OptimGroups)]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -231,6 +243,11 @@ def optim_header_symbols() -> list:
     return _declared(OPTIM_HEADER)
 
 
+def optim_groups_header_symbols() -> list:
+    """Every function name declared in include/egopack_optim_groups.h."""
+    return _declared(OPTIM_GROUPS_HEADER)
+
+
 _lib = None
 
 
@@ -244,7 +261,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m egopack_amd.build` "
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items()]:
+    for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -104,6 +104,7 @@ enum KernelId {
     KID_SUM_SCALE,
     KID_ADAM,
     KID_OPTIM,             // egk_optim_step: the update rules behind one launch interface (optim_rules.hip)
+    KID_OPTIM_GROUPS,      // egk_optim_step_groups: the same rules with lr / weight decay per parameter group (optim_rules.hip)
     KID_COUNT
 };
 

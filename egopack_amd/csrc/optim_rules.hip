@@ -41,42 +41,58 @@ __device__ __forceinline__ void optim_update(float& p, float g, float& a, float&
     }
 }
 
+// the four elements [i, i + 4) of a span in 16-byte accesses; ``consts()`` is asked for the constants once the loads are issued
+template <int KIND, typename GT, typename CF>
+__device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                                           long long i, CF consts, bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo) {
+    constexpr int NS = StateCount<KIND>::value;
+    float4 pv = *reinterpret_cast<float4*>(p + i);
+    const float4 gv = ld4t(g + i, 0, 4, true);
+    float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
+    if constexpr (NS >= 1) av = *reinterpret_cast<float4*>(s0 + i);
+    if constexpr (NS >= 2) bv = *reinterpret_cast<float4*>(s1 + i);
+    const OptimConsts c = consts();
+    float* pp = &pv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) optim_update<KIND>(pp[t], gp[t], ap[t], bp[t], c);
+    *reinterpret_cast<float4*>(p + i) = pv;
+    if constexpr (NS >= 1) *reinterpret_cast<float4*>(s0 + i) = av;
+    if constexpr (NS >= 2) *reinterpret_cast<float4*>(s1 + i) = bv;
+    if (shadow) st4t(shadow + i, 0, 4, true, pv);
+    if (shadow_lo) {  // bf16(p - bf16(p)): egk_split_bf16's bits
+        const float lo4[4] = {pp[0] - bf2f(f2bf(pp[0])), pp[1] - bf2f(f2bf(pp[1])), pp[2] - bf2f(f2bf(pp[2])), pp[3] - bf2f(f2bf(pp[3]))};
+        st4t(shadow_lo + i, 0, 4, true, make_float4(lo4[0], lo4[1], lo4[2], lo4[3]));
+    }
+}
+
+// the scalar tail [i, n) of a span (n - i < 4)
+template <int KIND, typename GT>
+__device__ __forceinline__ void optim_tail(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                                           long long i, long long n, const OptimConsts& c, bf16_t* __restrict__ shadow,
+                                           bf16_t* __restrict__ shadow_lo) {
+    constexpr int NS = StateCount<KIND>::value;
+    for (long long j = i; j < n; ++j) {
+        float a = 0.f, b = 0.f;
+        if constexpr (NS >= 1) a = s0[j];
+        if constexpr (NS >= 2) b = s1[j];
+        optim_update<KIND>(p[j], ld1t(g + j), a, b, c);
+        if constexpr (NS >= 1) s0[j] = a;
+        if constexpr (NS >= 2) s1[j] = b;
+        if (shadow) shadow[j] = f2bf(p[j]);
+        if (shadow_lo) shadow_lo[j] = f2bf(p[j] - bf2f(f2bf(p[j])));
+    }
+}
+
 // the elements [0, n) of one span, grid-stride over ``nblk`` workgroups
 template <int KIND, typename GT>
 __device__ __forceinline__ void optim_span(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
                                            long long n, const OptimConsts& c, bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
                                            int blk, int nblk) {
-    constexpr int NS = StateCount<KIND>::value;
     for (long long i = ((long long)blk * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)nblk * blockDim.x * 4) {
-        if (i + 4 <= n) {
-            float4 pv = *reinterpret_cast<float4*>(p + i);
-            const float4 gv = ld4t(g + i, 0, 4, true);
-            float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
-            if constexpr (NS >= 1) av = *reinterpret_cast<float4*>(s0 + i);
-            if constexpr (NS >= 2) bv = *reinterpret_cast<float4*>(s1 + i);
-            float* pp = &pv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) optim_update<KIND>(pp[t], gp[t], ap[t], bp[t], c);
-            *reinterpret_cast<float4*>(p + i) = pv;
-            if constexpr (NS >= 1) *reinterpret_cast<float4*>(s0 + i) = av;
-            if constexpr (NS >= 2) *reinterpret_cast<float4*>(s1 + i) = bv;
-            if (shadow) st4t(shadow + i, 0, 4, true, pv);
-            if (shadow_lo) {  // bf16(p - bf16(p)): egk_split_bf16's bits
-                const float lo4[4] = {pp[0] - bf2f(f2bf(pp[0])), pp[1] - bf2f(f2bf(pp[1])), pp[2] - bf2f(f2bf(pp[2])), pp[3] - bf2f(f2bf(pp[3]))};
-                st4t(shadow_lo + i, 0, 4, true, make_float4(lo4[0], lo4[1], lo4[2], lo4[3]));
-            }
-        } else {
-            for (long long j = i; j < n; ++j) {
-                float a = 0.f, b = 0.f;
-                if constexpr (NS >= 1) a = s0[j];
-                if constexpr (NS >= 2) b = s1[j];
-                optim_update<KIND>(p[j], ld1t(g + j), a, b, c);
-                if constexpr (NS >= 1) s0[j] = a;
-                if constexpr (NS >= 2) s1[j] = b;
-                if (shadow) shadow[j] = f2bf(p[j]);
-                if (shadow_lo) shadow_lo[j] = f2bf(p[j] - bf2f(f2bf(p[j])));
-            }
-        }
+        if (i + 4 <= n)
+            optim_quad<KIND, GT>(p, g, s0, s1, i, [&]() -> const OptimConsts& { return c; }, shadow, shadow_lo);
+        else
+            optim_tail<KIND, GT>(p, g, s0, s1, i, n, c, shadow, shadow_lo);
     }
 }
 
@@ -84,6 +100,26 @@ struct OptimHyper {  // the host's scalars of a launch
     float b1, b2, omb1, omb2, eps, wd, mu, damp1;
     int nesterov;
 };
+
+// the constants of a launch from its learning rate and weight decay (of the launch: optim_kernel; of a group: optim_groups_kernel)
+template <int KIND>
+__device__ __forceinline__ OptimConsts optim_consts(float lr, float wd, const float* __restrict__ hyper, const long long* __restrict__ t_dev,
+                                                    const OptimHyper& h) {
+#pragma clang fp contract(off)
+    OptimConsts c;
+    c.adam = AdamConsts{lr / hyper[1], hyper[2], hyper[3], h.b1, h.b2, h.eps, wd};
+    c.lr = lr;
+    c.decay = (float)(1.0 - (double)lr * (double)wd);  // (torch takes 1 - lr * weight_decay in double and rounds it once)
+    c.wd = wd;
+    c.gs = hyper[3];
+    c.omb1 = h.omb1;
+    c.omb2 = h.omb2;
+    c.mu = h.mu;
+    c.damp1 = h.damp1;
+    c.nesterov = h.nesterov != 0;
+    c.first = KIND == K_SGD_MOMENTUM ? *t_dev == 1 : false;  // (egk_adam_hyper has counted this step)
+    return c;
+}
 
 template <int KIND, typename GT, bool GATED>  // GT: element type of the gradient buffer (f32, or bf16 after a compressed all-reduce)
 __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0,
@@ -95,22 +131,7 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const
     if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
     // (a closed gate -- the gradient norm was not finite -- skips the step: one wave-uniform load, nothing else is touched)
     if (GATED && *gate == 0) return;
-    OptimConsts c;
-    {
-#pragma clang fp contract(off)
-        const float lr = hyper[0];
-        c.adam = AdamConsts{lr / hyper[1], hyper[2], hyper[3], h.b1, h.b2, h.eps, h.wd};
-        c.lr = lr;
-        c.decay = (float)(1.0 - (double)lr * (double)h.wd);  // (torch takes 1 - lr * weight_decay in double and rounds it once)
-        c.wd = h.wd;
-        c.gs = hyper[3];
-        c.omb1 = h.omb1;
-        c.omb2 = h.omb2;
-        c.mu = h.mu;
-        c.damp1 = h.damp1;
-        c.nesterov = h.nesterov != 0;
-        c.first = KIND == K_SGD_MOMENTUM ? *t_dev == 1 : false;  // (egk_adam_hyper has counted this step)
-    }
+    const OptimConsts c = optim_consts<KIND>(hyper[0], h.wd, hyper, t_dev, h);
     optim_span<KIND, GT>(p, g, s0, s1, n, c, shadow, shadow_lo, blockIdx.x, gridDim.x);
 }
 
@@ -126,48 +147,134 @@ static void optim_launch(hipStream_t s, unsigned grid, const egk_optim_desc& d, 
                            (long long*)d.bump_word, (long long)d.bump, (const int*)nullptr);
 }
 
+// ---- parameter groups: lr and weight decay per element from a segment table (include/egopack_optim_groups.h) ----------------------
+struct GroupTable {
+    long long base;
+    int n_seg, n_groups;
+    const long long* __restrict__ seg_begin;
+    const int* __restrict__ seg_group;
+    const float* __restrict__ group_hyper;
+};
+
+// the largest s in [lo, hi] with seg_begin[s] <= e (lo when there is none): every index read lies in [lo + 1, hi], whatever the table holds
+__device__ __forceinline__ int seg_find(const long long* __restrict__ seg_begin, int lo, int hi, long long e) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo + 1) >> 1);
+        if (seg_begin[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// optim_kernel with the constants of the group that holds the element.  The lookup: ONE search per workgroup and 1024-element block
+// for the segment of the block's first element -- workgroup-uniform, so it runs on the scalar unit while the block's vector loads are
+// in flight -- and one comparison that tells whether the block ends inside that segment.  Only the lanes of a block that straddles
+// a boundary search for themselves, over the at most 256 segments a block can touch.  A 16-byte group of elements never
+// straddles (boundaries and base are multiples of 4), so the scalar tail shares the segment of its first element.
+template <int KIND, typename GT, bool GATED>
+__global__ __launch_bounds__(256) void optim_groups_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0,
+                                                           float* __restrict__ s1, long long n, const float* __restrict__ hyper,
+                                                           const long long* __restrict__ t_dev, const OptimHyper h,
+                                                           bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
+                                                           long long* __restrict__ bump_word, long long bump, const int* __restrict__ gate,
+                                                           const GroupTable t) {
+    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
+    if (GATED && *gate == 0) return;
+    for (long long b0 = (long long)blockIdx.x * 1024; b0 < n; b0 += (long long)gridDim.x * 1024) {
+        const long long i = b0 + (long long)threadIdx.x * 4;
+        if (i >= n) continue;
+        auto consts = [&]() -> OptimConsts {
+            const long long first = t.base + b0, last = t.base + (b0 + 1024 < n ? b0 + 1024 : n) - 1;
+            int s = seg_find(t.seg_begin, 0, t.n_seg - 1, first);
+            if (t.seg_begin[s + 1] <= last) {  // (s + 1 <= n_seg: the table has n_seg + 1 entries)
+                const int hi = s + (int)threadIdx.x < t.n_seg - 1 ? s + (int)threadIdx.x : t.n_seg - 1;
+                s = seg_find(t.seg_begin, s, hi, t.base + i);
+            }
+            int grp = t.seg_group[s];
+            grp = grp < 0 ? 0 : grp >= t.n_groups ? t.n_groups - 1 : grp;
+            const float2 lw = *reinterpret_cast<const float2*>(t.group_hyper + 4 * grp);
+            return optim_consts<KIND>(lw.x, lw.y, hyper, t_dev, h);
+        };
+        if (i + 4 <= n)
+            optim_quad<KIND, GT>(p, g, s0, s1, i, consts, shadow, shadow_lo);
+        else
+            optim_tail<KIND, GT>(p, g, s0, s1, i, n, consts(), shadow, shadow_lo);
+    }
+}
+
+template <int KIND, typename GT>
+static void optim_groups_launch(hipStream_t s, unsigned grid, const egk_optim_desc& d, const OptimHyper& h, const GroupTable& t) {
+    if (d.gate)
+        hipLaunchKernelGGL((optim_groups_kernel<KIND, GT, true>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
+                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
+                           (long long*)d.bump_word, (long long)d.bump, (const int*)d.gate, t);
+    else
+        hipLaunchKernelGGL((optim_groups_kernel<KIND, GT, false>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
+                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
+                           (long long*)d.bump_word, (long long)d.bump, (const int*)nullptr, t);
+}
+
+// what both entry points refuse, before any launch; ``a``: the descriptor without the state the rule does not have, ``kind``: its kernel
+static int optim_check(const char* who, const egk_optim_desc* d, egk_optim_desc& a, int& kind) {
+    EGK_REQUIRE(d, "%s: null descriptor", who);
+    EGK_REQUIRE(d->rule == EGK_OPT_ADAM || d->rule == EGK_OPT_ADAMW || d->rule == EGK_OPT_SGD,
+                "%s: unknown rule %d (EGK_OPT_ADAM = 0, EGK_OPT_ADAMW = 1, EGK_OPT_SGD = 2)", who, (int)d->rule);
+    EGK_REQUIRE(d->g_dtype == EGK_F32 || d->g_dtype == EGK_BF16, "%s: unknown gradient dtype %d", who, (int)d->g_dtype);
+    EGK_REQUIRE(d->p && d->g && d->hyper, "%s: null pointer", who);
+    EGK_REQUIRE(d->n >= 0, "%s: n >= 0 (got %lld)", who, (long long)d->n);
+    const bool sgd = d->rule == EGK_OPT_SGD;
+    kind = !sgd ? (d->rule == EGK_OPT_ADAM ? K_ADAM : K_ADAMW) : d->momentum != 0.f ? K_SGD_MOMENTUM : K_SGD;
+    if (kind == K_ADAM || kind == K_ADAMW)
+        EGK_REQUIRE(d->state0 && d->state1, "%s: missing state pointer -- Adam and AdamW need state0 (exp_avg) and state1 (exp_avg_sq)", who);
+    if (kind == K_SGD_MOMENTUM)
+        EGK_REQUIRE(d->state0 && d->t_dev, "%s: missing state pointer -- SGD with momentum needs state0 (the momentum buffer) "
+                                           "and t_dev (the step counter)", who);
+    if (sgd) {
+        EGK_REQUIRE(d->momentum >= 0.f, "%s: momentum >= 0 (got %g)", who, (double)d->momentum);
+        EGK_REQUIRE(!d->nesterov || (d->momentum > 0.f && d->dampening == 0.f),
+                    "%s: nesterov momentum requires a momentum and zero dampening", who);
+    }
+    // (state the rule does not have is neither checked nor handed to the kernel)
+    a = *d;
+    if (kind == K_SGD) a.state0 = nullptr;
+    if (kind == K_SGD || kind == K_SGD_MOMENTUM) a.state1 = nullptr;
+    EGK_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.state0 | (uintptr_t)a.state1) & 15) == 0,
+                "%s: buffers must be 16-byte aligned", who);
+    EGK_REQUIRE(((uintptr_t)a.bf16_shadow & 7) == 0, "%s: shadow must be 8-byte aligned", who);
+    EGK_REQUIRE(((uintptr_t)a.bf16_lo_shadow & 7) == 0, "%s: low-half shadow must be 8-byte aligned", who);
+    return 0;
+}
+
+// bytes per parameter: p read + written, each state buffer read + written, the gradient read, the bf16 copies written
+static double optim_bytes(const egk_optim_desc& a, int kind) {
+    const double state_bytes = kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0;
+    return (8.0 + state_bytes + (a.g_dtype == EGK_BF16 ? 2.0 : 4.0) + (a.bf16_shadow ? 2.0 : 0.0) + (a.bf16_lo_shadow ? 2.0 : 0.0)) * (double)a.n;
+}
+
+// the grid of egk_adam_step*: one 1024-element group per workgroup up to 32768 of them (measured there)
+static unsigned optim_grid(long long n) {
+    const long long want = (n / 4 + 255) / 256;
+    const long long cap = 32768;
+    return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
+}
+
+static OptimHyper optim_hyper(const egk_optim_desc& a) {
+    return OptimHyper{(float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), a.eps, a.weight_decay, a.momentum,
+                      (float)(1.0 - (double)a.dampening), a.nesterov ? 1 : 0};
+}
+
 }  // namespace egk
 
 using namespace egk;
 
 extern "C" int egk_optim_step(egk_stream_t stream, const egk_optim_desc* d) {
-    EGK_REQUIRE(d, "egk_optim_step: null descriptor");
-    EGK_REQUIRE(d->rule == EGK_OPT_ADAM || d->rule == EGK_OPT_ADAMW || d->rule == EGK_OPT_SGD,
-                "egk_optim_step: unknown rule %d (EGK_OPT_ADAM = 0, EGK_OPT_ADAMW = 1, EGK_OPT_SGD = 2)", (int)d->rule);
-    EGK_REQUIRE(d->g_dtype == EGK_F32 || d->g_dtype == EGK_BF16, "egk_optim_step: unknown gradient dtype %d", (int)d->g_dtype);
-    EGK_REQUIRE(d->p && d->g && d->hyper, "egk_optim_step: null pointer");
-    EGK_REQUIRE(d->n >= 0, "egk_optim_step: n >= 0 (got %lld)", (long long)d->n);
-    const bool sgd = d->rule == EGK_OPT_SGD;
-    const int kind = !sgd ? (d->rule == EGK_OPT_ADAM ? K_ADAM : K_ADAMW) : d->momentum != 0.f ? K_SGD_MOMENTUM : K_SGD;
-    if (kind == K_ADAM || kind == K_ADAMW)
-        EGK_REQUIRE(d->state0 && d->state1, "egk_optim_step: missing state pointer -- Adam and AdamW need state0 (exp_avg) and state1 (exp_avg_sq)");
-    if (kind == K_SGD_MOMENTUM)
-        EGK_REQUIRE(d->state0 && d->t_dev, "egk_optim_step: missing state pointer -- SGD with momentum needs state0 (the momentum buffer) "
-                                           "and t_dev (the step counter)");
-    if (sgd) {
-        EGK_REQUIRE(d->momentum >= 0.f, "egk_optim_step: momentum >= 0 (got %g)", (double)d->momentum);
-        EGK_REQUIRE(!d->nesterov || (d->momentum > 0.f && d->dampening == 0.f),
-                    "egk_optim_step: nesterov momentum requires a momentum and zero dampening");
-    }
-    // (state the rule does not have is neither checked nor handed to the kernel)
-    egk_optim_desc a = *d;
-    if (kind == K_SGD) a.state0 = nullptr;
-    if (kind == K_SGD || kind == K_SGD_MOMENTUM) a.state1 = nullptr;
-    EGK_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.state0 | (uintptr_t)a.state1) & 15) == 0,
-                "egk_optim_step: buffers must be 16-byte aligned");
-    EGK_REQUIRE(((uintptr_t)a.bf16_shadow & 7) == 0, "egk_optim_step: shadow must be 8-byte aligned");
-    EGK_REQUIRE(((uintptr_t)a.bf16_lo_shadow & 7) == 0, "egk_optim_step: low-half shadow must be 8-byte aligned");
+    egk_optim_desc a;
+    int kind = 0;
+    if (const int rc = optim_check("egk_optim_step", d, a, kind)) return rc;
     if (a.n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    // bytes per parameter: p read + written, each state buffer read + written, the gradient read, the bf16 copies written
-    const double state_bytes = kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0;
-    ProfScope prof(KID_OPTIM, s, 0, (8.0 + state_bytes + (a.g_dtype == EGK_BF16 ? 2.0 : 4.0) + (a.bf16_shadow ? 2.0 : 0.0) +
-                                    (a.bf16_lo_shadow ? 2.0 : 0.0)) * (double)a.n);
-    // the grid of egk_adam_step*: one 1024-element group per workgroup up to 32768 of them (measured there)
-    const long long want = (a.n / 4 + 255) / 256;
-    const long long cap = 32768;
-    const unsigned grid = (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
-    const OptimHyper h{(float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), a.eps, a.weight_decay, a.momentum, (float)(1.0 - (double)a.dampening), a.nesterov ? 1 : 0};
+    ProfScope prof(KID_OPTIM, s, 0, optim_bytes(a, kind));
+    const unsigned grid = optim_grid(a.n);
+    const OptimHyper h = optim_hyper(a);
     switch (kind) {
         case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_ADAM, T>(s, grid, a, h))); break;
         case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_ADAMW, T>(s, grid, a, h))); break;
@@ -175,4 +282,30 @@ extern "C" int egk_optim_step(egk_stream_t stream, const egk_optim_desc* d) {
         default: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_SGD_MOMENTUM, T>(s, grid, a, h))); break;
     }
     return check_launch("egk_optim_step");
+}
+
+extern "C" int egk_optim_step_groups(egk_stream_t stream, const egk_optim_desc* d, const egk_optim_groups* g) {
+    egk_optim_desc a;
+    int kind = 0;
+    if (const int rc = optim_check("egk_optim_step_groups", d, a, kind)) return rc;
+    EGK_REQUIRE(g, "egk_optim_step_groups: null group table");
+    EGK_REQUIRE(g->n_seg >= 1 && g->n_seg <= 4096, "egk_optim_step_groups: n_seg in 1..4096 (got %d)", (int)g->n_seg);
+    EGK_REQUIRE(g->n_groups >= 1 && g->n_groups <= 64, "egk_optim_step_groups: n_groups in 1..64 (got %d)", (int)g->n_groups);
+    EGK_REQUIRE(g->seg_begin && g->seg_group && g->group_hyper, "egk_optim_step_groups: null table pointer");
+    EGK_REQUIRE(g->base >= 0 && g->base % 4 == 0, "egk_optim_step_groups: base must be a non-negative multiple of 4 (got %lld)", (long long)g->base);
+    EGK_REQUIRE(((uintptr_t)g->seg_begin & 7) == 0 && ((uintptr_t)g->seg_group & 3) == 0 && ((uintptr_t)g->group_hyper & 15) == 0,
+                "egk_optim_step_groups: misaligned table pointer (seg_begin 8-byte, seg_group 4-byte, group_hyper 16-byte)");
+    if (a.n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_OPTIM_GROUPS, s, 0, optim_bytes(a, kind));
+    const unsigned grid = optim_grid(a.n);
+    const OptimHyper h = optim_hyper(a);
+    const GroupTable t{(long long)g->base, (int)g->n_seg, (int)g->n_groups, (const long long*)g->seg_begin, (const int*)g->seg_group, g->group_hyper};
+    switch (kind) {
+        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_ADAM, T>(s, grid, a, h, t))); break;
+        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_ADAMW, T>(s, grid, a, h, t))); break;
+        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_SGD, T>(s, grid, a, h, t))); break;
+        default: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_SGD_MOMENTUM, T>(s, grid, a, h, t))); break;
+    }
+    return check_launch("egk_optim_step_groups");
 }

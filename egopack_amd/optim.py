@@ -13,7 +13,12 @@ frozen prototypes) are left alone, exactly as torch.optim.Adam skips ``grad is N
 slots, the bf16 copies and low halves, the device-side step constants, clipping, ``launch(grads, lo, hi, bump)``.  A rule
 (``FlatAdam``, ``FlatAdamW``, ``FlatSGD``) names its per-parameter state -- two buffers, one or none, in torch's
 state-dict names -- and issues its launch: ``FlatAdam`` through the egk_adam_step* entry points, the others through
-egk_optim_step (include/egopack_optim.h)."""
+egk_optim_step (include/egopack_optim.h).
+
+Parameter groups (a list of ``{"params": [...], "lr": ..., "weight_decay": ...}`` dicts, as torch.optim takes them) may differ in
+``lr`` and ``weight_decay``.  The flat layout does not depend on the grouping; the groups become a segment table over it
+(``group_segments``) that every launch resolves per element, in the one launch (egk_optim_step_groups,
+include/egopack_optim_groups.h).  One group -- a plain list, or a single dict -- issues exactly what it always issued."""
 from __future__ import annotations
 
 import math
@@ -52,22 +57,45 @@ def _refuse_unbuilt(name: str, amsgrad, maximize) -> None:
             raise ValueError(f"{name}: {key}=True is not built (the flat-buffer kernels implement the plain rule only)")
 
 
+# keys of a parameter group that may differ between groups: the kernel looks these two up per element
+_PER_GROUP_KEYS = ("lr", "weight_decay")
+# ... and keys that select the rule or its constants for the whole launch: a group that sets one differently is refused by name
+_SHARED_KEYS = ("betas", "eps", "momentum", "dampening", "nesterov", "decoupled_weight_decay", "amsgrad", "maximize")
+MAX_GROUPS, MAX_SEGMENTS = 64, 4096  # (include/egopack_optim_groups.h)
+
+
+def _unique(params):
+    seen, uniq = set(), []
+    for p in params:
+        if id(p) not in seen:
+            seen.add(id(p))
+            uniq.append(p)
+    return uniq
+
+
 class FlatOptimizer(torch.optim.Optimizer):
-    def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None):
-        """``state_keys``: torch's state-dict names of the rule's per-parameter buffers, in the order of ``state_buffers()``.
+    def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None, layout_order=None):
+        """``layout_order``: the parameters in the order their slots take in the flat buffers (default: constructor order, groups one
+        after the other).  A caller that splits one list into groups hands the list in here, and the layout -- backward order, the
+        regions the step slices, the classifier banks -- stays what the ungrouped optimizer builds.
+        ``state_keys``: torch's state-dict names of the rule's per-parameter buffers, in the order of ``state_buffers()``.
         ``max_grad_norm`` (None or 0: off): clip the global L2 norm of the gradient to it before every update --
         torch.nn.utils.clip_grad_norm_'s arithmetic, computed on the device inside the step (see ``norm_partials``)."""
         params = [p for p in params]
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"{type(self).__name__}: max_grad_norm must be None, 0 (off) or positive, got {max_grad_norm!r}")
-        if len({id(p) for p in params}) != len(params):  # the reference passes some parameters twice
-            seen, uniq = set(), []
-            for p in params:
-                if id(p) not in seen:
-                    seen.add(id(p))
-                    uniq.append(p)
-            params = uniq
+        if params and all(isinstance(g, dict) for g in params):
+            # parameter groups: a parameter listed twice INSIDE a group is kept once; one in two groups is torch's error
+            params = [{**g, "params": _unique([g["params"]] if torch.is_tensor(g["params"]) else list(g["params"]))} for g in params]
+        elif len({id(p) for p in params}) != len(params):  # the reference passes some parameters twice
+            params = _unique(params)
         super().__init__(params, defaults)
+        if len(self.param_groups) > MAX_GROUPS:
+            raise ValueError(f"{type(self).__name__}: at most {MAX_GROUPS} parameter groups (got {len(self.param_groups)})")
+        self._check_groups()
+        self.layout_order = list(layout_order) if layout_order is not None else None
+        self._segments = None       # [(begin, end, group)] over the flat buffers once materialised
+        self._group_host = None     # the per-group (lr, weight_decay) last uploaded
         self.flat_p = self.flat_g = self.flat_w16 = None
         self._state_keys = tuple(state_keys)
         self._state_bufs: List[torch.Tensor] = []  # one flat f32 buffer per state key
@@ -84,27 +112,97 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.norm_regions = None    # [lo, hi) pieces the eager ``step`` takes the norm's partial sums over (None: one piece)
         self._norm_cursor = 0       # partial-sum slots written since the last ``norm_finalize``
 
+    # -- parameter groups ---------------------------------------------------------------------------------------------------------
+    @property
+    def grouped(self) -> bool:
+        """Several parameter groups: the launches resolve lr / weight_decay per element (one group: the plain entry points)."""
+        return len(self.param_groups) > 1
+
+    def _check_groups(self) -> None:
+        """Groups may differ in ``lr`` and ``weight_decay``; any other key that differs is refused by name."""
+        first = self.param_groups[0]
+        for gi, g in enumerate(self.param_groups[1:], 1):
+            for key in (*self.defaults, *(k for k in _SHARED_KEYS if k not in self.defaults)):
+                if key not in _PER_GROUP_KEYS and g.get(key) != first.get(key):
+                    raise ValueError(f"{type(self).__name__}: parameter groups 0 and {gi} differ in {key!r} ({first.get(key)!r} and "
+                                     f"{g.get(key)!r}) -- only {' and '.join(_PER_GROUP_KEYS)} may differ between groups")
+
+    def _all_params(self) -> list:
+        """Every parameter in constructor order, groups one after the other: the indices of the state dict."""
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def _live(self) -> list:
+        """The parameters that have a gradient, in layout order."""
+        live = [p for p in self._all_params() if p.requires_grad and p.grad is not None]
+        if self.layout_order is not None:  # (stable: parameters the order does not name follow, in constructor order)
+            pos = {id(p): i for i, p in reversed(list(enumerate(self.layout_order)))}
+            live.sort(key=lambda p: pos.get(id(p), len(pos)))
+        return live
+
+    @staticmethod
+    def _slot_len(p) -> int:
+        # slots aligned to 16 bytes in the bf16 shadow (32 B in f32).  A matrix whose row count is not a multiple of
+        # 64 (the classifier layers: 478, 115, 2 ... rows) gets its slot padded to whole 64-row blocks: the padding
+        # stays zero under every rule (zero gradient, zero state, zero weight), and the padded bf16 copy is the K-major
+        # operand of the layer's dX contraction on the pipelined kernel (ops._Linear.backward).
+        if p.dim() == 2 and p.shape[0] % 64:
+            n = (p.shape[0] + 63) // 64 * 64 * p.shape[1]
+        elif p.dim() == 1 and getattr(p, "_egk_bank", None) is not None:
+            n = (p.numel() + 63) // 64 * 64  # a bank's bias vector lines up with the padded rows of its weights
+        else:
+            n = p.numel()
+        return (n + 7) // 8 * 8
+
+    def _layout(self, live):
+        """(parameters in flat order, slot lengths, segments) -- host arithmetic only.  The order is that of the live parameters of
+        all groups, banks pulled together: it does not depend on the grouping.  A slot with its alignment and 64-row padding belongs
+        to its parameter's group; adjacent slots of one group merge into one segment ``(begin, end, group)``."""
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+        live = self._bank_order(live)
+        sizes = [self._slot_len(p) for p in live]
+        segs, off = [], 0
+        for p, sz in zip(live, sizes):
+            gi = group_of[id(p)]
+            if segs and segs[-1][2] == gi:
+                segs[-1] = (segs[-1][0], off + sz, gi)
+            else:
+                segs.append((off, off + sz, gi))
+            off += sz
+        self._check_segments(segs, off)
+        return live, sizes, segs
+
+    def _check_segments(self, segs, total) -> None:
+        at = 0
+        for b, e, gi in segs:
+            if b != at or e <= b or b % 4 or e % 4 or not 0 <= gi < len(self.param_groups):
+                raise RuntimeError(f"{type(self).__name__}: bad segment table at [{b}, {e}) of group {gi} (expected begin {at}; "
+                                   "boundaries are multiples of 4, sorted, without gaps)")
+            at = e
+        if at != total:
+            raise RuntimeError(f"{type(self).__name__}: the segment table covers [0, {at}) of {total} elements")
+        if self.grouped and len(segs) > MAX_SEGMENTS:
+            raise RuntimeError(f"{type(self).__name__}: {len(segs)} segments of alternating parameter groups; one launch resolves at "
+                               f"most {MAX_SEGMENTS}")
+
+    def group_segments(self) -> list:
+        """``[(begin, end, group)]``: which parameter group owns which elements of the flat buffers -- sorted, gap-free, boundaries
+        multiples of 4.  Before the flat buffers exist: the table they would get from the parameters that have a gradient now."""
+        if self._segments is not None:
+            return list(self._segments)
+        live = self._live()
+        if not live:
+            raise RuntimeError(f"{type(self).__name__}.group_segments(): no parameter has a gradient")
+        return self._layout(live)[2]
+
     # -- construction of the flat buffers (first step, once the set of live gradients is known) -------
     def _materialise(self):
-        group = self.param_groups[0]
-        live = [p for p in group["params"] if p.requires_grad and p.grad is not None]
+        live = self._live()
         if not live:
             raise RuntimeError(f"{type(self).__name__}.step(): no parameter has a gradient")
         dev = live[0].device
         if dev.type != "cuda":
             raise RuntimeError(f"{type(self).__name__} needs parameters on a ROCm device (no CPU fallback)")
-        # slots aligned to 16 bytes in the bf16 shadow (32 B in f32).  A matrix whose row count is not a multiple of
-        # 64 (the classifier layers: 478, 115, 2 ... rows) gets its slot padded to whole 64-row blocks: the padding
-        # stays zero under every rule (zero gradient, zero state, zero weight), and the padded bf16 copy is the K-major
-        # operand of the layer's dX contraction on the pipelined kernel (ops._Linear.backward).
-        def slot(p):
-            if p.dim() == 2 and p.shape[0] % 64:
-                return (p.shape[0] + 63) // 64 * 64 * p.shape[1]
-            if p.dim() == 1 and getattr(p, "_egk_bank", None) is not None:
-                return (p.numel() + 63) // 64 * 64  # a bank's bias vector lines up with the padded rows of its weights
-            return p.numel()
-        live = self._bank_order(live)
-        sizes = [(slot(p) + 7) // 8 * 8 for p in live]
+        live, sizes, self._segments = self._layout(live)
         total = sum(sizes)
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -133,6 +231,12 @@ class FlatOptimizer(torch.optim.Optimizer):
         self._hyper_src = torch.zeros(2, dtype=torch.float32, device=dev)  # {lr, grad_scale}: uploaded when they change
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)        # optimizer steps taken (device-side counter)
         self._src_host, self._t_mirror = None, 0
+        if self.grouped:  # the tables every launch resolves lr / weight_decay from (group_hyper: uploaded by sync_hyper_source)
+            segs = self._segments
+            self._seg_begin = torch.tensor([b for b, _, _ in segs] + [segs[-1][1]], dtype=torch.int64, device=dev)
+            self._seg_group = torch.tensor([gi for _, _, gi in segs], dtype=torch.int32, device=dev)
+            self._group_hyper = torch.zeros(len(self.param_groups), 4, dtype=torch.float32, device=dev)
+            self._group_host = None
         if self.clipping:
             self._norm_buffers()
         if self._pending_state is not None:
@@ -208,26 +312,31 @@ class FlatOptimizer(torch.optim.Optimizer):
             raise RuntimeError(f"{type(self).__name__}.state_dict(): the moments are sharded over the ranks (dist.GradSync shard_update: "
                                "every rank holds its own 1 / world slice, zeros elsewhere) -- call GradSync.gather_moments(optimizer) "
                                "on EVERY rank before saving")
-        group = self.param_groups[0]
-        state = {}
-        for i, p in enumerate(group["params"]):
-            mv = self._moment_views.get(id(p))
-            if mv is not None:
-                state[i] = {"step": torch.tensor(float(self._steps_taken())),
-                            **{k: v.detach().clone() for k, v in zip(self._state_keys, mv)}}
+        state, groups, i = {}, [], 0
+        for group in self.param_groups:  # (torch's layout: the indices run on across the groups)
+            pg = {k: v for k, v in group.items() if k != "params"}
+            pg["params"] = list(range(i, i + len(group["params"])))
+            groups.append(pg)
+            for p in group["params"]:
+                mv = self._moment_views.get(id(p))
+                if mv is not None:
+                    state[i] = {"step": torch.tensor(float(self._steps_taken())),
+                                **{k: v.detach().clone() for k, v in zip(self._state_keys, mv)}}
+                i += 1
         if self._pending_state is not None and not state:
             return self._pending_state
-        pg = {k: v for k, v in group.items() if k != "params"}
-        pg["params"] = list(range(len(group["params"])))
-        return {"state": state, "param_groups": [pg]}
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, state_dict):
         """Hyper-parameters now; the state now if the flat buffers exist, otherwise when the first step builds them."""
         self._check_state_rule(state_dict)
-        pg = state_dict["param_groups"][0]
-        for k, v in pg.items():
-            if k not in ("params", *self._fixed_keys) and k in self.param_groups[0]:
-                self.param_groups[0][k] = v
+        if len(state_dict["param_groups"]) != len(self.param_groups):  # (torch.optim.Optimizer.load_state_dict's message)
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        for group, pg in zip(self.param_groups, state_dict["param_groups"]):
+            for k, v in pg.items():
+                if k not in ("params", *self._fixed_keys) and k in group:
+                    group[k] = v
+        self._check_groups()
         if self.materialised:
             self._apply_state(state_dict)
         else:  # snapshot: the caller may keep using (or another optimizer may step) the tensors it handed in
@@ -239,7 +348,7 @@ class FlatOptimizer(torch.optim.Optimizer):
             # The parameters with saved moments ARE the live set of the run that wrote the state: build the flat buffers
             # now, so that the first step after a resume runs on the layout (bf16 operand copies, classifier banks) every
             # later step of the interrupted run ran on -- a resumed run continues it bit for bit.
-            params = self.param_groups[0]["params"]
+            params = self._all_params()
             live = [params[int(i)] for i in state_dict["state"] if int(i) < len(params)]
             if live and all(p.is_cuda and p.requires_grad for p in live):
                 for p in live:
@@ -269,7 +378,7 @@ class FlatOptimizer(torch.optim.Optimizer):
                                f"is {type(self).__name__} and keeps {name(want)}")
 
     def _apply_state(self, state_dict):
-        params = self.param_groups[0]["params"]
+        params = self._all_params()
         steps = []
         with torch.no_grad():
             for i, st in state_dict["state"].items():
@@ -381,6 +490,13 @@ class FlatOptimizer(torch.optim.Optimizer):
             host[0], host[1] = src
             self._hyper_src.copy_(host, non_blocking=True)
             self._src_host = src
+        if self.grouped:  # the per-group {lr, weight_decay, 0, 0} rows the grouped launch reads: uploaded when any of them changes
+            rows = tuple((float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups)
+            if rows != self._group_host:
+                host = torch.zeros(len(rows), 4, dtype=torch.float32, pin_memory=True)
+                host[:, :2] = torch.tensor(rows, dtype=torch.float32)
+                self._group_hyper.copy_(host, non_blocking=True)
+                self._group_host = rows
         if self._t_mirror != self.step_count:
             host = torch.empty(1, dtype=torch.int64, pin_memory=True)
             host[0] = self.step_count
@@ -581,7 +697,9 @@ class FlatOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
     def _optim_step(self, rule: int, sl, grads, lo16, bump, gate, **scalars) -> None:
-        """One egk_optim_step launch (include/egopack_optim.h); ``scalars``: the descriptor's beta1 .. nesterov."""
+        """One egk_optim_step launch (include/egopack_optim.h); ``scalars``: the descriptor's beta1 .. nesterov.  With several
+        parameter groups: one egk_optim_step_groups launch (include/egopack_optim_groups.h) over the same descriptor, the segment
+        table and ``base`` = the slice's first element -- lr and weight_decay come from the table, per element."""
         d = _lib.OptimDesc()
         d.rule, d.g_dtype, d.n = rule, 1 if grads.dtype == torch.bfloat16 else 0, sl.stop - sl.start
         d.p, d.g, d.hyper, d.t_dev = self.flat_p[sl].data_ptr(), grads[sl].data_ptr(), self._hyper.data_ptr(), self._t_dev.data_ptr()
@@ -595,6 +713,12 @@ class FlatOptimizer(torch.optim.Optimizer):
             d.bump_word, d.bump = bump[0].data_ptr(), int(bump[1])
         d.gate = gate.data_ptr() if gate is not None else None
         import ctypes as C
+        if self.grouped:
+            t = _lib.OptimGroups()
+            t.base, t.n_seg, t.n_groups = sl.start, self._seg_group.numel(), len(self.param_groups)
+            t.seg_begin, t.seg_group, t.group_hyper = self._seg_begin.data_ptr(), self._seg_group.data_ptr(), self._group_hyper.data_ptr()
+            _ck(_lib.load().egk_optim_step_groups(_stream(), C.byref(d), C.byref(t)), "egk_optim_step_groups")
+            return
         _ck(_lib.load().egk_optim_step(_stream(), C.byref(d)), "egk_optim_step")
 
     @torch.no_grad()
@@ -616,7 +740,8 @@ class FlatAdam(FlatOptimizer):
 
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, max_grad_norm=None, *, decoupled_weight_decay: bool = False, amsgrad: bool = False,
-                 maximize: bool = False, foreach=None, fused=None, capturable: bool = False, differentiable: bool = False):
+                 maximize: bool = False, foreach=None, fused=None, capturable: bool = False, differentiable: bool = False,
+                 layout_order=None):
         _refuse_unbuilt(type(self).__name__, amsgrad, maximize)
         if not 0.0 <= lr:  # (torch.optim.Adam's checks and messages)
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -632,7 +757,8 @@ class FlatAdam(FlatOptimizer):
         self.decoupled_weight_decay = bool(decoupled_weight_decay)
         if self.decoupled_weight_decay:  # (what torch.optim.Adam needs to read the saved group as AdamW's; plain Adam's group as it was)
             defaults["decoupled_weight_decay"] = True
-        super().__init__(params, defaults, state_keys=("exp_avg", "exp_avg_sq"), max_grad_norm=max_grad_norm)
+        super().__init__(params, defaults, state_keys=("exp_avg", "exp_avg_sq"), max_grad_norm=max_grad_norm,
+                         layout_order=layout_order)
 
     _fixed_keys = ("decoupled_weight_decay",)
 
@@ -649,8 +775,9 @@ class FlatAdam(FlatOptimizer):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         n = sl.stop - sl.start
-        if self.decoupled_weight_decay:
-            self._optim_step(_lib.OPT_ADAMW, sl, grads, lo16, bump, gate, beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"])
+        if self.decoupled_weight_decay or self.grouped:  # (several groups: Adam's rule too goes through the descriptor, same bits)
+            self._optim_step(_lib.OPT_ADAMW if self.decoupled_weight_decay else _lib.OPT_ADAM, sl, grads, lo16, bump, gate,
+                             beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"])
             return
         if gate is not None:
             _ck(_lib.load().egk_adam_step_gated(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
@@ -689,7 +816,7 @@ class FlatSGD(FlatOptimizer):
 
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm=None, *, maximize: bool = False, foreach=None,
-                 fused=None, capturable: bool = False, differentiable: bool = False):
+                 fused=None, capturable: bool = False, differentiable: bool = False, layout_order=None):
         _refuse_unbuilt(type(self).__name__, False, maximize)
         if lr < 0.0:  # (torch.optim.SGD's checks and messages)
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -700,7 +827,8 @@ class FlatSGD(FlatOptimizer):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov))
-        super().__init__(params, defaults, state_keys=("momentum_buffer",) if momentum != 0 else (), max_grad_norm=max_grad_norm)
+        super().__init__(params, defaults, state_keys=("momentum_buffer",) if momentum != 0 else (), max_grad_norm=max_grad_norm,
+                         layout_order=layout_order)
 
     _fixed_keys = ("momentum",)  # (zero or not decides whether there is a buffer: the constructor's value stands)
 

@@ -147,9 +147,61 @@ def build_criteria(dsets):
 OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
 
 
-def build_optimizer(cfg, params):
+PARAM_GROUP_MODULES = ("temporal_graph", "tasks", "graphone")  # the keys of ``param_groups.lr_scale``
+
+
+def build_param_groups(cfg, model, tasks, graphone=None):
+    """What the optimizer is built over.  With the defaults (``param_groups: {no_decay_1d: false, lr_scale: {}}``): the flat
+    parameter list the entry points have always built -- the modules' ``configure_optimizers`` results spliced together, same
+    order, same objects.  Otherwise at most six torch-style group dicts (module x decays-or-not, empty ones dropped):
+    ``no_decay_1d`` gives the parameters with ``dim() <= 1`` (biases, LayerNorm weight and bias) ``weight_decay`` 0, and
+    ``lr_scale.<temporal_graph | tasks | graphone>`` multiplies ``optimizer.lr`` for that module's parameters (missing: 1.0).
+    ``param_groups:`` sits beside ``optimizer:``, not inside it, like ``grad_clip_norm``."""
+    wd = cfg.optimizer.weight_decay
+    parts = [("temporal_graph", list(model.configure_optimizers(wd))),
+             ("tasks", [p for t in TASKS for p in tasks[t].configure_optimizers(wd)]),
+             ("graphone", list(graphone.parameters()) if graphone is not None else [])]
+    flat = [p for _, ps in parts for p in ps]
+    pg = dict(cfg.get("param_groups") or {})
+    unknown = set(pg) - {"no_decay_1d", "lr_scale"}
+    if unknown:
+        raise ValueError(f"param_groups: unknown key(s) {sorted(unknown)} (no_decay_1d, lr_scale)")
+    no_decay = bool(pg.get("no_decay_1d", False))
+    scale = {k: float(v) for k, v in dict(pg.get("lr_scale") or {}).items()}
+    unknown = set(scale) - set(PARAM_GROUP_MODULES)
+    if unknown:
+        raise ValueError(f"param_groups.lr_scale: unknown key(s) {sorted(unknown)} ({', '.join(PARAM_GROUP_MODULES)})")
+    scaled = any(v != 1.0 for v in scale.values())
+    if not no_decay and not scaled:
+        return flat
+    groups, seen = {}, set()
+    for module, ps in parts:
+        for p in ps:
+            if id(p) in seen:  # (the reference passes some parameters twice: the first mention decides)
+                continue
+            seen.add(id(p))
+            bare = no_decay and p.dim() <= 1
+            key = (module if scaled else "all", bare)
+            if key not in groups:
+                groups[key] = {"params": [], "name": key[0] + ("/no_decay" if bare else ""),
+                               "lr": float(cfg.optimizer.lr) * scale.get(module, 1.0) if scaled else float(cfg.optimizer.lr),
+                               "weight_decay": 0.0 if bare else float(wd)}
+            groups[key]["params"].append(p)
+    return [g for g in groups.values() if g["params"]]
+
+
+def log_param_groups(logger, optimizer) -> None:
+    """One line per parameter group: name, tensors, elements, lr, weight_decay."""
+    for i, g in enumerate(optimizer.param_groups):
+        logger.info("parameter group %d (%s): %d tensors, %d elements, lr %.6g, weight_decay %.6g", i, g.get("name", "all"),
+                    len(g["params"]), sum(p.numel() for p in g["params"]), g["lr"], g.get("weight_decay", 0.0))
+
+
+def build_optimizer(cfg, params, layout_order=None):
     """``_target_: torch.optim.Adam | AdamW | SGD`` of the config is served by the flat-buffer optimizer of the same rule (same
-    arithmetic, same keyword arguments); ``torch.optim.Adam`` with ``decoupled_weight_decay: true`` is AdamW's rule."""
+    arithmetic, same keyword arguments); ``torch.optim.Adam`` with ``decoupled_weight_decay: true`` is AdamW's rule.
+    ``params``: a parameter list or the group dicts of ``build_param_groups``; ``layout_order``: with groups, the flat list they
+    were cut from -- the flat buffers keep its order (optim.FlatOptimizer)."""
     ocfg = dict(cfg.optimizer)
     target = ocfg.pop("_target_")
     if target not in OPTIMIZERS:
@@ -159,7 +211,9 @@ def build_optimizer(cfg, params):
         cls = FlatAdamW
         ocfg.setdefault("weight_decay", 0.0)  # (torch.optim.Adam's default, not AdamW's)
     # (``grad_clip_norm`` sits beside ``optimizer:``, not inside it: that block is handed to Hydra's instantiate by the reference)
-    return cls(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0))
+    grouped = bool(params) and isinstance(params[0], dict)
+    extra = {"layout_order": layout_order} if grouped and layout_order is not None else {}
+    return cls(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0), **extra)
 
 
 def log_grad_norms(logger, epoch: int, step) -> None:

@@ -745,5 +745,7 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 
 /* the update rules of the flat-buffer optimizer behind one launch interface (egk_optim_step) */
 #include "egopack_optim.h"
+/* ... with lr and weight decay per parameter group, looked up per element from a segment table (egk_optim_step_groups) */
+#include "egopack_optim_groups.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -150,7 +150,8 @@ def main(argv=None):
     if world > 1:
         for p in params:  # same start everywhere (seeded identically; broadcast makes it unconditional)
             torch.distributed.broadcast(p.data, src=0)
-    optimizer = T.build_optimizer(cfg, params)
+    optimizer = T.build_optimizer(cfg, T.build_param_groups(cfg, model, tasks), layout_order=params)
+    T.log_param_groups(logger, optimizer)
     scheduler = T.build_scheduler(cfg, optimizer)
     compress = str(cfg.get("grad_compress", "none"))  # element type of the gradient all-reduce: none (f32) | bf16
     sync = edist.GradSync(world, compress=compress) if world > 1 else None

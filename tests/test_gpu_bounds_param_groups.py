@@ -1,0 +1,131 @@
+"""Guard-band tests of include/egopack_optim_groups.h: egk_optim_step_groups touches only what its descriptor and its group table
+name.
+
+The form of tests/test_gpu_bounds_optim.py (helpers and ``Guards`` of tests/test_gpu_bounds.py are imported; nothing is registered
+there): every device argument -- the three tables included -- sits in a sentinel-filled window, the outputs are compared BIT FOR BIT
+with one egk_optim_step launch per segment (tests/param_groups_common.py, the references of tests/test_gpu_param_groups.py),
+everything outside the windows must keep the sentinel bits, and a second run on plain buffers must give the same bits.  The ledger
+of this header is in tests/test_param_groups_cpu.py; the module imports without a GPU."""
+import ctypes as C
+
+import pytest
+import torch
+
+from tests import param_groups_common as PG
+from tests import test_gpu_bounds as B
+from tests.test_gpu_bounds import Guards, S, bf16, f32, i32, i64, ok, refused, same
+
+CASES = []  # (id, function, variant dict, covers, second run on plain buffers?) -- this header's own list
+
+
+def case(*covers, variants=None, plain=True):
+    def deco(fn):
+        for v in variants or [dict()]:
+            v = dict(v)
+            second = v.pop("plain", plain)
+            vid = v.pop("id", None) or "-".join(f"{k}={B._fmt(x)}" for k, x in v.items())
+            CASES.append((fn.__name__ + ("-" + vid if vid else ""), fn, v, covers, second))
+        fn.covers = covers
+        return fn
+    return deco
+
+
+def covered():
+    """Every entry point some case declares it covers (the ledger in tests/test_param_groups_cpu.py)."""
+    return sorted({name for _, _, _, cov, _ in CASES for name in cov})
+
+
+@case("egk_optim_step_groups",
+      variants=[dict(kind="adam", n=1003, gdt=f32), dict(kind="adam", n=4099, gdt=bf16, gate=1), dict(kind="adam", n=1003, gdt=f32, gate=0),
+                dict(kind="adamw", n=1003, gdt=f32, gate=1), dict(kind="adamw", n=4099, gdt=bf16, base=1024),
+                dict(kind="adamw", n=1003, gdt=bf16, gate=0), dict(kind="adamw", n=4099, gdt=f32, lo=False), dict(kind="adamw", n=0, gdt=f32),
+                dict(kind="sgd", n=1003, gdt=f32), dict(kind="sgd", n=4099, gdt=bf16, gate=1), dict(kind="sgd", n=1003, gdt=f32, gate=0),
+                dict(kind="sgd_momentum", n=1003, gdt=f32), dict(kind="sgd_momentum", n=4099, gdt=bf16, gate=1, base=8),
+                dict(kind="sgd_momentum", n=1003, gdt=bf16, gate=0), dict(kind="sgd_momentum", n=4099, gdt=f32, lo=False, gate=1)])
+def optim_step_groups(lib, ops, G, kind, n, gdt, gate=None, lo=True, base=0):
+    """Five segments over three groups; ``base``: the launch is a slice [base, base + m) of the table's range.  ``hyper[0]`` and
+    the descriptor's weight_decay are NaN: they are ignored."""
+    from egopack_amd import _lib
+    key = n if n else 1003
+    begins, m = PG.SEG_BEGINS[key], max(n - base, 0)
+    prob = PG.problem(m, kind, gdt)
+    ns = prob["n_state"]
+    Pp, Gg, H = G.v("p", m, f32, init=prob["p"]), G.v("g", m, gdt, init=prob["g"]), G.v("hyper", 4, f32, init=prob["hyper"])
+    S0 = G.v("state0", m, f32, init=prob["a"]) if ns >= 1 else None
+    S1 = G.v("state1", m, f32, init=prob["b"]) if ns >= 2 else None
+    T = G.v("t_dev", 1, i64, init=prob["t"], poison=0)
+    hi, lo16 = G.v("bf16_shadow", m, bf16), (G.v("bf16_lo_shadow", m, bf16) if lo else None)
+    bump = G.v("bump_word", 1, i64, init=torch.tensor([100]), poison=0)
+    gt = G.v("gate", 1, i32, init=torch.tensor([gate]), poison=1) if gate is not None else None
+    # the tables: a stray read in front of or behind seg_begin finds an offset far outside the launch, one of seg_group a group id
+    # outside the table (clamped by the kernel, into a row of group_hyper that holds NaN here), one of group_hyper a NaN
+    SB = G.v("seg_begin", len(begins), i64, init=torch.tensor(begins), poison=1 << 40)
+    SG = G.v("seg_group", len(PG.SEG_GROUPS), i32, init=torch.tensor(PG.SEG_GROUPS, dtype=torch.int32), poison=3)
+    rows = PG.hyper_rows(PG.GROUP_HYPER + [(float("nan"), float("nan"))])
+    GH = G.v("group_hyper", rows.numel(), f32, init=rows.reshape(-1))
+    d = PG.descriptor(kind, gdt, m, Pp.ptr, Gg.ptr, S0.ptr if S0 is not None else 0, S1.ptr if S1 is not None else 0, H.ptr, T.ptr,
+                      hi.ptr, lo16.ptr if lo16 is not None else 0, bump.ptr, gt.ptr if gt is not None else None)
+    t = PG.group_table(base, SB.ptr, SG.ptr, GH.ptr, n_groups=4, n_seg=len(PG.SEG_GROUPS))
+    ok(lib.egk_optim_step_groups(S(), C.byref(d), C.byref(t)), "egk_optim_step_groups")
+    G.check()
+    assert bump.view.tolist() == [107 if m > 0 else 100], "bump_word"
+    assert T.view.tolist() == prob["t"].tolist(), "t_dev is read, never written"
+    if gate == 0:  # a skipped step: nothing but *bump_word changes
+        same(Pp.view, prob["p"], "p")
+        if S0 is not None:
+            same(S0.view, prob["a"], "state0")
+        if S1 is not None:
+            same(S1.view, prob["b"], "state1")
+        assert bool(hi.is_sentinel().all()) and (lo16 is None or bool(lo16.is_sentinel().all())), "a gated-off step wrote a bf16 copy"
+    elif m > 0:
+        ref = PG.reference(prob, begins, PG.SEG_GROUPS, PG.GROUP_HYPER, gate=gate, lo=lo, base=base)
+        assert bool(torch.isfinite(ref["p"]).all()) and not torch.equal(ref["p"], prob["p"])
+        same(Pp.view, ref["p"], "p")
+        if S0 is not None:
+            same(S0.view, ref["state0"], "state0")
+        if S1 is not None:
+            same(S1.view, ref["state1"], "state1")
+        same(hi.view.view(torch.int16), ref["hi"], "bf16_shadow")
+        if lo16 is not None:
+            same(lo16.view.view(torch.int16), ref["lo"], "bf16_lo_shadow")
+    # refused on the host, nothing launched
+    if m > 4:
+        t.base = base + 2
+        refused(lib.egk_optim_step_groups(S(), C.byref(d), C.byref(t)), "multiple of 4")
+        t.base = base
+        t.seg_begin = SB.ptr + 4
+        refused(lib.egk_optim_step_groups(S(), C.byref(d), C.byref(t)), "misaligned table pointer")
+        t.seg_begin = SB.ptr
+        d.p = Pp.ptr + 4
+        refused(lib.egk_optim_step_groups(S(), C.byref(d), C.byref(t)), "16-byte aligned")
+        d.p = Pp.ptr
+        G.check()
+        assert bump.view.tolist() == [107], "a refused call moved the offset word"
+    out = dict(p=Pp, hi=hi)
+    for k, x in (("state0", S0), ("state1", S1), ("lo", lo16)):
+        if x is not None:
+            out[k] = x
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,fn,variant,covers,plain", CASES, ids=[c[0] for c in CASES])
+def test_bounds_param_groups(name, fn, variant, covers, plain):
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from egopack_amd import _lib, ops
+    lib = _lib.load()
+    try:
+        G = Guards()
+        out = fn(lib, ops, G, **variant)
+        G.check()
+        if plain and out:
+            got = {k: B._bits(v) for k, v in out.items()}
+            H = Guards(plain=True)
+            base = fn(lib, ops, H, **variant)
+            torch.cuda.synchronize()
+            for k, v in base.items():
+                b = B._bits(v)
+                assert got[k].shape == b.shape and torch.equal(got[k], b), f"{k}: the guarded call and the contiguous call differ in bits"
+    finally:
+        torch.cuda.synchronize()
