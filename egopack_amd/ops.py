@@ -217,7 +217,11 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 
 def _rm(t: torch.Tensor) -> torch.Tensor:
-    """row-major 2-D matrix with unit column stride (any row stride: padded logits are views)"""
+    """row-major 2-D matrix with unit column stride (any row stride >= the width: padded logits are views).
+    CONTRACT: only for callers that forward ``stride(0)`` of the result to a launch that takes a leading dimension and reads
+    one element at a time (``cross_entropy``, ``_bank_gradient_operand``, ``to_act_rows``).  A launch WITHOUT a leading
+    dimension gets packed rows (``_c`` / ``_match``); a contraction operand goes through ``_ld_rows`` / ``_operand_rows``,
+    which also look at the alignment."""
     _dt(t)
     if getattr(t, "_egk_virtual", False):
         _materialise_virtual(t)
@@ -226,6 +230,19 @@ def _rm(t: torch.Tensor) -> torch.Tensor:
     if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
         return t
     return t.contiguous()
+
+
+def _ld_rows(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """[rows, cols] contraction operand of element type ``dtype`` whose row stride the caller FORWARDS as the leading dimension.
+    A packed tensor of that type comes back as it is.  A view with unit column stride and a row stride >= the width comes back
+    as it is when its pointer and its row stride are whole 16-byte groups (the real stride goes to the launch, nothing is copied);
+    every other layout (transposed, broadcast, an odd row stride, an unaligned pointer, another element type) is packed."""
+    if t.dtype != dtype:
+        return cast_raw(t, dtype)
+    t = _rm(t)
+    if not t.is_contiguous() and (t.data_ptr() % 16 or (t.stride(0) * t.element_size()) % 16):
+        t = t.contiguous()
+    return t
 
 
 def _pad8(n: int) -> int:
@@ -1081,6 +1098,14 @@ def step_schedule(side_streams: bool, grouping: bool, count: Optional[int] = Non
         install(*prev)
 
 
+def _operand_layout_ok(g: torch.Tensor, esize: int) -> bool:
+    """A [rows, cols] tensor a contraction can read where it lies, its ``stride(0)`` as the leading dimension: unit column stride,
+    a row stride of whole 16-byte groups that is NOT below the width (0: the gradient of a row reduction has strides (0, 1)), a
+    16-byte aligned pointer."""
+    return bool(g.dim() == 2 and g.stride(1) == 1 and g.stride(0) >= g.shape[1] and (g.stride(0) * esize) % 16 == 0
+                and g.data_ptr() % 16 == 0)
+
+
 def _operand_rows(g: torch.Tensor, dtype: torch.dtype, pad_cols: int = 0) -> torch.Tensor:
     """[rows, cols] gradient as a contraction operand of element type ``dtype`` with a 16-byte aligned row stride.
     (autograd hands the gradient of an f32 output back as contiguous f32 whatever the loss emitted, and a width
@@ -1090,8 +1115,7 @@ def _operand_rows(g: torch.Tensor, dtype: torch.dtype, pad_cols: int = 0) -> tor
     esize = 2 if dtype == torch.bfloat16 else 4
     rows, cols = g.shape if g.dim() == 2 else (0, 0)
     want_pad = pad_cols > cols
-    ok = g.dim() == 2 and g.stride(1) == 1 and (g.stride(0) * esize) % 16 == 0 and g.data_ptr() % 16 == 0
-    if g.dtype == dtype and ok and not want_pad:
+    if g.dtype == dtype and _operand_layout_ok(g, esize) and not want_pad:
         return g
     if g.dim() != 2 or g.stride(1) != 1:
         g = g.contiguous()
@@ -1105,7 +1129,9 @@ def _operand_rows(g: torch.Tensor, dtype: torch.dtype, pad_cols: int = 0) -> tor
 
 
 def _match(g: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    g = _rm(g) if g.dim() == 2 else _c(g)
+    """PACKED tensor of element type ``dtype`` for a launch that has no leading dimension (the LayerNorm backward kernels, the
+    flat gates and copies): a contiguous tensor of that type comes back as it is, every view is copied."""
+    g = _c(g)
     return g if g.dtype == dtype else cast_raw(g, dtype)
 
 
@@ -1208,7 +1234,7 @@ class _Linear(torch.autograd.Function):
         K2 = 0
         W2op = None
         if x2 is not None:
-            x2 = _match(x2, x.dtype)
+            x2 = _ld_rows(x2, x.dtype)  # (its real row stride goes to the launch as lda2)
             K2 = x2.shape[1]
             W2op = weight_operand(W2, x.dtype)
         res = _c(residual) if residual is not None else None
@@ -1229,7 +1255,8 @@ class _Linear(torch.autograd.Function):
             # reach anything that reads memory without asking this module for the pointer (torch operators, .cpu())
             defer = (slab_ok and compute == X3 and _slab_defer["on"] and _x3["cache"] is not None and not torch.is_grad_enabled()
                      and not relu and res is None and y.dtype == torch.float32 and y.is_contiguous() and N <= 1024 and N % 4 == 0)
-            ws = gemm(M, N, x, K1, Wop, K1, K1, y, y.stride(0), A2=x2, lda2=K2, B2=W2op, ldb2=K2, K2=K2, bias=bias_c, residual=res,
+            ws = gemm(M, N, x, K1, Wop, K1, K1, y, y.stride(0), A2=x2, lda2=x2.stride(0) if x2 is not None else 0, B2=W2op, ldb2=K2, K2=K2,
+                      bias=bias_c, residual=res,
                       ldr=N, act=1 if relu else 0, compute=compute, defer_reduce=defer)
             if ws is not None:
                 _slab_mark(y, ws, M, N, bias_c)
@@ -1283,7 +1310,7 @@ class _Linear(torch.autograd.Function):
             db = None if slot_b is not None else db_out
         if has_x2 and needs[3]:
             K2 = x2.shape[1]
-            dx2 = torch.empty_like(x2)
+            dx2 = torch.empty_like(x2, memory_format=torch.contiguous_format)
             gemm(M, K2, g, g.stride(0), W2, K2, N, dx2, K2, transB=True, compute=ctx.compute)
         if needs[1]:
             slot = _grad_slot(Wp)
@@ -1328,7 +1355,7 @@ class _Linear(torch.autograd.Function):
             slot = _grad_slot(W2p)
             out2 = slot if slot is not None else torch.zeros(W2.shape, dtype=torch.float32, device=g.device)
             _wgrad_launch(slot is not None, (g, x2),
-                          lambda: gemm(N, K2, g, g.stride(0), x2, K2, M, out2, K2, transA=True, transB=True,
+                          lambda: gemm(N, K2, g, g.stride(0), x2, x2.stride(0), M, out2, K2, transA=True, transB=True,
                                        accumulate=True, compute=ctx.compute))
             dW2 = None if slot is not None else out2
         dres = _match(dy, ctx.res_dtype) if (has_res and needs[5]) else None
@@ -1558,8 +1585,9 @@ class _MultiLinear(torch.autograd.Function):
     def backward(ctx, dy):
         Wop, *xs = ctx.saved_tensors
         Wp, bp = ctx.params
-        dy = _match(dy, xs[0].dtype)
+        dy = _ld_rows(dy, xs[0].dtype)
         N, K = Wop.shape
+        ldy = dy.stride(0)  # (a padded view keeps its row stride: the contractions and the column sum take it)
         needs = ctx.needs_input_grad
         dW = db = None
         dxs = []
@@ -1567,7 +1595,7 @@ class _MultiLinear(torch.autograd.Function):
         for i, (x, m) in enumerate(zip(xs, ctx.rows)):
             if needs[3 + i]:
                 dx = torch.empty_like(x)
-                gemm(m, K, dy[off:off + m], N, Wop, K, N, dx, K, transB=True, compute=ctx.compute)
+                gemm(m, K, dy[off:off + m], ldy, Wop, K, N, dx, K, transB=True, compute=ctx.compute)
                 dxs.append(dx)
             else:
                 dxs.append(None)
@@ -1579,7 +1607,7 @@ class _MultiLinear(torch.autograd.Function):
             def launch_dw():
                 off = 0
                 for x, m in zip(xs, ctx.rows):
-                    gemm(N, K, dy[off:off + m], N, x, K, m, out, K, transA=True, transB=True, accumulate=True,
+                    gemm(N, K, dy[off:off + m], ldy, x, K, m, out, K, transA=True, transB=True, accumulate=True,
                          compute=ctx.compute, slot_final=len(xs) == 1)  # (several launches add up one gradient: not final in any of them)
                     off += m
             _wgrad_launch(slot is not None, (dy, *xs), launch_dw)
@@ -2576,6 +2604,7 @@ class _LiveRows(torch.autograd.Function):
     def forward(ctx, x, idx, inv):
         _need_gpu(x)
         x = _c(x)
+        idx, inv = idx.contiguous(), inv.contiguous()
         out = torch.empty((idx.numel(), x.shape[1]), dtype=x.dtype, device=x.device)
         _ck(_lib.load().egk_gather_rows(_stream(), _p(x), _dt(x), x.stride(0), x.shape[0], _p(idx), _p(out), _dt(out), idx.numel(),
                                         x.shape[1]), "egk_gather_rows")
@@ -2602,6 +2631,7 @@ def expand_rows(v, inv, out=None):
     """A per-row vector of the compacted batch back at full length: out[i] = v[inv[i]], 0 where inv[i] < 0 (the loss vector of
     the reference has one element per node, zero on ignored nodes: criterion/wrapper.py:67-82)."""
     v2 = _c(v.detach().reshape(-1, 1))
+    inv = inv.contiguous()
     if out is None:
         out = torch.empty(inv.numel(), dtype=v2.dtype, device=v2.device)
     _ck(_lib.load().egk_gather_rows(_stream(), _p(v2), _dt(v2), 1, v2.shape[0], _p(inv), _p(out), _dt(out), inv.numel(), 1),
