@@ -22,6 +22,8 @@ HEADER = HERE.parent / "include" / "egopack_hip.h"
 OPTIM_HEADER = HERE.parent / "include" / "egopack_optim.h"  # included by egopack_hip.h; its symbols: OPTIM_SIGNATURES
 OPTIM_GROUPS_HEADER = HERE.parent / "include" / "egopack_optim_groups.h"  # likewise; its symbols: OPTIM_GROUPS_SIGNATURES
 
+EMA_HEADER = HERE.parent / "include" / "egopack_ema.h"  # likewise; its symbols: EMA_SIGNATURES
+
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
 
@@ -95,6 +97,11 @@ class OptimDesc(C.Structure):
 class OptimGroups(C.Structure):
     """struct egk_optim_groups (include/egopack_optim_groups.h)."""
     _fields_ = [("base", i64), ("n_seg", i32), ("n_groups", i32), ("seg_begin", vp), ("seg_group", vp), ("group_hyper", vp)]
+
+
+class EmaDesc(C.Structure):
+    """struct egk_ema_desc (include/egopack_ema.h)."""
+    _fields_ = [("ema", vp), ("decay", C.c_double), ("warmup", i32)]
 
 
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
@@ -227,6 +234,13 @@ OPTIM_GROUPS_SIGNATURES = {
 }
 
 
+# ... and include/egopack_ema.h (the fourth ledger: tests/test_ema_cpu.py over tests/test_gpu_bounds_ema.py)
+EMA_SIGNATURES = {
+    "egk_optim_step_ema": (C.c_int, [vp, C.POINTER(OptimDesc), C.POINTER(OptimGroups), C.POINTER(EmaDesc)]),
+    "egk_ema_swap": (C.c_int, [vp, vp, vp, i64]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -248,6 +262,11 @@ def optim_groups_header_symbols() -> list:
     return _declared(OPTIM_GROUPS_HEADER)
 
 
+def ema_header_symbols() -> list:
+    """Every function name declared in include/egopack_ema.h."""
+    return _declared(EMA_HEADER)
+
+
 _lib = None
 
 
@@ -261,7 +280,8 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m egopack_amd.build` "
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items()]:
+    for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
+                              *EMA_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

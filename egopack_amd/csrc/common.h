@@ -105,6 +105,8 @@ enum KernelId {
     KID_ADAM,
     KID_OPTIM,             // egk_optim_step: the update rules behind one launch interface (optim_rules.hip)
     KID_OPTIM_GROUPS,      // egk_optim_step_groups: the same rules with lr / weight decay per parameter group (optim_rules.hip)
+    KID_OPTIM_EMA,         // egk_optim_step_ema: the same rules with a moving average of the weights kept in the launch (optim_rules.hip)
+    KID_EMA_SWAP,          // egk_ema_swap: parameters <-> their average
     KID_COUNT
 };
 

@@ -342,8 +342,15 @@ class GradSync:
                                "(sharded_update): each rank holds 1 / world of the reduced gradient, the global norm would need a "
                                "collective of its own in front of every Adam slice -- use the all-reduce exchange (the default)")
 
+    def _refuse_ema(self, opt) -> None:
+        if getattr(opt, "ema", False):
+            raise ValueError("the weight average (ema_decay / ema.decay) does not combine with the sharded update (sharded_update): each "
+                             "rank steps 1 / world of the parameters, so the average would be sharded like the moments -- use the "
+                             "all-reduce exchange (the default), where every rank runs the full launch")
+
     def _start_sharded(self, opt, lo, hi, after=()) -> None:
         self._refuse_clipping(opt)
+        self._refuse_ema(opt)
         flat_g = opt.flat_g
         gpu = flat_g.is_cuda
         compress = self.compress == "bf16" and gpu
@@ -427,6 +434,7 @@ class GradSync:
     # ---- sharded update of the WHOLE buffer in one piece (one-piece backward: reduce_and_step) -------------------------------------
     def _sharded_step(self, opt) -> None:
         self._refuse_clipping(opt)
+        self._refuse_ema(opt)
         flat_g, n = opt.flat_g, opt.flat_g.numel()
         per, lo, hi, body = self.shard_bounds(n)
         real = dist.get_world_size(self.group) if dist.is_initialized() else 1

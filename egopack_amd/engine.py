@@ -1472,8 +1472,10 @@ class StepBase:
 
     def replay(self):
         """One training step from the captured graph(s)."""
-        self._count_losses(self._static_out[1])
         opt = self.optimizer
+        if getattr(opt, "_ema_swapped", False):  # (the graph's optimizer launch runs without ``opt.launch`` on the host: its check is made here)
+            raise RuntimeError("replay(): inside optimizer.ema_weights() the parameters hold the average -- no step there")
+        self._count_losses(self._static_out[1])
         if not self._rng_in_graph:
             ops.advance_rng_device(opt.flat_p.device)
         if isinstance(self._graph, list):

@@ -18,9 +18,16 @@ egk_optim_step (include/egopack_optim.h).
 Parameter groups (a list of ``{"params": [...], "lr": ..., "weight_decay": ...}`` dicts, as torch.optim takes them) may differ in
 ``lr`` and ``weight_decay``.  The flat layout does not depend on the grouping; the groups become a segment table over it
 (``group_segments``) that every launch resolves per element, in the one launch (egk_optim_step_groups,
-include/egopack_optim_groups.h).  One group -- a plain list, or a single dict -- issues exactly what it always issued."""
+include/egopack_optim_groups.h).  One group -- a plain list, or a single dict -- issues exactly what it always issued.
+
+``ema_decay`` (None or 0: off) keeps an exponential moving average of the weights in ``flat_ema``, updated INSIDE the optimizer
+launch (egk_optim_step_ema, include/egopack_ema.h): it follows the steps that happen, not the ones the clip gate skips, and costs
+no launch.  ``ema_weights()`` swaps the average into the parameters (bf16 copies and low halves included) for validation and for
+saving; the state dict carries it under a third top-level key, ``"ema"``."""
 from __future__ import annotations
 
+import contextlib
+import logging
 import math
 from typing import Iterable, List
 
@@ -28,6 +35,8 @@ import torch
 
 from . import _lib
 from .ops import _ck, _p, _stream
+
+logger = logging.getLogger("egopack")
 
 
 def _minus_ranges(ranges, lo, hi):
@@ -74,14 +83,20 @@ def _unique(params):
 
 
 class FlatOptimizer(torch.optim.Optimizer):
-    def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None, layout_order=None):
+    def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None, layout_order=None,
+                 ema_decay=None, ema_warmup=False):
         """``layout_order``: the parameters in the order their slots take in the flat buffers (default: constructor order, groups one
         after the other).  A caller that splits one list into groups hands the list in here, and the layout -- backward order, the
         regions the step slices, the classifier banks -- stays what the ungrouped optimizer builds.
         ``state_keys``: torch's state-dict names of the rule's per-parameter buffers, in the order of ``state_buffers()``.
         ``max_grad_norm`` (None or 0: off): clip the global L2 norm of the gradient to it before every update --
-        torch.nn.utils.clip_grad_norm_'s arithmetic, computed on the device inside the step (see ``norm_partials``)."""
+        torch.nn.utils.clip_grad_norm_'s arithmetic, computed on the device inside the step (see ``norm_partials``).
+        ``ema_decay`` (None or 0: off; otherwise inside (0, 1)): keep ``flat_ema``, the moving average of the weights, inside every
+        launch: ema += (1 - d_t) * (p_new - ema) with d_t = ema_decay, or min(ema_decay, (1 + t) / (10 + t)) at step t with
+        ``ema_warmup``."""
         params = [p for p in params]
+        if ema_decay is not None and ema_decay != 0 and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"{type(self).__name__}: ema_decay must be None, 0 (off) or inside (0, 1), got {ema_decay!r}")
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"{type(self).__name__}: max_grad_norm must be None, 0 (off) or positive, got {max_grad_norm!r}")
         if params and all(isinstance(g, dict) for g in params):
@@ -111,6 +126,15 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
         self.norm_regions = None    # [lo, hi) pieces the eager ``step`` takes the norm's partial sums over (None: one piece)
         self._norm_cursor = 0       # partial-sum slots written since the last ``norm_finalize``
+        self.ema_decay = float(ema_decay) if ema_decay else 0.0
+        self.ema_warmup = bool(ema_warmup)
+        self.flat_ema = None        # the moving average of flat_p (same layout), with ``ema_decay`` only
+        self._ema_swapped = False   # inside ``ema_weights()``: flat_p holds the average, flat_ema the raw weights
+
+    @property
+    def ema(self) -> bool:
+        """A moving average of the weights is kept (``ema_decay`` > 0)."""
+        return self.ema_decay > 0.0
 
     # -- parameter groups ---------------------------------------------------------------------------------------------------------
     @property
@@ -225,6 +249,8 @@ class FlatOptimizer(torch.optim.Optimizer):
                     p._egk_shadow_rows64 = self.flat_w16[off:off + rows64 * p.shape[1]].view(rows64, p.shape[1])
                 off += sz
         self.active = live
+        if self.ema:  # (the average starts at the parameters; the padding of the slots is zero in both and stays zero)
+            self.flat_ema = self.flat_p.clone()
         self._bank_views(live)
         self.refresh_shadows()
         self._hyper = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -325,24 +351,49 @@ class FlatOptimizer(torch.optim.Optimizer):
                 i += 1
         if self._pending_state is not None and not state:
             return self._pending_state
-        return {"state": state, "param_groups": groups}
+        out = {"state": state, "param_groups": groups}
+        if self.ema:
+            if self._ema_swapped:
+                raise RuntimeError(f"{type(self).__name__}.state_dict(): inside ema_weights() the parameters hold the average -- "
+                                   "take the optimizer's state outside the context")
+            values, params = {}, self._all_params()
+            for i, p in enumerate(params):
+                view = self._ema_view(p)
+                if view is not None:
+                    values[i] = view.detach().clone()
+            out["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "values": values}
+        return out
+
+    def _ema_view(self, p):
+        """The slot of ``p`` in ``flat_ema`` in the parameter's shape (None: no slot, or no average)."""
+        if self.flat_ema is None or id(p) not in self._slot_of:
+            return None
+        off = self._slot_of[id(p)][0]
+        return self.flat_ema[off:off + p.numel()].view(p.shape)
 
     def load_state_dict(self, state_dict):
         """Hyper-parameters now; the state now if the flat buffers exist, otherwise when the first step builds them."""
         self._check_state_rule(state_dict)
         if len(state_dict["param_groups"]) != len(self.param_groups):  # (torch.optim.Optimizer.load_state_dict's message)
             raise ValueError("loaded state dict has a different number of parameter groups")
+        ema = self._check_ema_state(state_dict)
         for group, pg in zip(self.param_groups, state_dict["param_groups"]):
             for k, v in pg.items():
                 if k not in ("params", *self._fixed_keys) and k in group:
                     group[k] = v
         self._check_groups()
         if self.materialised:
+            if self.ema and ema is None:
+                with torch.no_grad():
+                    self.flat_ema.copy_(self.flat_p)
             self._apply_state(state_dict)
         else:  # snapshot: the caller may keep using (or another optimizer may step) the tensors it handed in
             self._pending_state = {"state": {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                                              for i, st in state_dict["state"].items()},
                                    "param_groups": state_dict["param_groups"]}
+            if ema is not None:
+                self._pending_state["ema"] = {"decay": ema["decay"], "warmup": ema["warmup"],
+                                              "values": {i: v.detach().clone() for i, v in ema["values"].items()}}
             steps = [self._entry_steps(s) for s in state_dict["state"].values()]
             self.step_count = int(max(steps)) if steps else 0
             # The parameters with saved moments ARE the live set of the run that wrote the state: build the flat buffers
@@ -355,6 +406,27 @@ class FlatOptimizer(torch.optim.Optimizer):
                     if p.grad is None:
                         p.grad = torch.zeros_like(p)
                 self._materialise()
+
+    def _check_ema_state(self, state_dict):
+        """The ``"ema"`` entry of a loaded state dict that this optimizer restores (None: nothing to restore), checked before anything
+        is changed.  The decay and the warm-up stay the constructor's: the entry's own are what the saved run used."""
+        held = state_dict.get("ema")
+        if held is None:
+            if self.ema:
+                logger.info("%s: the loaded optimizer state holds no weight average -- the average starts from the loaded parameters",
+                            type(self).__name__)
+            return None
+        if not self.ema:
+            logger.info("%s: the loaded optimizer state holds a weight average (decay %g) and ema_decay is off -- ignored",
+                        type(self).__name__, float(held.get("decay", 0.0)))
+            return None
+        params = self._all_params()
+        for i, v in held["values"].items():
+            if int(i) >= len(params) or tuple(v.shape) != tuple(params[int(i)].shape):
+                want = tuple(params[int(i)].shape) if int(i) < len(params) else None
+                raise ValueError(f"{type(self).__name__}.load_state_dict(): the weight average of parameter {i} has shape "
+                                 f"{tuple(v.shape)}, the parameter has {want}")
+        return held
 
     # keys of a parameter group that select the kernel (the rule itself, the number of state buffers): a loaded state leaves them
     _fixed_keys = ()
@@ -388,6 +460,11 @@ class FlatOptimizer(torch.optim.Optimizer):
                 for k, view in zip(self._state_keys, mv):
                     view.copy_(st[k])
                 steps.append(self._entry_steps(st))
+            if self.ema and state_dict.get("ema") is not None:
+                for i, v in state_dict["ema"]["values"].items():
+                    view = self._ema_view(params[int(i)])
+                    if view is not None:
+                        view.copy_(v)
         if steps:
             self.step_count = int(max(steps))
 
@@ -677,6 +754,8 @@ class FlatOptimizer(torch.optim.Optimizer):
         flat buffer; dist.GradSync hands in its bf16 copy after a compressed all-reduce).  ``[lo, hi)``: element range
         of the flat buffers to update (multiples of 8; the pipelined gradient exchange steps chunk by chunk).
         ``bump`` = (int64 device word, stride): the word moves on by ``stride`` inside this launch."""
+        if self._ema_swapped:
+            raise RuntimeError(f"{type(self).__name__}.launch(): inside ema_weights() the parameters hold the average -- no step there")
         grads = self.flat_g if grads is None else grads
         hi = self.flat_p.numel() if hi is None else hi
         if hi <= lo:
@@ -699,7 +778,9 @@ class FlatOptimizer(torch.optim.Optimizer):
     def _optim_step(self, rule: int, sl, grads, lo16, bump, gate, **scalars) -> None:
         """One egk_optim_step launch (include/egopack_optim.h); ``scalars``: the descriptor's beta1 .. nesterov.  With several
         parameter groups: one egk_optim_step_groups launch (include/egopack_optim_groups.h) over the same descriptor, the segment
-        table and ``base`` = the slice's first element -- lr and weight_decay come from the table, per element."""
+        table and ``base`` = the slice's first element -- lr and weight_decay come from the table, per element.  With ``ema_decay``:
+        one egk_optim_step_ema launch (include/egopack_ema.h) over the same descriptor and table (or none), the same update and
+        ``flat_ema`` moved towards the new parameters inside it."""
         d = _lib.OptimDesc()
         d.rule, d.g_dtype, d.n = rule, 1 if grads.dtype == torch.bfloat16 else 0, sl.stop - sl.start
         d.p, d.g, d.hyper, d.t_dev = self.flat_p[sl].data_ptr(), grads[sl].data_ptr(), self._hyper.data_ptr(), self._t_dev.data_ptr()
@@ -713,16 +794,53 @@ class FlatOptimizer(torch.optim.Optimizer):
             d.bump_word, d.bump = bump[0].data_ptr(), int(bump[1])
         d.gate = gate.data_ptr() if gate is not None else None
         import ctypes as C
+        t = None
         if self.grouped:
             t = _lib.OptimGroups()
             t.base, t.n_seg, t.n_groups = sl.start, self._seg_group.numel(), len(self.param_groups)
             t.seg_begin, t.seg_group, t.group_hyper = self._seg_begin.data_ptr(), self._seg_group.data_ptr(), self._group_hyper.data_ptr()
+        if self.ema:
+            e = _lib.EmaDesc()
+            e.ema, e.decay, e.warmup = self.flat_ema[sl].data_ptr(), self.ema_decay, int(self.ema_warmup)
+            _ck(_lib.load().egk_optim_step_ema(_stream(), C.byref(d), C.byref(t) if t is not None else None, C.byref(e)),
+                "egk_optim_step_ema")
+            return
+        if t is not None:
             _ck(_lib.load().egk_optim_step_groups(_stream(), C.byref(d), C.byref(t)), "egk_optim_step_groups")
             return
         _ck(_lib.load().egk_optim_step(_stream(), C.byref(d)), "egk_optim_step")
 
+    # -- the moving average of the weights ---------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The model computes with the averaged weights inside this context (validation, saving them): ``flat_p`` and ``flat_ema``
+        are exchanged by one launch (egk_ema_swap) and the bf16 copies and low halves re-derived, so every compute mode sees the
+        average; on exit the same again -- parameters, copies and low halves are bit for bit what they were.  Outside captures;
+        no ``step`` / ``launch`` inside, no nesting.  Before the flat buffers exist the average IS the parameters: nothing to do."""
+        if not self.ema:
+            raise RuntimeError(f"{type(self).__name__}.ema_weights(): built without ema_decay")
+        if self._ema_swapped:
+            raise RuntimeError(f"{type(self).__name__}.ema_weights(): already inside the context (no nesting)")
+        self._ema_swapped = True
+        try:
+            self._swap_ema()
+            yield self
+        finally:
+            try:
+                self._swap_ema()
+            finally:
+                self._ema_swapped = False
+
+    def _swap_ema(self) -> None:
+        if not self.materialised:
+            return
+        _ck(_lib.load().egk_ema_swap(_stream(), _p(self.flat_p), _p(self.flat_ema), self.flat_p.numel()), "egk_ema_swap")
+        self.refresh_shadows()
+
     @torch.no_grad()
     def step(self, closure=None, grads=None):
+        if self._ema_swapped:
+            raise RuntimeError(f"{type(self).__name__}.step(): inside ema_weights() the parameters hold the average -- no step there")
         if not self.materialised:
             self._materialise()
         self.prepare_hyper()
@@ -741,7 +859,7 @@ class FlatAdam(FlatOptimizer):
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, max_grad_norm=None, *, decoupled_weight_decay: bool = False, amsgrad: bool = False,
                  maximize: bool = False, foreach=None, fused=None, capturable: bool = False, differentiable: bool = False,
-                 layout_order=None):
+                 layout_order=None, ema_decay=None, ema_warmup=False):
         _refuse_unbuilt(type(self).__name__, amsgrad, maximize)
         if not 0.0 <= lr:  # (torch.optim.Adam's checks and messages)
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -758,7 +876,7 @@ class FlatAdam(FlatOptimizer):
         if self.decoupled_weight_decay:  # (what torch.optim.Adam needs to read the saved group as AdamW's; plain Adam's group as it was)
             defaults["decoupled_weight_decay"] = True
         super().__init__(params, defaults, state_keys=("exp_avg", "exp_avg_sq"), max_grad_norm=max_grad_norm,
-                         layout_order=layout_order)
+                         layout_order=layout_order, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     _fixed_keys = ("decoupled_weight_decay",)
 
@@ -775,7 +893,8 @@ class FlatAdam(FlatOptimizer):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         n = sl.stop - sl.start
-        if self.decoupled_weight_decay or self.grouped:  # (several groups: Adam's rule too goes through the descriptor, same bits)
+        # (several groups, or the weight average: Adam's rule too goes through the descriptor, same bits)
+        if self.decoupled_weight_decay or self.grouped or self.ema:
             self._optim_step(_lib.OPT_ADAMW if self.decoupled_weight_decay else _lib.OPT_ADAM, sl, grads, lo16, bump, gate,
                              beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"])
             return
@@ -816,7 +935,8 @@ class FlatSGD(FlatOptimizer):
 
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm=None, *, maximize: bool = False, foreach=None,
-                 fused=None, capturable: bool = False, differentiable: bool = False, layout_order=None):
+                 fused=None, capturable: bool = False, differentiable: bool = False, layout_order=None, ema_decay=None,
+                 ema_warmup=False):
         _refuse_unbuilt(type(self).__name__, False, maximize)
         if lr < 0.0:  # (torch.optim.SGD's checks and messages)
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -828,7 +948,7 @@ class FlatSGD(FlatOptimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov))
         super().__init__(params, defaults, state_keys=("momentum_buffer",) if momentum != 0 else (), max_grad_norm=max_grad_norm,
-                         layout_order=layout_order)
+                         layout_order=layout_order, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     _fixed_keys = ("momentum",)  # (zero or not decides whether there is a buffer: the constructor's value stands)
 

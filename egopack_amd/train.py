@@ -213,7 +213,39 @@ def build_optimizer(cfg, params, layout_order=None):
     # (``grad_clip_norm`` sits beside ``optimizer:``, not inside it: that block is handed to Hydra's instantiate by the reference)
     grouped = bool(params) and isinstance(params[0], dict)
     extra = {"layout_order": layout_order} if grouped and layout_order is not None else {}
-    return cls(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0), **extra)
+    # (``ema:`` sits beside ``optimizer:`` for the same reason; decay 0 = off)
+    ema = dict(cfg.get("ema") or {})
+    unknown = set(ema) - {"decay", "warmup", "validate", "save"}
+    if unknown:
+        raise ValueError(f"ema: unknown key(s) {sorted(unknown)} (decay, warmup, validate, save)")
+    return cls(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0), ema_decay=float(ema.get("decay", 0) or 0),
+               ema_warmup=bool(ema.get("warmup", False)), **extra)
+
+
+def ema_scope(cfg, optimizer):
+    """The context a validation loop runs in: ``optimizer.ema_weights()`` with ``ema.decay`` > 0 and ``ema.validate`` set, otherwise
+    one that does nothing."""
+    import contextlib
+    ema = dict(cfg.get("ema") or {})
+    if getattr(optimizer, "ema", False) and bool(ema.get("validate", True)):
+        return optimizer.ema_weights()
+    return contextlib.nullcontext()
+
+
+def ema_saved(cfg) -> bool:
+    """``ema.save`` of the config (default true): ``save_checkpoint`` also writes the averaged weights when there is an average."""
+    return bool(dict(cfg.get("ema") or {}).get("save", True))
+
+
+def log_validation_weights(logger, cfg, optimizer, epoch: int) -> None:
+    """One line per validation: which weights are scored."""
+    ema = dict(cfg.get("ema") or {})
+    if getattr(optimizer, "ema", False) and bool(ema.get("validate", True)):
+        logger.info("epoch %d: validating the averaged weights (ema.decay %g%s)", epoch, optimizer.ema_decay,
+                    ", warm-up" if optimizer.ema_warmup else "")
+    else:
+        logger.info("epoch %d: validating the raw weights%s", epoch,
+                    " (ema.validate is off)" if getattr(optimizer, "ema", False) else "")
 
 
 def log_grad_norms(logger, epoch: int, step) -> None:
@@ -233,28 +265,54 @@ def build_scheduler(cfg, optimizer):
     return sched
 
 
-def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimizer=None, scheduler=None, loaders=None):
-    """Reference key layout (main_temporal.py:410-417, main_egopack.py:453-460) + what the reference does not keep and
-    a resumed run needs: the optimiser state (torch.optim.Adam's per-parameter layout) and the schedule state."""
-    path.parent.mkdir(parents=True, exist_ok=True)
+def _module_states(model, tasks, epoch: int, graphone=None) -> dict:
+    """The modules' state dicts on the host under the reference's keys."""
     ckpt = {"temporal_graph": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "epoch": epoch}
     for t, key in CKPT_KEYS.items():
         ckpt[key] = {k: v.detach().cpu().clone() for k, v in tasks[t].state_dict().items()}
     if graphone is not None:
         ckpt["graphone"] = {k: v.detach().cpu().clone() for k, v in graphone.state_dict().items()}
+    return ckpt
+
+
+def _write(ckpt: dict, path: Path) -> None:
+    tmp = path.with_suffix(path.suffix + ".tmp")
+    torch.save(ckpt, tmp)
+    tmp.replace(path)  # a killed run never leaves a half-written checkpoint behind
+    logger.info("saved %s", path)
+
+
+def ema_checkpoint_path(path: Path) -> Path:
+    """``checkpoint.pth`` -> ``checkpoint_ema.pth``, beside it."""
+    return path.with_name(path.stem + "_ema" + path.suffix)
+
+
+def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimizer=None, scheduler=None, loaders=None,
+                    save_ema: bool = False):
+    """Reference key layout (main_temporal.py:410-417, main_egopack.py:453-460) + what the reference does not keep and
+    a resumed run needs: the optimiser state (torch.optim.Adam's per-parameter layout) and the schedule state.
+    ``save_ema`` (``ema.save`` of the config; an optimizer that keeps a weight average): a second file beside it,
+    ``checkpoint_ema.pth``, with the reference's key layout alone and the AVERAGED weights in place of the parameters -- the
+    modules' state dicts taken inside ``optimizer.ema_weights()``; any loader of the reference's layout and ``resume_from=``
+    take it as it is.  The ordinary file keeps the raw weights and the average under the optimizer's ``"ema"`` key."""
+    path.parent.mkdir(parents=True, exist_ok=True)
+    if save_ema and getattr(optimizer, "ema", False):
+        with optimizer.ema_weights():
+            averaged = _module_states(model, tasks, epoch, graphone)
+        _write(averaged, ema_checkpoint_path(path))
+    ckpt = _module_states(model, tasks, epoch, graphone)
     if optimizer is not None:
         sd = optimizer.state_dict()
         sd["state"] = {i: {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in st.items()} for i, st in sd["state"].items()}
+        if sd.get("ema") is not None:
+            sd["ema"] = {**sd["ema"], "values": {i: v.cpu() for i, v in sd["ema"]["values"].items()}}
         ckpt["optimizer"] = sd
     if scheduler is not None:
         ckpt["scheduler"] = scheduler.state_dict()
     if loaders is not None:  # shuffle generators of the training loaders + dropout streams: exact continuation
         ckpt["rng"] = {"loaders": {t: dl.state_dict() for t, dl in loaders.items() if hasattr(dl, "state_dict")},
                        "dropout": ops.get_rng_state(), "torch": torch.get_rng_state()}
-    tmp = path.with_suffix(path.suffix + ".tmp")
-    torch.save(ckpt, tmp)
-    tmp.replace(path)  # a killed run never leaves a half-written checkpoint behind
-    logger.info("saved %s", path)
+    _write(ckpt, path)
 
 
 def load_checkpoint(path, model, tasks, strict_tasks: bool = True, device="cpu", graphone=None, optimizer=None,

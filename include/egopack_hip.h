@@ -747,5 +747,7 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 #include "egopack_optim.h"
 /* ... with lr and weight decay per parameter group, looked up per element from a segment table (egk_optim_step_groups) */
 #include "egopack_optim_groups.h"
+/* ... and with an exponential moving average of the weights kept inside the launch (egk_optim_step_ema, egk_ema_swap) */
+#include "egopack_ema.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -181,20 +181,27 @@ def main(argv=None):
         if cfg.save_model and cfg.get("save_every", 0) and epoch % cfg.save_every == 0 and sync is not None:
             sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
         if cfg.save_model and cfg.get("save_every", 0) and epoch % cfg.save_every == 0 and rank == 0:
-            T.save_checkpoint(ckpt_path, model, tasks, epoch, optimizer=optimizer, scheduler=scheduler, loaders=dl_train)
+            T.save_checkpoint(ckpt_path, model, tasks, epoch, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
+                              save_ema=T.ema_saved(cfg))
         if epoch >= cfg.num_epochs - 5:  # all ranks: the validation split is sharded by batch
-            logger.info("validation losses: %s", validate_losses(step, dl_val, device))
-            metrics = validate_metrics(epoch, model, tasks, step.enabled, dsets_val, dl_val, device)
+            T.log_validation_weights(logger, cfg, optimizer, epoch)
+            with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
+                logger.info("validation losses: %s", validate_losses(step, dl_val, device))
+                metrics = validate_metrics(epoch, model, tasks, step.enabled, dsets_val, dl_val, device)
     if cfg.num_epochs < first_epoch and cfg.get("validate_untrained", False):  # (num_epochs=0: metrics of the initial state)
-        metrics = validate_metrics(0, model, tasks, step.enabled, dsets_val, dl_val, device)
+        T.log_validation_weights(logger, cfg, optimizer, 0)
+        with T.ema_scope(cfg, optimizer):
+            metrics = validate_metrics(0, model, tasks, step.enabled, dsets_val, dl_val, device)
     if cfg.save_model and sync is not None:
         sync.gather_moments(optimizer)
     if cfg.save_model and rank == 0:
-        T.save_checkpoint(ckpt_path, model, tasks, cfg.num_epochs, optimizer=optimizer, scheduler=scheduler, loaders=dl_train)
+        T.save_checkpoint(ckpt_path, model, tasks, cfg.num_epochs, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
+                          save_ema=T.ema_saved(cfg))
     if world > 1:
         torch.distributed.destroy_process_group()
     # (callers that drive main() from Python -- the tests -- get the last validation metrics and the trained modules)
-    return {"metrics": metrics, "model": model, "tasks": tasks, "step": step, "loaders": dl_train, "val_datasets": dsets_val}
+    return {"metrics": metrics, "model": model, "tasks": tasks, "step": step, "loaders": dl_train, "val_datasets": dsets_val,
+            "val_loaders": dl_val, "optimizer": optimizer}
 
 
 if __name__ == "__main__":
