@@ -23,6 +23,7 @@ OPTIM_HEADER = HERE.parent / "include" / "egopack_optim.h"  # included by egopac
 OPTIM_GROUPS_HEADER = HERE.parent / "include" / "egopack_optim_groups.h"  # likewise; its symbols: OPTIM_GROUPS_SIGNATURES
 
 EMA_HEADER = HERE.parent / "include" / "egopack_ema.h"  # likewise; its symbols: EMA_SIGNATURES
+CE_BALANCED_HEADER = HERE.parent / "include" / "egopack_ce_balanced.h"  # likewise; its symbols: CE_BALANCED_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -85,6 +86,11 @@ class CETask(C.Structure):
     """struct egk_ce_task (include/egopack_hip.h)."""
     _fields_ = [("logits", vp * 4), ("ld", i64 * 4), ("C", i32 * 4), ("pad", i32 * 4), ("dcol", i64 * 4), ("n_heads", i32),
                 ("y", vp), ("y_stride", i64), ("loss", vp), ("dlogits", vp), ("ldd", i64), ("rows", i32), ("gscale", f32)]
+
+
+class CEWTask(C.Structure):
+    """struct egk_ce_w_task (include/egopack_ce_balanced.h): a task of the fused cross entropy + its per-class vectors."""
+    _fields_ = [("base", CETask), ("weight", vp * 4), ("offset", vp * 4)]
 
 
 class OptimDesc(C.Structure):
@@ -241,6 +247,14 @@ EMA_SIGNATURES = {
 }
 
 
+# ... and include/egopack_ce_balanced.h (the fifth ledger: tests/test_class_balance_cpu.py over tests/test_gpu_bounds_class_balance.py)
+CE_BALANCED_SIGNATURES = {
+    "egk_ce_w_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, i32, f32, i32]),
+    "egk_ce_w_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, f32, i32]),
+    "egk_ce_w_fused_multi": (C.c_int, [vp, C.POINTER(CEWTask), i32, f32, i32]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -267,6 +281,11 @@ def ema_header_symbols() -> list:
     return _declared(EMA_HEADER)
 
 
+def ce_balanced_header_symbols() -> list:
+    """Every function name declared in include/egopack_ce_balanced.h."""
+    return _declared(CE_BALANCED_HEADER)
+
+
 _lib = None
 
 
@@ -281,7 +300,7 @@ def load() -> C.CDLL:
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
-                              *EMA_SIGNATURES.items()]:
+                              *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

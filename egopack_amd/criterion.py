@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 import logging
-from typing import Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -11,17 +11,32 @@ from . import ops
 logger = logging.getLogger(__name__)
 
 
-class CrossEntropyNone(torch.nn.Module):
-    """nn.CrossEntropyLoss(reduction='none', ignore_index=-1[, label_smoothing]) on the HIP path."""
+def _class_vector(v, what: str) -> Optional[torch.Tensor]:
+    """A per-class vector as the f32 tensor the kernels read (None stays None)."""
+    if v is None:
+        return None
+    v = torch.as_tensor(v)
+    if v.dim() != 1 or not (v.is_floating_point() or v.numel() == 0):
+        raise ValueError(f"{what}: expected a 1-D floating-point vector with one entry per class, got {v.dtype} {tuple(v.shape)}")
+    return v.detach().to(torch.float32).contiguous().clone()
 
-    def __init__(self, ignore_index: int = -1, label_smoothing: float = 0.0):
+
+class CrossEntropyNone(torch.nn.Module):
+    """nn.CrossEntropyLoss(reduction='none', ignore_index=-1[, label_smoothing][, weight]) on the HIP path.  ``offset``: a
+    per-class vector added to the logits inside the loss only (logit adjustment).  Both are non-persistent buffers (single-head
+    use; ``MetricSelectorWrapper`` carries one pair per head)."""
+
+    def __init__(self, ignore_index: int = -1, label_smoothing: float = 0.0, weight=None, offset=None):
         super().__init__()
         if ignore_index != -1:
             raise ValueError("the hot path uses ignore_index=-1")
         self.label_smoothing = label_smoothing
+        self.register_buffer("weight", _class_vector(weight, "CrossEntropyNone: weight"), persistent=False)
+        self.register_buffer("offset", _class_vector(offset, "CrossEntropyNone: offset"), persistent=False)
 
     def forward(self, logits, target):
-        return ops.cross_entropy(logits, target, self.label_smoothing)
+        w, a = (self.weight, self.offset) if self.training else (None, None)  # (``eval()``: the plain cross entropy)
+        return ops.cross_entropy(logits, target, self.label_smoothing, weight=w, offset=a)  # (no vector: the plain launches)
 
 
 class BCEWithLogitsNone(torch.nn.Module):
@@ -35,22 +50,46 @@ class MetricSelectorWrapper(torch.nn.Module):
     """Apply a per-head criterion to the heads selected by the dataset's label structure and sum the
     per-head loss vectors.  Needs only ``dataset.has_joint_label`` and ``dataset.num_labels``."""
 
-    def __init__(self, criterion: torch.nn.Module, dataset, joint_label_training: bool = False) -> None:
+    def __init__(self, criterion: torch.nn.Module, dataset, joint_label_training: bool = False, *,
+                 class_weights: Optional[Sequence] = None, class_offsets: Optional[Sequence] = None) -> None:
+        """``class_weights`` / ``class_offsets``: one per-class vector or None per head of the task (label column), applied inside
+        the cross entropy of that head (``ops.cross_entropy(weight=, offset=)``); kept as non-persistent buffers."""
         super().__init__()
         if not dataset.has_joint_label and joint_label_training:
             logger.warning("The flag join_labels is set to True but the dataset has no joint label")
             joint_label_training = False
         self.criterion, self.dataset, self.joint_label = criterion, dataset, joint_label_training
+        self.n_balance = 0
+        for name, vecs in (("class_weight", class_weights), ("class_offset", class_offsets)):
+            vecs = list(vecs) if vecs is not None else []
+            if vecs and self.n_balance and len(vecs) != self.n_balance:
+                raise ValueError(f"MetricSelectorWrapper: {len(vecs)} {name} entries, {self.n_balance} of the other kind")
+            self.n_balance = max(self.n_balance, len(vecs))
+            for h, v in enumerate(vecs):
+                self.register_buffer(f"{name}_{h}", _class_vector(v, f"MetricSelectorWrapper: {name} of head {h}"), persistent=False)
+
+    def _heads(self, n_logits: int):
+        if self.dataset.has_joint_label:
+            return [n_logits - 1] if self.joint_label else list(range(self.dataset.num_labels - 1))
+        return list(range(self.dataset.num_labels))
+
+    def select_balance(self, logits: Tuple[torch.Tensor, ...]):
+        """(weights, offsets) of the heads ``select`` chooses, one vector or None per chosen head -- (None, None) when the wrapper
+        carries no vector or is in ``eval()`` mode (the vectors shape the training loss only)."""
+        if not self.n_balance or not self.training:  # (``eval()``: the plain cross entropy, e.g. validation losses)
+            return None, None
+        heads = self._heads(len(logits))
+        if heads and max(heads) >= self.n_balance:
+            raise ValueError(f"MetricSelectorWrapper: class-balance vectors for {self.n_balance} heads, head {max(heads)} is selected")
+        out = tuple(tuple(getattr(self, f"{name}_{h}", None) for h in heads) for name in ("class_weight", "class_offset"))
+        return tuple(None if all(v is None for v in vecs) else vecs for vecs in out)
 
     def select(self, logits: Tuple[torch.Tensor, ...], ground_truths: torch.Tensor):
         """(logits of the heads that count, their label columns, label smoothing): what ``forward`` hands to the cross
         entropy (the engine batches the cross entropies of several tasks into one launch from these)."""
         if len(logits) != ground_truths.shape[1]:
             raise ValueError("The number of predictions must match the number of ground truth labels")
-        if self.dataset.has_joint_label:
-            heads = [len(logits) - 1] if self.joint_label else list(range(self.dataset.num_labels - 1))
-        else:
-            heads = list(range(self.dataset.num_labels))
+        heads = self._heads(len(logits))
         smoothing = getattr(self.criterion, "label_smoothing", 0.0)
         if heads == list(range(ground_truths.shape[1])):
             return tuple(logits), ground_truths, smoothing  # all heads: the common case on the path
@@ -58,4 +97,5 @@ class MetricSelectorWrapper(torch.nn.Module):
 
     def forward(self, logits: Tuple[torch.Tensor, ...], ground_truths: torch.Tensor) -> torch.Tensor:
         sel, gt, smoothing = self.select(logits, ground_truths)
-        return ops.cross_entropy(sel, gt, smoothing)  # one fused per-row sum over the heads
+        weights, offsets = self.select_balance(logits)
+        return ops.cross_entropy(sel, gt, smoothing, weight=weights, offset=offsets)  # one fused per-row sum over the heads

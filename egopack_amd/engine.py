@@ -1670,8 +1670,10 @@ class MTLStep(StepBase):
             # the cross entropies of the banked tasks as ONE launch (each writes its own loss vector and gradient operand)
             sel = [self.criteria[t].select(logits, labels[t]) for t, logits in zip(banked, all_logits)]
             if len({s_[2] for s_ in sel}) == 1:
+                # (the criteria's class-balance vectors ride in the same launch; without any it is the launch it always was)
+                bal = [self.criteria[t].select_balance(logits) for t, logits in zip(banked, all_logits)]
                 multi = ops.cross_entropy_multi([(s_[0], s_[1]) for s_ in sel], [self.weights[t] / n_loss[t] for t in banked],
-                                                sel[0][2])
+                                                sel[0][2], weights=[w for w, _ in bal], offsets=[a for _, a in bal])
             for i, (t, logits) in enumerate(zip(banked, all_logits)):
                 if multi is not None:
                     v = multi[i]
@@ -1725,7 +1727,8 @@ class MTLStep(StepBase):
 
     def _compact_head_ok(self, t: str, d, leaf) -> bool:
         """Task ``t``'s head runs on its labelled rows: a multi-head cross-entropy head (MetricSelectorWrapper over
-        CrossEntropyNone with ignore_index -1: the row's loss and gradient are exactly zero when every head's label is -1),
+        CrossEntropyNone with ignore_index -1: the row's loss and gradient are exactly zero when every head's label is -1 --
+        with the wrapper's class-balance vectors too: an ignored row's loss and gradient are 0 whatever its weights and offsets),
         no active dropout in the head (its masks are drawn by row position), the batch built by data.collate with its
         ``live_*`` index arrays on the features' device."""
         if not self.compact_heads or t not in ("ar", "lta"):

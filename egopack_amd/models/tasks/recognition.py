@@ -47,11 +47,43 @@ class MultiHeadTask(ProjectionTask):
     def forward_aux_logits(self, features: torch.Tensor, t: TaskLiteral = "ar", *args, **kwargs):
         return tuple(apply_classifier(c, features) for c in self.aux_classifiers[t])
 
+    def set_class_balance(self, weights=None, offsets=None) -> None:
+        """Per-class vectors of the training loss, one entry (a vector of ``heads[h]`` values or None) per head: ``weights`` as
+        nn.CrossEntropyLoss(weight=...), ``offsets`` added to the logits inside the loss only.  Non-persistent buffers: they follow
+        ``.to(device)`` and stay out of the state dict, whose key layout is the reference's.  None, None removes them."""
+        from ...criterion import _class_vector
+        for name, vecs in (("class_weight", weights), ("class_offset", offsets)):
+            vecs = list(vecs) if vecs is not None else [None] * len(self.heads)
+            if len(vecs) != len(self.heads):
+                raise ValueError(f"{self.name}: {len(vecs)} {name} entries for {len(self.heads)} heads")
+            for h, v in enumerate(vecs):
+                v = _class_vector(v, f"{self.name}: {name} of head {h}")
+                if v is not None and v.numel() != self.heads[h]:
+                    raise ValueError(f"{self.name}: {name} of head {h} has {v.numel()} entries, the head has {self.heads[h]} classes")
+                if v is not None:
+                    v = v.to(self.classifiers[h][1].weight.device)
+                key = f"{name}_{h}"
+                if key in self._buffers:
+                    self._buffers[key] = v
+                else:
+                    self.register_buffer(key, v, persistent=False)
+
+    def class_balance(self):
+        """(weights, offsets) as ``ops.cross_entropy`` takes them: a tuple with one vector or None per head, or None."""
+        out = []
+        for name in ("class_weight", "class_offset"):
+            vecs = tuple(getattr(self, f"{name}_{h}", None) for h in range(len(self.heads)))
+            out.append(None if all(v is None for v in vecs) else vecs)
+        return tuple(out)
+
     def compute_loss(self, logits: Tuple[torch.Tensor, ...], targets: torch.Tensor, return_separate_losses: bool = False):
-        """sum over heads of CrossEntropy(reduction='none', ignore_index=-1)."""
-        total = ops.cross_entropy(tuple(logits), targets)
+        """sum over heads of CrossEntropy(reduction='none', ignore_index=-1).  While training, with the class-balance vectors of
+        ``set_class_balance``; a validation loss (``eval()``) is always the plain cross entropy, so curves compare across runs."""
+        weights, offsets = self.class_balance() if self.training else (None, None)
+        total = ops.cross_entropy(tuple(logits), targets, weight=weights, offset=offsets)  # (no vector: the plain launches)
         if return_separate_losses:
-            return total, tuple(ops.cross_entropy(l, targets[:, i].contiguous()) for i, l in enumerate(logits))
+            w, a = weights or [None] * len(logits), offsets or [None] * len(logits)
+            return total, tuple(ops.cross_entropy(l, targets[:, i].contiguous(), weight=w[i], offset=a[i]) for i, l in enumerate(logits))
         return total
 
 

@@ -2786,10 +2786,63 @@ class loss_seed:
         _loss_seed["coef"] = self.prev
 
 
+def _vp(t):
+    """Device pointer of an optional vector (None: a null pointer -- the launch's default for it)."""
+    return None if t is None else _p(t)
+
+
+def _class_balance(weight, offset, logits, where="cross_entropy"):
+    """The ``weight`` / ``offset`` arguments of the cross entropies as (weights, offsets), one packed f32 vector or None per
+    head -- or None when every vector is None (the caller then issues exactly the launches it issues without the arguments).
+    Each argument: None, one tensor (a single head), or a tuple / list with one tensor or None per head.  The vectors are
+    constants of the loss: no gradient reaches them."""
+    out = []
+    for name, arg in (("weight", weight), ("offset", offset)):
+        if arg is None:
+            vecs = [None] * len(logits)
+        elif torch.is_tensor(arg):
+            if len(logits) != 1:
+                raise ValueError(f"{where}: {name} is one tensor but there are {len(logits)} heads (pass one entry per head)")
+            vecs = [arg]
+        else:
+            vecs = list(arg)
+            if len(vecs) != len(logits):
+                raise ValueError(f"{where}: {name} has {len(vecs)} entries for {len(logits)} heads")
+        packed = []
+        for h, (v, l) in enumerate(zip(vecs, logits)):
+            if v is None:
+                packed.append(None)
+                continue
+            if not torch.is_tensor(v) or v.dtype != torch.float32:
+                raise ValueError(f"{where}: {name} of head {h} must be a float32 tensor, got "
+                                 f"{v.dtype if torch.is_tensor(v) else type(v).__name__}")
+            if v.device != l.device:
+                raise ValueError(f"{where}: {name} of head {h} is on {v.device}, the logits on {l.device}")
+            if v.dim() != 1 or v.shape[0] != l.shape[-1]:
+                raise ValueError(f"{where}: {name} of head {h} has shape {tuple(v.shape)}, the head has {l.shape[-1]} classes")
+            packed.append(_c(v.detach()))
+        out.append(tuple(packed))
+    if all(v is None for vecs in out for v in vecs):
+        return None
+    return tuple(out)
+
+
+def _ce_w_task(t, logits, pads, starts, y, loss, gbuf, rows, coef, bal):
+    """Fill one ``egk_ce_w_task``: a task of the fused cross entropy (``_CE._fused`` / ``_CEMulti``) and its per-class vectors."""
+    b = t.base
+    for h, l in enumerate(logits):
+        b.logits[h], b.ld[h], b.C[h], b.pad[h], b.dcol[h] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
+        t.weight[h] = None if bal is None or bal[0][h] is None else bal[0][h].data_ptr()
+        t.offset[h] = None if bal is None or bal[1][h] is None else bal[1][h].data_ptr()
+    b.n_heads, b.y, b.y_stride, b.loss = len(logits), y.data_ptr(), y.shape[1], loss.data_ptr()
+    b.dlogits, b.ldd, b.rows, b.gscale = gbuf.data_ptr(), gbuf.stride(0), rows, float(coef)
+
+
 class _CE(torch.autograd.Function):
     @staticmethod
-    def _fused(ctx, smoothing, y, logits):
-        """One launch for loss and gradient when the seed is known and every head's logits are blocks of ONE bank buffer."""
+    def _fused(ctx, smoothing, y, logits, bal=None):
+        """One launch for loss and gradient when the seed is known and every head's logits are blocks of ONE bank buffer.
+        ``bal``: the per-class vectors (``_class_balance``) -- the same launch with them applied (egk_ce_w_fused_multi, one task)."""
         if _loss_seed["coef"] is None or not _bank_handoff["on"] or y.dim() != 2 or y.shape[1] != len(logits) or len(logits) > 4:
             return None
         dsts = [getattr(l, "_egk_grad_dst", None) for l in logits]
@@ -2810,8 +2863,13 @@ class _CE(torch.autograd.Function):
         Cs = (C.c_int32 * n)(*[l.shape[1] for l in logits])
         pad = (C.c_int32 * n)(*[e - s0 for s0, e in zip(starts, ends)])
         dcol = (C.c_int64 * n)(*starts)
-        _ck(lib.egk_ce_fused(_stream(), lp, ld, Cs, pad, dcol, n, _p(y), y.shape[1], _p(loss), _p(gbuf), gbuf.stride(0), rows,
-                             smoothing, float(_loss_seed["coef"]), _dt(gbuf)), "egk_ce_fused")
+        if bal is None:
+            _ck(lib.egk_ce_fused(_stream(), lp, ld, Cs, pad, dcol, n, _p(y), y.shape[1], _p(loss), _p(gbuf), gbuf.stride(0), rows,
+                                 smoothing, float(_loss_seed["coef"]), _dt(gbuf)), "egk_ce_fused")
+        else:
+            arr = (_lib.CEWTask * 1)()
+            _ce_w_task(arr[0], logits, pad, starts, y, loss, gbuf, rows, float(_loss_seed["coef"]), bal)
+            _ck(lib.egk_ce_w_fused_multi(_stream(), arr, 1, smoothing, _dt(gbuf)), "egk_ce_w_fused_multi")
         if starts[0] > 0:
             gbuf[:, :starts[0]].zero_()
         state["filled"].update(starts)
@@ -2820,14 +2878,16 @@ class _CE(torch.autograd.Function):
         return loss
 
     @staticmethod
-    def forward(ctx, smoothing, y, gdt, *logits):
+    def forward(ctx, smoothing, y, gdt, bal, *logits):
         # loss[n] = sum_h CE(logits[h][n], y[n, h]) with ignore_index -1 (y: [N] or [N, heads] int64)
+        # bal: None, or (weights, offsets) with one packed f32 vector or None per head -- the launches of egopack_ce_balanced.h
         _need_gpu(y, *logits)
         lib = _lib.load()
         rows = logits[0].shape[0]
         y = y.contiguous()
         ctx.fused = False
-        fused = _CE._fused(ctx, smoothing, y, logits)
+        ctx.bal = bal
+        fused = _CE._fused(ctx, smoothing, y, logits, bal)
         if fused is not None:
             return fused
         loss = torch.empty(rows, dtype=torch.float32, device=logits[0].device)
@@ -2840,8 +2900,12 @@ class _CE(torch.autograd.Function):
             l = _rm(l)
             lse = torch.empty(rows, dtype=torch.float32, device=l.device)
             yh = y if y.dim() == 1 else y[:, h]
-            _ck(lib.egk_ce_fwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ystride, _p(loss), _p(lse), rows,
-                               l.shape[1], smoothing, int(h > 0)), "egk_ce_fwd")
+            if bal is None:
+                _ck(lib.egk_ce_fwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ystride, _p(loss), _p(lse), rows,
+                                   l.shape[1], smoothing, int(h > 0)), "egk_ce_fwd")
+            else:
+                _ck(lib.egk_ce_w_fwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ystride, _vp(bal[0][h]), _vp(bal[1][h]),
+                                     _p(loss), _p(lse), rows, l.shape[1], smoothing, int(h > 0)), "egk_ce_w_fwd")
             saved += [l, lse]
         ctx.smoothing, ctx.ystride, ctx.nh, ctx.gdt = smoothing, ystride, len(logits), gdt
         ctx.save_for_backward(y, *saved)
@@ -2851,10 +2915,19 @@ class _CE(torch.autograd.Function):
     def backward(ctx, gloss):
         lib = _lib.load()
         if ctx.fused:  # the gradient is already in the bank's operand buffer: placeholders for autograd
-            return (None, None, None, *[torch.empty(s_, dtype=torch.float32, device=gloss.device) for s_ in ctx.shapes])
+            return (None, None, None, None, *[torch.empty(s_, dtype=torch.float32, device=gloss.device) for s_ in ctx.shapes])
         y, *saved = ctx.saved_tensors
         gloss = _f32c(gloss)
         grads = []
+        bal = ctx.bal
+
+        def bwd(h, l, yh, lse, out, ldd, Cn, dt):
+            if bal is None:
+                _ck(lib.egk_ce_bwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ctx.ystride, _p(lse), _p(gloss),
+                                   _p(out), ldd, rows, Cn, ctx.smoothing, dt), "egk_ce_bwd")
+            else:
+                _ck(lib.egk_ce_w_bwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ctx.ystride, _vp(bal[0][h]),
+                                     _vp(bal[1][h]), _p(lse), _p(gloss), _p(out), ldd, rows, Cn, ctx.smoothing, dt), "egk_ce_w_bwd")
         for h in range(ctx.nh):
             l, lse = saved[2 * h], saved[2 * h + 1]
             rows, Cn = l.shape
@@ -2865,14 +2938,12 @@ class _CE(torch.autograd.Function):
                 # classifier_bank's operand buffer takes the gradient directly; ``d`` stays an uninitialised placeholder
                 gbuf, c0, state = dst
                 out = gbuf[:, c0:c0 + Cn]
-                _ck(lib.egk_ce_bwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ctx.ystride, _p(lse), _p(gloss),
-                                   _p(out), gbuf.stride(0), rows, Cn, ctx.smoothing, _dt(gbuf)), "egk_ce_bwd")
+                bwd(h, l, yh, lse, out, gbuf.stride(0), Cn, _dt(gbuf))
                 state["filled"].add(c0)
             else:
-                _ck(lib.egk_ce_bwd(_stream(), _p(l), l.stride(0), C.c_void_p(yh.data_ptr()), ctx.ystride, _p(lse), _p(gloss),
-                                   _p(d), d.stride(0), rows, Cn, ctx.smoothing, _dt(d)), "egk_ce_bwd")
+                bwd(h, l, yh, lse, d, d.stride(0), Cn, _dt(d))
             grads.append(d)
-        return (None, None, None, *grads)
+        return (None, None, None, None, *grads)
 
 
 def _ce_fused_plan(y, logits):
@@ -2900,10 +2971,11 @@ class _CEMulti(torch.autograd.Function):
     as ONE launch, ``egk_ce_fused_multi``."""
 
     @staticmethod
-    def forward(ctx, smoothing, coefs, heads_per_task, plans, *tensors):
+    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, *tensors):
+        # bal: None, or one entry per task -- None or the (weights, offsets) of ``_class_balance`` -- the launch with the vectors
         lib = _lib.load()
         n = len(coefs)
-        arr = (_lib.CETask * n)()
+        arr = (_lib.CETask * n)() if bal is None else (_lib.CEWTask * n)()
         losses, shapes, k = [], [], 0
         for i in range(n):
             y = tensors[k]
@@ -2913,22 +2985,28 @@ class _CEMulti(torch.autograd.Function):
             rows = logits[0].shape[0]
             loss = torch.empty(rows, dtype=torch.float32, device=gbuf.device)
             t = arr[i]
-            for h, l in enumerate(logits):
-                t.logits[h], t.ld[h], t.C[h], t.pad[h], t.dcol[h] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
-            t.n_heads, t.y, t.y_stride, t.loss = len(logits), y.data_ptr(), y.shape[1], loss.data_ptr()
-            t.dlogits, t.ldd, t.rows, t.gscale = gbuf.data_ptr(), gbuf.stride(0), rows, float(coefs[i])
+            if bal is not None:
+                _ce_w_task(t, logits, pads, starts, y, loss, gbuf, rows, coefs[i], bal[i])
+            else:
+                for h, l in enumerate(logits):
+                    t.logits[h], t.ld[h], t.C[h], t.pad[h], t.dcol[h] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
+                t.n_heads, t.y, t.y_stride, t.loss = len(logits), y.data_ptr(), y.shape[1], loss.data_ptr()
+                t.dlogits, t.ldd, t.rows, t.gscale = gbuf.data_ptr(), gbuf.stride(0), rows, float(coefs[i])
             losses.append(loss)
             shapes.append([tuple(l.shape) for l in logits])
             state["filled"].update(starts)
             state["pads"] = True
-        _ck(lib.egk_ce_fused_multi(_stream(), arr, n, float(smoothing), _dt(plans[0][0])), "egk_ce_fused_multi")
+        if bal is None:
+            _ck(lib.egk_ce_fused_multi(_stream(), arr, n, float(smoothing), _dt(plans[0][0])), "egk_ce_fused_multi")
+        else:
+            _ck(lib.egk_ce_w_fused_multi(_stream(), arr, n, float(smoothing), _dt(plans[0][0])), "egk_ce_w_fused_multi")
         ctx.shapes, ctx.heads = shapes, heads_per_task
         ctx.set_materialize_grads(False)
         return tuple(losses)
 
     @staticmethod
     def backward(ctx, *glosses):
-        out = [None, None, None, None]
+        out = [None, None, None, None, None]
         dev = next(g.device for g in glosses if g is not None)
         for shp in ctx.shapes:  # placeholders: the gradients are already in the banks' operand buffers
             out.append(None)  # y
@@ -2936,17 +3014,24 @@ class _CEMulti(torch.autograd.Function):
         return tuple(out)
 
 
-def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0):
+def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None):
     """[loss_t] of ``cross_entropy(logits_t, y_t, smoothing)`` for several tasks whose backward seeds ``coefs`` are known, in ONE
     launch that also writes every task's gradient operand -- or None when some task does not qualify for the fused form
-    (the caller then takes them one by one).  ``tasks``: [(logits tuple, y [N, heads] int64)]."""
+    (the caller then takes them one by one).  ``tasks``: [(logits tuple, y [N, heads] int64)].
+    ``weights`` / ``offsets``: None, or one entry per task, each what ``cross_entropy`` takes as ``weight`` / ``offset``; with
+    every vector None the launch is the one without the arguments."""
+    for name, arg in (("weights", weights), ("offsets", offsets)):
+        if arg is not None and len(arg) != len(tasks):
+            raise ValueError(f"cross_entropy_multi: {name} has {len(arg)} entries for {len(tasks)} tasks")
     if not (2 <= len(tasks) <= 4) or not torch.is_grad_enabled():
         return None
-    plans, flat, heads = [], [], []
+    plans, flat, heads, bal = [], [], [], []
     dt = None
-    for logits, y in tasks:
+    for i, (logits, y) in enumerate(tasks):
         if torch.is_tensor(logits):
             logits = (logits,)
+        bal.append(_class_balance(weights[i] if weights is not None else None, offsets[i] if offsets is not None else None,
+                                  logits, f"cross_entropy_multi (task {i})"))
         y = y.contiguous()
         plan = _ce_fused_plan(y, logits)
         if plan is None or (dt is not None and plan[0].dtype != dt):
@@ -2955,16 +3040,21 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0):
         plans.append(plan)
         heads.append(len(logits))
         flat += [y, *logits]
-    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, *flat))
+    if all(b is None for b in bal):
+        bal = None
+    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, *flat))
 
 
-def cross_entropy(logits, y, smoothing: float = 0.0):
+def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None):
     """Per-row CrossEntropy(reduction='none', ignore_index=-1), summed over heads when ``logits`` is
     a tuple and y is [N, heads].  Logits are f32; their gradient is emitted in the element type the
-    producing contraction wants (bf16 in 'bf16' mode)."""
+    producing contraction wants (bf16 in 'bf16' mode).
+    ``weight`` / ``offset``: per-class f32 vectors of length C on the logits' device -- None, one tensor (a single head), or a
+    tuple with one tensor or None per head: F.cross_entropy(x + offset, y, weight=weight, ...) per head, computed inside the
+    row pass (include/egopack_ce_balanced.h).  Constants: no gradient reaches them.  All None: the plain launches."""
     if torch.is_tensor(logits):
         logits = (logits,)
-    return _CE.apply(float(smoothing), y, _state["act"], *logits)
+    return _CE.apply(float(smoothing), y, _state["act"], _class_balance(weight, offset, logits), *logits)
 
 
 class _BCE(torch.autograd.Function):

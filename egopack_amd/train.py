@@ -138,10 +138,168 @@ def start_loader_workers(loaders) -> None:
             dl.start_workers()
 
 
-def build_criteria(dsets):
-    return {"ar": MetricSelectorWrapper(CrossEntropyNone(), dsets["ar"]),
-            "lta": MetricSelectorWrapper(CrossEntropyNone(), dsets["lta"]),
+def build_criteria(dsets, class_balance=None):
+    """``class_balance``: what ``build_class_balance`` returns -- the AR / LTA wrappers then carry its per-class vectors."""
+    cb = class_balance or {}
+    kw = {t: dict(class_weights=cb[t]["weights"], class_offsets=cb[t]["offsets"]) if t in cb else {} for t in ("ar", "lta")}
+    return {"ar": MetricSelectorWrapper(CrossEntropyNone(), dsets["ar"], **kw["ar"]),
+            "lta": MetricSelectorWrapper(CrossEntropyNone(), dsets["lta"], **kw["lta"]),
             "oscc": CrossEntropyNone(), "pnr": BCEWithLogitsNone()}
+
+
+# ---- class-balanced cross entropy of the AR / LTA heads (``class_balance:`` of the config) ---------------------------------------
+# OSCC (two balanced classes) and PNR (a BCE: that would be ``pos_weight``) are not part of it.
+CLASS_BALANCE_MODES = ("none", "weight", "logit_adjust")
+CLASS_BALANCE_SCHEMES = ("effective_number", "inverse_frequency")
+CLASS_BALANCE_TASKS = ("ar", "lta")
+CLASS_BALANCE_DEFAULTS = {"mode": "none", "scheme": "effective_number", "beta": 0.999, "power": 1.0, "tau": 1.0, "normalize": True,
+                          "tasks": ["ar", "lta"]}
+
+
+def class_balance_config(cfg) -> dict:
+    """The ``class_balance:`` block with its defaults filled in; an unknown key, mode, scheme or task is a ValueError naming it."""
+    raw = cfg.get("class_balance") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(CLASS_BALANCE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"class_balance: unknown key(s) {sorted(unknown)} ({', '.join(CLASS_BALANCE_DEFAULTS)})")
+    cb = {**CLASS_BALANCE_DEFAULTS, **raw}
+    cb["mode"], cb["scheme"] = str(cb["mode"]).lower(), str(cb["scheme"]).lower()
+    if cb["mode"] not in CLASS_BALANCE_MODES:
+        raise ValueError(f"class_balance.mode: unknown mode '{cb['mode']}' ({' | '.join(CLASS_BALANCE_MODES)})")
+    if cb["scheme"] not in CLASS_BALANCE_SCHEMES:
+        raise ValueError(f"class_balance.scheme: unknown scheme '{cb['scheme']}' ({' | '.join(CLASS_BALANCE_SCHEMES)})")
+    cb["tasks"] = [str(t) for t in (cb["tasks"] or [])]
+    unknown = set(cb["tasks"]) - set(CLASS_BALANCE_TASKS)
+    if unknown:
+        raise ValueError(f"class_balance.tasks: unknown task(s) {sorted(unknown)} ({', '.join(CLASS_BALANCE_TASKS)})")
+    cb["beta"], cb["power"], cb["tau"], cb["normalize"] = float(cb["beta"]), float(cb["power"]), float(cb["tau"]), bool(cb["normalize"])
+    if not 0.0 <= cb["beta"] < 1.0:
+        raise ValueError(f"class_balance.beta: {cb['beta']} is outside [0, 1)")
+    return cb
+
+
+def label_counts(dataset) -> list:
+    """Per head the number of labels >= 0 of every class over all nodes of all samples of ``dataset`` (int64, length C).  The
+    WHOLE split, not a rank's shard: every rank computes the same vectors without a collective.  A dataset that holds its label
+    table (the resident datasets' ``_tables()['y']``) is counted from it; otherwise one pass over the samples.
+    That pass reads ``dataset[i]``, features included: it costs one read of the split at start-up, and on a dataset whose
+    ``__getitem__`` is stateful (one that draws from a random stream per call) it advances that state once per sample before
+    training starts, so a run with ``class_balance`` on and one with it off then see different samples.  The datasets of this
+    project are pure functions of the index or hold a label table; a dataset that is neither should offer ``_tables``."""
+    Cs = tuple(dataset.num_class_labels)
+    if hasattr(dataset, "_tables"):
+        y = torch.as_tensor(dataset._tables()["y"])
+        ys = [y.reshape(-1, y.shape[-1]) if y.dim() >= 2 else y.reshape(-1, 1)]
+    else:
+        # (``dataset[i]``, the sample the loaders deliver: the synthetic datasets draw their labels behind their features from one
+        #  random stream, so ``__getitem__(i, with_x=False)`` is another sample's labels there -- it is the resident datasets'
+        #  label source only, and those are counted from their table above)
+        ys = []
+        for i in range(len(dataset)):
+            y = torch.as_tensor(dataset[i].y)
+            ys.append(y.reshape(-1, y.shape[-1]) if y.dim() >= 2 else y.reshape(-1, 1))
+    y = torch.cat(ys).to(torch.int64) if ys else torch.zeros((0, len(Cs)), dtype=torch.int64)
+    if y.shape[1] < len(Cs):
+        raise ValueError(f"class_balance: the dataset's labels have {y.shape[1]} columns, its heads are {Cs}")
+    counts = []
+    for h, Cn in enumerate(Cs):
+        col = y[:, h]
+        col = col[(col >= 0) & (col < Cn)]
+        counts.append(torch.bincount(col, minlength=Cn).to(torch.int64))
+    return counts
+
+
+def class_weights(counts, scheme: str = "effective_number", beta: float = 0.999, power: float = 1.0,
+                  normalize: bool = True) -> torch.Tensor:
+    """Per-class weights from label counts, float64.  With n' = max(n, 1) (a class without a label weighs what a class with one
+    does): effective_number (Cui et al. 2019) w = (1 - beta) / (1 - beta ** n'); inverse_frequency w = n' ** -power.
+    ``normalize``: w *= sum(n) / sum(n * w) -- the mean weight over the training labels is 1, so the objective keeps its scale
+    and the task weights keep their meaning."""
+    n = torch.as_tensor(counts).to(torch.float64)
+    n1 = n.clamp(min=1.0)
+    if scheme == "effective_number":
+        w = (1.0 - beta) / (1.0 - torch.pow(torch.tensor(beta, dtype=torch.float64), n1)) if beta > 0 else torch.ones_like(n1)
+    elif scheme == "inverse_frequency":
+        w = torch.pow(n1, -power)
+    else:
+        raise ValueError(f"class_balance.scheme: unknown scheme '{scheme}' ({' | '.join(CLASS_BALANCE_SCHEMES)})")
+    if normalize and float((n * w).sum()) > 0:
+        w = w * (n.sum() / (n * w).sum())
+    return w
+
+
+def logit_offsets(counts, tau: float = 1.0) -> torch.Tensor:
+    """Logit adjustment (Menon et al. 2021), float64: a_c = tau * log(n'_c / sum(n')), n' = max(n, 1)."""
+    n1 = torch.as_tensor(counts).to(torch.float64).clamp(min=1.0)
+    return tau * torch.log(n1 / n1.sum())
+
+
+def build_class_balance(cfg, dsets_train, device=None, tasks=None) -> dict:
+    """{task: {"weights": [f32 vector per head] | None, "offsets": [...] | None, "counts": [int64 vector per head]}} for the tasks
+    of ``class_balance.tasks`` -- {} with ``mode: none`` (nothing is counted, nothing is built: the criteria and the launches are
+    the ones without the feature).  ``tasks``: the tasks the caller trains (None: all) -- the labels of the others are not
+    counted.  Formulas in float64, rounded once to f32."""
+    cb = class_balance_config(cfg)
+    if cb["mode"] == "none":
+        return {}
+    out = {}
+    for t in CLASS_BALANCE_TASKS:
+        if t not in cb["tasks"] or t not in dsets_train or (tasks is not None and t not in tasks):
+            continue
+        counts = label_counts(dsets_train[t])
+        if cb["mode"] == "weight":
+            vecs = [class_weights(c, cb["scheme"], cb["beta"], cb["power"], cb["normalize"]) for c in counts]
+        else:
+            vecs = [logit_offsets(c, cb["tau"]) for c in counts]
+        vecs = [v.to(torch.float32) if device is None else v.to(torch.float32).to(device) for v in vecs]
+        out[t] = {"weights": vecs if cb["mode"] == "weight" else None, "offsets": vecs if cb["mode"] == "logit_adjust" else None,
+                  "counts": counts}
+    return out
+
+
+def log_class_balance(logger, cfg, class_balance) -> None:
+    """One line per head: mode, smallest and largest weight or offset, classes without a label."""
+    if not class_balance:
+        return
+    cb = class_balance_config(cfg)
+    for t, entry in class_balance.items():
+        vecs = entry["weights"] if entry["weights"] is not None else entry["offsets"]
+        what = "weight" if entry["weights"] is not None else "offset"
+        for h, (v, n) in enumerate(zip(vecs, entry["counts"])):
+            logger.info("class balance %s head %d (%d classes): mode %s, %s in [%.6g, %.6g], %d zero-count classes, %d labels",
+                        t, h, v.numel(), cb["mode"] + ("/" + cb["scheme"] if cb["mode"] == "weight" else ""), what,
+                        float(v.min()), float(v.max()), int((n == 0).sum()), int(n.sum()))
+
+
+def class_balance_state(cfg, class_balance) -> Optional[dict]:
+    """The checkpoint's top-level ``"class_balance"`` entry: the config block and the vectors (host tensors); None when off."""
+    if not class_balance:
+        return None
+    host = lambda vs: None if vs is None else [v.detach().cpu().clone() for v in vs]
+    return {"config": class_balance_config(cfg),
+            "vectors": {t: {"weights": host(e["weights"]), "offsets": host(e["offsets"])} for t, e in class_balance.items()}}
+
+
+def check_class_balance(logger, ckpt: dict, cfg, class_balance) -> bool:
+    """On resume: the vectors rebuilt from the config and the training split against the ones the checkpoint stores, bit for bit.
+    A difference (or one side without vectors) is ONE warning line; returns whether they agree."""
+    stored, now = ckpt.get("class_balance"), class_balance_state(cfg, class_balance)
+    same = (stored is None) == (now is None)
+    if same and now is not None:
+        a, b = stored.get("vectors", {}), now["vectors"]
+        same = a.keys() == b.keys()
+        for t in (a if same else ()):
+            for kind in ("weights", "offsets"):
+                va, vb = a[t].get(kind), b[t].get(kind)
+                if (va is None) != (vb is None) or (va is not None and (len(va) != len(vb) or any(
+                        x.shape != y_.shape or not torch.equal(x.cpu().view(torch.int32), y_.view(torch.int32)) for x, y_ in zip(va, vb)))):
+                    same = False
+    if not same:
+        logger.warning("class balance: the vectors built for this run differ from the checkpoint's (config %s, stored %s): "
+                       "the run continues with the ones built now", class_balance_config(cfg),
+                       None if stored is None else stored.get("config"))
+    return same
 
 
 OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
@@ -288,13 +446,14 @@ def ema_checkpoint_path(path: Path) -> Path:
 
 
 def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimizer=None, scheduler=None, loaders=None,
-                    save_ema: bool = False):
+                    save_ema: bool = False, class_balance: Optional[dict] = None):
     """Reference key layout (main_temporal.py:410-417, main_egopack.py:453-460) + what the reference does not keep and
     a resumed run needs: the optimiser state (torch.optim.Adam's per-parameter layout) and the schedule state.
     ``save_ema`` (``ema.save`` of the config; an optimizer that keeps a weight average): a second file beside it,
     ``checkpoint_ema.pth``, with the reference's key layout alone and the AVERAGED weights in place of the parameters -- the
     modules' state dicts taken inside ``optimizer.ema_weights()``; any loader of the reference's layout and ``resume_from=``
-    take it as it is.  The ordinary file keeps the raw weights and the average under the optimizer's ``"ema"`` key."""
+    take it as it is.  The ordinary file keeps the raw weights and the average under the optimizer's ``"ema"`` key.
+    ``class_balance`` (``class_balance_state``; None when off): stored under the top-level key ``"class_balance"``."""
     path.parent.mkdir(parents=True, exist_ok=True)
     if save_ema and getattr(optimizer, "ema", False):
         with optimizer.ema_weights():
@@ -309,6 +468,8 @@ def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimiz
         ckpt["optimizer"] = sd
     if scheduler is not None:
         ckpt["scheduler"] = scheduler.state_dict()
+    if class_balance is not None:
+        ckpt["class_balance"] = class_balance
     if loaders is not None:  # shuffle generators of the training loaders + dropout streams: exact continuation
         ckpt["rng"] = {"loaders": {t: dl.state_dict() for t, dl in loaders.items() if hasattr(dl, "state_dict")},
                        "dropout": ops.get_rng_state(), "torch": torch.get_rng_state()}

@@ -749,5 +749,7 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 #include "egopack_optim_groups.h"
 /* ... and with an exponential moving average of the weights kept inside the launch (egk_optim_step_ema, egk_ema_swap) */
 #include "egopack_ema.h"
+/* the cross entropies with per-class weights and logit offsets applied inside the row pass (egk_ce_w_fwd / _bwd / _fused_multi) */
+#include "egopack_ce_balanced.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -118,6 +118,13 @@ def main(argv=None):
     }
     for t in tasks.values():
         t.to(device)
+    # class_balance: the enabled AR / LTA task trains with per-class weights / logit offsets (its ``compute_loss`` while training);
+    # only its labels are counted.  ``resume_from`` here is the multi-task pre-training checkpoint (backbone and task heads, no
+    # optimizer state): its vectors belong to that run's objective, not to this one, so nothing is compared with them.
+    balance = T.build_class_balance(cfg, dsets_train, device=device, tasks=[t for t, w in weights.items() if w > 0])
+    T.log_class_balance(logger, cfg, balance)
+    for t, e in balance.items():
+        tasks[t].set_class_balance(e["weights"], e["offsets"])
     if cfg.resume_from:
         logger.info("resuming from %s", cfg.resume_from)
         T.load_checkpoint(cfg.resume_from, model, tasks, strict_tasks=False, device=device)
@@ -163,7 +170,8 @@ def main(argv=None):
     if cfg.save_model and rank == 0:
         name = f"{cfg.artifact_prefix}_egopack_" + "-".join(sorted(t for t, w in weights.items() if w > 0))
         T.save_checkpoint(Path(cfg.checkpoint_dir) / name / "checkpoint.pth", model, tasks, cfg.num_epochs,
-                          graphone=graphone, optimizer=optimizer, save_ema=T.ema_saved(cfg))
+                          graphone=graphone, optimizer=optimizer, save_ema=T.ema_saved(cfg),
+                          class_balance=T.class_balance_state(cfg, balance))
     if world > 1:
         torch.distributed.destroy_process_group()
 

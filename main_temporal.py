@@ -36,6 +36,8 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
     step.model.train()
     for t in step.tasks.values():
         t.train()
+    for c in step.criteria.values():
+        c.train()  # (class-balance vectors apply to the training loss only)
     order = ("ar", "lta", "oscc", "pnr")
     it = 0
     step.loss_sums()  # (clears the per-task loss sums: they accumulate inside the step, on the device, until the epoch ends)
@@ -73,6 +75,8 @@ def validate_losses(step: engine.MTLStep, loaders, device="cuda"):
     step.model.eval()
     for t in step.tasks.values():
         t.eval()
+    for c in step.criteria.values():
+        c.eval()  # (validation losses are the plain cross entropy whatever ``class_balance`` says: curves compare across runs)
     out = {}
     for t in step.enabled:
         s, n = 0.0, 0
@@ -161,8 +165,10 @@ def main(argv=None):
         # scale, staged backward) on ONE GPU -- everything of the N-GPU step except the peers' contributions
         edist.init_single_rank_group()  # (no-op when the caller already owns a group; free rendezvous port otherwise)
         sync = edist.GradSync(dry, compress=compress)
-    step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train), weights, optimizer,
-                          fused_backbone=cfg.fused_backbone, sync=sync)
+    # class_balance: per-class weights / logit offsets of the AR and LTA heads from the label counts of the whole training split
+    balance = T.build_class_balance(cfg, dsets_train, device=device)
+    T.log_class_balance(logger, cfg, balance)
+    step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train, balance), weights, optimizer, fused_backbone=cfg.fused_backbone, sync=sync)
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))  # several ranks: graph-LN statistics over the GLOBAL batch
 
@@ -172,6 +178,7 @@ def main(argv=None):
         ck = T.load_checkpoint(cfg.resume_from, model, tasks, strict_tasks=True, device=device, optimizer=optimizer,
                                scheduler=scheduler, loaders=dl_train)
         first_epoch = int(ck.get("epoch", 0)) + 1
+        T.check_class_balance(logger, ck, cfg, balance)  # (rebuilt above; compared bit for bit with the stored vectors)
         logger.info("resumed from %s at epoch %d", cfg.resume_from, first_epoch)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
@@ -182,7 +189,7 @@ def main(argv=None):
             sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
         if cfg.save_model and cfg.get("save_every", 0) and epoch % cfg.save_every == 0 and rank == 0:
             T.save_checkpoint(ckpt_path, model, tasks, epoch, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
-                              save_ema=T.ema_saved(cfg))
+                              save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance))
         if epoch >= cfg.num_epochs - 5:  # all ranks: the validation split is sharded by batch
             T.log_validation_weights(logger, cfg, optimizer, epoch)
             with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
@@ -196,7 +203,7 @@ def main(argv=None):
         sync.gather_moments(optimizer)
     if cfg.save_model and rank == 0:
         T.save_checkpoint(ckpt_path, model, tasks, cfg.num_epochs, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
-                          save_ema=T.ema_saved(cfg))
+                          save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance))
     if world > 1:
         torch.distributed.destroy_process_group()
     # (callers that drive main() from Python -- the tests -- get the last validation metrics and the trained modules)
