@@ -24,6 +24,7 @@ OPTIM_GROUPS_HEADER = HERE.parent / "include" / "egopack_optim_groups.h"  # like
 
 EMA_HEADER = HERE.parent / "include" / "egopack_ema.h"  # likewise; its symbols: EMA_SIGNATURES
 CE_BALANCED_HEADER = HERE.parent / "include" / "egopack_ce_balanced.h"  # likewise; its symbols: CE_BALANCED_SIGNATURES
+BCE_BALANCED_HEADER = HERE.parent / "include" / "egopack_bce_balanced.h"  # likewise; its symbols: BCE_BALANCED_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -255,6 +256,14 @@ CE_BALANCED_SIGNATURES = {
 }
 
 
+# ... and include/egopack_bce_balanced.h (the sixth ledger: tests/test_pnr_balance_cpu.py over tests/test_gpu_bounds_pnr_balance.py)
+BCE_BALANCED_SIGNATURES = {
+    "egk_bce_w_fwd": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, f32]),
+    "egk_bce_w_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, f32, f32, f32, i32]),
+    "egk_rowdot_bce_w": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, i32]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -286,6 +295,11 @@ def ce_balanced_header_symbols() -> list:
     return _declared(CE_BALANCED_HEADER)
 
 
+def bce_balanced_header_symbols() -> list:
+    """Every function name declared in include/egopack_bce_balanced.h."""
+    return _declared(BCE_BALANCED_HEADER)
+
+
 _lib = None
 
 
@@ -300,7 +314,7 @@ def load() -> C.CDLL:
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
-                              *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items()]:
+                              *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

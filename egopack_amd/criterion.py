@@ -40,10 +40,22 @@ class CrossEntropyNone(torch.nn.Module):
 
 
 class BCEWithLogitsNone(torch.nn.Module):
-    """nn.BCEWithLogitsLoss(reduction='none'); the caller passes ``y.float()`` as the reference does."""
+    """nn.BCEWithLogitsLoss(reduction='none'); the caller passes ``y.float()`` as the reference does.
+    ``pos`` / ``neg`` / ``gamma``: the class factor of a positive / a negative node and the focal exponent, applied inside the
+    kernels (``ops.bce_with_logits``) while the module is in training mode; plain attributes, all None: the plain loss."""
+
+    def __init__(self, pos=None, neg=None, gamma=None):
+        super().__init__()
+        self._balance = ops.bce_shape(pos, neg, gamma, "BCEWithLogitsNone")
+
+    def balance(self):
+        """(pos, neg, gamma), or None when the criterion carries no scalar or is in ``eval()`` mode (the scalars shape the
+        training loss only)."""
+        return self._balance if self.training else None
 
     def forward(self, logits, target):
-        return ops.bce_with_logits(logits, target)
+        pos, neg, gamma = self.balance() or (None, None, None)
+        return ops.bce_with_logits(logits, target, pos, neg, gamma)  # (no scalar: the plain launches)
 
 
 class MetricSelectorWrapper(torch.nn.Module):

@@ -9,6 +9,7 @@
 //     lane->column map is the same for every row, and are finished by a small second launch that
 //     sums the per-workgroup partials in a fixed order (bitwise reproducible, no atomics).
 // All of these are HBM-bound: algorithmic bytes are listed per kernel in DESIGN.md.
+#include "bce_shaped.h"
 #include "common.h"
 
 namespace egk {
@@ -932,11 +933,13 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
 //   df_n = g_n * w;   dw = sum_n g_n f_n;   db = sum_n g_n
 // dw / db leave as per-workgroup partial rows ws[blk][cols + 4] (column ``cols`` = db), summed in block order by
 // rowdot_reduce_kernel: fixed order, no atomics.
-template <int NV, typename T, bool FULL>
+// SHAPED (egk_rowdot_bce_w, include/egopack_bce_balanced.h): loss_n and g_n are bce_shaped.h's -- a class factor and a focal
+// exponent, wave-uniform kernel arguments -- in place of the two expressions above; everything else is this kernel.
+template <int NV, typename T, bool FULL, bool SHAPED = false>
 __global__ __launch_bounds__(256) void rowdot_bce_kernel(const T* __restrict__ f, const T* __restrict__ w, const float* __restrict__ bias,
                                                          const long long* __restrict__ y, float* __restrict__ logits,
                                                          float* __restrict__ loss, T* __restrict__ df, float* __restrict__ ws,
-                                                         int rows, int cols, float seed) {
+                                                         int rows, int cols, float seed, const BceShape sh = BceShape{1.f, 1.f, 0.f}) {
     extern __shared__ __attribute__((aligned(16))) float red_[];  // [WPB][NV * 256 + 4]
     float (*red)[NV * 256 + 4] = reinterpret_cast<float (*)[NV * 256 + 4]>(red_);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -958,14 +961,17 @@ __global__ __launch_bounds__(256) void rowdot_bce_kernel(const T* __restrict__ f
 #pragma unroll
             for (int t = 0; t < 4; ++t) d = fmaf(el(r.v[i], t), el(wv.v[i], t), d);  // out-of-range columns load as 0
         const float z = wave_sum(d) + b0;
-        const float t = (float)y[row];
+        const long long yr = y[row];
+        const float t = (float)yr;
         if (lane == 0) {
             logits[row] = z;
-            loss[row] = (1.f - t) * z + fmaxf(-z, 0.f) + log1pf(expf(-fabsf(z)));
+            if constexpr (SHAPED) loss[row] = bce_shaped_loss(z, yr, sh);
+            else loss[row] = (1.f - t) * z + fmaxf(-z, 0.f) + log1pf(expf(-fabsf(z)));
         }
         if (df) {
             T gr;
-            st1t(&gr, (1.f / (1.f + expf(-z)) - t) * seed);  // the gradient in the operand element type
+            if constexpr (SHAPED) st1t(&gr, bce_shaped_grad(z, yr, seed, sh));
+            else st1t(&gr, (1.f / (1.f + expf(-z)) - t) * seed);  // the gradient in the operand element type
             const float g = ld1t(&gr);
             gsum += g;  // (identical in every lane)
             Row<NV> o;
@@ -1555,6 +1561,28 @@ int egk_rowdot_bce(egk_stream_t stream, const void* f, const void* w, const floa
                                                  WPB * (NV * 256 + 4) * sizeof(float), s, (const T*)f,
                                                  (const T*)w, bias, (const long long*)y, logits, loss, (T*)df, ws, rows, cols, seed));
     return check_launch("egk_rowdot_bce");
+}
+
+/* egk_rowdot_bce with the shaped loss of include/egopack_bce_balanced.h: the same kernel, grid, workspace layout and refusals. */
+int egk_rowdot_bce_w(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
+                     float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, float pos, float neg, float gamma,
+                     int32_t dtype) {
+    EGK_REQUIRE(f && w && y && logits && loss, "egk_rowdot_bce_w: null pointer");
+    EGK_REQUIRE(!df || ws, "egk_rowdot_bce_w: gradients need the partial-row workspace");
+    EGK_REQUIRE(rows >= 0, "egk_rowdot_bce_w: rows must be >= 0");
+    EGK_REQUIRE(cols >= 1, "egk_rowdot_bce_w: cols must be >= 1");
+    EGK_REQUIRE(bce_shape_ok(pos, neg, gamma), "egk_rowdot_bce_w: pos, neg and gamma must be finite and >= 0 (got %g, %g, %g)",
+                (double)pos, (double)neg, (double)gamma);
+    EGK_REQUIRE_VEC_ALIGNED("egk_rowdot_bce_w", (cols & 3) || aligned_to(vec_bytes(dtype), {f, w, df}));
+    if (rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
+    ProfScope prof(KID_BCE_BALANCED, s, 2.0 * rows * cols * (df ? 3 : 1), eb * rows * cols * (df ? 2 : 1) + 16.0 * rows);
+    DISPATCH_NV(cols, dtype, hipLaunchKernelGGL((rowdot_bce_kernel<NV, T, FULL, true>), dim3(row_grid(rows)), dim3(256),
+                                                 WPB * (NV * 256 + 4) * sizeof(float), s, (const T*)f,
+                                                 (const T*)w, bias, (const long long*)y, logits, loss, (T*)df, ws, rows, cols, seed,
+                                                 BceShape{pos, neg, gamma}));
+    return check_launch("egk_rowdot_bce_w");
 }
 
 int32_t egk_rowdot_ce2_max_rows(void) { return CE2_MAX_ROWS; }

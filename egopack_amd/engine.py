@@ -1632,7 +1632,8 @@ class MTLStep(StepBase):
                 if oscc_one:
                     one_pass = task.fused_head_loss(f, d, d.y, getattr(self.criteria[t], "label_smoothing", 0.0))
                 elif n_loss and self._one_pass_head_ok(t):
-                    one_pass = task.fused_head_loss(f, d.y)  # one-logit classifier + BCE + their gradients: one row pass
+                    # one-logit classifier + BCE + their gradients: one row pass (with the criterion's pos / neg / gamma, if any)
+                    one_pass = task.fused_head_loss(f, d.y, balance=self.criteria[t].balance())
                 if one_pass is not None:
                     v, logits = one_pass
                 elif oscc_one:  # (did not apply after all: the contraction path WITHOUT an announced seed, as before)

@@ -40,14 +40,28 @@ class PNRTask(ProjectionTask):
             raise ValueError("PNR task has no auxiliary classifiers.")
         return apply_classifier(self.aux_classifiers[t], features)
 
-    def fused_head_loss(self, features: torch.Tensor, targets: torch.Tensor):
+    def set_loss_balance(self, pos=None, neg=None, gamma=None) -> None:
+        """The class factor of a positive / a negative node and the focal exponent of the training loss (``compute_loss`` while
+        ``self.training``; include/egopack_bce_balanced.h).  A plain attribute: the state-dict keys stay the reference's.  All
+        None: the plain BCE."""
+        self._loss_balance = ops.bce_shape(pos, neg, gamma, "PNRTask.set_loss_balance")
+
+    def loss_balance(self):
+        """(pos, neg, gamma) or None."""
+        return getattr(self, "_loss_balance", None)
+
+    def fused_head_loss(self, features: torch.Tensor, targets: torch.Tensor, balance=None):
         """(loss vector, logits) of ``BCEWithLogits(forward_logits(features), targets)`` in ONE row pass that also emits the
         gradients (ops.linear1_bce), or None when it does not apply (classifier dropout active, no announced loss seed):
-        a one-logit classifier is a row reduction, not matrix work."""
+        a one-logit classifier is a row reduction, not matrix work.  ``balance``: None or the caller's (pos, neg, gamma) -- the
+        same pass with the shaped loss."""
         drop, lin = self.classifier[0], self.classifier[1]
         if (self.training and getattr(drop, "p", 0) > 0) or not ops.linear1_bce_ok(features, lin.weight):
             return None
-        return ops.linear1_bce(features, lin.weight, lin.bias, targets)
+        pos, neg, gamma = balance or (None, None, None)
+        return ops.linear1_bce(features, lin.weight, lin.bias, targets, pos, neg, gamma)
 
     def compute_loss(self, logits: torch.Tensor, targets: torch.Tensor):
-        return ops.bce_with_logits(logits, targets)
+        """The scalars of ``set_loss_balance`` shape the training loss only: a validation loss (``eval()``) is the plain BCE."""
+        pos, neg, gamma = (self.loss_balance() if self.training else None) or (None, None, None)
+        return ops.bce_with_logits(logits, targets, pos, neg, gamma)

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -3057,15 +3058,30 @@ def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None):
     return _CE.apply(float(smoothing), y, _state["act"], _class_balance(weight, offset, logits), *logits)
 
 
+def bce_shape(pos, neg, gamma, where="bce_with_logits"):
+    """The (pos, neg, gamma) triple of include/egopack_bce_balanced.h as three Python floats, or None when all three are None (the
+    plain launches).  A missing one defaults to 1, 1, 0; constants: no gradient reaches them."""
+    if pos is None and neg is None and gamma is None:
+        return None
+    sh = tuple(float(d if v is None else v) for v, d in ((pos, 1.0), (neg, 1.0), (gamma, 0.0)))
+    if not all(math.isfinite(v) and v >= 0.0 for v in sh):
+        raise ValueError(f"{where}: pos, neg and gamma must be finite and >= 0, got {sh}")
+    return sh
+
+
 class _BCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, y, gdt):
+    def forward(ctx, logits, y, gdt, shape):
+        # shape: None, or the (pos, neg, gamma) of ``bce_shape`` -- the shaped launches (egk_bce_w_fwd / _bwd)
         _need_gpu(logits, y)
         logits = _f32c(logits)
         y = y.contiguous()
         loss = torch.empty_like(logits)
-        _ck(_lib.load().egk_bce_fwd(_stream(), _p(logits), _p(y), _p(loss), logits.numel()), "egk_bce_fwd")
-        ctx.gdt = gdt
+        if shape is None:
+            _ck(_lib.load().egk_bce_fwd(_stream(), _p(logits), _p(y), _p(loss), logits.numel()), "egk_bce_fwd")
+        else:
+            _ck(_lib.load().egk_bce_w_fwd(_stream(), _p(logits), _p(y), _p(loss), logits.numel(), *shape), "egk_bce_w_fwd")
+        ctx.gdt, ctx.shape = gdt, shape
         ctx.save_for_backward(logits, y)
         return loss
 
@@ -3074,15 +3090,23 @@ class _BCE(torch.autograd.Function):
         logits, y = ctx.saved_tensors
         g = _f32c(g)
         d = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
-        _ck(_lib.load().egk_bce_bwd(_stream(), _p(logits), _p(y), _p(g), _p(d), logits.numel(), _dt(d)), "egk_bce_bwd")
-        return d, None, None
+        if ctx.shape is None:
+            _ck(_lib.load().egk_bce_bwd(_stream(), _p(logits), _p(y), _p(g), _p(d), logits.numel(), _dt(d)), "egk_bce_bwd")
+        else:
+            _ck(_lib.load().egk_bce_w_bwd(_stream(), _p(logits), _p(y), _p(g), _p(d), logits.numel(), *ctx.shape, _dt(d)),
+                "egk_bce_w_bwd")
+        return d, None, None, None
 
 
-def bce_with_logits(logits, y):
-    """BCEWithLogitsLoss(reduction='none') against y.float(); y int64 of the same shape."""
+def bce_with_logits(logits, y, pos=None, neg=None, gamma=None):
+    """BCEWithLogitsLoss(reduction='none') against y.float(); y int64 of the same shape.
+    ``pos`` / ``neg`` / ``gamma``: Python floats >= 0 -- the class factor of a positive / a negative node and the focal exponent,
+    applied inside the kernels (include/egopack_bce_balanced.h): neg * BCEWithLogitsLoss(pos_weight=pos / neg) for gamma 0, the
+    sigmoid focal loss with alpha_t = pos / neg otherwise.  All None: the plain launches; any given: the shaped ones (also for
+    1, 1, 0), a missing one being 1, 1, 0."""
     if y.dtype != torch.int64:
         y = y.to(torch.int64)
-    return _BCE.apply(logits, y, _state["act"])
+    return _BCE.apply(logits, y, _state["act"], bce_shape(pos, neg, gamma))
 
 
 class _RowDotBCE(torch.autograd.Function):
@@ -3090,7 +3114,8 @@ class _RowDotBCE(torch.autograd.Function):
     (egk_rowdot_bce): used when the seed of the loss vector's backward is known (``loss_seed``)."""
 
     @staticmethod
-    def forward(ctx, f, W, b, y, seed):
+    def forward(ctx, f, W, b, y, seed, shape):
+        # shape: None, or the (pos, neg, gamma) of ``bce_shape`` -- the same pass with the shaped loss (egk_rowdot_bce_w)
         _need_gpu(f, W, y)
         lib = _lib.load()
         f = _c(f)
@@ -3102,8 +3127,12 @@ class _RowDotBCE(torch.autograd.Function):
         loss = torch.empty(rows, dtype=torch.float32, device=f.device)
         df = torch.empty_like(f)
         ws = torch.empty(lib.egk_rowdot_ws_rows(rows) * (cols + 4), dtype=torch.float32, device=f.device)
-        _ck(lib.egk_rowdot_bce(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(ws), rows, cols,
-                               float(seed), _dt(f)), "egk_rowdot_bce")
+        if shape is None:
+            _ck(lib.egk_rowdot_bce(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(ws), rows, cols,
+                                   float(seed), _dt(f)), "egk_rowdot_bce")
+        else:
+            _ck(lib.egk_rowdot_bce_w(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(ws), rows, cols,
+                                     float(seed), *shape, _dt(f)), "egk_rowdot_bce_w")
         slot_w, slot_b = _grad_slot(W), _grad_slot(b)
         dw = slot_w if slot_w is not None else torch.zeros(W.shape, dtype=torch.float32, device=f.device)
         db = (slot_b if slot_b is not None else torch.zeros(b.shape, dtype=torch.float32, device=f.device)) if b is not None else None
@@ -3117,7 +3146,7 @@ class _RowDotBCE(torch.autograd.Function):
     def backward(ctx, gloss, _glogits):
         df, dw, db = ctx.ret  # computed in forward from the announced seed (the constant weight / numel of the objective)
         ctx.ret = None        # (sole owner of df from here: autograd keeps it as the leaf's gradient instead of cloning it)
-        return df, dw, db, None, None
+        return df, dw, db, None, None, None
 
 
 def linear1_bce_ok(f, W) -> bool:
@@ -3128,15 +3157,15 @@ def linear1_bce_ok(f, W) -> bool:
                 and (f.dtype == torch.bfloat16 or (f.dtype == torch.float32 and _state["compute"] == F32)))
 
 
-def linear1_bce(f, W, b, y):
+def linear1_bce(f, W, b, y, pos=None, neg=None, gamma=None):
     """(loss [N], logits [N]) of BCEWithLogits(reduction='none')(Linear(H, 1)(f).squeeze(), y.float()) -- reference
     models/tasks/pnr.py:37-52 + main_temporal.py:117-121 -- in one row pass that also writes d f, d W, d b.  Requires
-    ``linear1_bce_ok``."""
+    ``linear1_bce_ok``.  ``pos`` / ``neg`` / ``gamma``: as ``bce_with_logits`` -- the same pass with the shaped loss."""
     if not linear1_bce_ok(f, W):
         raise RuntimeError("linear1_bce: needs an announced loss seed (ops.loss_seed) and a device feature matrix")
     if y.dtype != torch.int64:
         y = y.to(torch.int64)
-    return _RowDotBCE.apply(f, W, b, y, float(_loss_seed["coef"]))
+    return _RowDotBCE.apply(f, W, b, y, float(_loss_seed["coef"]), bce_shape(pos, neg, gamma, "linear1_bce"))
 
 
 class _RowDotCE2(torch.autograd.Function):

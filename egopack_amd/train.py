@@ -138,17 +138,19 @@ def start_loader_workers(loaders) -> None:
             dl.start_workers()
 
 
-def build_criteria(dsets, class_balance=None):
-    """``class_balance``: what ``build_class_balance`` returns -- the AR / LTA wrappers then carry its per-class vectors."""
+def build_criteria(dsets, class_balance=None, pnr_balance=None):
+    """``class_balance``: what ``build_class_balance`` returns -- the AR / LTA wrappers then carry its per-class vectors.
+    ``pnr_balance``: what ``build_pnr_balance`` returns -- the PNR criterion then carries its pos / neg / gamma."""
     cb = class_balance or {}
     kw = {t: dict(class_weights=cb[t]["weights"], class_offsets=cb[t]["offsets"]) if t in cb else {} for t in ("ar", "lta")}
+    pb = {k: pnr_balance[k] for k in ("pos", "neg", "gamma")} if pnr_balance else {}
     return {"ar": MetricSelectorWrapper(CrossEntropyNone(), dsets["ar"], **kw["ar"]),
             "lta": MetricSelectorWrapper(CrossEntropyNone(), dsets["lta"], **kw["lta"]),
-            "oscc": CrossEntropyNone(), "pnr": BCEWithLogitsNone()}
+            "oscc": CrossEntropyNone(), "pnr": BCEWithLogitsNone(**pb)}
 
 
 # ---- class-balanced cross entropy of the AR / LTA heads (``class_balance:`` of the config) ---------------------------------------
-# OSCC (two balanced classes) and PNR (a BCE: that would be ``pos_weight``) are not part of it.
+# OSCC (two balanced classes) is not part of it; PNR (a BCE) has its own block, ``pnr_balance:`` (below).
 CLASS_BALANCE_MODES = ("none", "weight", "logit_adjust")
 CLASS_BALANCE_SCHEMES = ("effective_number", "inverse_frequency")
 CLASS_BALANCE_TASKS = ("ar", "lta")
@@ -302,6 +304,113 @@ def check_class_balance(logger, ckpt: dict, cfg, class_balance) -> bool:
     return same
 
 
+# ---- positive-class weighting / focal loss of the PNR head (``pnr_balance:`` of the config) ---------------------------------------
+# One positive node per sequence of T candidates: three scalars (pos, neg, gamma) shape the BCE inside the kernels of the step
+# (include/egopack_bce_balanced.h).  Training loss only, like ``class_balance``.
+PNR_BALANCE_MODES = ("none", "pos_weight", "focal")
+PNR_BALANCE_DEFAULTS = {"mode": "none", "pos_weight": "auto", "power": 1.0, "normalize": True, "alpha": 0.25, "gamma": 2.0}
+
+
+def pnr_balance_config(cfg) -> dict:
+    """The ``pnr_balance:`` block with its defaults filled in; an unknown key or mode is a ValueError naming it."""
+    raw = cfg.get("pnr_balance") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(PNR_BALANCE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"pnr_balance: unknown key(s) {sorted(unknown)} ({', '.join(PNR_BALANCE_DEFAULTS)})")
+    pb = {**PNR_BALANCE_DEFAULTS, **raw}
+    pb["mode"] = str(pb["mode"]).lower()
+    if pb["mode"] not in PNR_BALANCE_MODES:
+        raise ValueError(f"pnr_balance.mode: unknown mode '{pb['mode']}' ({' | '.join(PNR_BALANCE_MODES)})")
+    if isinstance(pb["pos_weight"], str):
+        if pb["pos_weight"].lower() != "auto":
+            raise ValueError(f"pnr_balance.pos_weight: '{pb['pos_weight']}' is neither 'auto' nor a number > 0")
+        pb["pos_weight"] = "auto"
+    else:
+        pb["pos_weight"] = float(pb["pos_weight"])
+        if not (pb["pos_weight"] > 0.0 and pb["pos_weight"] < float("inf")):
+            raise ValueError(f"pnr_balance.pos_weight: {pb['pos_weight']} is neither 'auto' nor a number > 0")
+    pb["power"], pb["normalize"], pb["alpha"], pb["gamma"] = float(pb["power"]), bool(pb["normalize"]), float(pb["alpha"]), float(pb["gamma"])
+    if not pb["alpha"] <= 1.0:
+        raise ValueError(f"pnr_balance.alpha: {pb['alpha']} is above 1 (pos = alpha, neg = 1 - alpha; < 0: both 1)")
+    if not (0.0 <= pb["gamma"] < float("inf")):
+        raise ValueError(f"pnr_balance.gamma: {pb['gamma']} is not a finite number >= 0")
+    return pb
+
+
+def pnr_label_counts(dataset) -> tuple:
+    """(n_pos, n_neg): the nodes labelled != 0 / == 0 over all samples of ``dataset``, the WHOLE split on every rank.  From the
+    label table of a dataset that holds one (``_tables()['y']``), one pass over ``dataset[i].y`` otherwise: the caveats of
+    ``label_counts`` apply."""
+    if hasattr(dataset, "_tables"):
+        y = torch.as_tensor(dataset._tables()["y"]).reshape(-1)
+    else:
+        ys = [torch.as_tensor(dataset[i].y).reshape(-1) for i in range(len(dataset))]
+        y = torch.cat(ys) if ys else torch.zeros(0, dtype=torch.int64)
+    n_pos = int((y != 0).sum())
+    return n_pos, int(y.numel()) - n_pos
+
+
+def pnr_scalars(pb: dict, n_pos: int, n_neg: int) -> tuple:
+    """(pos, neg, gamma) of a validated ``pnr_balance`` block and the counts: float64 arithmetic, each rounded once to f32
+    (returned as the Python float of that f32).  pos_weight: pw = (n_neg / max(n_pos, 1)) ** power (``auto``) or the number given;
+    ``normalize``: pos = pw k, neg = k with k = N / (pw n_pos + n_neg) -- the mean factor over the training labels is 1, so the
+    objective keeps its scale.  focal: pos = alpha, neg = 1 - alpha (alpha < 0: both 1), gamma as given."""
+    if pb["mode"] == "pos_weight":
+        pw = (n_neg / max(n_pos, 1)) ** pb["power"] if pb["pos_weight"] == "auto" else float(pb["pos_weight"])
+        den = pw * n_pos + n_neg
+        k = (n_pos + n_neg) / den if (pb["normalize"] and den > 0) else 1.0
+        out = (pw * k, k, 0.0)
+    elif pb["mode"] == "focal":
+        out = (1.0, 1.0, pb["gamma"]) if pb["alpha"] < 0 else (pb["alpha"], 1.0 - pb["alpha"], pb["gamma"])
+    else:
+        raise ValueError(f"pnr_balance.mode: no scalars for mode '{pb['mode']}'")
+    return tuple(float(torch.tensor(v, dtype=torch.float64).to(torch.float32)) for v in out)
+
+
+def build_pnr_balance(cfg, dsets_train, tasks=None) -> Optional[dict]:
+    """{"pos", "neg", "gamma": Python floats holding f32 values, "n_pos", "n_neg": the counts of the training split} -- None with
+    ``mode: none`` (nothing is counted, nothing is built: the criterion and the launches are the ones without the feature) and
+    when PNR is not among ``tasks`` (the tasks the caller trains; None: all)."""
+    pb = pnr_balance_config(cfg)
+    if pb["mode"] == "none" or (tasks is not None and "pnr" not in tasks) or "pnr" not in dsets_train:
+        return None
+    n_pos, n_neg = pnr_label_counts(dsets_train["pnr"])
+    pos, neg, gamma = pnr_scalars(pb, n_pos, n_neg)
+    return {"pos": pos, "neg": neg, "gamma": gamma, "n_pos": n_pos, "n_neg": n_neg}
+
+
+def log_pnr_balance(logger, cfg, pnr_balance) -> None:
+    """One line: mode, the counts, pos, neg, gamma."""
+    if pnr_balance:
+        logger.info("pnr balance: mode %s, %d positive / %d negative nodes, pos %.9g, neg %.9g, gamma %.9g", pnr_balance_config(cfg)["mode"],
+                    pnr_balance["n_pos"], pnr_balance["n_neg"], pnr_balance["pos"], pnr_balance["neg"], pnr_balance["gamma"])
+
+
+def pnr_balance_state(cfg, pnr_balance) -> Optional[dict]:
+    """The checkpoint's top-level ``"pnr_balance"`` entry: the config block, the counts and the scalars (an f32 tensor
+    [pos, neg, gamma]); None when off."""
+    if not pnr_balance:
+        return None
+    return {"config": pnr_balance_config(cfg), "counts": {"n_pos": pnr_balance["n_pos"], "n_neg": pnr_balance["n_neg"]},
+            "scalars": torch.tensor([pnr_balance[k] for k in ("pos", "neg", "gamma")], dtype=torch.float32)}
+
+
+def check_pnr_balance(logger, ckpt: dict, cfg, pnr_balance) -> bool:
+    """On resume: the scalars rebuilt from the config and the training split against the ones the checkpoint stores, bit for bit.
+    A difference (or one side without scalars) is ONE warning line; returns whether they agree."""
+    stored, now = ckpt.get("pnr_balance"), pnr_balance_state(cfg, pnr_balance)
+    same = (stored is None) == (now is None)
+    if same and now is not None:
+        a = torch.as_tensor(stored.get("scalars", [])).cpu()
+        same = a.dtype == torch.float32 and a.shape == now["scalars"].shape and torch.equal(a.view(torch.int32), now["scalars"].view(torch.int32))
+    if not same:
+        logger.warning("pnr balance: the scalars built for this run differ from the checkpoint's (now %s, stored %s): "
+                       "the run continues with the ones built now", None if now is None else now["scalars"].tolist(),
+                       None if stored is None else torch.as_tensor(stored.get("scalars", [])).tolist())
+    return same
+
+
 OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
 
 
@@ -446,14 +555,15 @@ def ema_checkpoint_path(path: Path) -> Path:
 
 
 def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimizer=None, scheduler=None, loaders=None,
-                    save_ema: bool = False, class_balance: Optional[dict] = None):
+                    save_ema: bool = False, class_balance: Optional[dict] = None, pnr_balance: Optional[dict] = None):
     """Reference key layout (main_temporal.py:410-417, main_egopack.py:453-460) + what the reference does not keep and
     a resumed run needs: the optimiser state (torch.optim.Adam's per-parameter layout) and the schedule state.
     ``save_ema`` (``ema.save`` of the config; an optimizer that keeps a weight average): a second file beside it,
     ``checkpoint_ema.pth``, with the reference's key layout alone and the AVERAGED weights in place of the parameters -- the
     modules' state dicts taken inside ``optimizer.ema_weights()``; any loader of the reference's layout and ``resume_from=``
     take it as it is.  The ordinary file keeps the raw weights and the average under the optimizer's ``"ema"`` key.
-    ``class_balance`` (``class_balance_state``; None when off): stored under the top-level key ``"class_balance"``."""
+    ``class_balance`` (``class_balance_state``; None when off): stored under the top-level key ``"class_balance"``;
+    ``pnr_balance`` (``pnr_balance_state``) likewise under ``"pnr_balance"``."""
     path.parent.mkdir(parents=True, exist_ok=True)
     if save_ema and getattr(optimizer, "ema", False):
         with optimizer.ema_weights():
@@ -470,6 +580,8 @@ def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimiz
         ckpt["scheduler"] = scheduler.state_dict()
     if class_balance is not None:
         ckpt["class_balance"] = class_balance
+    if pnr_balance is not None:
+        ckpt["pnr_balance"] = pnr_balance
     if loaders is not None:  # shuffle generators of the training loaders + dropout streams: exact continuation
         ckpt["rng"] = {"loaders": {t: dl.state_dict() for t, dl in loaders.items() if hasattr(dl, "state_dict")},
                        "dropout": ops.get_rng_state(), "torch": torch.get_rng_state()}

@@ -751,5 +751,7 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 #include "egopack_ema.h"
 /* the cross entropies with per-class weights and logit offsets applied inside the row pass (egk_ce_w_fwd / _bwd / _fused_multi) */
 #include "egopack_ce_balanced.h"
+/* BCE-with-logits with a class factor per label value and a focal exponent applied inside the pass (egk_bce_w_fwd / _bwd, egk_rowdot_bce_w) */
+#include "egopack_bce_balanced.h"
 
 #endif /* EGOPACK_HIP_H */

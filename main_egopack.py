@@ -125,6 +125,11 @@ def main(argv=None):
     T.log_class_balance(logger, cfg, balance)
     for t, e in balance.items():
         tasks[t].set_class_balance(e["weights"], e["offsets"])
+    # pnr_balance: an enabled PNR task trains with pos / neg / gamma inside its BCE (its ``compute_loss`` while training)
+    pnr_balance = T.build_pnr_balance(cfg, dsets_train, tasks=[t for t, w in weights.items() if w > 0])
+    T.log_pnr_balance(logger, cfg, pnr_balance)
+    if pnr_balance:
+        tasks["pnr"].set_loss_balance(pnr_balance["pos"], pnr_balance["neg"], pnr_balance["gamma"])
     if cfg.resume_from:
         logger.info("resuming from %s", cfg.resume_from)
         T.load_checkpoint(cfg.resume_from, model, tasks, strict_tasks=False, device=device)
@@ -171,7 +176,7 @@ def main(argv=None):
         name = f"{cfg.artifact_prefix}_egopack_" + "-".join(sorted(t for t, w in weights.items() if w > 0))
         T.save_checkpoint(Path(cfg.checkpoint_dir) / name / "checkpoint.pth", model, tasks, cfg.num_epochs,
                           graphone=graphone, optimizer=optimizer, save_ema=T.ema_saved(cfg),
-                          class_balance=T.class_balance_state(cfg, balance))
+                          class_balance=T.class_balance_state(cfg, balance), pnr_balance=T.pnr_balance_state(cfg, pnr_balance))
     if world > 1:
         torch.distributed.destroy_process_group()
 

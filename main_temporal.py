@@ -168,7 +168,11 @@ def main(argv=None):
     # class_balance: per-class weights / logit offsets of the AR and LTA heads from the label counts of the whole training split
     balance = T.build_class_balance(cfg, dsets_train, device=device)
     T.log_class_balance(logger, cfg, balance)
-    step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train, balance), weights, optimizer, fused_backbone=cfg.fused_backbone, sync=sync)
+    # pnr_balance: pos / neg / gamma of the PNR head's BCE from the positive and negative node counts of the whole training split
+    pnr_balance = T.build_pnr_balance(cfg, dsets_train, tasks=[t for t, w in weights.items() if w > 0])
+    T.log_pnr_balance(logger, cfg, pnr_balance)
+    step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train, balance, pnr_balance), weights, optimizer,
+                          fused_backbone=cfg.fused_backbone, sync=sync)
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))  # several ranks: graph-LN statistics over the GLOBAL batch
 
@@ -179,6 +183,7 @@ def main(argv=None):
                                scheduler=scheduler, loaders=dl_train)
         first_epoch = int(ck.get("epoch", 0)) + 1
         T.check_class_balance(logger, ck, cfg, balance)  # (rebuilt above; compared bit for bit with the stored vectors)
+        T.check_pnr_balance(logger, ck, cfg, pnr_balance)  # (likewise the PNR scalars)
         logger.info("resumed from %s at epoch %d", cfg.resume_from, first_epoch)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
@@ -189,7 +194,8 @@ def main(argv=None):
             sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
         if cfg.save_model and cfg.get("save_every", 0) and epoch % cfg.save_every == 0 and rank == 0:
             T.save_checkpoint(ckpt_path, model, tasks, epoch, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
-                              save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance))
+                              save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance),
+                              pnr_balance=T.pnr_balance_state(cfg, pnr_balance))
         if epoch >= cfg.num_epochs - 5:  # all ranks: the validation split is sharded by batch
             T.log_validation_weights(logger, cfg, optimizer, epoch)
             with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
@@ -203,7 +209,8 @@ def main(argv=None):
         sync.gather_moments(optimizer)
     if cfg.save_model and rank == 0:
         T.save_checkpoint(ckpt_path, model, tasks, cfg.num_epochs, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
-                          save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance))
+                          save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance),
+                          pnr_balance=T.pnr_balance_state(cfg, pnr_balance))
     if world > 1:
         torch.distributed.destroy_process_group()
     # (callers that drive main() from Python -- the tests -- get the last validation metrics and the trained modules)
