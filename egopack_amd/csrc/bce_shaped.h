@@ -1,7 +1,7 @@
 // The shaped BCE-with-logits of include/egopack_bce_balanced.h for ONE node: a class factor (pos for y != 0, neg otherwise) and a
-// focal exponent gamma.  Written once for the three kernels that use it (loss_bce_balanced.hip, rowdot_bce_kernel<SHAPED> in
-// norm_ops.hip).  The three scalars are kernel arguments: ``gamma == 0`` is a wave-uniform branch whose arithmetic is the plain
-// kernels' (bce_fwd_kernel / bce_bwd_kernel) times the class factor, so pos = neg = 1 gives their bits.
+// focal exponent gamma.  Written once for the three kernels that use it (bce_fwd_kernel / bce_bwd_kernel<SHAPED> in loss.hip,
+// rowdot_bce_kernel<SHAPED> in norm_ops.hip).  The three scalars are kernel arguments: ``gamma == 0`` is a wave-uniform branch
+// whose arithmetic is the plain instantiations' times the class factor, so pos = neg = 1 gives their bits.
 #pragma once
 
 #include <math.h>

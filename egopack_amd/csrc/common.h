@@ -107,8 +107,8 @@ enum KernelId {
     KID_OPTIM_GROUPS,      // egk_optim_step_groups: the same rules with lr / weight decay per parameter group (optim_rules.hip)
     KID_OPTIM_EMA,         // egk_optim_step_ema: the same rules with a moving average of the weights kept in the launch (optim_rules.hip)
     KID_EMA_SWAP,          // egk_ema_swap: parameters <-> their average
-    KID_CE_BALANCED,       // egk_ce_w_fwd / _bwd / _fused_multi: cross entropy with per-class weights and logit offsets (loss_balanced.hip)
-    KID_BCE_BALANCED,      // egk_bce_w_fwd / _bwd, egk_rowdot_bce_w: BCE-with-logits with class factors and a focal exponent (loss_bce_balanced.hip, norm_ops.hip)
+    KID_CE_BALANCED,       // egk_ce_w_fwd / _bwd / _fused_multi: cross entropy with per-class weights and logit offsets (loss.hip)
+    KID_BCE_BALANCED,      // egk_bce_w_fwd / _bwd, egk_rowdot_bce_w: BCE-with-logits with class factors and a focal exponent (loss.hip, norm_ops.hip)
     KID_COUNT
 };
 

@@ -1,242 +1,11 @@
-// Loss kernels (cross-entropy with ignore_index / label smoothing, BCE-with-logits), small
-// elementwise helpers (dropout, axpby, scaled sum) and the single-launch Adam step over the flat
-// parameter buffer.  All HBM-bound / latency-bound.
+// Small elementwise helpers (dropout, ReLU gate, axpby, scaled and weighted sums, block copies, zero fills), the single-launch
+// Adam step over the flat parameter buffer and the global gradient norm.  All HBM-bound / latency-bound.  (The loss kernels are in
+// loss.hip.)
 #include <math.h>
 
 #include "common.h"
 
 namespace egk {
-
-constexpr int WPB = 4;
-
-// ---- cross entropy: one wave per row ------------------------------------------------------------
-// loss = lse - (1-eps)*x_y - eps/C * sum_c x_c     (0 for y == -1)
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, long long ld,
-                                                     const long long* __restrict__ y, long long ys, float* __restrict__ loss,
-                                                     float* __restrict__ lse, int rows, int C, float smoothing,
-                                                     int accumulate) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
-    for (int row = rw.first; row < rw.end; row += rw.step) {
-        const float* lr = logits + (long long)row * ld;
-        float mx = -INFINITY;
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lr[c]);
-        mx = wave_max(mx);
-        float se = 0.f, sx = 0.f;
-        for (int c = lane; c < C; c += 64) {
-            const float v = lr[c];
-            se += expf(v - mx);
-            sx += v;
-        }
-        se = wave_sum(se);
-        sx = wave_sum(sx);
-        if (lane == 0) {
-            const float l = mx + logf(se);
-            lse[row] = l;
-            const long long t = y[(long long)row * ys];
-            float o = 0.f;
-            if (t >= 0 && t < C) o = l - (1.f - smoothing) * lr[t] - (smoothing > 0.f ? smoothing / C * sx : 0.f);
-            loss[row] = accumulate ? loss[row] + o : o;
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, long long ld,
-                                                     const long long* __restrict__ y, long long ys,
-                                                     const float* __restrict__ lse, const float* __restrict__ gloss,
-                                                     T* __restrict__ dlogits, long long ldd, int rows, int C,
-                                                     float smoothing) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
-    for (int row = rw.first; row < rw.end; row += rw.step) {
-        const float* lr = logits + (long long)row * ld;
-        T* dr = dlogits + (long long)row * ldd;
-        const long long t = y[(long long)row * ys];
-        const bool live = t >= 0 && t < C;
-        const float g = live ? gloss[row] : 0.f;
-        const float l = lse[row];
-        const float sm = smoothing > 0.f ? smoothing / C : 0.f;
-        for (int c = lane; c < C; c += 64) {
-            float d = 0.f;
-            if (live) d = g * (expf(lr[c] - l) - (c == t ? 1.f - smoothing : 0.f) - sm);
-            st1t(dr + c, d);
-        }
-    }
-}
-
-// ---- fused multi-head cross entropy: loss AND its gradient in one launch -----------------------------------------------------
-// The training heads of the engine know the gradient of the objective with respect to every loss-vector element when the
-// loss is computed: objective = sum_t w_t * mean(loss_t)  =>  d objective / d loss_t[n] = w_t / N_t, a constant.  One wave
-// per row then does, for every head h of the task (verb, noun): loss[n] += CE_h(n) and
-//   dlogits_h[n, c] = gscale * (softmax_h(n)[c] - target_h(n)[c])      (0 for ignored rows)
-// written straight into the classifier bank's operand buffer, zero-filling the bank's pad columns [C_h, pad_h) on the way
-// (the buffer needs no memset).  Replaces 2 forward + 2 backward launches per two-head task.
-constexpr int CE_MAX_HEADS = 4;
-struct CEHeads {
-    const float* logits[CE_MAX_HEADS];
-    long long ld[CE_MAX_HEADS];
-    int C[CE_MAX_HEADS];
-    int pad[CE_MAX_HEADS];     // columns [C, pad) of the gradient block are set to zero
-    long long dcol[CE_MAX_HEADS];  // first column of the head's block in the gradient buffer
-};
-template <typename T>
-__global__ __launch_bounds__(256) void ce_fused_kernel(const CEHeads H, int n_heads, const long long* __restrict__ y, long long ys,
-                                                       float* __restrict__ loss, T* __restrict__ dlogits, long long ldd, int rows,
-                                                       float smoothing, float gscale) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
-    for (int row = rw.first; row < rw.end; row += rw.step) {
-        float total = 0.f;
-        for (int h = 0; h < n_heads; ++h) {
-            const float* lr = H.logits[h] + (long long)row * H.ld[h];
-            const int C = H.C[h];
-            T* dr = dlogits + (long long)row * ldd + H.dcol[h];
-            const long long t = y[(long long)row * ys + h];
-            const bool live = t >= 0 && t < C;
-            float mx = -INFINITY;
-            for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lr[c]);
-            mx = wave_max(mx);
-            float se = 0.f, sx = 0.f;
-            for (int c = lane; c < C; c += 64) {
-                const float v = lr[c];
-                se += expf(v - mx);
-                sx += v;
-            }
-            se = wave_sum(se);
-            sx = wave_sum(sx);
-            const float l = mx + logf(se);
-            if (live) total += l - (1.f - smoothing) * lr[t] - (smoothing > 0.f ? smoothing / C * sx : 0.f);
-            const float sm = smoothing > 0.f ? smoothing / C : 0.f;
-            for (int c = lane; c < H.pad[h]; c += 64) {
-                float d = 0.f;
-                if (live && c < C) d = gscale * (expf(lr[c] - l) - (c == t ? 1.f - smoothing : 0.f) - sm);
-                st1t(dr + c, d);
-            }
-        }
-        if (lane == 0) loss[row] = total;
-    }
-}
-
-// the same for several TASKS in one launch (blockIdx.y = task): the AR and LTA heads of a multi-task step
-constexpr int CE_MAX_TASKS = 4;
-struct CETasks {
-    CEHeads H[CE_MAX_TASKS];
-    int n_heads[CE_MAX_TASKS];
-    const long long* y[CE_MAX_TASKS];
-    long long ys[CE_MAX_TASKS];
-    float* loss[CE_MAX_TASKS];
-    void* dlogits[CE_MAX_TASKS];
-    long long ldd[CE_MAX_TASKS];
-    int rows[CE_MAX_TASKS];
-    float gscale[CE_MAX_TASKS];
-};
-template <typename T>
-__global__ __launch_bounds__(256) void ce_fused_multi_kernel(const CETasks P, float smoothing) {
-    const int k = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const CEHeads& H = P.H[k];
-    const int n_heads = P.n_heads[k], rows = P.rows[k];
-    const long long* __restrict__ y = P.y[k];
-    const long long ys = P.ys[k], ldd = P.ldd[k];
-    float* __restrict__ loss = P.loss[k];
-    T* __restrict__ dlogits = (T*)P.dlogits[k];
-    const float gscale = P.gscale[k];
-    const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
-    for (int row = rw.first; row < rw.end; row += rw.step) {
-        float total = 0.f;
-        for (int h = 0; h < n_heads; ++h) {  // (the arithmetic of ce_fused_kernel, statement for statement)
-            const float* lr = H.logits[h] + (long long)row * H.ld[h];
-            const int C = H.C[h];
-            T* dr = dlogits + (long long)row * ldd + H.dcol[h];
-            const long long t = y[(long long)row * ys + h];
-            const bool live = t >= 0 && t < C;
-            float mx = -INFINITY;
-            for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lr[c]);
-            mx = wave_max(mx);
-            float se = 0.f, sx = 0.f;
-            for (int c = lane; c < C; c += 64) {
-                const float v = lr[c];
-                se += expf(v - mx);
-                sx += v;
-            }
-            se = wave_sum(se);
-            sx = wave_sum(sx);
-            const float l = mx + logf(se);
-            if (live) total += l - (1.f - smoothing) * lr[t] - (smoothing > 0.f ? smoothing / C * sx : 0.f);
-            const float sm = smoothing > 0.f ? smoothing / C : 0.f;
-            for (int c = lane; c < H.pad[h]; c += 64) {
-                float d = 0.f;
-                if (live && c < C) d = gscale * (expf(lr[c] - l) - (c == t ? 1.f - smoothing : 0.f) - sm);
-                st1t(dr + c, d);
-            }
-        }
-        if (lane == 0) loss[row] = total;
-    }
-}
-
-// ---- BCE with logits ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ x, const long long* __restrict__ y,
-                                                      float* __restrict__ loss, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = x[i], t = (float)y[i];
-    // torch: (1 - t) * x + max(-x, 0) + log1p(exp(-|x|))
-    loss[i] = (1.f - t) * v + fmaxf(-v, 0.f) + log1pf(expf(-fabsf(v)));
-}
-template <typename T>
-__global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ x, const long long* __restrict__ y,
-                                                      const float* __restrict__ gloss, T* __restrict__ dx, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = x[i];
-    st1t(dx + i, (1.f / (1.f + expf(-v)) - (float)y[i]) * gloss[i]);
-}
-
-// ---- sigmoid losses against one-hot class targets (OSCCTask.compute_loss 'bce' / 'focal', reference oscc.py:91-96) ---
-// element i = (row, c) of [rows, C] logits; target t = (y[row] == c).  kind 0: BCE-with-logits; kind 1: torchvision
-// sigmoid_focal_loss(alpha, gamma):  p_t = sigmoid(z), z = (2t-1) x;  L = a_t (1-p_t)^gamma (-log p_t),
-// a_t = alpha t + (1-alpha)(1-t) (alpha < 0: no weighting);  dL/dx = (2t-1) a_t (1-p_t)^gamma (gamma p_t log p_t - (1-p_t)).
-__device__ __forceinline__ float log_sigmoid(float z) { return -(fmaxf(-z, 0.f) + log1pf(expf(-fabsf(z)))); }
-
-__global__ __launch_bounds__(256) void onehot_sigmoid_fwd_kernel(const float* __restrict__ x, const long long* __restrict__ y,
-                                                                 float* __restrict__ loss, int n, int C, int kind, float alpha,
-                                                                 float gamma) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = x[i];
-    const float t = y[i / C] == (long long)(i % C) ? 1.f : 0.f;
-    const float ce = (1.f - t) * v + fmaxf(-v, 0.f) + log1pf(expf(-fabsf(v)));
-    if (kind == 0) {
-        loss[i] = ce;
-        return;
-    }
-    const float p = 1.f / (1.f + expf(-v));
-    const float pt = p * t + (1.f - p) * (1.f - t);
-    float l = ce * (gamma == 2.f ? (1.f - pt) * (1.f - pt) : powf(1.f - pt, gamma));
-    if (alpha >= 0.f) l *= alpha * t + (1.f - alpha) * (1.f - t);
-    loss[i] = l;
-}
-template <typename T>
-__global__ __launch_bounds__(256) void onehot_sigmoid_bwd_kernel(const float* __restrict__ x, const long long* __restrict__ y,
-                                                                 const float* __restrict__ gloss, T* __restrict__ dx, int n,
-                                                                 int C, int kind, float alpha, float gamma) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = x[i];
-    const float t = y[i / C] == (long long)(i % C) ? 1.f : 0.f;
-    float d;
-    if (kind == 0) {
-        d = 1.f / (1.f + expf(-v)) - t;
-    } else {
-        const float sg = 2.f * t - 1.f, z = sg * v;
-        const float pt = 1.f / (1.f + expf(-z)), q = 1.f - pt;
-        const float mod = gamma == 2.f ? q * q : powf(q, gamma);
-        const float a = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;
-        d = sg * a * mod * (gamma * pt * log_sigmoid(z) - q);
-    }
-    st1t(dx + i, d * gloss[i]);
-}
 
 // ---- dropout ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -549,10 +318,6 @@ static inline unsigned ew_grid(long long n, int per_thread) {
     long long b = (n / per_thread + 255) / 256;
     return (unsigned)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
-static inline int row_grid(int rows) {
-    int g = cdiv(rows, WPB);
-    return g < 1 ? 1 : (g > 2048 ? 2048 : g);
-}
 
 }  // namespace egk
 
@@ -560,124 +325,6 @@ using namespace egk;
 
 
 extern "C" {
-
-int egk_ce_fwd(egk_stream_t stream, const float* logits, int64_t ld, const int64_t* y, int64_t y_stride, float* loss,
-               float* lse, int32_t rows, int32_t C, float smoothing, int32_t accumulate) {
-    EGK_REQUIRE(logits && y && loss && lse, "egk_ce_fwd: null pointer");
-    EGK_REQUIRE(C >= 1, "egk_ce_fwd: C must be >= 1");
-    if (rows == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_CE_FWD, s, 0, 4.0 * rows * C);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(row_grid(rows)), dim3(256), 0, s, logits, (long long)ld, (const long long*)y,
-                       (long long)y_stride, loss, lse, rows, C, smoothing, accumulate);
-    return check_launch("egk_ce_fwd");
-}
-
-int egk_ce_bwd(egk_stream_t stream, const float* logits, int64_t ld, const int64_t* y, int64_t y_stride, const float* lse,
-               const float* gloss, void* dlogits, int64_t ldd, int32_t rows, int32_t C, float smoothing, int32_t dtype) {
-    EGK_REQUIRE(logits && y && lse && gloss && dlogits, "egk_ce_bwd: null pointer");
-    if (rows == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_CE_BWD, s, 0, 8.0 * rows * C);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(row_grid(rows)), dim3(256), 0, s, logits, (long long)ld,
-                                             (const long long*)y, (long long)y_stride, lse, gloss, (T*)dlogits, (long long)ldd, rows,
-                                             C, smoothing));
-    return check_launch("egk_ce_bwd");
-}
-
-int egk_ce_fused(egk_stream_t stream, const float* const* logits, const int64_t* ld, const int32_t* C, const int32_t* pad,
-                 const int64_t* dcol, int32_t n_heads, const int64_t* y, int64_t y_stride, float* loss, void* dlogits, int64_t ldd,
-                 int32_t rows, float smoothing, float gscale, int32_t dtype) {
-    EGK_REQUIRE(logits && ld && C && pad && dcol && y && loss && dlogits, "egk_ce_fused: null pointer");
-    EGK_REQUIRE(n_heads >= 1 && n_heads <= CE_MAX_HEADS, "egk_ce_fused: 1 .. %d heads", CE_MAX_HEADS);
-    if (rows == 0) return 0;
-    CEHeads H;
-    double bytes = 0;
-    for (int h = 0; h < CE_MAX_HEADS; ++h) {
-        const int k = h < n_heads ? h : n_heads - 1;
-        EGK_REQUIRE(logits[k] && C[k] >= 1 && pad[k] >= C[k], "egk_ce_fused: bad head %d", k);
-        H.logits[h] = logits[k]; H.ld[h] = ld[k]; H.C[h] = C[k]; H.pad[h] = pad[k]; H.dcol[h] = dcol[k];
-        if (h < n_heads) bytes += 6.0 * rows * C[k];
-    }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_CE_FWD, s, 0, bytes);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(ce_fused_kernel<T>, dim3(row_grid(rows)), dim3(256), 0, s, H, n_heads, (const long long*)y,
-                                             (long long)y_stride, loss, (T*)dlogits, (long long)ldd, rows, smoothing, gscale));
-    return check_launch("egk_ce_fused");
-}
-
-int egk_ce_fused_multi(egk_stream_t stream, const egk_ce_task* tasks, int32_t count, float smoothing, int32_t dtype) {
-    EGK_REQUIRE(tasks && count >= 1 && count <= CE_MAX_TASKS, "egk_ce_fused_multi: 1 .. %d tasks", CE_MAX_TASKS);
-    CETasks P;
-    double bytes = 0;
-    int max_rows = 0;
-    for (int i = 0; i < CE_MAX_TASKS; ++i) {
-        const egk_ce_task& t = tasks[i < count ? i : count - 1];
-        EGK_REQUIRE(t.y && t.loss && t.dlogits && t.n_heads >= 1 && t.n_heads <= CE_MAX_HEADS && t.rows >= 0,
-                    "egk_ce_fused_multi: bad task %d", i);
-        for (int h = 0; h < CE_MAX_HEADS; ++h) {
-            const int k = h < t.n_heads ? h : t.n_heads - 1;
-            EGK_REQUIRE(t.logits[k] && t.C[k] >= 1 && t.pad[k] >= t.C[k], "egk_ce_fused_multi: bad head %d of task %d", k, i);
-            P.H[i].logits[h] = t.logits[k]; P.H[i].ld[h] = t.ld[k]; P.H[i].C[h] = t.C[k]; P.H[i].pad[h] = t.pad[k];
-            P.H[i].dcol[h] = t.dcol[k];
-            if (i < count && h < t.n_heads) bytes += 6.0 * t.rows * t.C[k];
-        }
-        P.n_heads[i] = t.n_heads; P.y[i] = (const long long*)t.y; P.ys[i] = t.y_stride; P.loss[i] = t.loss;
-        P.dlogits[i] = t.dlogits; P.ldd[i] = t.ldd; P.rows[i] = i < count ? t.rows : 0; P.gscale[i] = t.gscale;
-        if (i < count && t.rows > max_rows) max_rows = t.rows;
-    }
-    if (max_rows == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_CE_FWD, s, 0, bytes);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(ce_fused_multi_kernel<T>, dim3(row_grid(max_rows), count), dim3(256), 0, s, P, smoothing));
-    return check_launch("egk_ce_fused_multi");
-}
-
-int egk_bce_fwd(egk_stream_t stream, const float* logits, const int64_t* y, float* loss, int32_t n) {
-    EGK_REQUIRE(logits && y && loss, "egk_bce_fwd: null pointer");
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_BCE_FWD, s, 0, 16.0 * n);
-    hipLaunchKernelGGL(bce_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, logits, (const long long*)y, loss, n);
-    return check_launch("egk_bce_fwd");
-}
-
-int egk_bce_bwd(egk_stream_t stream, const float* logits, const int64_t* y, const float* gloss, void* dlogits, int32_t n,
-                int32_t dtype) {
-    EGK_REQUIRE(logits && y && gloss && dlogits, "egk_bce_bwd: null pointer");
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_BCE_BWD, s, 0, 20.0 * n);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(bce_bwd_kernel<T>, dim3(cdiv(n, 256)), dim3(256), 0, s, logits, (const long long*)y,
-                                             gloss, (T*)dlogits, n));
-    return check_launch("egk_bce_bwd");
-}
-
-int egk_onehot_sigmoid_loss_fwd(egk_stream_t stream, const float* logits, const int64_t* y, float* loss, int32_t rows, int32_t C,
-                                int32_t kind, float alpha, float gamma) {
-    EGK_REQUIRE(logits && y && loss, "egk_onehot_sigmoid_loss_fwd: null pointer");
-    EGK_REQUIRE(C >= 1 && (kind == 0 || kind == 1), "egk_onehot_sigmoid_loss_fwd: bad C / kind");
-    const int n = rows * C;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_BCE_FWD, s, 0, 8.0 * n + 8.0 * rows);
-    hipLaunchKernelGGL(onehot_sigmoid_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, logits, (const long long*)y, loss, n, C,
-                       kind, alpha, gamma);
-    return check_launch("egk_onehot_sigmoid_loss_fwd");
-}
-
-int egk_onehot_sigmoid_loss_bwd(egk_stream_t stream, const float* logits, const int64_t* y, const float* gloss, void* dlogits,
-                                int32_t rows, int32_t C, int32_t kind, float alpha, float gamma, int32_t dtype) {
-    EGK_REQUIRE(logits && y && gloss && dlogits, "egk_onehot_sigmoid_loss_bwd: null pointer");
-    EGK_REQUIRE(C >= 1 && (kind == 0 || kind == 1), "egk_onehot_sigmoid_loss_bwd: bad C / kind");
-    const int n = rows * C;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_BCE_BWD, s, 0, 12.0 * n + 8.0 * rows);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(onehot_sigmoid_bwd_kernel<T>, dim3(cdiv(n, 256)), dim3(256), 0, s, logits,
-                                             (const long long*)y, gloss, (T*)dlogits, n, C, kind, alpha, gamma));
-    return check_launch("egk_onehot_sigmoid_loss_bwd");
-}
 
 int egk_dropout_fwd(egk_stream_t stream, const void* x, void* y, uint8_t* mask, int64_t n, float p, uint64_t seed,
                     uint64_t offset, const uint64_t* dev_offset, int32_t dtype) {

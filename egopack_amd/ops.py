@@ -2828,54 +2828,80 @@ def _class_balance(weight, offset, logits, where="cross_entropy"):
     return tuple(out)
 
 
-def _ce_w_task(t, logits, pads, starts, y, loss, gbuf, rows, coef, bal):
-    """Fill one ``egk_ce_w_task``: a task of the fused cross entropy (``_CE._fused`` / ``_CEMulti``) and its per-class vectors."""
-    b = t.base
+def _ce_task(t, logits, pads, starts, y, loss, gbuf, rows, coef):
+    """Fill one ``egk_ce_task``: a task of the fused cross entropy (``_CE._fused`` / ``_CEMulti``)."""
     for h, l in enumerate(logits):
-        b.logits[h], b.ld[h], b.C[h], b.pad[h], b.dcol[h] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
+        t.logits[h], t.ld[h], t.C[h], t.pad[h], t.dcol[h] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
+    t.n_heads, t.y, t.y_stride, t.loss = len(logits), y.data_ptr(), y.shape[1], loss.data_ptr()
+    t.dlogits, t.ldd, t.rows, t.gscale = gbuf.data_ptr(), gbuf.stride(0), rows, float(coef)
+
+
+def _ce_w_task(t, logits, pads, starts, y, loss, gbuf, rows, coef, bal):
+    """Fill one ``egk_ce_w_task``: ``_ce_task`` and the task's per-class vectors."""
+    _ce_task(t.base, logits, pads, starts, y, loss, gbuf, rows, coef)
+    for h in range(len(logits)):
         t.weight[h] = None if bal is None or bal[0][h] is None else bal[0][h].data_ptr()
         t.offset[h] = None if bal is None or bal[1][h] is None else bal[1][h].data_ptr()
-    b.n_heads, b.y, b.y_stride, b.loss = len(logits), y.data_ptr(), y.shape[1], loss.data_ptr()
-    b.dlogits, b.ldd, b.rows, b.gscale = gbuf.data_ptr(), gbuf.stride(0), rows, float(coef)
+
+
+def _ce_fused_plan(y, logits, from_col0):
+    """What the fused cross entropy needs of one task -- (gradient operand, its state, column starts, block widths) -- or None
+    when it does not apply: the bank hand-off is on, y is [N, heads] for at most 4 heads, and the heads' f32 logits are blocks, in
+    column order, of ONE bank buffer whose gradient operand none of them has filled yet.  ``from_col0``: the first block must
+    start at column 0 (a caller that passes False fills the columns in front of it itself)."""
+    if not _bank_handoff["on"] or y.dim() != 2 or y.shape[1] != len(logits) or len(logits) > 4:
+        return None
+    dsts = [getattr(l, "_egk_grad_dst", None) for l in logits]
+    if any(d is None for d in dsts) or any(d[0] is not dsts[0][0] or d[2] is not dsts[0][2] for d in dsts):
+        return None
+    gbuf, state = dsts[0][0], dsts[0][2]
+    if any(d[1] in state["filled"] for d in dsts) or any(l.dtype != torch.float32 or l.stride(1) != 1 for l in logits):
+        return None
+    starts = sorted(d[1] for d in dsts)
+    if [d[1] for d in dsts] != starts or (from_col0 and starts[0] != 0):
+        return None
+    ends = starts[1:] + [gbuf.shape[1]]
+    return gbuf, state, starts, [e - s0 for s0, e in zip(starts, ends)]
+
+
+def _ce_fused_launch(tasks, smoothing, bal):
+    """ONE launch for the loss vectors AND the gradient operands of ``tasks`` = [(plan, logits, y, coef)]; ``bal``: None (the
+    plain launch), or per task None / the (weights, offsets) of ``_class_balance``.  Returns the loss vectors."""
+    lib = _lib.load()
+    arr = ((_lib.CETask if bal is None else _lib.CEWTask) * len(tasks))()
+    losses = []
+    for i, ((gbuf, state, starts, pads), logits, y, coef) in enumerate(tasks):
+        rows = logits[0].shape[0]
+        loss = torch.empty(rows, dtype=torch.float32, device=gbuf.device)
+        if bal is None:
+            _ce_task(arr[i], logits, pads, starts, y, loss, gbuf, rows, coef)
+        else:
+            _ce_w_task(arr[i], logits, pads, starts, y, loss, gbuf, rows, coef, bal[i])
+        losses.append(loss)
+        state["filled"].update(starts)
+        state["pads"] = True
+    dt = _dt(tasks[0][0][0])
+    if bal is None:
+        _ck(lib.egk_ce_fused_multi(_stream(), arr, len(tasks), float(smoothing), dt), "egk_ce_fused_multi")
+    else:
+        _ck(lib.egk_ce_w_fused_multi(_stream(), arr, len(tasks), float(smoothing), dt), "egk_ce_w_fused_multi")
+    return losses
 
 
 class _CE(torch.autograd.Function):
     @staticmethod
     def _fused(ctx, smoothing, y, logits, bal=None):
-        """One launch for loss and gradient when the seed is known and every head's logits are blocks of ONE bank buffer.
-        ``bal``: the per-class vectors (``_class_balance``) -- the same launch with them applied (egk_ce_w_fused_multi, one task)."""
-        if _loss_seed["coef"] is None or not _bank_handoff["on"] or y.dim() != 2 or y.shape[1] != len(logits) or len(logits) > 4:
+        """One launch for loss and gradient when the seed is known and every head's logits are blocks of ONE bank buffer
+        (``_ce_fused_plan``): the fused launch with one task.  ``bal``: the per-class vectors (``_class_balance``)."""
+        seed = _loss_seed["coef"]
+        plan = None if seed is None else _ce_fused_plan(y, logits, from_col0=False)
+        if plan is None:
             return None
-        dsts = [getattr(l, "_egk_grad_dst", None) for l in logits]
-        if any(d is None for d in dsts) or any(d[0] is not dsts[0][0] or d[2] is not dsts[0][2] for d in dsts):
-            return None
-        gbuf, state = dsts[0][0], dsts[0][2]
-        if any(d[1] in state["filled"] for d in dsts) or any(l.dtype != torch.float32 or l.stride(1) != 1 for l in logits):
-            return None
-        lib = _lib.load()
-        rows, n = logits[0].shape[0], len(logits)
-        starts = sorted(d[1] for d in dsts)
-        if [d[1] for d in dsts] != starts:
-            return None
-        ends = starts[1:] + [gbuf.shape[1]]
-        loss = torch.empty(rows, dtype=torch.float32, device=gbuf.device)
-        lp = (C.c_void_p * n)(*[l.data_ptr() for l in logits])
-        ld = (C.c_int64 * n)(*[l.stride(0) for l in logits])
-        Cs = (C.c_int32 * n)(*[l.shape[1] for l in logits])
-        pad = (C.c_int32 * n)(*[e - s0 for s0, e in zip(starts, ends)])
-        dcol = (C.c_int64 * n)(*starts)
-        if bal is None:
-            _ck(lib.egk_ce_fused(_stream(), lp, ld, Cs, pad, dcol, n, _p(y), y.shape[1], _p(loss), _p(gbuf), gbuf.stride(0), rows,
-                                 smoothing, float(_loss_seed["coef"]), _dt(gbuf)), "egk_ce_fused")
-        else:
-            arr = (_lib.CEWTask * 1)()
-            _ce_w_task(arr[0], logits, pad, starts, y, loss, gbuf, rows, float(_loss_seed["coef"]), bal)
-            _ck(lib.egk_ce_w_fused_multi(_stream(), arr, 1, smoothing, _dt(gbuf)), "egk_ce_w_fused_multi")
+        gbuf, starts = plan[0], plan[2]
+        loss, = _ce_fused_launch([(plan, logits, y, seed)], smoothing, None if bal is None else [bal])
         if starts[0] > 0:
             gbuf[:, :starts[0]].zero_()
-        state["filled"].update(starts)
-        state["pads"] = True
-        ctx.fused, ctx.shapes, ctx.seed = True, [tuple(l.shape) for l in logits], float(_loss_seed["coef"])
+        ctx.fused, ctx.shapes, ctx.seed = True, [tuple(l.shape) for l in logits], float(seed)
         return loss
 
     @staticmethod
@@ -2947,26 +2973,6 @@ class _CE(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
-def _ce_fused_plan(y, logits):
-    """What the fused cross entropy needs of one task -- (gradient operand, its state, column starts, block widths) -- or None
-    when it does not apply (see ``_CE._fused``)."""
-    if _loss_seed["coef"] is None and not _bank_handoff["on"]:
-        return None
-    if not _bank_handoff["on"] or y.dim() != 2 or y.shape[1] != len(logits) or len(logits) > 4:
-        return None
-    dsts = [getattr(l, "_egk_grad_dst", None) for l in logits]
-    if any(d is None for d in dsts) or any(d[0] is not dsts[0][0] or d[2] is not dsts[0][2] for d in dsts):
-        return None
-    gbuf, state = dsts[0][0], dsts[0][2]
-    if any(d[1] in state["filled"] for d in dsts) or any(l.dtype != torch.float32 or l.stride(1) != 1 for l in logits):
-        return None
-    starts = sorted(d[1] for d in dsts)
-    if [d[1] for d in dsts] != starts or starts[0] != 0:
-        return None
-    ends = starts[1:] + [gbuf.shape[1]]
-    return gbuf, state, starts, [e - s0 for s0, e in zip(starts, ends)]
-
-
 class _CEMulti(torch.autograd.Function):
     """The fused cross entropies of several tasks (each: loss + gradient written into its bank's operand buffer, ``_CE._fused``)
     as ONE launch, ``egk_ce_fused_multi``."""
@@ -2974,33 +2980,14 @@ class _CEMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, *tensors):
         # bal: None, or one entry per task -- None or the (weights, offsets) of ``_class_balance`` -- the launch with the vectors
-        lib = _lib.load()
-        n = len(coefs)
-        arr = (_lib.CETask * n)() if bal is None else (_lib.CEWTask * n)()
-        losses, shapes, k = [], [], 0
-        for i in range(n):
+        tasks, shapes, k = [], [], 0
+        for i, coef in enumerate(coefs):
             y = tensors[k]
             logits = tensors[k + 1:k + 1 + heads_per_task[i]]
             k += 1 + heads_per_task[i]
-            gbuf, state, starts, pads = plans[i]
-            rows = logits[0].shape[0]
-            loss = torch.empty(rows, dtype=torch.float32, device=gbuf.device)
-            t = arr[i]
-            if bal is not None:
-                _ce_w_task(t, logits, pads, starts, y, loss, gbuf, rows, coefs[i], bal[i])
-            else:
-                for h, l in enumerate(logits):
-                    t.logits[h], t.ld[h], t.C[h], t.pad[h], t.dcol[h] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
-                t.n_heads, t.y, t.y_stride, t.loss = len(logits), y.data_ptr(), y.shape[1], loss.data_ptr()
-                t.dlogits, t.ldd, t.rows, t.gscale = gbuf.data_ptr(), gbuf.stride(0), rows, float(coefs[i])
-            losses.append(loss)
+            tasks.append((plans[i], logits, y, coef))
             shapes.append([tuple(l.shape) for l in logits])
-            state["filled"].update(starts)
-            state["pads"] = True
-        if bal is None:
-            _ck(lib.egk_ce_fused_multi(_stream(), arr, n, float(smoothing), _dt(plans[0][0])), "egk_ce_fused_multi")
-        else:
-            _ck(lib.egk_ce_w_fused_multi(_stream(), arr, n, float(smoothing), _dt(plans[0][0])), "egk_ce_w_fused_multi")
+        losses = _ce_fused_launch(tasks, smoothing, bal)
         ctx.shapes, ctx.heads = shapes, heads_per_task
         ctx.set_materialize_grads(False)
         return tuple(losses)
@@ -3034,7 +3021,7 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
         bal.append(_class_balance(weights[i] if weights is not None else None, offsets[i] if offsets is not None else None,
                                   logits, f"cross_entropy_multi (task {i})"))
         y = y.contiguous()
-        plan = _ce_fused_plan(y, logits)
+        plan = _ce_fused_plan(y, logits, from_col0=True)
         if plan is None or (dt is not None and plan[0].dtype != dt):
             return None
         dt = plan[0].dtype

@@ -20,8 +20,9 @@
  *
  * Part of the C ABI of libegopack_hip.so: egopack_hip.h includes this file, a C user includes that one.  The boundary rules
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no synchronisation, capturable; 0 = ok, negative =
- * EGK_E*, positive = hipError_t; a launch touches only what its arguments name).  The kernels of egopack_hip.h compute what they
- * computed: a caller that passes no scalar runs the old entry points.
+ * EGK_E*, positive = hipError_t; a launch touches only what its arguments name).  egk_bce_w_fwd / _bwd are the kernels of
+ * egk_bce_fwd / _bwd with the loss expression switched by a template flag (csrc/loss.hip); the plain entry points compute what
+ * they computed: a caller that passes no scalar runs them.
  *
  * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_pnr_balance.py and their ledger in
  * tests/test_pnr_balance_cpu.py, in the form of the five older ledgers.  Profile id "bce_balanced" counts all three.

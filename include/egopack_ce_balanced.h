@@ -17,7 +17,8 @@
  * Part of the C ABI of libegopack_hip.so: egopack_hip.h includes this file, a C user includes that one.  The boundary rules
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no synchronisation, capturable; 0 = ok, negative =
  * EGK_E*, positive = hipError_t; a launch touches only what its arguments name).  One wave per row, the row ownership and the
- * grid of the plain kernels; the kernels of egopack_hip.h are untouched, so a caller that passes no vector runs the old code.
+ * grid of the plain entry points, whose kernels these are with the vectors switched on by a template flag (csrc/loss.hip); a
+ * caller that passes no vector runs the plain instantiation and gets the bits it always got.
  *
  * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_class_balance.py and their ledger in
  * tests/test_class_balance_cpu.py, in the form of the four older ledgers.  Profile id "ce_balanced" counts all three.

@@ -576,7 +576,9 @@ int egk_segment_sum_rows_f64(egk_stream_t s, const void* x, const int32_t* order
 /* ---- losses ---------------------------------------------------------------------------
  * nn.CrossEntropyLoss(reduction='none', ignore_index=-1[, label_smoothing]) criterion/wrapper.py:67-82,
  * recognition.py:63, oscc.py:90.  loss[n] (+)= CE(logits[n,:], y[n*y_stride]); lse[n] saved.
- * bwd: dlogits[n,c] = gscale[n] * (softmax - target_dist)   (0 for ignored rows). */
+ * bwd: dlogits[n,c] = gscale[n] * (softmax - target_dist)   (0 for ignored rows).
+ * The cross-entropy and BCE entry points below validate before it looks at the sizes: rows (n) < 0, C < 1, pad < C, an unknown dtype and a null
+ * pointer are refused with EGK_EINVAL also when rows (n) == 0; a valid call with no rows launches nothing and returns 0. */
 int egk_ce_fwd(egk_stream_t s, const float* logits, int64_t ld, const int64_t* y, int64_t y_stride, float* loss,
                float* lse, int32_t rows, int32_t C, float smoothing, int32_t accumulate);
 int egk_ce_bwd(egk_stream_t s, const float* logits, int64_t ld, const int64_t* y, int64_t y_stride, const float* lse,

@@ -180,7 +180,7 @@ def ce(lib, ops, G, rows, Cn, pad, ys, sm, dt, acc):
     return dict(loss=loss, lse=lse, dlogits=D)
 
 
-def _ce_fused_task(G, tag, g, rows, Cs, pads, lpad, dpad, dt, sm, gscale):
+def _ce_fused_task(G, tag, g, rows, Cs, pads, lpad, dpad, dt, sm, gscale, every_third=False):
     """One task of egk_ce_fused(_multi): n heads, their column blocks [dcol, dcol + pad) inside ONE gradient matrix, with
     sentinel columns in front of, between and behind the blocks."""
     n = len(Cs)
@@ -188,6 +188,9 @@ def _ce_fused_task(G, tag, g, rows, Cs, pads, lpad, dpad, dt, sm, gscale):
     y = torch.stack([torch.randint(0, c, (rows,), generator=g) for c in Cs] + [torch.zeros(rows, dtype=i64)], 1)  # y_stride = n + 1
     y[1::4, 0] = -1
     y[2::5, n - 1] = -1
+    if every_third:                                                   # every third label of every head, rows with one head ignored among them
+        for h in range(n):
+            y[h::3, h] = -1
     dcol, col = [], 3
     for p in pads:
         dcol.append(col)
@@ -231,25 +234,56 @@ def ce_fused(lib, ops, G, rows, Cs, pads, lpad, dpad, dt, sm):
     return dict(loss=t["loss"], dlogits=t["D"])
 
 
-@case("egk_ce_fused_multi", variants=[dict(dt=bf16, lpad=0, dpad=0), dict(dt=f32, lpad=3, dpad=5)])
-def ce_fused_multi(lib, ops, G, dt, lpad, dpad):
+def _ce_task_array(tasks):
     from egopack_amd import _lib
-    g = gen(91)
-    specs = [(77, (115, 478), (128, 512), 0.5), (33, (20,), (64,), 0.25), (0, (5,), (8,), 1.0)]  # (the third task has no rows)
-    tasks = [_ce_fused_task(G, f"task{i}.", g, r, cs, pd, lpad, dpad, dt, 0.1, gs) for i, (r, cs, pd, gs) in enumerate(specs)]
     arr = (_lib.CETask * len(tasks))()
     for a, t in zip(arr, tasks):
         for h in range(t["n"]):
             a.logits[h], a.ld[h], a.C[h], a.pad[h], a.dcol[h] = t["L"][h].ptr, t["L"][h].ld, t["Cs"][h], t["pads"][h], t["dcol"][h]
         a.n_heads, a.y, a.y_stride, a.loss, a.dlogits, a.ldd = t["n"], t["Y"].ptr, t["n"] + 1, t["loss"].ptr, t["D"].ptr, t["D"].ld
         a.rows, a.gscale = t["rows"], t["gscale"]
-    ok(lib.egk_ce_fused_multi(S(), arr, len(tasks), 0.1, edt(dt)), "egk_ce_fused_multi")
+    return arr
+
+
+@case("egk_ce_fused_multi", variants=[dict(dt=bf16, lpad=0, dpad=0), dict(dt=f32, lpad=3, dpad=5)])
+def ce_fused_multi(lib, ops, G, dt, lpad, dpad):
+    from egopack_amd import _lib
+    g = gen(91)
+    specs = [(77, (115, 478), (128, 512), 0.5), (33, (20,), (64,), 0.25), (0, (5,), (8,), 1.0)]  # (the third task has no rows)
+    tasks = [_ce_fused_task(G, f"task{i}.", g, r, cs, pd, lpad, dpad, dt, 0.1, gs) for i, (r, cs, pd, gs) in enumerate(specs)]
+    ok(lib.egk_ce_fused_multi(S(), _ce_task_array(tasks), len(tasks), 0.1, edt(dt)), "egk_ce_fused_multi")
     G.check()
     out = {}
     for i, t in enumerate(tasks):
         _ce_fused_check(t, f"task{i}.")
         out[f"loss{i}"], out[f"dlogits{i}"] = t["loss"], t["D"]
     return out
+
+
+@case("egk_ce_fused", "egk_ce_fused_multi", variants=[dict(rows=r, dt=dt, sm=sm) for r in (32, 77) for dt in (f32, bf16) for sm in (0.0, 0.1)])
+def ce_fused_forms(lib, ops, G, rows, dt, sm):
+    """include/egopack_hip.h: per task, egk_ce_fused_multi gives the bits of egk_ce_fused.  One task through egk_ce_fused, through
+    egk_ce_fused_multi(count = 1), and as entry 0 and as entry 1 of a two-task launch beside a shorter task: loss and the whole
+    gradient window (pad columns and the untouched sentinel columns included) have the same bits.  rows = 32: eight workgroups,
+    the XCD-contiguous row walk; rows = 77: twenty workgroups, the round-robin walk (csrc/common.h: row_walk)."""
+    Cs, pads, gs = (115, 478), (128, 512), 0.37
+    A = [_ce_fused_task(G, f"form{i}.", gen(rows + 5), rows, Cs, pads, 0, 0, dt, sm, gs, every_third=True) for i in range(4)]
+    B = [_ce_fused_task(G, f"other{i}.", gen(17), 21, (20,), (64,), 0, 0, dt, sm, 0.25) for i in range(2)]
+    t, n = A[0], len(Cs)
+    ok(lib.egk_ce_fused(S(), ptr_array(t["L"]), (C.c_int64 * n)(*[l.ld for l in t["L"]]), (C.c_int32 * n)(*Cs), (C.c_int32 * n)(*pads),
+                        (C.c_int64 * n)(*t["dcol"]), n, P(t["Y"]), n + 1, P(t["loss"]), P(t["D"]), t["D"].ld, rows, sm, gs, edt(dt)),
+       "egk_ce_fused")
+    ok(lib.egk_ce_fused_multi(S(), _ce_task_array([A[1]]), 1, sm, edt(dt)), "egk_ce_fused_multi (one task)")
+    ok(lib.egk_ce_fused_multi(S(), _ce_task_array([A[2], B[0]]), 2, sm, edt(dt)), "egk_ce_fused_multi (entry 0)")
+    ok(lib.egk_ce_fused_multi(S(), _ce_task_array([B[1], A[3]]), 2, sm, edt(dt)), "egk_ce_fused_multi (entry 1)")
+    G.check()
+    _ce_fused_check(t, "egk_ce_fused: ")
+    for other, what in zip(A[1:], ("count = 1", "entry 0 of 2", "entry 1 of 2")):
+        same(other["loss"].bits(), t["loss"].bits(), f"loss, egk_ce_fused_multi {what} against egk_ce_fused")
+        same(other["D"].bits(), t["D"].bits(), f"dlogits, egk_ce_fused_multi {what} against egk_ce_fused")
+    same(B[1]["loss"].bits(), B[0]["loss"].bits(), "loss of the shorter task, entry 0 against entry 1")
+    same(B[1]["D"].bits(), B[0]["D"].bits(), "dlogits of the shorter task, entry 0 against entry 1")
+    return dict(loss=t["loss"], dlogits=t["D"])
 
 
 @case("egk_bce_fwd", "egk_bce_bwd", variants=[dict(n=333, dt=f32), dict(n=256, dt=bf16), dict(n=0, dt=f32)])

@@ -191,6 +191,76 @@ def test_fused_launch_on_the_bank_logits_equals_the_unfused_pair(mode, eps, comp
         assert not operand[::3, c0:pad_end].float().ne(0).any(), "ignored rows have a gradient"
 
 
+def _plain_bank_logits(rows, seed):
+    """(logits, gradient operand) of a fresh ``_bank_task`` on seeded features; call under ``bank_grad_handoff``."""
+    from egopack_amd import ops
+    task, _ = _bank_task()
+    x = torch.randn(rows, 64, generator=gen(seed)).to(DEV).to(ops.act_dtype()).requires_grad_(True)
+    logits = task.forward_logits(x)
+    return logits, logits[0]._egk_grad_dst[0]
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+def test_single_task_fused_launch_has_the_bits_of_the_multi_task_launch(mode, eps, compute_restored):
+    """No vectors.  ``ops.cross_entropy`` on bank logits under an announced seed (``_CE._fused``: one fused launch) gives the loss
+    and the operand buffer, pad columns included, of ``ops.cross_entropy_multi`` on the same task beside a second one -- both
+    plan the task with the same rules and fill the same launch argument."""
+    from egopack_amd import _lib, ops
+    from tests.test_gpu_bounds import _counted
+    rows, coefs = (ROWS, 40), (0.37 / ROWS, 0.11 / 40)
+    _, y, _ = _problem((115, 478), 17)
+    y2 = y[:40].clone()
+    with ops.compute_mode(mode):
+        with _counted(_lib.load()) as c, ops.bank_grad_handoff(), ops.loss_seed(coefs[0]):
+            logits, gbuf = _plain_bank_logits(rows[0], 2)
+            one = ops.cross_entropy(logits, y.to(DEV), eps)
+        assert c.names.get("ce_fwd") == 1 and "ce_bwd" not in c.names and "ce_balanced" not in c.names, c.names
+        with _counted(_lib.load()) as c, ops.bank_grad_handoff():
+            pair = [_plain_bank_logits(rows[0], 2), _plain_bank_logits(rows[1], 3)]
+            losses = ops.cross_entropy_multi([(pair[0][0], y.to(DEV)), (pair[1][0], y2.to(DEV))], coefs, eps)
+        assert losses is not None and len(losses) == 2, "the two bank tasks did not qualify for the one-launch form"
+        assert c.names.get("ce_fwd") == 1 and "ce_bwd" not in c.names and "ce_balanced" not in c.names, c.names
+    for a, b in zip(logits, pair[0][0]):
+        assert torch.equal(a.detach(), b.detach()), "the two runs did not see the same logits"
+    assert gbuf.shape == (ROWS, 640) and gbuf.dtype == (BF if mode == "bf16" else torch.float32)
+    assert torch.equal(one.detach(), losses[0].detach()), "loss bits"
+    assert torch.equal(gbuf.view(torch.int16 if mode == "bf16" else torch.int32),
+                       pair[0][1].view(torch.int16 if mode == "bf16" else torch.int32)), "operand bits"
+    assert not gbuf[:, 115:128].float().ne(0).any() and not gbuf[:, 128 + 478:].float().ne(0).any(), "pad columns are not exactly 0"
+    assert one.detach()[::3].eq(0).all() and not gbuf[::3].float().ne(0).any(), "ignored rows"
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_a_first_block_behind_column_0_takes_the_single_task_fused_launch_only(mode, compute_restored):
+    """The nouns alone: their block starts at column 128 of the bank's operand.  ``cross_entropy_multi`` does not take such a task
+    (None: its launch argument has no way to clear the columns in front); ``ops.cross_entropy`` still issues the single-task
+    fused launch -- the bits the block has when both heads go through it -- and zero-fills the leading columns itself."""
+    from egopack_amd import _lib, ops
+    from tests.test_gpu_bounds import _counted
+    eps, coef = 0.1, 0.37 / ROWS
+    _, y, _ = _problem((115, 478), 17)
+    yn = y[:, 1:2].contiguous()
+    with ops.compute_mode(mode):
+        with ops.bank_grad_handoff(), ops.loss_seed(coef):
+            both, gboth = _plain_bank_logits(ROWS, 2)
+            ops.cross_entropy(both, y.to(DEV), eps)
+        with ops.bank_grad_handoff():
+            pair = [_plain_bank_logits(ROWS, 2), _plain_bank_logits(40, 3)]
+            assert ops.cross_entropy_multi([((pair[0][0][1],), yn.to(DEV)), (pair[1][0], y[:40].to(DEV))], (coef, coef), eps) is None
+        with _counted(_lib.load()) as c, ops.bank_grad_handoff(), ops.loss_seed(coef):
+            logits, gbuf = _plain_bank_logits(ROWS, 2)
+            gbuf.fill_(float("nan"))
+            loss = ops.cross_entropy((logits[1],), yn.to(DEV), eps)
+        assert c.names.get("ce_fwd") == 1 and "ce_bwd" not in c.names and "ce_balanced" not in c.names, c.names
+        ref = ops.cross_entropy((logits[1].detach().clone(),), yn.to(DEV), eps)
+    assert not gbuf[:, :128].float().ne(0).any(), "the columns in front of the first block are not exactly 0"
+    bits = torch.int16 if mode == "bf16" else torch.int32
+    assert torch.equal(gbuf[:, 128:].contiguous().view(bits), gboth[:, 128:].contiguous().view(bits)), "the nouns' block and its pad columns"
+    torch.testing.assert_close(loss.detach(), ref.detach(), **CB.LOSS_TOL)
+    assert loss.detach()[::3].eq(0).all()
+
+
 def _fused_call(lib, tasks, eps, dt):
     """egk_ce_w_fused_multi over ``tasks`` = [(logits list, y, weights, offsets, pads, gscale)] on plain device tensors; returns
     [(loss, operand)] per task.  The operand has two spare columns behind the last block (they must keep their fill)."""
