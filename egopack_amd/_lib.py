@@ -25,6 +25,7 @@ OPTIM_GROUPS_HEADER = HERE.parent / "include" / "egopack_optim_groups.h"  # like
 EMA_HEADER = HERE.parent / "include" / "egopack_ema.h"  # likewise; its symbols: EMA_SIGNATURES
 CE_BALANCED_HEADER = HERE.parent / "include" / "egopack_ce_balanced.h"  # likewise; its symbols: CE_BALANCED_SIGNATURES
 BCE_BALANCED_HEADER = HERE.parent / "include" / "egopack_bce_balanced.h"  # likewise; its symbols: BCE_BALANCED_SIGNATURES
+TASK_SCALE_HEADER = HERE.parent / "include" / "egopack_task_scale.h"  # likewise; its symbols: TASK_SCALE_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -264,6 +265,20 @@ BCE_BALANCED_SIGNATURES = {
 }
 
 
+# ... and include/egopack_task_scale.h (the seventh ledger: tests/test_task_weighting_cpu.py over tests/test_gpu_bounds_task_weighting.py)
+TASK_SCALE_SIGNATURES = {
+    "egk_ce_fused_multi_s": (C.c_int, [vp, vp, vp, i32, f32, i32]),
+    "egk_ce_w_fused_multi_s": (C.c_int, [vp, C.POINTER(CEWTask), vp, i32, f32, i32]),
+    "egk_rowdot_bce_s": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, i32]),
+    "egk_rowdot_bce_w_s": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, f32, f32, f32, i32]),
+    "egk_rowdot_ce2_s": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, i32]),
+    "egk_rowdot_ce2_multi_s": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32]),
+    "egk_task_scale_prepare": (C.c_int, [vp, vp, vp, i32]),
+    "egk_task_scale_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]),
+    "egk_fill_scaled_from": (C.c_int, [vp, vp, i64, f32, vp]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -300,6 +315,11 @@ def bce_balanced_header_symbols() -> list:
     return _declared(BCE_BALANCED_HEADER)
 
 
+def task_scale_header_symbols() -> list:
+    """Every function name declared in include/egopack_task_scale.h."""
+    return _declared(TASK_SCALE_HEADER)
+
+
 _lib = None
 
 
@@ -314,7 +334,8 @@ def load() -> C.CDLL:
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
-                              *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items()]:
+                              *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items(),
+                              *TASK_SCALE_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

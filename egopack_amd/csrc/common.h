@@ -109,6 +109,7 @@ enum KernelId {
     KID_EMA_SWAP,          // egk_ema_swap: parameters <-> their average
     KID_CE_BALANCED,       // egk_ce_w_fwd / _bwd / _fused_multi: cross entropy with per-class weights and logit offsets (loss.hip)
     KID_BCE_BALANCED,      // egk_bce_w_fwd / _bwd, egk_rowdot_bce_w: BCE-with-logits with class factors and a focal exponent (loss.hip, norm_ops.hip)
+    KID_TASK_SCALE,        // the entry points of include/egopack_task_scale.h: the _s head launches, prepare, grad, fill (loss.hip, norm_ops.hip, loss_optim.hip)
     KID_COUNT
 };
 
@@ -167,6 +168,19 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// The backward seed of a head kernel with its task factor in device memory (include/egopack_task_scale.h): c * scale[0] as ONE
+// separately rounded f32 product, formed before anything else uses it, so that a launch with (c, scale) writes the bits of the
+// launch with fl32(c * scale[0]) by value.  The product is written HERE, under the pragma (which covers the operations written
+// lexically in this function: the multiply carries no contract flag, so nothing it is inlined into can fuse it with an add).
+// ``scale`` is a kernel argument: the load is wave-uniform, one 4-byte read per wave.  NULL: the seed as given -- the launches
+// without a scale keep their bits.
+__device__ __forceinline__ float scaled_seed(float c, const float* __restrict__ scale) {
+#pragma clang fp contract(off)
+    if (!scale) return c;
+    const float s = scale[0];
+    return c * s;
 }
 
 // Philox4x32-10 (Salmon et al. 2011).  counter = (ctr_lo, ctr_hi, 0, 0), key = seed.

@@ -184,6 +184,7 @@ struct CETasks {
     int n_heads[CE_MAX_TASKS];
     int rows[CE_MAX_TASKS];
     float gscale[CE_MAX_TASKS];
+    const float* scale[CE_MAX_TASKS];  // the task factor of gscale in device memory (egk_ce_fused_multi_s / egk_ce_w_fused_multi_s), or null
 };
 template <typename T, bool BAL>
 __global__ __launch_bounds__(256) void ce_fused_multi_kernel(const CETasks P, float smoothing) {
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(256) void ce_fused_multi_kernel(const CETasks P, fl
     const long long ys = P.ys[k], ldd = P.ldd[k];
     float* __restrict__ loss = P.loss[k];
     T* __restrict__ dlogits = (T*)P.dlogits[k];
-    const float gscale = P.gscale[k];
+    const float gscale = scaled_seed(P.gscale[k], P.scale[k]);  // (common.h: one rounded product, the seed itself without a scale)
     const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
     for (int row = rw.first; row < rw.end; row += rw.step) {
         float total = 0.f;
@@ -325,11 +326,13 @@ static int ce_bwd_launch(const char* who, int kid, egk_stream_t stream, const fl
 
 // Validates and packs the tasks of egk_ce_fused / egk_ce_fused_multi / egk_ce_w_fused_multi and launches them on the grid
 // (row_grid(longest task), count).  ``wtasks``: the tasks with their vectors (BAL), else ``tasks``.  The slots behind ``count``
-// repeat the last task with no rows: no wild pointers in the argument.
+// repeat the last task with no rows: no wild pointers in the argument.  ``scales`` (the _s entry points of
+// include/egopack_task_scale.h; ``scaled``): one device float per task that multiplies the task's gscale inside the kernel.
 template <bool BAL>
 static int ce_fused_launch(const char* who, int kid, egk_stream_t stream, const egk_ce_task* tasks, const egk_ce_w_task* wtasks,
-                           int32_t count, float smoothing, int32_t dtype) {
+                           int32_t count, float smoothing, int32_t dtype, bool scaled = false, const float* const* scales = nullptr) {
     EGK_REQUIRE(BAL ? (const void*)wtasks : (const void*)tasks, "%s: null pointer", who);
+    EGK_REQUIRE(!scaled || scales, "%s: null pointer (scales)", who);
     EGK_REQUIRE(count >= 1 && count <= CE_MAX_TASKS, "%s: 1 .. %d tasks", who, CE_MAX_TASKS);
     EGK_REQUIRE(dtype == EGK_F32 || dtype == EGK_BF16, "%s: unknown activation dtype %d", who, (int)dtype);
     CETasks P;
@@ -355,6 +358,9 @@ static int ce_fused_launch(const char* who, int kid, egk_stream_t stream, const 
         }
         P.n_heads[i] = t.n_heads; P.y[i] = (const long long*)t.y; P.ys[i] = t.y_stride; P.loss[i] = t.loss;
         P.dlogits[i] = t.dlogits; P.ldd[i] = t.ldd; P.rows[i] = i < count ? t.rows : 0; P.gscale[i] = t.gscale;
+        P.scale[i] = scaled ? scales[j] : nullptr;
+        EGK_REQUIRE(!scaled || P.scale[i], "%s: null pointer (scale of task %d)", who, i);
+        EGK_REQUIRE(aligned_to(4, {P.scale[i]}), "%s: the scale of task %d is not 4-byte aligned", who, i);
         if (i < count && t.rows > max_rows) max_rows = t.rows;
     }
     if (max_rows == 0) return 0;
@@ -446,6 +452,16 @@ int egk_ce_fused_multi(egk_stream_t stream, const egk_ce_task* tasks, int32_t co
 
 int egk_ce_w_fused_multi(egk_stream_t stream, const egk_ce_w_task* tasks, int32_t count, float smoothing, int32_t dtype) {
     return ce_fused_launch<true>("egk_ce_w_fused_multi", KID_CE_BALANCED, stream, nullptr, tasks, count, smoothing, dtype);
+}
+
+int egk_ce_fused_multi_s(egk_stream_t stream, const egk_ce_task* tasks, const float* const* scales, int32_t count, float smoothing,
+                         int32_t dtype) {
+    return ce_fused_launch<false>("egk_ce_fused_multi_s", KID_TASK_SCALE, stream, tasks, nullptr, count, smoothing, dtype, true, scales);
+}
+
+int egk_ce_w_fused_multi_s(egk_stream_t stream, const egk_ce_w_task* tasks, const float* const* scales, int32_t count, float smoothing,
+                           int32_t dtype) {
+    return ce_fused_launch<true>("egk_ce_w_fused_multi_s", KID_TASK_SCALE, stream, nullptr, tasks, count, smoothing, dtype, true, scales);
 }
 
 int egk_bce_fwd(egk_stream_t stream, const float* logits, const int64_t* y, float* loss, int32_t n) {

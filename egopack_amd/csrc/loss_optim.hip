@@ -314,6 +314,65 @@ __global__ __launch_bounds__(SUMSQ_THREADS) void grad_norm_finalize_kernel(const
     }
 }
 
+// ---- task weights in device memory (include/egopack_task_scale.h) ---------------------------------------------------------------
+// scale[t] = exp(-s[t]) in f64, rounded to f32 once: exactly 1 for s = 0
+__global__ __launch_bounds__(64) void task_scale_prepare_kernel(const float* __restrict__ s, float* __restrict__ scale, int n) {
+    const int t = threadIdx.x;
+    if (t < n) scale[t] = (float)exp(-(double)s[t]);
+}
+
+// out[i] = fl32(coef * scale[0]): the seed of a head that runs off the announced-seed paths, as the tensor its backward starts from
+__global__ __launch_bounds__(256) void fill_scaled_from_kernel(float* __restrict__ out, long long n, float coef,
+                                                               const float* __restrict__ scale) {
+    const float v = scaled_seed(coef, scale);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = v;
+}
+
+struct TaskGrad {
+    const float* x[MAXVEC];   // loss vectors (null: the task is absent from this step)
+    long long n[MAXVEC];      // their elements
+    double count[MAXVEC];     // what the task's mean divides by (>= 1)
+    double w[MAXVEC];
+    int tasks;
+};
+// sum of x[0 .. n) in f64 by the 1024 threads of a workgroup, in a fixed order (strided per thread, the wave's butterfly, the 16
+// waves in wave order): the same bits on every launch.  Valid in thread 0; every thread of the workgroup must call it.
+__device__ __forceinline__ double block_sum_f64(const float* __restrict__ x, long long n, double* part) {
+    double a = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 1024) a += (double)x[i];
+    a = wave_sum(a);
+    __syncthreads();  // part[] free (the previous vector consumed)
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 16; ++i) t += part[i];
+    return t;
+}
+// Workgroup t owns task t: L_t = sum(loss_t) / count_t, acc[t] += sum(loss_t), ds[t] = w_t (1 - scale_t L_t) -- one writer each.
+// Workgroup 0 also walks every task in order for the reported objective (the same sums, so the same bits): no atomics, no workspace.
+// s == null: fixed scales (the ``manual`` mode) -- no ds, objective = sum_t w_t scale_t L_t.
+__global__ __launch_bounds__(1024) void task_scale_grad_kernel(const TaskGrad v, const float* __restrict__ s,
+                                                               const float* __restrict__ scale, float* __restrict__ ds,
+                                                               float* __restrict__ objective, double* __restrict__ acc) {
+    __shared__ double part[16];
+    const int me = blockIdx.x;
+    double J = 0.0;
+    for (int k = me == 0 ? 0 : me; k < (me == 0 ? v.tasks : me + 1); ++k) {
+        const bool present = v.x[k] != nullptr;
+        const double S = block_sum_f64(v.x[k], present ? v.n[k] : 0, part);
+        if (threadIdx.x == 0) {
+            const double L = S / v.count[k], sc = (double)scale[k];
+            if (k == me) {
+                if (acc) acc[k] += S;
+                if (s) ds[k] = present ? (float)(v.w[k] * (1.0 - sc * L)) : 0.f;
+            }
+            if (present) J += v.w[k] * (sc * L + (s ? (double)s[k] : 0.0));
+        }
+    }
+    if (me == 0 && threadIdx.x == 0) objective[0] = (float)J;
+}
+
 static inline unsigned ew_grid(long long n, int per_thread) {
     long long b = (n / per_thread + 255) / 256;
     return (unsigned)(b < 1 ? 1 : b > 4096 ? 4096 : b);
@@ -426,6 +485,49 @@ int egk_fill_scaled_multi(egk_stream_t stream, const float* scalar, const float*
     const long long blocks = (nmax + 255) / 256;
     hipLaunchKernelGGL(fill_scaled_multi_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks), count), dim3(256), 0, s, scalar, v);
     return check_launch("egk_fill_scaled_multi");
+}
+
+int egk_task_scale_prepare(egk_stream_t stream, const float* s_, float* scale, int32_t n) {
+    EGK_REQUIRE(s_ && scale, "egk_task_scale_prepare: null pointer");
+    EGK_REQUIRE(n >= 1 && n <= MAXVEC, "egk_task_scale_prepare: 1..%d tasks", MAXVEC);
+    EGK_REQUIRE(aligned_to(4, {s_, scale}), "egk_task_scale_prepare: s and scale must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_TASK_SCALE, s, 0, 8.0 * n);
+    hipLaunchKernelGGL(task_scale_prepare_kernel, dim3(1), dim3(64), 0, s, s_, scale, n);
+    return check_launch("egk_task_scale_prepare");
+}
+
+int egk_task_scale_grad(egk_stream_t stream, const float* const* loss, const int64_t* ns, const int64_t* counts, const float* w,
+                        const float* s_, const float* scale, float* ds, float* objective, double* acc, int32_t n) {
+    EGK_REQUIRE(loss && ns && counts && w && scale && objective, "egk_task_scale_grad: null pointer");
+    EGK_REQUIRE(!s_ || ds, "egk_task_scale_grad: null pointer (ds: the gradient of s)");
+    EGK_REQUIRE(n >= 1 && n <= MAXVEC, "egk_task_scale_grad: 1..%d tasks", MAXVEC);
+    EGK_REQUIRE(aligned_to(4, {s_, scale, ds, objective}) && aligned_to(8, {acc}), "egk_task_scale_grad: misaligned pointer");
+    TaskGrad v{};
+    double bytes = 0;
+    for (int k = 0; k < n; ++k) {
+        EGK_REQUIRE(ns[k] >= 0, "egk_task_scale_grad: negative length (task %d)", k);
+        EGK_REQUIRE(aligned_to(4, {loss[k]}), "egk_task_scale_grad: misaligned loss vector (task %d)", k);
+        v.x[k] = loss[k]; v.n[k] = ns[k]; v.w[k] = (double)w[k];
+        v.count[k] = (double)(counts[k] > 0 ? counts[k] : (ns[k] > 0 ? ns[k] : 1));
+        if (loss[k]) bytes += 8.0 * ns[k];  // (workgroup 0 reads every vector again)
+    }
+    v.tasks = n;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_TASK_SCALE, s, 0, bytes);
+    hipLaunchKernelGGL(task_scale_grad_kernel, dim3(n), dim3(1024), 0, s, v, s_, scale, ds, objective, acc);
+    return check_launch("egk_task_scale_grad");
+}
+
+int egk_fill_scaled_from(egk_stream_t stream, float* out, int64_t n, float coef, const float* scale) {
+    EGK_REQUIRE(out && scale, "egk_fill_scaled_from: null pointer");
+    EGK_REQUIRE(n >= 0, "egk_fill_scaled_from: n must be >= 0");
+    EGK_REQUIRE(aligned_to(4, {out, scale}), "egk_fill_scaled_from: out and scale must be 4-byte aligned");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_TASK_SCALE, s, 0, 4.0 * n);
+    hipLaunchKernelGGL(fill_scaled_from_kernel, dim3(ew_grid(n, 1)), dim3(256), 0, s, out, (long long)n, coef, scale);
+    return check_launch("egk_fill_scaled_from");
 }
 
 int egk_copy_blocks(egk_stream_t stream, const void* const* srcs, const int64_t* nbytes, void* dst, int32_t count) {

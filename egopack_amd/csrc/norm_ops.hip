@@ -935,13 +935,16 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
 // rowdot_reduce_kernel: fixed order, no atomics.
 // SHAPED (egk_rowdot_bce_w, include/egopack_bce_balanced.h): loss_n and g_n are bce_shaped.h's -- a class factor and a focal
 // exponent, wave-uniform kernel arguments -- in place of the two expressions above; everything else is this kernel.
+// ``scale`` (the _s entry points, include/egopack_task_scale.h): the seed's task factor in device memory, or null (common.h).
 template <int NV, typename T, bool FULL, bool SHAPED = false>
 __global__ __launch_bounds__(256) void rowdot_bce_kernel(const T* __restrict__ f, const T* __restrict__ w, const float* __restrict__ bias,
                                                          const long long* __restrict__ y, float* __restrict__ logits,
                                                          float* __restrict__ loss, T* __restrict__ df, float* __restrict__ ws,
-                                                         int rows, int cols, float seed, const BceShape sh = BceShape{1.f, 1.f, 0.f}) {
+                                                         int rows, int cols, float seed, const float* __restrict__ scale,
+                                                         const BceShape sh = BceShape{1.f, 1.f, 0.f}) {
     extern __shared__ __attribute__((aligned(16))) float red_[];  // [WPB][NV * 256 + 4]
     float (*red)[NV * 256 + 4] = reinterpret_cast<float (*)[NV * 256 + 4]>(red_);
+    seed = scaled_seed(seed, scale);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if constexpr (FULL) cols = NV * 256;
     const bool vec = FULL || (cols & 3) == 0;
@@ -1070,9 +1073,10 @@ template <typename T>
 __global__ __launch_bounds__(256) void rowdot_ce2_rows_kernel(const CE2Sources S, const long long* __restrict__ y,
                                                               float* __restrict__ logits, float* __restrict__ loss,
                                                               float* __restrict__ gws, int cols, float scale, float smoothing,
-                                                              float seed) {
+                                                              float seed, const float* __restrict__ task_scale) {
     __shared__ float part[CE2_MAX_SRC][2];
     __shared__ float gsh[2];
+    seed = scaled_seed(seed, task_scale);  // (include/egopack_task_scale.h; null: the seed as given)
     const int row = blockIdx.x, lane = threadIdx.x & 63, k = threadIdx.x >> 6;
     const bool vec = (cols & 3) == 0;
     const bool on = k < S.n;
@@ -1548,53 +1552,102 @@ int egk_graphln_bwd(egk_stream_t stream, const void* dy, const void* x, const fl
  * receives the partial rows of dw / db; egk_rowdot_reduce ACCUMULATES them into dw [cols] and db [1]. */
 int32_t egk_rowdot_ws_rows(int32_t rows) { return row_grid(rows); }
 
-int egk_rowdot_bce(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
-                   float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, int32_t dtype) {
-    EGK_REQUIRE(f && w && y && logits && loss, "egk_rowdot_bce: null pointer");
-    EGK_REQUIRE(!df || ws, "egk_rowdot_bce: gradients need the partial-row workspace");
-    EGK_REQUIRE_VEC_ALIGNED("egk_rowdot_bce", (cols & 3) || aligned_to(vec_bytes(dtype), {f, w, df}));
-    if (rows == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
-    ProfScope prof(KID_BCE_FWD, s, 2.0 * rows * cols * (df ? 3 : 1), eb * rows * cols * (df ? 2 : 1) + 16.0 * rows);
-    DISPATCH_NV(cols, dtype, hipLaunchKernelGGL((rowdot_bce_kernel<NV, T, FULL>), dim3(row_grid(rows)), dim3(256),
-                                                 WPB * (NV * 256 + 4) * sizeof(float), s, (const T*)f,
-                                                 (const T*)w, bias, (const long long*)y, logits, loss, (T*)df, ws, rows, cols, seed));
-    return check_launch("egk_rowdot_bce");
+}  // extern "C"
+
+// what the _s entry points of include/egopack_task_scale.h refuse beside their siblings' refusals; 0 or EGK_EINVAL
+static int task_scale_check(const char* who, bool scaled, const float* scale) {
+    EGK_REQUIRE(!scaled || scale, "%s: null pointer (scale)", who);
+    EGK_REQUIRE(aligned_to(4, {scale}), "%s: scale is not 4-byte aligned", who);
+    return 0;
 }
 
-/* egk_rowdot_bce with the shaped loss of include/egopack_bce_balanced.h: the same kernel, grid, workspace layout and refusals. */
-int egk_rowdot_bce_w(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
-                     float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, float pos, float neg, float gamma,
-                     int32_t dtype) {
-    EGK_REQUIRE(f && w && y && logits && loss, "egk_rowdot_bce_w: null pointer");
-    EGK_REQUIRE(!df || ws, "egk_rowdot_bce_w: gradients need the partial-row workspace");
-    EGK_REQUIRE(rows >= 0, "egk_rowdot_bce_w: rows must be >= 0");
-    EGK_REQUIRE(cols >= 1, "egk_rowdot_bce_w: cols must be >= 1");
-    EGK_REQUIRE(bce_shape_ok(pos, neg, gamma), "egk_rowdot_bce_w: pos, neg and gamma must be finite and >= 0 (got %g, %g, %g)",
-                (double)pos, (double)neg, (double)gamma);
-    EGK_REQUIRE_VEC_ALIGNED("egk_rowdot_bce_w", (cols & 3) || aligned_to(vec_bytes(dtype), {f, w, df}));
+// egk_rowdot_bce and egk_rowdot_bce_s (``scaled``: the seed's task factor is read from ``scale``): one launcher
+static int rowdot_bce_launch(const char* who, int kid, egk_stream_t stream, const void* f, const void* w, const float* bias,
+                             const int64_t* y, float* logits, float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed,
+                             bool scaled, const float* scale, int32_t dtype) {
+    EGK_REQUIRE(f && w && y && logits && loss, "%s: null pointer", who);
+    if (int e = task_scale_check(who, scaled, scale)) return e;
+    EGK_REQUIRE(!df || ws, "%s: gradients need the partial-row workspace", who);
+    EGK_REQUIRE_VEC_ALIGNED(who, (cols & 3) || aligned_to(vec_bytes(dtype), {f, w, df}));
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
-    ProfScope prof(KID_BCE_BALANCED, s, 2.0 * rows * cols * (df ? 3 : 1), eb * rows * cols * (df ? 2 : 1) + 16.0 * rows);
+    ProfScope prof(kid, s, 2.0 * rows * cols * (df ? 3 : 1), eb * rows * cols * (df ? 2 : 1) + 16.0 * rows);
+    DISPATCH_NV(cols, dtype, hipLaunchKernelGGL((rowdot_bce_kernel<NV, T, FULL>), dim3(row_grid(rows)), dim3(256),
+                                                 WPB * (NV * 256 + 4) * sizeof(float), s, (const T*)f,
+                                                 (const T*)w, bias, (const long long*)y, logits, loss, (T*)df, ws, rows, cols, seed,
+                                                 scaled ? scale : nullptr));
+    return check_launch(who);
+}
+
+// egk_rowdot_bce_w and egk_rowdot_bce_w_s: the same kernel, grid, workspace layout and refusals with the shaped loss of
+// include/egopack_bce_balanced.h
+static int rowdot_bce_w_launch(const char* who, int kid, egk_stream_t stream, const void* f, const void* w, const float* bias,
+                               const int64_t* y, float* logits, float* loss, void* df, float* ws, int32_t rows, int32_t cols,
+                               float seed, bool scaled, const float* scale, float pos, float neg, float gamma, int32_t dtype) {
+    EGK_REQUIRE(f && w && y && logits && loss, "%s: null pointer", who);
+    if (int e = task_scale_check(who, scaled, scale)) return e;
+    EGK_REQUIRE(!df || ws, "%s: gradients need the partial-row workspace", who);
+    EGK_REQUIRE(rows >= 0, "%s: rows must be >= 0", who);
+    EGK_REQUIRE(cols >= 1, "%s: cols must be >= 1", who);
+    EGK_REQUIRE(bce_shape_ok(pos, neg, gamma), "%s: pos, neg and gamma must be finite and >= 0 (got %g, %g, %g)", who, (double)pos,
+                (double)neg, (double)gamma);
+    EGK_REQUIRE_VEC_ALIGNED(who, (cols & 3) || aligned_to(vec_bytes(dtype), {f, w, df}));
+    if (rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
+    ProfScope prof(kid, s, 2.0 * rows * cols * (df ? 3 : 1), eb * rows * cols * (df ? 2 : 1) + 16.0 * rows);
     DISPATCH_NV(cols, dtype, hipLaunchKernelGGL((rowdot_bce_kernel<NV, T, FULL, true>), dim3(row_grid(rows)), dim3(256),
                                                  WPB * (NV * 256 + 4) * sizeof(float), s, (const T*)f,
                                                  (const T*)w, bias, (const long long*)y, logits, loss, (T*)df, ws, rows, cols, seed,
-                                                 BceShape{pos, neg, gamma}));
-    return check_launch("egk_rowdot_bce_w");
+                                                 scaled ? scale : nullptr, BceShape{pos, neg, gamma}));
+    return check_launch(who);
+}
+
+extern "C" {
+
+int egk_rowdot_bce(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
+                   float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, int32_t dtype) {
+    return rowdot_bce_launch("egk_rowdot_bce", KID_BCE_FWD, stream, f, w, bias, y, logits, loss, df, ws, rows, cols, seed, false, nullptr,
+                             dtype);
+}
+
+int egk_rowdot_bce_s(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
+                     float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, const float* scale, int32_t dtype) {
+    return rowdot_bce_launch("egk_rowdot_bce_s", KID_TASK_SCALE, stream, f, w, bias, y, logits, loss, df, ws, rows, cols, seed, true,
+                             scale, dtype);
+}
+
+int egk_rowdot_bce_w(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
+                     float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, float pos, float neg, float gamma,
+                     int32_t dtype) {
+    return rowdot_bce_w_launch("egk_rowdot_bce_w", KID_BCE_BALANCED, stream, f, w, bias, y, logits, loss, df, ws, rows, cols, seed, false,
+                               nullptr, pos, neg, gamma, dtype);
+}
+
+int egk_rowdot_bce_w_s(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits,
+                       float* loss, void* df, float* ws, int32_t rows, int32_t cols, float seed, const float* scale, float pos,
+                       float neg, float gamma, int32_t dtype) {
+    return rowdot_bce_w_launch("egk_rowdot_bce_w_s", KID_TASK_SCALE, stream, f, w, bias, y, logits, loss, df, ws, rows, cols, seed, true,
+                               scale, pos, neg, gamma, dtype);
 }
 
 int32_t egk_rowdot_ce2_max_rows(void) { return CE2_MAX_ROWS; }
 
-int egk_rowdot_ce2_multi(egk_stream_t stream, int32_t n_src, const void* const* f, const void* const* w, const float* const* bias,
-                         const int64_t* y, float* logits, float* loss, void* const* df, float* const* dw, float* const* db,
-                         float* gws, int32_t rows, int32_t cols, int32_t average, float smoothing, float seed, int32_t dtype) {
+}  // extern "C"
+
+// egk_rowdot_ce2_multi and egk_rowdot_ce2_multi_s (``scaled``: the seed's task factor is read from ``scale`` by the row launch;
+// the column launch reads the rounded gradients the row launch left in ``gws``)
+static int rowdot_ce2_launch(const char* who, int kid, egk_stream_t stream, int32_t n_src, const void* const* f, const void* const* w,
+                             const float* const* bias, const int64_t* y, float* logits, float* loss, void* const* df,
+                             float* const* dw, float* const* db, float* gws, int32_t rows, int32_t cols, int32_t average,
+                             float smoothing, float seed, bool scaled, const float* scale, int32_t dtype) {
     // seed < 0 is not a gradient scale: the sign bit of ``average`` is not available either -- the phase rides in bits 1-2 of ``average``
     const int phase = (average >> 1) & 3;  // 0: both launches; 1: the row launch only; 2: the column launch only (gws from a phase-1 call)
     average &= 1;
-    EGK_REQUIRE(f && w && y && logits && loss && n_src >= 1 && n_src <= CE2_MAX_SRC, "egk_rowdot_ce2_multi: 1 .. %d sources", CE2_MAX_SRC);
-    EGK_REQUIRE(rows >= 0 && rows <= CE2_MAX_ROWS && cols >= 1, "egk_rowdot_ce2_multi: at most %d rows", CE2_MAX_ROWS);
+    EGK_REQUIRE(f && w && y && logits && loss && n_src >= 1 && n_src <= CE2_MAX_SRC, "%s: 1 .. %d sources", who, CE2_MAX_SRC);
+    EGK_REQUIRE(rows >= 0 && rows <= CE2_MAX_ROWS && cols >= 1, "%s: at most %d rows", who, CE2_MAX_ROWS);
+    if (int e = task_scale_check(who, scaled, scale)) return e;
     if (rows == 0) return 0;
     CE2Sources S;
     bool want = false, want_w = false;
@@ -1606,23 +1659,40 @@ int egk_rowdot_ce2_multi(egk_stream_t stream, int32_t n_src, const void* const* 
         S.df[k] = (in && df) ? df[k] : nullptr;
         S.dw[k] = (in && dw) ? dw[k] : nullptr;
         S.db[k] = (in && db) ? db[k] : nullptr;
-        EGK_REQUIRE(!in || (S.f[k] && S.w[k]), "egk_rowdot_ce2_multi: null source");
-        EGK_REQUIRE_VEC_ALIGNED("egk_rowdot_ce2_multi", (cols & 3) || aligned_to(vec_bytes(dtype), {S.f[k], S.w[k], S.df[k]}));
+        EGK_REQUIRE(!in || (S.f[k] && S.w[k]), "%s: null source", who);
+        EGK_REQUIRE_VEC_ALIGNED(who, (cols & 3) || aligned_to(vec_bytes(dtype), {S.f[k], S.w[k], S.df[k]}));
         want = want || S.df[k] || S.dw[k] || S.db[k];
         want_w = want_w || S.dw[k] || S.db[k];
     }
     S.n = n_src;
-    EGK_REQUIRE(!want || gws, "egk_rowdot_ce2_multi: gradients need the [rows][2] workspace");
+    EGK_REQUIRE(!want || gws, "%s: gradients need the [rows][2] workspace", who);
     hipStream_t s = (hipStream_t)stream;
     const double eb = dtype == EGK_BF16 ? 2.0 : 4.0;
-    ProfScope prof(KID_CE_FWD, s, 4.0 * rows * cols * n_src * (want ? 3 : 1), eb * rows * cols * n_src * (want ? 3 : 1));
+    ProfScope prof(kid, s, 4.0 * rows * cols * n_src * (want ? 3 : 1), eb * rows * cols * n_src * (want ? 3 : 1));
     EGK_DISPATCH_T(dtype, {
         if (phase != 2)
             hipLaunchKernelGGL(rowdot_ce2_rows_kernel<T>, dim3(rows), dim3(256), 0, s, S, (const long long*)y, logits, loss,
-                               want ? gws : nullptr, cols, average ? 1.f / n_src : 1.f, smoothing, seed);
+                               want ? gws : nullptr, cols, average ? 1.f / n_src : 1.f, smoothing, seed, scaled ? scale : nullptr);
         if (want_w && phase != 1) hipLaunchKernelGGL(rowdot_ce2_cols_kernel<T>, dim3(cdiv(cols, 256), n_src), dim3(64), 0, s, S, gws, rows, cols);
     });
-    return check_launch("egk_rowdot_ce2_multi");
+    return check_launch(who);
+}
+
+extern "C" {
+
+int egk_rowdot_ce2_multi(egk_stream_t stream, int32_t n_src, const void* const* f, const void* const* w, const float* const* bias,
+                         const int64_t* y, float* logits, float* loss, void* const* df, float* const* dw, float* const* db,
+                         float* gws, int32_t rows, int32_t cols, int32_t average, float smoothing, float seed, int32_t dtype) {
+    return rowdot_ce2_launch("egk_rowdot_ce2_multi", KID_CE_FWD, stream, n_src, f, w, bias, y, logits, loss, df, dw, db, gws, rows, cols,
+                             average, smoothing, seed, false, nullptr, dtype);
+}
+
+int egk_rowdot_ce2_multi_s(egk_stream_t stream, int32_t n_src, const void* const* f, const void* const* w, const float* const* bias,
+                           const int64_t* y, float* logits, float* loss, void* const* df, float* const* dw, float* const* db,
+                           float* gws, int32_t rows, int32_t cols, int32_t average, float smoothing, float seed, const float* scale,
+                           int32_t dtype) {
+    return rowdot_ce2_launch("egk_rowdot_ce2_multi_s", KID_TASK_SCALE, stream, n_src, f, w, bias, y, logits, loss, df, dw, db, gws, rows,
+                             cols, average, smoothing, seed, true, scale, dtype);
 }
 
 int egk_rowdot_ce2(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits, float* loss,
@@ -1630,6 +1700,15 @@ int egk_rowdot_ce2(egk_stream_t stream, const void* f, const void* w, const floa
     EGK_REQUIRE(f && w && y && logits && loss, "egk_rowdot_ce2: null pointer");
     EGK_REQUIRE(!df || dw, "egk_rowdot_ce2: gradients need dw");
     return egk_rowdot_ce2_multi(stream, 1, &f, &w, &bias, y, logits, loss, &df, &dw, &db, gws, rows, cols, 0, smoothing, seed, dtype);
+}
+
+int egk_rowdot_ce2_s(egk_stream_t stream, const void* f, const void* w, const float* bias, const int64_t* y, float* logits, float* loss,
+                     void* df, float* dw, float* db, float* gws, int32_t rows, int32_t cols, float smoothing, float seed,
+                     const float* scale, int32_t dtype) {
+    EGK_REQUIRE(f && w && y && logits && loss, "egk_rowdot_ce2_s: null pointer");
+    EGK_REQUIRE(!df || dw, "egk_rowdot_ce2_s: gradients need dw");
+    return egk_rowdot_ce2_multi_s(stream, 1, &f, &w, &bias, y, logits, loss, &df, &dw, &db, gws, rows, cols, 0, smoothing, seed, scale,
+                                  dtype);
 }
 
 int egk_rowdot_reduce(egk_stream_t stream, const float* ws, float* dw, float* db, int32_t rows, int32_t cols) {

@@ -348,9 +348,16 @@ class GradSync:
                              "rank steps 1 / world of the parameters, so the average would be sharded like the moments -- use the "
                              "all-reduce exchange (the default), where every rank runs the full launch")
 
+    def _refuse_task_weighting(self, opt) -> None:
+        if getattr(opt, "task_weighting", None) not in (None, "none"):
+            raise ValueError(f"task weighting (task_weighting.mode: {opt.task_weighting}) does not combine with the sharded update "
+                             "(sharded_update): the log-variances' gradient is formed on every rank from its own loss vectors and "
+                             "their slot would be stepped by one rank alone -- use the all-reduce exchange (the default)")
+
     def _start_sharded(self, opt, lo, hi, after=()) -> None:
         self._refuse_clipping(opt)
         self._refuse_ema(opt)
+        self._refuse_task_weighting(opt)
         flat_g = opt.flat_g
         gpu = flat_g.is_cuda
         compress = self.compress == "bf16" and gpu
@@ -435,6 +442,7 @@ class GradSync:
     def _sharded_step(self, opt) -> None:
         self._refuse_clipping(opt)
         self._refuse_ema(opt)
+        self._refuse_task_weighting(opt)
         flat_g, n = opt.flat_g, opt.flat_g.numel()
         per, lo, hi, body = self.shard_bounds(n)
         real = dist.get_world_size(self.group) if dist.is_initialized() else 1

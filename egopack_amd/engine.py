@@ -13,6 +13,7 @@
 from __future__ import annotations
 
 import contextlib
+import math
 import queue
 import threading
 from typing import Dict, Mapping, Optional, Sequence
@@ -23,6 +24,7 @@ from . import ops, switches
 from .data import Data, merge_batches
 from .criterion import MetricSelectorWrapper
 from .dist import GradSync
+from .optim import TASK_WEIGHTING_MODES
 
 TASK_ORDER = ("ar", "lta", "oscc", "pnr")  # order of the loss terms in main_temporal.train
 
@@ -593,6 +595,12 @@ class StepBase:
         self._steps_seen = 0
         self.loop_counts = {"replayed": 0, "eager": 0}  # per training loop; the entry points log and reset it per epoch
         self._train_static = None   # the static batches of the captured step and its sets of input buffers
+        # task weighting (MTLStep ``task_weighting``; include/egopack_task_scale.h) -- idle: off
+        self.task_mode = "none"       # none | manual | uncertainty
+        self.task_scale = None        # f32 [len(enabled)] on the device: the factor of every head's backward seed, read by the kernels
+        self.task_log_var = None      # uncertainty: the models.TaskLogVariance whose parameter the optimizer steps
+        self._task_scale_host = None  # the scales as last set from the host (manual; 1.0 each before that)
+        self.captures = 0             # captures taken by this step object (a changed task scale must not add one)
         # optional launch(es) in front of every step, inside the captured graph too: e.g. the feature-store gather that
         # materialises the step's input block from its index matrix (feature_store.FeatureStore.gather(idx, out=buffer))
         self.input_hook = None
@@ -805,6 +813,7 @@ class StepBase:
     def forward_backward(self, batches, merged=None):
         self._live_last = self._live(batches)
         self.optimizer.zero_grad()
+        self._task_scale_head()
         if self.input_hook is not None:
             self.input_hook()
         with self._issuing(batches, merged):
@@ -857,8 +866,16 @@ class StepBase:
                 opt.zero_flat_grads()
                 if hyper:
                     opt.prepare_hyper(in_capture=True)
+                self._task_scale_head()  # (uncertainty: scale = exp(-log_var), joined with the clear before the heads read it)
         ops.defer_after_next_launch(issue_zero)
         self._zero_pending = True
+
+    def _task_scale_head(self) -> None:
+        """The launch at the head of a step with learned task weights (MTLStep); nothing otherwise."""
+
+    def _task_scale_for(self, device):
+        """The per-task scale vector of the heads' seeds on ``device`` (MTLStep with task weighting); None otherwise."""
+        return None
 
     def _join_zero(self):
         """Wait for the gradient clear forked by ``_fork_grad_clear`` before the first launch that writes a gradient."""
@@ -922,6 +939,7 @@ class StepBase:
         if self.sync is not None:
             self.sync.begin_step()
         self.optimizer.zero_grad()
+        self._task_scale_head()
         if self.input_hook is not None:
             self.input_hook()
         with self._issuing(batches, merged):
@@ -1130,7 +1148,9 @@ class StepBase:
 
     def _capture_once(self, batches, merged, warmup):
         opt = self.optimizer
+        self.captures += 1
         self._loss_acc_for(next(self.model.parameters()).device)  # (the running loss sums' slots: allocated outside the capture)
+        self._task_scale_for(next(self.model.parameters()).device)  # (likewise the task-scale vector, when there is one)
         if self._exact_ln_on() and not self._one_graph_exchange_ok():
             raise RuntimeError("exact_graph_ln sums the graph-LayerNorm statistics over the ranks inside the step: this process "
                                "group's collectives cannot be captured in a hipGraph -- use step() / train_step() (eager) in this mode")
@@ -1514,11 +1534,95 @@ class MTLStep(StepBase):
 
     def __init__(self, model, tasks: Mapping[str, torch.nn.Module], criteria: Mapping[str, torch.nn.Module],
                  weights: Mapping[str, float], optimizer, fused_backbone: bool = True, sync: Optional[GradSync] = None,
-                 parallel_heads: bool = True):
+                 parallel_heads: bool = True, task_weighting: str = "none", log_var=None):
+        """``task_weighting``: none | manual | uncertainty.  ``manual``: ``set_task_scale`` changes the balance of the
+        tasks between two steps, replays included.  ``uncertainty``: ``log_var``, a models.TaskLogVariance over ``enabled`` whose
+        parameter is the LAST parameter of ``optimizer`` (train.build_optimizer), is learned with the weights."""
         self._init_base(model, tasks, weights, optimizer, fused_backbone, sync, parallel_heads)
         self.criteria = dict(criteria)
         self._head_batches = None  # the batches of the step being issued, for the heads (``_heads_forward_backward``)
         self._coef_grads = {}      # per task the constant its head's backward starts from (w_t / numel), filled once
+        self._init_task_weighting(task_weighting, log_var)
+
+    # ---- task weights in device memory (include/egopack_task_scale.h, DESIGN 3.11) ---------------------------------------------------
+    # Every head's backward seed w_t / N_t is multiplied INSIDE its kernel by task_scale[i] (i: the task's place in ``enabled``), one
+    # separately rounded f32 product.  manual: the host writes the vector; uncertainty: exp(-log_var), written by one launch at the
+    # head of the step, and the rider that reports the objective also stores d J / d log_var into the parameter's gradient slot.
+    def _init_task_weighting(self, mode, log_var) -> None:
+        mode = str(mode or "none").lower()
+        if mode not in TASK_WEIGHTING_MODES:
+            raise ValueError(f"task_weighting: unknown mode '{mode}' ({' | '.join(TASK_WEIGHTING_MODES)})")
+        if mode == "uncertainty":
+            if log_var is None or tuple(getattr(log_var, "tasks", ())) != tuple(self.enabled):
+                raise ValueError(f"task_weighting uncertainty: log_var must be a TaskLogVariance over the enabled tasks {self.enabled}, "
+                                 f"got {None if log_var is None else tuple(getattr(log_var, 'tasks', ()))}")
+            known = {id(p) for g in self.optimizer.param_groups for p in g["params"]}
+            if id(log_var.log_var) not in known:
+                raise ValueError("task_weighting uncertainty: log_var is not a parameter of the optimizer (train.build_optimizer(log_var=...))")
+        elif log_var is not None:
+            raise ValueError(f"task_weighting {mode}: log_var is for the uncertainty mode")
+        if mode != "none":
+            if not (self.headwise_backward and self.enabled):
+                raise ValueError("task_weighting needs the head-wise backward (headwise_backward) and an enabled task")
+            self._task_scale_host = [1.0] * len(self.enabled)
+        self.task_mode, self.task_log_var = mode, (log_var if mode == "uncertainty" else None)
+        if hasattr(self.optimizer, "task_weighting"):
+            self.optimizer.task_weighting = mode  # (dist.GradSync refuses the sharded update by name)
+
+    def _task_scale_for(self, device):
+        """The scale vector on ``device`` (None when the feature is off), created outside captures."""
+        if self.task_mode == "none":
+            return None
+        sc = self.task_scale
+        if sc is None or sc.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the task-scale vector must exist before a capture (run one eager step first)")
+            sc = self.task_scale = torch.tensor(self._task_scale_host, dtype=torch.float32, device=device)
+        return sc
+
+    def set_task_scale(self, scales: Mapping[str, float]) -> None:
+        """manual mode: task t's share of the objective becomes w_t * scales[t] from the next step on -- eager or replayed, no new
+        capture.  One small asynchronous copy from a fresh pinned buffer on the current stream; tasks not named keep their scale."""
+        if self.task_mode != "manual":
+            raise ValueError(f"set_task_scale: task_weighting.mode is '{self.task_mode}' (manual sets scales from the host)")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_task_scale: not inside a capture (the copy would become a node with today's values)")
+        unknown = [t for t in scales if t not in self.enabled]
+        if unknown:
+            raise ValueError(f"set_task_scale: {unknown} not among the enabled tasks {self.enabled}")
+        for t, v in scales.items():
+            v = float(v)
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"set_task_scale: the scale of {t} must be finite and >= 0, got {v}")
+            self._task_scale_host[self.enabled.index(t)] = v
+        if self.task_scale is not None:
+            host = torch.tensor(self._task_scale_host, dtype=torch.float32)
+            self.task_scale.copy_(host.pin_memory() if self.task_scale.is_cuda else host, non_blocking=True)
+
+    def task_scales(self) -> Dict[str, float]:
+        """{task: the scale the kernels read now} (one device synchronisation; 1.0 each when the feature is off)."""
+        if self.task_scale is None:
+            return {t: (1.0 if self._task_scale_host is None else self._task_scale_host[i]) for i, t in enumerate(self.enabled)}
+        return dict(zip(self.enabled, self.task_scale.tolist()))
+
+    def _task_scale_head(self) -> None:
+        if self.task_mode == "uncertainty":
+            p = self.task_log_var.log_var
+            ops.task_scale_prepare(p.detach(), self._task_scale_for(p.device))
+
+    def _seed_grad(self, key, v, t, coef, scale):
+        """The tensor head ``t``'s backward starts from: the constant ``coef`` filled once -- with a task scale, fl32(coef * scale)
+        filled by one launch per step (egk_fill_scaled_from), and only when the head left the announced-seed paths (a head on
+        them never reads the tensor)."""
+        g = self._coef_grads.get(key)
+        if g is None or g._egk_coef != coef:
+            g = self._coef_grads[key] = torch.full_like(v, coef, dtype=v.dtype).detach()
+            g._egk_coef = coef
+        if scale is not None and not ops.seed_consumed(v):
+            if v.dtype != torch.float32:
+                raise RuntimeError(f"head {t}: a {v.dtype} loss vector cannot start from a scaled seed")
+            ops.fill_scaled_from(g, coef, scale)
+        return g
 
     def _head(self, t: str, feat, d):
         task = self.tasks[t]
@@ -1617,6 +1721,9 @@ class MTLStep(StepBase):
         else:
             specs = {}
 
+        sc_vec = self._task_scale_for(next(iter(leaves.values())).device) if leaves else None
+        sc = {t: (None if sc_vec is None else sc_vec[i:i + 1]) for i, t in enumerate(self.enabled)}  # each task's word of the vector
+
         def head(t, leaf):
             # AR / LTA: one loss element per node, back-propagated below with the constant w_t / numel -- known before the
             # loss is computed, so the cross entropy emits its gradient in the same launch (ops.loss_seed)
@@ -1625,7 +1732,7 @@ class MTLStep(StepBase):
             oscc_one = self._one_pass_oscc_ok(t) and batches[t].y.dim() == 1
             if oscc_one:
                 n_loss = int(batches[t].y.numel())  # one loss element per sequence
-            with ops.loss_seed(self.weights[t] / n_loss if n_loss else None):
+            with ops.loss_seed(self.weights[t] / n_loss if n_loss else None, scale=sc[t]):
                 task, d = self.tasks[t], batches[t]
                 f = leaf if grouped else task.forward_features(leaf)  # grouped: ``leaf`` is the projected feature block
                 one_pass = None
@@ -1649,11 +1756,7 @@ class MTLStep(StepBase):
                 raise RuntimeError(f"head {t}: {n_out} loss elements where {n_loss} were announced to the fused loss")
             if v.numel():
                 # the constant the objective's backward hands this head (w_t / numel): one tensor per task, filled once
-                key = (t, v.numel(), n_out, v.dtype, v.device)
-                g = self._coef_grads.get(key)
-                if g is None or g._egk_coef != self.weights[t] / n_out:
-                    g = self._coef_grads[key] = torch.full_like(v, self.weights[t] / n_out, dtype=v.dtype).detach()
-                    g._egk_coef = self.weights[t] / n_out
+                g = self._seed_grad((t, v.numel(), n_out, v.dtype, v.device), v, t, self.weights[t] / n_out, sc[t])
                 v.backward(gradient=g)
             return full_vector(t, v), logits
         # the multi-head classifier banks of several tasks (AR and LTA: same widths, own rows and weights) as ONE chain of
@@ -1674,20 +1777,17 @@ class MTLStep(StepBase):
                 # (the criteria's class-balance vectors ride in the same launch; without any it is the launch it always was)
                 bal = [self.criteria[t].select_balance(logits) for t, logits in zip(banked, all_logits)]
                 multi = ops.cross_entropy_multi([(s_[0], s_[1]) for s_ in sel], [self.weights[t] / n_loss[t] for t in banked],
-                                                sel[0][2], weights=[w for w, _ in bal], offsets=[a for _, a in bal])
+                                                sel[0][2], weights=[w for w, _ in bal], offsets=[a for _, a in bal],
+                                                scales=None if sc_vec is None else [sc[t] for t in banked])
             for i, (t, logits) in enumerate(zip(banked, all_logits)):
                 if multi is not None:
                     v = multi[i]
                 else:
-                    with ops.loss_seed(self.weights[t] / n_loss[t]):
+                    with ops.loss_seed(self.weights[t] / n_loss[t], scale=sc[t]):
                         v = self.criteria[t](logits, labels[t])
                 if v.numel() != proj_leaves[t].shape[0]:
                     raise RuntimeError(f"head {t}: {v.numel()} loss elements for {proj_leaves[t].shape[0]} rows")
-                key = (t, v.numel(), n_loss[t], v.dtype, v.device)
-                g = self._coef_grads.get(key)
-                if g is None or g._egk_coef != self.weights[t] / n_loss[t]:
-                    g = self._coef_grads[key] = torch.full_like(v, self.weights[t] / n_loss[t], dtype=v.dtype).detach()
-                    g._egk_coef = self.weights[t] / n_loss[t]
+                g = self._seed_grad((t, v.numel(), n_loss[t], v.dtype, v.device), v, t, self.weights[t] / n_loss[t], sc[t])
                 vs.append(v)
                 gs.append(g)
                 banked_vectors[t] = full_vector(t, v)
@@ -1719,9 +1819,24 @@ class MTLStep(StepBase):
                 order = list(self.enabled)
                 total = torch.empty((), dtype=torch.float32, device=next(iter(src.values())).device)
                 acc = self._loss_acc_for(total.device)
-                ops.park_rider(lambda: ops.weighted_mean_sum_into(total, [src.get(t) for t in order], [self.weights[t] for t in order],
-                                                                  [cnt.get(t) for t in order], acc=acc),
-                               (total, *[src[t] for t in order if t in src]))
+                if sc_vec is None:
+                    ops.park_rider(lambda: ops.weighted_mean_sum_into(total, [src.get(t) for t in order], [self.weights[t] for t in order],
+                                                                      [cnt.get(t) for t in order], acc=acc),
+                                   (total, *[src[t] for t in order if t in src]))
+                else:
+                    # with task scales the rider is egk_task_scale_grad: the objective under the scales, the RAW loss sums, and in the
+                    # uncertainty mode d J / d log_var stored into the parameter's gradient slot (its one writer: final with the
+                    # heads' weight gradients it rides beside, before anything reads the heads' region of the flat gradient)
+                    lv = ds = None
+                    if self.task_mode == "uncertainty":
+                        p = self.task_log_var.log_var
+                        lv, ds = p.detach(), ops._grad_slot(p)
+                        if ds is None:  # (the first step, before the flat buffers exist: an ordinary .grad)
+                            ds = p.grad = torch.zeros_like(p)
+                    out1 = total.view(1)
+                    ops.park_rider(lambda: ops.task_scale_grad_into(out1, [src.get(t) for t in order], [self.weights[t] for t in order],
+                                                                    sc_vec, [cnt.get(t) for t in order], log_var=lv, ds=ds, acc=acc),
+                                   (total, *[src[t] for t in order if t in src]))
         return total, vectors, leaves
 
     compact_heads = True  # heads on the labelled rows only (data.live_label_rows); False: every row
@@ -1756,6 +1871,8 @@ class MTLStep(StepBase):
 
     def _backward_pass(self, batches, merged=None):
         if not self.headwise_backward:
+            if self.task_mode != "none":
+                raise RuntimeError("task weighting scales the seeds of the head-wise backward: headwise_backward must stay on")
             return super()._backward_pass(batches, merged)
         self._head_batches = batches
         feats = self.features(batches, merged)
@@ -1777,6 +1894,8 @@ class MTLStep(StepBase):
         if not hasattr(opt, "region_of") or not hasattr(model, "net") or getattr(model, "temporal_pooling", None) is None:
             return None
         head_params = [p for t in self.enabled for p in self.tasks[t].parameters()]
+        if self.task_log_var is not None:  # (the log-variances' slot follows the heads' slots: one region)
+            head_params += list(self.task_log_var.parameters())
         mid_params = list(model.net.parameters())
         mid_ids = {id(p) for p in mid_params}
         trn_params = [p for p in model.parameters() if id(p) not in mid_ids]
@@ -1853,7 +1972,11 @@ class EgoPackStep(StepBase):
 
     def __init__(self, model, tasks: Mapping[str, torch.nn.Module], graphone, weights: Mapping[str, float], optimizer,
                  backprop_temporal_graph: bool = True, temporal_graph_train_mode: bool = False,
-                 sync: Optional[GradSync] = None, fused_backbone: bool = True, parallel_heads: bool = True):
+                 sync: Optional[GradSync] = None, fused_backbone: bool = True, parallel_heads: bool = True,
+                 task_weighting: str = "none"):
+        if str(task_weighting or "none").lower() != "none":
+            raise ValueError(f"task_weighting.mode '{task_weighting}': the EgoPack step trains ONE primary task -- there is no balance "
+                             "between tasks to adjust or learn (task weighting is for the multi-task step of main_temporal.py)")
         self._init_base(model, tasks, weights, optimizer, fused_backbone, sync, parallel_heads)
         self.graphone = graphone
         self.backprop, self.train_mode = backprop_temporal_graph, temporal_graph_train_mode

@@ -2768,23 +2768,43 @@ def _grad_dtype_of(t: torch.Tensor) -> torch.dtype:
     return getattr(t, "_egk_grad_dtype", torch.float32)
 
 
-_loss_seed = {"coef": None}
+_loss_seed = {"coef": None, "scale": None}
 
 
 class loss_seed:
     """``with loss_seed(c):`` -- inside, the caller guarantees that the loss vector computed next is back-propagated with the
     constant gradient ``c`` for every element (the engine's training heads: objective = sum_t w_t * mean(loss_t), so
     c = w_t / numel).  A multi-head cross entropy whose logits come from ``classifier_bank`` then computes loss AND gradient
-    in one launch (egk_ce_fused) and its backward is a no-op."""
+    in one launch (egk_ce_fused) and its backward is a no-op.
+    ``scale`` (optional): a one-element f32 device tensor -- the constant gradient is fl32(c * scale[0]), the product formed inside
+    the launch from the value the tensor holds when the launch RUNS (include/egopack_task_scale.h): a captured step follows a
+    scale that changes between two replays.  Without one the launches are the ones without the argument."""
 
-    def __init__(self, coef):
-        self.coef = coef
+    def __init__(self, coef, scale=None):
+        self.coef, self.scale = coef, (None if coef is None else _scale_arg(scale, "loss_seed"))
 
     def __enter__(self):
-        self.prev, _loss_seed["coef"] = _loss_seed["coef"], self.coef
+        self.prev = (_loss_seed["coef"], _loss_seed["scale"])
+        _loss_seed["coef"], _loss_seed["scale"] = self.coef, self.scale
 
     def __exit__(self, *a):
-        _loss_seed["coef"] = self.prev
+        _loss_seed["coef"], _loss_seed["scale"] = self.prev
+
+
+def seed_consumed(v) -> bool:
+    """The loss vector ``v`` comes straight from a launch that already wrote its gradient from the announced seed (the fused cross
+    entropies, the one-pass heads): its backward never reads the gradient it is handed."""
+    return bool(getattr(getattr(v, "grad_fn", None), "fused", False))
+
+
+def _scale_arg(scale, where):
+    """A task scale as the launches take it: None, or ONE f32 element on a device (a view into the step's scale vector)."""
+    if scale is None:
+        return None
+    if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or not scale.is_cuda:
+        raise ValueError(f"{where}: scale must be a float32 device tensor of one element, got "
+                         f"{(scale.dtype, tuple(scale.shape), str(scale.device)) if torch.is_tensor(scale) else type(scale).__name__}")
+    return scale.detach()
 
 
 def _vp(t):
@@ -2864,9 +2884,10 @@ def _ce_fused_plan(y, logits, from_col0):
     return gbuf, state, starts, [e - s0 for s0, e in zip(starts, ends)]
 
 
-def _ce_fused_launch(tasks, smoothing, bal):
+def _ce_fused_launch(tasks, smoothing, bal, scales=None):
     """ONE launch for the loss vectors AND the gradient operands of ``tasks`` = [(plan, logits, y, coef)]; ``bal``: None (the
-    plain launch), or per task None / the (weights, offsets) of ``_class_balance``.  Returns the loss vectors."""
+    plain launch), or per task None / the (weights, offsets) of ``_class_balance``; ``scales``: None, or one task scale
+    (``_scale_arg``) per task -- the _s launches of include/egopack_task_scale.h.  Returns the loss vectors."""
     lib = _lib.load()
     arr = ((_lib.CETask if bal is None else _lib.CEWTask) * len(tasks))()
     losses = []
@@ -2881,7 +2902,13 @@ def _ce_fused_launch(tasks, smoothing, bal):
         state["filled"].update(starts)
         state["pads"] = True
     dt = _dt(tasks[0][0][0])
-    if bal is None:
+    if scales is not None:
+        sc = (C.c_void_p * len(tasks))(*[t.data_ptr() for t in scales])
+        if bal is None:
+            _ck(lib.egk_ce_fused_multi_s(_stream(), arr, sc, len(tasks), float(smoothing), dt), "egk_ce_fused_multi_s")
+        else:
+            _ck(lib.egk_ce_w_fused_multi_s(_stream(), arr, sc, len(tasks), float(smoothing), dt), "egk_ce_w_fused_multi_s")
+    elif bal is None:
         _ck(lib.egk_ce_fused_multi(_stream(), arr, len(tasks), float(smoothing), dt), "egk_ce_fused_multi")
     else:
         _ck(lib.egk_ce_w_fused_multi(_stream(), arr, len(tasks), float(smoothing), dt), "egk_ce_w_fused_multi")
@@ -2898,7 +2925,9 @@ class _CE(torch.autograd.Function):
         if plan is None:
             return None
         gbuf, starts = plan[0], plan[2]
-        loss, = _ce_fused_launch([(plan, logits, y, seed)], smoothing, None if bal is None else [bal])
+        scale = _loss_seed["scale"]
+        loss, = _ce_fused_launch([(plan, logits, y, seed)], smoothing, None if bal is None else [bal],
+                                 None if scale is None else [scale])
         if starts[0] > 0:
             gbuf[:, :starts[0]].zero_()
         ctx.fused, ctx.shapes, ctx.seed = True, [tuple(l.shape) for l in logits], float(seed)
@@ -2978,8 +3007,9 @@ class _CEMulti(torch.autograd.Function):
     as ONE launch, ``egk_ce_fused_multi``."""
 
     @staticmethod
-    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, *tensors):
+    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, scales, *tensors):
         # bal: None, or one entry per task -- None or the (weights, offsets) of ``_class_balance`` -- the launch with the vectors
+        # scales: None, or one task scale per task -- the launch that multiplies each coef by its scale inside (egk_ce_*_fused_multi_s)
         tasks, shapes, k = [], [], 0
         for i, coef in enumerate(coefs):
             y = tensors[k]
@@ -2987,14 +3017,14 @@ class _CEMulti(torch.autograd.Function):
             k += 1 + heads_per_task[i]
             tasks.append((plans[i], logits, y, coef))
             shapes.append([tuple(l.shape) for l in logits])
-        losses = _ce_fused_launch(tasks, smoothing, bal)
-        ctx.shapes, ctx.heads = shapes, heads_per_task
+        losses = _ce_fused_launch(tasks, smoothing, bal, scales)
+        ctx.shapes, ctx.heads, ctx.fused = shapes, heads_per_task, True
         ctx.set_materialize_grads(False)
         return tuple(losses)
 
     @staticmethod
     def backward(ctx, *glosses):
-        out = [None, None, None, None, None]
+        out = [None, None, None, None, None, None]
         dev = next(g.device for g in glosses if g is not None)
         for shp in ctx.shapes:  # placeholders: the gradients are already in the banks' operand buffers
             out.append(None)  # y
@@ -3002,13 +3032,19 @@ class _CEMulti(torch.autograd.Function):
         return tuple(out)
 
 
-def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None):
+def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None, scales=None):
     """[loss_t] of ``cross_entropy(logits_t, y_t, smoothing)`` for several tasks whose backward seeds ``coefs`` are known, in ONE
     launch that also writes every task's gradient operand -- or None when some task does not qualify for the fused form
     (the caller then takes them one by one).  ``tasks``: [(logits tuple, y [N, heads] int64)].
     ``weights`` / ``offsets``: None, or one entry per task, each what ``cross_entropy`` takes as ``weight`` / ``offset``; with
-    every vector None the launch is the one without the arguments."""
-    for name, arg in (("weights", weights), ("offsets", offsets)):
+    every vector None the launch is the one without the arguments.
+    ``scales``: None, or one one-element f32 device tensor per task: task i's seed is fl32(coefs[i] * scales[i][0]), formed inside
+    the launch (include/egopack_task_scale.h).  None: exactly the launch without the argument."""
+    if scales is not None:
+        if any(sc is None for sc in scales):
+            raise ValueError("cross_entropy_multi: scales has a None entry (every task needs its scale, or pass scales=None)")
+        scales = [_scale_arg(sc, f"cross_entropy_multi (task {i})") for i, sc in enumerate(scales)]
+    for name, arg in (("weights", weights), ("offsets", offsets), ("scales", scales)):
         if arg is not None and len(arg) != len(tasks):
             raise ValueError(f"cross_entropy_multi: {name} has {len(arg)} entries for {len(tasks)} tasks")
     if not (2 <= len(tasks) <= 4) or not torch.is_grad_enabled():
@@ -3030,7 +3066,7 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
         flat += [y, *logits]
     if all(b is None for b in bal):
         bal = None
-    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, *flat))
+    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, scales, *flat))
 
 
 def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None):
@@ -3101,8 +3137,9 @@ class _RowDotBCE(torch.autograd.Function):
     (egk_rowdot_bce): used when the seed of the loss vector's backward is known (``loss_seed``)."""
 
     @staticmethod
-    def forward(ctx, f, W, b, y, seed, shape):
+    def forward(ctx, f, W, b, y, seed, shape, scale=None):
         # shape: None, or the (pos, neg, gamma) of ``bce_shape`` -- the same pass with the shaped loss (egk_rowdot_bce_w)
+        # scale: None, or the task scale the seed is multiplied by inside the pass (egk_rowdot_bce_s / _w_s)
         _need_gpu(f, W, y)
         lib = _lib.load()
         f = _c(f)
@@ -3114,7 +3151,13 @@ class _RowDotBCE(torch.autograd.Function):
         loss = torch.empty(rows, dtype=torch.float32, device=f.device)
         df = torch.empty_like(f)
         ws = torch.empty(lib.egk_rowdot_ws_rows(rows) * (cols + 4), dtype=torch.float32, device=f.device)
-        if shape is None:
+        if scale is not None and shape is None:
+            _ck(lib.egk_rowdot_bce_s(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(ws), rows, cols,
+                                     float(seed), _p(scale), _dt(f)), "egk_rowdot_bce_s")
+        elif scale is not None:
+            _ck(lib.egk_rowdot_bce_w_s(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(ws), rows, cols,
+                                       float(seed), _p(scale), *shape, _dt(f)), "egk_rowdot_bce_w_s")
+        elif shape is None:
             _ck(lib.egk_rowdot_bce(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(ws), rows, cols,
                                    float(seed), _dt(f)), "egk_rowdot_bce")
         else:
@@ -3125,6 +3168,7 @@ class _RowDotBCE(torch.autograd.Function):
         db = (slot_b if slot_b is not None else torch.zeros(b.shape, dtype=torch.float32, device=f.device)) if b is not None else None
         _ck(lib.egk_rowdot_reduce(_stream(), _p(ws), _p(dw), _p(db), rows, cols), "egk_rowdot_reduce")
         ctx.ret = (df, None if slot_w is not None else dw, None if (slot_b is not None or b is None) else db)
+        ctx.fused = True  # (``seed_consumed``)
         ctx.mark_non_differentiable(logits)
         ctx.set_materialize_grads(False)  # (no zero tensor for the logits' absent gradient: a launch of its own)
         return loss, logits
@@ -3133,7 +3177,7 @@ class _RowDotBCE(torch.autograd.Function):
     def backward(ctx, gloss, _glogits):
         df, dw, db = ctx.ret  # computed in forward from the announced seed (the constant weight / numel of the objective)
         ctx.ret = None        # (sole owner of df from here: autograd keeps it as the leaf's gradient instead of cloning it)
-        return df, dw, db, None, None, None
+        return df, dw, db, None, None, None, None
 
 
 def linear1_bce_ok(f, W) -> bool:
@@ -3152,7 +3196,7 @@ def linear1_bce(f, W, b, y, pos=None, neg=None, gamma=None):
         raise RuntimeError("linear1_bce: needs an announced loss seed (ops.loss_seed) and a device feature matrix")
     if y.dtype != torch.int64:
         y = y.to(torch.int64)
-    return _RowDotBCE.apply(f, W, b, y, float(_loss_seed["coef"]), bce_shape(pos, neg, gamma, "linear1_bce"))
+    return _RowDotBCE.apply(f, W, b, y, float(_loss_seed["coef"]), bce_shape(pos, neg, gamma, "linear1_bce"), _loss_seed["scale"])
 
 
 class _RowDotCE2(torch.autograd.Function):
@@ -3160,7 +3204,7 @@ class _RowDotCE2(torch.autograd.Function):
     gradients (egk_rowdot_ce2): used when the seed of the loss vector's backward is known (``loss_seed``)."""
 
     @staticmethod
-    def forward(ctx, f, W, b, y, smoothing, seed):
+    def forward(ctx, f, W, b, y, smoothing, seed, scale=None):
         _need_gpu(f, W, y)
         lib = _lib.load()
         f = _c(f)
@@ -3175,9 +3219,14 @@ class _RowDotCE2(torch.autograd.Function):
         dw = slot_w if slot_w is not None else torch.zeros(W.shape, dtype=torch.float32, device=f.device)
         db = (slot_b if slot_b is not None else torch.zeros(b.shape, dtype=torch.float32, device=f.device)) if b is not None else None
         gws = torch.empty(rows, 2, dtype=torch.float32, device=f.device)
-        _ck(lib.egk_rowdot_ce2(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(dw), _p(db), _p(gws), rows,
-                               cols, float(smoothing), float(seed), _dt(f)), "egk_rowdot_ce2")
+        if scale is None:
+            _ck(lib.egk_rowdot_ce2(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(dw), _p(db), _p(gws), rows,
+                                   cols, float(smoothing), float(seed), _dt(f)), "egk_rowdot_ce2")
+        else:  # the seed's task factor read inside the launch (include/egopack_task_scale.h)
+            _ck(lib.egk_rowdot_ce2_s(_stream(), _p(f), _p(w_op), _p(bias), _p(y), _p(logits), _p(loss), _p(df), _p(dw), _p(db), _p(gws),
+                                     rows, cols, float(smoothing), float(seed), _p(scale), _dt(f)), "egk_rowdot_ce2_s")
         ctx.ret = (df, None if slot_w is not None else dw, None if (slot_b is not None or b is None) else db)
+        ctx.fused = True  # (``seed_consumed``)
         ctx.mark_non_differentiable(logits)
         ctx.set_materialize_grads(False)
         return loss, logits
@@ -3186,14 +3235,15 @@ class _RowDotCE2(torch.autograd.Function):
     def backward(ctx, gloss, _glogits):
         df, dw, db = ctx.ret  # computed in forward from the announced seed (the constant weight / numel of the objective)
         ctx.ret = None
-        return df, dw, db, None, None, None
+        return df, dw, db, None, None, None, None
 
 
 class _RowDotCE2Multi(torch.autograd.Function):
     """``_RowDotCE2`` over n sources with their own classifiers: logits = (mean | sum)_k Linear_k(f_k) (egk_rowdot_ce2_multi)."""
 
     @staticmethod
-    def forward(ctx, y, smoothing, average, seed, n, *tensors):
+    def forward(ctx, y, smoothing, average, seed, scale, n, *tensors):
+        # scale: None, or the task scale the seed is multiplied by inside the row launch (egk_rowdot_ce2_multi_s)
         fs, Ws, bs = tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n]
         _need_gpu(fs[0], y)
         lib = _lib.load()
@@ -3205,7 +3255,7 @@ class _RowDotCE2Multi(torch.autograd.Function):
         dev = fs[0].device
         logits = torch.empty(rows, 2, dtype=torch.float32, device=dev)
         loss = torch.empty(rows, dtype=torch.float32, device=dev)
-        need = ctx.needs_input_grad[5:]
+        need = ctx.needs_input_grad[6:]
         need_f, need_w, need_b = need[:n], need[n:2 * n], need[2 * n:3 * n]
         dfs = [torch.empty_like(f) if nf else None for f, nf in zip(fs, need_f)]
         slots_w, slots_b = [_grad_slot(W) for W in Ws], [_grad_slot(b) for b in bs]
@@ -3217,9 +3267,14 @@ class _RowDotCE2Multi(torch.autograd.Function):
         gws = torch.empty(rows, 2, dtype=torch.float32, device=dev)
 
         def launch(phase):  # (0: both launches; 1: the row launch -- loss, logits, d f; 2: the column launch -- d W, d b)
-            _ck(lib.egk_rowdot_ce2_multi(_stream(), n, arr(fs), arr(w_ops), arr(biases), _p(y), _p(logits), _p(loss), arr(dfs), arr(dws),
-                                         arr(dbs), _p(gws), rows, cols, int(bool(average)) | (phase << 1), float(smoothing), float(seed),
-                                         _dt(fs[0])), "egk_rowdot_ce2_multi")
+            if scale is None:
+                _ck(lib.egk_rowdot_ce2_multi(_stream(), n, arr(fs), arr(w_ops), arr(biases), _p(y), _p(logits), _p(loss), arr(dfs), arr(dws),
+                                             arr(dbs), _p(gws), rows, cols, int(bool(average)) | (phase << 1), float(smoothing), float(seed),
+                                             _dt(fs[0])), "egk_rowdot_ce2_multi")
+            else:
+                _ck(lib.egk_rowdot_ce2_multi_s(_stream(), n, arr(fs), arr(w_ops), arr(biases), _p(y), _p(logits), _p(loss), arr(dfs),
+                                               arr(dws), arr(dbs), _p(gws), rows, cols, int(bool(average)) | (phase << 1), float(smoothing),
+                                               float(seed), _p(scale), _dt(fs[0])), "egk_rowdot_ce2_multi_s")
         in_slots = all((dw is None or sw is not None) for dw, sw in zip(dws, slots_w)) and all(
             (db is None or sb is not None) for db, sb in zip(dbs, slots_b))
         if in_slots and any(d is not None for d in (*dws, *dbs)):
@@ -3233,6 +3288,7 @@ class _RowDotCE2Multi(torch.autograd.Function):
         ctx.keep = (fs, w_ops, biases, gws)
         ctx.ret = (dfs, [None if (sw is not None) else dw for dw, sw in zip(dws, slots_w)],
                    [None if (sb is not None) else db for db, sb in zip(dbs, slots_b)])
+        ctx.fused = True  # (``seed_consumed``)
         ctx.mark_non_differentiable(logits)
         ctx.set_materialize_grads(False)
         return loss, logits
@@ -3241,7 +3297,7 @@ class _RowDotCE2Multi(torch.autograd.Function):
     def backward(ctx, gloss, _glogits):
         dfs, dws, dbs = ctx.ret  # computed in forward from the announced seed
         ctx.ret = ctx.keep = None
-        return (None, None, None, None, None, *dfs, *dws, *dbs)
+        return (None, None, None, None, None, None, *dfs, *dws, *dbs)
 
 
 def linear2_ce_multi(fs, Ws, bs, y, smoothing: float = 0.0, average: bool = False):
@@ -3252,7 +3308,7 @@ def linear2_ce_multi(fs, Ws, bs, y, smoothing: float = 0.0, average: bool = Fals
         raise RuntimeError("linear2_ce_multi: needs an announced loss seed (ops.loss_seed) and 1 .. 4 small device feature matrices")
     if y.dtype != torch.int64:
         y = y.to(torch.int64)
-    return _RowDotCE2Multi.apply(y, float(smoothing), bool(average), float(_loss_seed["coef"]), len(fs), *fs, *Ws, *bs)
+    return _RowDotCE2Multi.apply(y, float(smoothing), bool(average), float(_loss_seed["coef"]), _loss_seed["scale"], len(fs), *fs, *Ws, *bs)
 
 
 def linear2_ce_ok(rows: int, f, W) -> bool:
@@ -3272,7 +3328,7 @@ def linear2_ce(f, W, b, y, smoothing: float = 0.0):
         raise RuntimeError("linear2_ce: needs an announced loss seed (ops.loss_seed) and a small device feature matrix")
     if y.dtype != torch.int64:
         y = y.to(torch.int64)
-    return _RowDotCE2.apply(f, W, b, y, float(smoothing), float(_loss_seed["coef"]))
+    return _RowDotCE2.apply(f, W, b, y, float(smoothing), float(_loss_seed["coef"]), _loss_seed["scale"])
 
 
 class _OneHotSigmoid(torch.autograd.Function):
@@ -3424,6 +3480,57 @@ def weighted_mean_sum_into(out, vectors, weights, counts=None, acc=None):
             raise ValueError("weighted_mean_sum_into: acc must be a contiguous float64 tensor with one element per vector")
         _ck(_lib.load().egk_weighted_sums_acc(_stream(), xs, ns, cf, k, _p(out), _p(acc)), "egk_weighted_sums_acc")
     return out
+
+
+# ---- task weights in device memory (include/egopack_task_scale.h) ------------------------------------------------------------------
+@torch.no_grad()
+def task_scale_prepare(log_var, scale):
+    """scale[t] = exp(-log_var[t]) (f64 inside, rounded to f32 once; exactly 1 for 0): one launch.  Both f32 [n] on a device, n <= 8."""
+    _need_gpu(log_var, scale)
+    if log_var.dtype != torch.float32 or scale.dtype != torch.float32 or log_var.numel() != scale.numel() \
+            or not (log_var.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("task_scale_prepare: log_var and scale must be contiguous float32 tensors of one length")
+    _ck(_lib.load().egk_task_scale_prepare(_stream(), _p(log_var), _p(scale), log_var.numel()), "egk_task_scale_prepare")
+    return scale
+
+
+@torch.no_grad()
+def fill_scaled_from(out, coef, scale):
+    """out[:] = fl32(coef * scale[0]) in one launch: the tensor a head's backward starts from when its seed has a task scale and the
+    head runs off the announced-seed paths.  ``out``: contiguous f32; ``scale``: one f32 element on the same device."""
+    _need_gpu(out, scale)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("fill_scaled_from: out must be a contiguous float32 tensor")
+    _ck(_lib.load().egk_fill_scaled_from(_stream(), _p(out), out.numel(), float(coef), _p(_scale_arg(scale, "fill_scaled_from"))),
+        "egk_fill_scaled_from")
+    return out
+
+
+@torch.no_grad()
+def task_scale_grad_into(objective, vectors, weights, scale, counts=None, log_var=None, ds=None, acc=None):
+    """The rider of a step with task scales, ONE launch (egk_task_scale_grad): with L_t = sum(vectors[t]) / (counts[t] or numel),
+    summed in f64 in a fixed order,
+        objective[0] = sum_t w_t (scale_t L_t + log_var_t)  and  ds[t] = w_t (1 - scale_t L_t)     (``log_var`` given)
+        objective[0] = sum_t w_t  scale_t L_t                                                     (``log_var`` None)
+    over the vectors that are not None and not empty (ds = 0 for the others: a task without a loss element in this step is absent
+    from it -- it adds nothing to the objective and does not move its log-variance), and acc[t] += sum(vectors[t]) -- the RAW per-task sums, as
+    ``weighted_mean_sum_into`` feeds them.  ``scale`` / ``log_var`` / ``ds``: f32 [len(vectors)]; ``acc``: f64 [len(vectors)]."""
+    k = len(vectors)
+    vs = [_f32c(v) if v is not None else None for v in vectors]
+    counts = counts if counts is not None else [None] * k
+    for name, t, dt in (("scale", scale, torch.float32), ("log_var", log_var, torch.float32), ("ds", ds, torch.float32),
+                        ("acc", acc, torch.float64)):
+        if t is not None and (t.dtype != dt or t.numel() < k or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"task_scale_grad_into: {name} must be a contiguous {dt} device tensor with one element per vector")
+    if scale is None or (log_var is not None and ds is None):
+        raise ValueError("task_scale_grad_into: scale is required, and ds with log_var")
+    xs = (C.c_void_p * k)(*[v.data_ptr() if (v is not None and v.numel()) else None for v in vs])
+    ns = (C.c_int64 * k)(*[v.numel() if v is not None else 0 for v in vs])
+    cn = (C.c_int64 * k)(*[0 if c is None else int(c) for c in counts])
+    wf = (C.c_float * k)(*[float(w) for w in weights])
+    _ck(_lib.load().egk_task_scale_grad(_stream(), xs, ns, cn, wf, _vp(log_var), _p(scale), _vp(ds), _p(objective), _vp(acc), k),
+        "egk_task_scale_grad")
+    return objective
 
 
 def weighted_mean_sum(vectors, weights, counts=None):

@@ -82,6 +82,12 @@ def _unique(params):
     return uniq
 
 
+# task weighting: the modes of ``task_weighting.mode`` and the name of the parameter group that holds the log-variances
+# -- the one definition engine.MTLStep, train and dist read
+TASK_WEIGHTING_MODES = ("none", "manual", "uncertainty")
+TASK_WEIGHTING_GROUP = "task_weighting"
+
+
 class FlatOptimizer(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None, layout_order=None,
                  ema_decay=None, ema_warmup=False):
@@ -130,6 +136,7 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.ema_warmup = bool(ema_warmup)
         self.flat_ema = None        # the moving average of flat_p (same layout), with ``ema_decay`` only
         self._ema_swapped = False   # inside ``ema_weights()``: flat_p holds the average, flat_ema the raw weights
+        self.task_weighting = "none"  # the step's task_weighting.mode (engine.MTLStep sets it; dist.GradSync reads it)
 
     @property
     def ema(self) -> bool:
@@ -350,7 +357,9 @@ class FlatOptimizer(torch.optim.Optimizer):
                                 **{k: v.detach().clone() for k, v in zip(self._state_keys, mv)}}
                 i += 1
         if self._pending_state is not None and not state:
-            return self._pending_state
+            # (the loaded state, with THIS optimizer's groups: a state loaded without the trailing task_weighting group must not
+            #  be written back as if this optimizer had none)
+            return {**self._pending_state, "param_groups": groups}
         out = {"state": state, "param_groups": groups}
         if self.ema:
             if self._ema_swapped:
@@ -374,7 +383,15 @@ class FlatOptimizer(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         """Hyper-parameters now; the state now if the flat buffers exist, otherwise when the first step builds them."""
         self._check_state_rule(state_dict)
-        if len(state_dict["param_groups"]) != len(self.param_groups):  # (torch.optim.Optimizer.load_state_dict's message)
+        # A state saved WITHOUT learned task weights loads into an optimizer that has them: it lacks exactly the trailing
+        # ``task_weighting`` group and its parameter (the last index), which then start with fresh moments -- an ``uncertainty`` run
+        # warm-started from a fixed-weight run (train.load_task_weighting says so in its one log line).
+        fresh = []
+        if (len(state_dict["param_groups"]) == len(self.param_groups) - 1
+                and self.param_groups[-1].get("name") == TASK_WEIGHTING_GROUP
+                and sum(len(g["params"]) for g in state_dict["param_groups"]) == len(self._all_params()) - len(self.param_groups[-1]["params"])):
+            fresh = list(self.param_groups[-1]["params"])
+        elif len(state_dict["param_groups"]) != len(self.param_groups):  # (torch.optim.Optimizer.load_state_dict's message)
             raise ValueError("loaded state dict has a different number of parameter groups")
         ema = self._check_ema_state(state_dict)
         for group, pg in zip(self.param_groups, state_dict["param_groups"]):
@@ -401,6 +418,7 @@ class FlatOptimizer(torch.optim.Optimizer):
             # later step of the interrupted run ran on -- a resumed run continues it bit for bit.
             params = self._all_params()
             live = [params[int(i)] for i in state_dict["state"] if int(i) < len(params)]
+            live += [p for p in fresh if live]  # (they join the layout now: their slot follows the heads' slots as in a fresh run)
             if live and all(p.is_cuda and p.requires_grad for p in live):
                 for p in live:
                     if p.grad is None:

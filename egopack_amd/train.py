@@ -13,7 +13,7 @@ from . import data as D
 from . import ops
 from .config import Cfg, compose, instantiate
 from .criterion import BCEWithLogitsNone, CrossEntropyNone, MetricSelectorWrapper
-from .optim import FlatAdam, FlatAdamW, FlatSGD
+from .optim import TASK_WEIGHTING_GROUP, TASK_WEIGHTING_MODES, FlatAdam, FlatAdamW, FlatSGD
 
 logger = logging.getLogger("egopack")
 TASKS = ("ar", "oscc", "lta", "pnr")
@@ -411,6 +411,90 @@ def check_pnr_balance(logger, ckpt: dict, cfg, pnr_balance) -> bool:
     return same
 
 
+# ---- adjustable / learned task weights (``task_weighting:`` of the config; include/egopack_task_scale.h) ---------------
+TASK_WEIGHTING_DEFAULTS = {"mode": "none", "lr_scale": 1.0}
+
+
+def task_weighting_config(cfg) -> dict:
+    """The ``task_weighting:`` block with its defaults filled in; an unknown key or mode is a ValueError that lists the known ones."""
+    raw = cfg.get("task_weighting") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(TASK_WEIGHTING_DEFAULTS)
+    if unknown:
+        raise ValueError(f"task_weighting: unknown key(s) {sorted(unknown)} ({', '.join(TASK_WEIGHTING_DEFAULTS)})")
+    tw = {**TASK_WEIGHTING_DEFAULTS, **raw}
+    tw["mode"] = str(tw["mode"]).lower()
+    if tw["mode"] not in TASK_WEIGHTING_MODES:
+        raise ValueError(f"task_weighting.mode: unknown mode '{tw['mode']}' ({' | '.join(TASK_WEIGHTING_MODES)})")
+    tw["lr_scale"] = float(tw["lr_scale"])
+    if not (tw["lr_scale"] > 0.0 and tw["lr_scale"] < float("inf")):
+        raise ValueError(f"task_weighting.lr_scale: {tw['lr_scale']} is not a finite number > 0")
+    return tw
+
+
+def build_task_weighting(cfg, enabled, device=None):
+    """The models.TaskLogVariance of an ``uncertainty`` run over the enabled tasks (in the step's order), on ``device``; None in
+    the other modes (nothing is built: the optimizer and the launches are the ones without the feature)."""
+    if task_weighting_config(cfg)["mode"] != "uncertainty":
+        return None
+    from .models import TaskLogVariance
+    lv = TaskLogVariance(enabled)
+    return lv.to(device) if device is not None else lv
+
+
+def log_task_weighting(logger, epoch: int, step) -> None:
+    """One line per epoch: s_t and the effective weights w_t exp(-s_t) (uncertainty), or the scales set from the host and
+    w_t scale_t (manual); nothing with the feature off.  One device synchronisation, like ``loss_sums``."""
+    mode = getattr(step, "task_mode", "none")
+    if mode == "uncertainty":
+        eff = step.task_log_var.effective_weights(step.weights)
+        logger.info("epoch %d: task weighting (uncertainty): %s", epoch,
+                    {t: {"s": round(s_, 6), "weight": round(w_, 6)} for t, (s_, w_) in eff.items()})
+    elif mode == "manual":
+        logger.info("epoch %d: task weighting (manual): %s", epoch,
+                    {t: {"scale": round(v, 6), "weight": round(step.weights[t] * v, 6)} for t, v in step.task_scales().items()})
+
+
+def task_weighting_state(cfg, step) -> Optional[dict]:
+    """The checkpoint's top-level ``"task_weighting"`` entry: the config block, the task order and ``log_var`` (uncertainty) or the
+    scales (manual), as f32 tensors on the host; None when off."""
+    mode = getattr(step, "task_mode", "none")
+    if mode == "none":
+        return None
+    out = {"config": task_weighting_config(cfg), "tasks": list(step.enabled)}
+    if mode == "uncertainty":
+        out["log_var"] = step.task_log_var.log_var.detach().float().cpu().clone()
+    else:
+        out["scales"] = torch.tensor([step.task_scales()[t] for t in step.enabled], dtype=torch.float32)
+    return out
+
+
+def load_task_weighting(logger, ckpt: dict, step) -> bool:
+    """On resume: ``log_var`` / the scales of the checkpoint's ``"task_weighting"`` entry go into the step (the optimizer state of
+    ``log_var`` travels in the optimizer's state dict).  A checkpoint without the entry -- or one of another mode or task order --
+    starts from s = 0 / scale 1 with ONE log line; that includes a checkpoint a fixed-weight run wrote with its optimizer state:
+    optim.FlatOptimizer.load_state_dict takes a state that lacks exactly the trailing ``task_weighting`` group and starts its
+    parameter with fresh moments.  Returns whether the entry was taken."""
+    mode = getattr(step, "task_mode", "none")
+    if mode == "none":
+        return False
+    stored = ckpt.get("task_weighting")
+    key = "log_var" if mode == "uncertainty" else "scales"
+    if not stored or list(stored.get("tasks", [])) != list(step.enabled) or stored.get(key) is None:
+        logger.info("task weighting: the checkpoint has no '%s' for the tasks %s (stored: %s): starting from %s", key, list(step.enabled),
+                    None if not stored else {"mode": stored.get("config", {}).get("mode"), "tasks": stored.get("tasks")},
+                    "s = 0 (fresh optimizer moments for log_var)" if mode == "uncertainty" else "scale 1")
+        return False
+    vals = torch.as_tensor(stored[key]).float().reshape(-1)
+    if mode == "uncertainty":
+        with torch.no_grad():
+            p = step.task_log_var.log_var
+            p.copy_(vals.to(p.device))
+    else:
+        step.set_task_scale(dict(zip(step.enabled, vals.tolist())))
+    return True
+
+
 OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
 
 
@@ -464,11 +548,14 @@ def log_param_groups(logger, optimizer) -> None:
                     len(g["params"]), sum(p.numel() for p in g["params"]), g["lr"], g.get("weight_decay", 0.0))
 
 
-def build_optimizer(cfg, params, layout_order=None):
+def build_optimizer(cfg, params, layout_order=None, log_var=None):
     """``_target_: torch.optim.Adam | AdamW | SGD`` of the config is served by the flat-buffer optimizer of the same rule (same
     arithmetic, same keyword arguments); ``torch.optim.Adam`` with ``decoupled_weight_decay: true`` is AdamW's rule.
     ``params``: a parameter list or the group dicts of ``build_param_groups``; ``layout_order``: with groups, the flat list they
-    were cut from -- the flat buffers keep its order (optim.FlatOptimizer)."""
+    were cut from -- the flat buffers keep its order (optim.FlatOptimizer).
+    ``log_var`` (``build_task_weighting``; None: nothing changes): its parameter becomes the LAST parameter, in a group of its own
+    named ``task_weighting`` with weight_decay 0 and lr = optimizer.lr * task_weighting.lr_scale, through the parameter-group
+    table; its slot follows the heads' slots in the flat buffers and is clipped and exchanged like any slot."""
     ocfg = dict(cfg.optimizer)
     target = ocfg.pop("_target_")
     if target not in OPTIMIZERS:
@@ -479,6 +566,14 @@ def build_optimizer(cfg, params, layout_order=None):
         ocfg.setdefault("weight_decay", 0.0)  # (torch.optim.Adam's default, not AdamW's)
     # (``grad_clip_norm`` sits beside ``optimizer:``, not inside it: that block is handed to Hydra's instantiate by the reference)
     grouped = bool(params) and isinstance(params[0], dict)
+    if log_var is not None:
+        own = list(log_var.parameters())
+        flat = [p for g in params for p in g["params"]] if grouped else list(params)
+        layout_order = [*(layout_order if (grouped and layout_order is not None) else flat), *own]
+        params = [*(params if grouped else [{"params": flat, "name": "all"}]),
+                  {"params": own, "name": TASK_WEIGHTING_GROUP, "lr": float(cfg.optimizer.lr) * task_weighting_config(cfg)["lr_scale"],
+                   "weight_decay": 0.0}]
+        grouped = True
     extra = {"layout_order": layout_order} if grouped and layout_order is not None else {}
     # (``ema:`` sits beside ``optimizer:`` for the same reason; decay 0 = off)
     ema = dict(cfg.get("ema") or {})
@@ -555,7 +650,8 @@ def ema_checkpoint_path(path: Path) -> Path:
 
 
 def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimizer=None, scheduler=None, loaders=None,
-                    save_ema: bool = False, class_balance: Optional[dict] = None, pnr_balance: Optional[dict] = None):
+                    save_ema: bool = False, class_balance: Optional[dict] = None, pnr_balance: Optional[dict] = None,
+                    task_weighting: Optional[dict] = None):
     """Reference key layout (main_temporal.py:410-417, main_egopack.py:453-460) + what the reference does not keep and
     a resumed run needs: the optimiser state (torch.optim.Adam's per-parameter layout) and the schedule state.
     ``save_ema`` (``ema.save`` of the config; an optimizer that keeps a weight average): a second file beside it,
@@ -563,7 +659,8 @@ def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimiz
     modules' state dicts taken inside ``optimizer.ema_weights()``; any loader of the reference's layout and ``resume_from=``
     take it as it is.  The ordinary file keeps the raw weights and the average under the optimizer's ``"ema"`` key.
     ``class_balance`` (``class_balance_state``; None when off): stored under the top-level key ``"class_balance"``;
-    ``pnr_balance`` (``pnr_balance_state``) likewise under ``"pnr_balance"``."""
+    ``pnr_balance`` (``pnr_balance_state``) likewise under ``"pnr_balance"``, ``task_weighting`` (``task_weighting_state``) under
+    ``"task_weighting"``."""
     path.parent.mkdir(parents=True, exist_ok=True)
     if save_ema and getattr(optimizer, "ema", False):
         with optimizer.ema_weights():
@@ -582,6 +679,8 @@ def save_checkpoint(path: Path, model, tasks, epoch: int, graphone=None, optimiz
         ckpt["class_balance"] = class_balance
     if pnr_balance is not None:
         ckpt["pnr_balance"] = pnr_balance
+    if task_weighting is not None:
+        ckpt["task_weighting"] = task_weighting
     if loaders is not None:  # shuffle generators of the training loaders + dropout streams: exact continuation
         ckpt["rng"] = {"loaders": {t: dl.state_dict() for t, dl in loaders.items() if hasattr(dl, "state_dict")},
                        "dropout": ops.get_rng_state(), "torch": torch.get_rng_state()}

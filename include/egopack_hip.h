@@ -755,5 +755,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 #include "egopack_ce_balanced.h"
 /* BCE-with-logits with a class factor per label value and a focal exponent applied inside the pass (egk_bce_w_fwd / _bwd, egk_rowdot_bce_w) */
 #include "egopack_bce_balanced.h"
+/* the task factor of a head's backward seed read from device memory: adjustable and learned task weights (the _s head launches,
+ * egk_task_scale_prepare / _grad, egk_fill_scaled_from) */
+#include "egopack_task_scale.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -160,7 +160,8 @@ def main(argv=None):
     sync = edist.GradSync(world) if world > 1 else None
     step = engine.EgoPackStep(model, tasks, graphone, weights, optimizer,
                               backprop_temporal_graph=cfg.backprop_temporal_graph,
-                              temporal_graph_train_mode=cfg.temporal_graph_train_mode, sync=sync)
+                              temporal_graph_train_mode=cfg.temporal_graph_train_mode, sync=sync,
+                              task_weighting=T.task_weighting_config(cfg)["mode"])  # (any mode but none: a ValueError that says why)
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))
     for epoch in range(1, cfg.num_epochs + 1):

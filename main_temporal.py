@@ -63,6 +63,7 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
     logger.info("epoch %d: %d iterations, train loss %s", epoch, it,
                 {t: round(s_ / max(n_, 1), 4) for t, (s_, n_) in step.loss_sums().items() if n_})
     T.log_grad_norms(logger, epoch, step)
+    T.log_task_weighting(logger, epoch, step)  # (s_t and w_t exp(-s_t), or the manual scales; nothing with the feature off)
     lc = getattr(step, "loop_counts", None)
     if lc is not None:  # how many steps replayed the captured graph and how many ran eagerly (shape changes, warm-up)
         logger.info("epoch %d: %d steps replayed the captured step, %d ran eagerly", epoch, lc["replayed"], lc["eager"])
@@ -154,7 +155,12 @@ def main(argv=None):
     if world > 1:
         for p in params:  # same start everywhere (seeded identically; broadcast makes it unconditional)
             torch.distributed.broadcast(p.data, src=0)
-    optimizer = T.build_optimizer(cfg, T.build_param_groups(cfg, model, tasks), layout_order=params)
+    # task_weighting: the balance between the tasks, adjustable (manual) or learned (uncertainty) inside the captured step
+    tw_mode = T.task_weighting_config(cfg)["mode"]
+    log_var = T.build_task_weighting(cfg, [t for t in engine.MTLStep.order if weights.get(t, 0) > 0 and t in tasks], device)
+    if world > 1 and log_var is not None:
+        torch.distributed.broadcast(log_var.log_var.data, src=0)
+    optimizer = T.build_optimizer(cfg, T.build_param_groups(cfg, model, tasks), layout_order=params, log_var=log_var)
     T.log_param_groups(logger, optimizer)
     scheduler = T.build_scheduler(cfg, optimizer)
     compress = str(cfg.get("grad_compress", "none"))  # element type of the gradient all-reduce: none (f32) | bf16
@@ -172,7 +178,7 @@ def main(argv=None):
     pnr_balance = T.build_pnr_balance(cfg, dsets_train, tasks=[t for t, w in weights.items() if w > 0])
     T.log_pnr_balance(logger, cfg, pnr_balance)
     step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train, balance, pnr_balance), weights, optimizer,
-                          fused_backbone=cfg.fused_backbone, sync=sync)
+                          fused_backbone=cfg.fused_backbone, sync=sync, task_weighting=tw_mode, log_var=log_var)
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))  # several ranks: graph-LN statistics over the GLOBAL batch
 
@@ -184,6 +190,7 @@ def main(argv=None):
         first_epoch = int(ck.get("epoch", 0)) + 1
         T.check_class_balance(logger, ck, cfg, balance)  # (rebuilt above; compared bit for bit with the stored vectors)
         T.check_pnr_balance(logger, ck, cfg, pnr_balance)  # (likewise the PNR scalars)
+        T.load_task_weighting(logger, ck, step)  # (log_var / the manual scales; without the entry: s = 0, one log line)
         logger.info("resumed from %s at epoch %d", cfg.resume_from, first_epoch)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
@@ -195,7 +202,7 @@ def main(argv=None):
         if cfg.save_model and cfg.get("save_every", 0) and epoch % cfg.save_every == 0 and rank == 0:
             T.save_checkpoint(ckpt_path, model, tasks, epoch, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
                               save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance),
-                              pnr_balance=T.pnr_balance_state(cfg, pnr_balance))
+                              pnr_balance=T.pnr_balance_state(cfg, pnr_balance), task_weighting=T.task_weighting_state(cfg, step))
         if epoch >= cfg.num_epochs - 5:  # all ranks: the validation split is sharded by batch
             T.log_validation_weights(logger, cfg, optimizer, epoch)
             with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
@@ -210,7 +217,7 @@ def main(argv=None):
     if cfg.save_model and rank == 0:
         T.save_checkpoint(ckpt_path, model, tasks, cfg.num_epochs, optimizer=optimizer, scheduler=scheduler, loaders=dl_train,
                           save_ema=T.ema_saved(cfg), class_balance=T.class_balance_state(cfg, balance),
-                          pnr_balance=T.pnr_balance_state(cfg, pnr_balance))
+                          pnr_balance=T.pnr_balance_state(cfg, pnr_balance), task_weighting=T.task_weighting_state(cfg, step))
     if world > 1:
         torch.distributed.destroy_process_group()
     # (callers that drive main() from Python -- the tests -- get the last validation metrics and the trained modules)
