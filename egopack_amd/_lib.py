@@ -26,6 +26,7 @@ EMA_HEADER = HERE.parent / "include" / "egopack_ema.h"  # likewise; its symbols:
 CE_BALANCED_HEADER = HERE.parent / "include" / "egopack_ce_balanced.h"  # likewise; its symbols: CE_BALANCED_SIGNATURES
 BCE_BALANCED_HEADER = HERE.parent / "include" / "egopack_bce_balanced.h"  # likewise; its symbols: BCE_BALANCED_SIGNATURES
 TASK_SCALE_HEADER = HERE.parent / "include" / "egopack_task_scale.h"  # likewise; its symbols: TASK_SCALE_SIGNATURES
+SAMPLE_HEADER = HERE.parent / "include" / "egopack_sample.h"  # likewise; its symbols: SAMPLE_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -112,6 +113,13 @@ class EmaDesc(C.Structure):
     _fields_ = [("ema", vp), ("decay", C.c_double), ("warmup", i32)]
 
 
+class SampleTask(C.Structure):
+    """struct egk_sample_task (include/egopack_sample.h): one head of a categorical-sampling launch."""
+    _fields_ = [("logits", vp), ("ld", i64), ("C", i32), ("head", i32), ("out", vp), ("out_row_stride", i64), ("out_k_stride", i64),
+                ("lo", vp), ("hi", vp), ("total", vp)]
+
+
+SAMPLE_MAX_TASKS, SAMPLE_MAX_K = 8, 1024  # EGK_SAMPLE_MAX_* (include/egopack_sample.h)
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
 
 # name -> (restype, argtypes); mirrors include/egopack_hip.h one to one
@@ -279,6 +287,12 @@ TASK_SCALE_SIGNATURES = {
 }
 
 
+# ... and include/egopack_sample.h (the eighth ledger: tests/test_lta_sampling_cpu.py over tests/test_gpu_bounds_lta_sampling.py)
+SAMPLE_SIGNATURES = {
+    "egk_categorical_sample": (C.c_int, [vp, C.POINTER(SampleTask), i32, i32, i32, u64, i64, i64, i32]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -320,6 +334,11 @@ def task_scale_header_symbols() -> list:
     return _declared(TASK_SCALE_HEADER)
 
 
+def sample_header_symbols() -> list:
+    """Every function name declared in include/egopack_sample.h."""
+    return _declared(SAMPLE_HEADER)
+
+
 _lib = None
 
 
@@ -335,7 +354,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
                               *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items(),
-                              *TASK_SCALE_SIGNATURES.items()]:
+                              *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -110,6 +110,7 @@ enum KernelId {
     KID_CE_BALANCED,       // egk_ce_w_fwd / _bwd / _fused_multi: cross entropy with per-class weights and logit offsets (loss.hip)
     KID_BCE_BALANCED,      // egk_bce_w_fwd / _bwd, egk_rowdot_bce_w: BCE-with-logits with class factors and a focal exponent (loss.hip, norm_ops.hip)
     KID_TASK_SCALE,        // the entry points of include/egopack_task_scale.h: the _s head launches, prepare, grad, fill (loss.hip, norm_ops.hip, loss_optim.hip)
+    KID_CATEGORICAL_SAMPLE, // egk_categorical_sample: K seeded categorical samples per logits row, all heads in one launch (sample.hip)
     KID_COUNT
 };
 

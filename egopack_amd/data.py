@@ -85,6 +85,10 @@ class LazyData(Data):
             raise AttributeError(name) from None
 
 
+# Plain attributes of a batch that describe its VALUES, not its shape (``ordinal``: the batch's index in the single-process batch
+# order, data.BatchLoader): a captured step bakes nothing of them, so they are part of no layout or capture signature.
+VALUE_FIELDS = (".ordinal",)
+
 HEAVY_DEGREE = 24  # = egk_csr_heavy_threshold() (tests/test_cabi.py checks the two agree)
 HEAVY_IN_LAUNCH_DEGREE = 64  # listed rows up to this many edges: one workgroup each inside the gather launch (heavy_mode 1)
 
@@ -696,7 +700,7 @@ def to_device_packed(datas: Sequence["Data"], device, non_blocking: bool = True,
             return ("dc", v, {f.name: walk(getattr(v, f.name), f"{path}.{f.name}") for f in fields(v)})
         if isinstance(v, (list, tuple)) and v and all(torch.is_tensor(t) for t in v):
             return ("l", v, [walk(t, f"{path}[{i}]") for i, t in enumerate(v)])
-        if isinstance(v, (int, float, bool, str)) and "._" not in path:
+        if isinstance(v, (int, float, bool, str)) and "._" not in path and not path.endswith(VALUE_FIELDS):
             sig.append((path, v))
         elif (isinstance(v, (list, tuple)) and "._" not in path
               and all(isinstance(e, (int, float, bool, str)) for e in v)):
@@ -883,7 +887,9 @@ class BatchLoader:
     def load_state_dict(self, state: dict) -> None:
         self.gen.set_state(state["generator"].cpu())  # (a checkpoint loaded with map_location=device moved it)
 
-    def _chunks(self):
+    def _numbered_chunks(self):
+        """(b, chunk): ``b`` counts the batches cut from this rank's index list BEFORE the rank filter of shard="batches" -- there
+        the index of the batch in the single-process batch order, the same on every rank that gets it."""
         idx = self._indices()
         by_batch = self.world_size > 1 and self.shard == "batches"
         for b, i in enumerate(range(0, len(idx), self.batch_size)):
@@ -892,14 +898,25 @@ class BatchLoader:
                 return
             if by_batch and b % self.world_size != self.rank:
                 continue
+            yield b, chunk
+
+    def _chunks(self):
+        for _, chunk in self._numbered_chunks():
             yield chunk
+
+    @staticmethod
+    def _stamp(batch, ordinal: int):
+        """``batch.ordinal``: a plain int (no tensor; ``Data.to`` and the collation processes carry it along, VALUE_FIELDS keeps it
+        out of the signatures).  The seeded LTA sampler keys its draws by it (validate.validate_lta)."""
+        batch.ordinal = int(ordinal)
+        return batch
 
     def __iter__(self):
         if self.workers > 0:
             yield from self._iter_workers()
             return
-        for chunk in self._chunks():
-            b = collate_chunk(self.dataset, chunk)
+        for ordinal, chunk in self._numbered_chunks():
+            b = self._stamp(collate_chunk(self.dataset, chunk), ordinal)
             yield b.pin_memory() if self.pin_memory else b
 
     # -- worker processes (opt-in: ``workers`` > 0) ------------------------------------------------------------------
@@ -931,15 +948,17 @@ class BatchLoader:
         self._epoch = getattr(self, "_epoch", -1) + 1
         pending = collections.deque()
         try:
-            for n, chunk in enumerate(self._chunks()):
+            for n, (ordinal, chunk) in enumerate(self._numbered_chunks()):
                 # the sampling stream of a chunk is a function of (loader seed, epoch, chunk index): the batches do not
                 # depend on which worker builds them
-                pending.append(self._pool.apply_async(_worker_collate, (chunk, (self.seed, self._epoch, n))))
+                pending.append((ordinal, self._pool.apply_async(_worker_collate, (chunk, (self.seed, self._epoch, n)))))
                 if len(pending) >= 2 * self.workers:
-                    b = unpack_data(*pending.popleft().get(timeout=300))
+                    ordinal_, res = pending.popleft()
+                    b = self._stamp(unpack_data(*res.get(timeout=300)), ordinal_)
                     yield b.pin_memory() if self.pin_memory else b
             while pending:
-                b = unpack_data(*pending.popleft().get(timeout=300))
+                ordinal_, res = pending.popleft()
+                b = self._stamp(unpack_data(*res.get(timeout=300)), ordinal_)
                 yield b.pin_memory() if self.pin_memory else b
         finally:
             if pending:  # the consumer stopped early: drop the in-flight work with its processes (a new pool next time)

@@ -331,7 +331,7 @@ def _walk(obj, prefix=""):
 
 # Edge-sized arrays live in the static buffers of a captured step at a CAPACITY (data.EDGE_FIELDS / EDGE_BUCKET): the LTA edge
 # count moves by a few entries from batch to batch, no kernel takes E, and the signature compares capacities.
-from .data import EDGE_BUCKET, EDGE_FIELDS, edge_capacity as _edge_capacity  # noqa: E402
+from .data import EDGE_BUCKET, EDGE_FIELDS, VALUE_FIELDS, edge_capacity as _edge_capacity  # noqa: E402
 
 
 def _is_edge_field(path: str) -> bool:
@@ -346,6 +346,8 @@ def batch_signature(batches: Mapping[str, Data], merged=None) -> tuple:
     for name, obj in [*sorted(batches.items()), ("merged", merged)]:
         for path, v in _walk(obj, name):
             if "._" in path or (torch.is_tensor(v) and v.dim() >= 1 and path.endswith(".x_base")):  # (x_base aliases x)
+                continue
+            if path.endswith(VALUE_FIELDS):  # (the batch ordinal: a value, baked into nothing)
                 continue
             if torch.is_tensor(v):
                 shape = tuple(v.shape)

@@ -3872,6 +3872,62 @@ def scatter_add_rows_f64(x, label, bank, count, groups=None):
                                             seg_label.numel(), x.shape[1], bank.shape[0], _dt(x)), "egk_segment_sum_rows_f64")
 
 
+# ---- seeded categorical sampling (include/egopack_sample.h) -----------------------------------------------------------
+# The sampler's Philox KEY is the user's seed XOR this constant ("LTA_SAMP" in ASCII).  The dropout kernels use the process seed
+# itself as their key (``manual_seed``): with one seed for both, the two consumers hold different keys and never draw the same
+# (key, counter) pair, whatever their counters are.
+SAMPLER_KEY_SALT = 0x4C54415F53414D50
+
+
+def sampler_key(seed: int) -> int:
+    """The Philox key of ``categorical_sample_multi`` for a user seed."""
+    return (int(seed) ^ SAMPLER_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
+
+
+@torch.no_grad()
+def categorical_sample_multi(logits_list, K: int, seed: int, ordinal: int, row0: int = 0, debug: bool = False):
+    """K samples per row from softmax(logits[row]) for every head of ``logits_list`` ([N, C_h] f32 or bf16, one N) in ONE launch:
+    a list of int64 [N, K].  Sample k of row r of head h is a function of (seed, ordinal, row0 + r, h, k) alone -- ``ordinal``: the
+    batch's index in the single-process batch order, ``h``: the head's position in the list.  Rows with a NaN or without a finite
+    maximum come back as -1.  ``debug``: also a list of (lo, hi, total) per head, f32 [N, K] (the bracket of the prefix sums that
+    selected each sample).  Views with a unit class stride are read in place through their row stride."""
+    if not 1 <= len(logits_list) <= _lib.SAMPLE_MAX_TASKS:
+        raise ValueError(f"categorical_sample_multi: 1 .. {_lib.SAMPLE_MAX_TASKS} heads (got {len(logits_list)})")
+    _need_gpu(*logits_list)
+    if any(l.dim() != 2 or l.shape[0] != logits_list[0].shape[0] for l in logits_list):
+        raise ValueError(f"categorical_sample_multi: heads of [N, C_h] with one N (got {[tuple(l.shape) for l in logits_list]})")
+    if len({l.dtype for l in logits_list}) > 1:  # (one element type per launch; a bf16 head and its widening give the same samples)
+        logits_list = [cast_raw(_c(l), torch.float32) for l in logits_list]
+    logits_list = [_rm(l) for l in logits_list]
+    N, dev = logits_list[0].shape[0], logits_list[0].device
+    if not 1 <= int(K) <= _lib.SAMPLE_MAX_K:
+        raise RuntimeError(f"categorical_sample_multi: K in 1 .. {_lib.SAMPLE_MAX_K} (got {K})")
+    outs = [torch.empty((N, K), dtype=torch.int64, device=dev) for _ in logits_list]
+    dbg = [tuple(torch.empty((N, K), dtype=torch.float32, device=dev) for _ in range(3)) for _ in logits_list] if debug else None
+    if N == 0:  # (no rows: nothing to launch, and an empty tensor has no pointer to hand over)
+        return (outs, dbg) if debug else outs
+    tasks = (_lib.SampleTask * len(logits_list))()
+    for h, (t, l, o) in enumerate(zip(tasks, logits_list, outs)):
+        t.logits, t.ld, t.C, t.head = _p(l), max(l.stride(0), l.shape[1]), l.shape[1], h  # (a one-row tensor's stride is arbitrary)
+        t.out, t.out_row_stride, t.out_k_stride = _p(o), K, 1
+        if debug:
+            t.lo, t.hi, t.total = (_p(d) for d in dbg[h])
+    _ck(_lib.load().egk_categorical_sample(_stream(), tasks, len(logits_list), N, int(K), sampler_key(seed), int(ordinal), int(row0),
+                                           _dt(logits_list[0])), "egk_categorical_sample")
+    return (outs, dbg) if debug else outs
+
+
+class FutureSampler:
+    """The seeded sampler of the LTA futures (``lta_sampling.mode=philox``): stateless -- nothing to checkpoint, the samples of a
+    batch depend on (seed, the batch's ordinal, row, head, k) alone."""
+
+    def __init__(self, seed: int = 0):
+        self.seed = int(seed)
+
+    def __call__(self, logits, K: int, ordinal: int, row0: int = 0):
+        return categorical_sample_multi(list(logits), K, self.seed, ordinal, row0)
+
+
 # ---- phase stamps (development) ---------------------------------------------------------------------------------
 _stamps = {"buf": None, "names": []}
 

@@ -432,6 +432,37 @@ def task_weighting_config(cfg) -> dict:
     return tw
 
 
+# ---- the seeded sampler of the LTA futures (``lta_sampling:`` of the config; include/egopack_sample.h) ------------------
+LTA_SAMPLING_DEFAULTS = {"mode": "torch", "seed": 0}
+LTA_SAMPLING_MODES = ("torch", "philox")
+
+
+def lta_sampling_config(cfg) -> dict:
+    """The ``lta_sampling:`` block with its defaults filled in; an unknown key or mode is a ValueError that lists the known ones."""
+    raw = cfg.get("lta_sampling") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(LTA_SAMPLING_DEFAULTS)
+    if unknown:
+        raise ValueError(f"lta_sampling: unknown key(s) {sorted(unknown)} ({', '.join(LTA_SAMPLING_DEFAULTS)})")
+    ls = {**LTA_SAMPLING_DEFAULTS, **raw}
+    ls["mode"] = str(ls["mode"]).lower()
+    if ls["mode"] not in LTA_SAMPLING_MODES:
+        raise ValueError(f"lta_sampling.mode: unknown mode '{ls['mode']}' ({' | '.join(LTA_SAMPLING_MODES)})")
+    if isinstance(ls["seed"], bool) or not isinstance(ls["seed"], int) or not 0 <= ls["seed"] < 2 ** 64:
+        raise ValueError(f"lta_sampling.seed: {ls['seed']!r} is not an integer in [0, 2^64)")
+    return ls
+
+
+def build_lta_sampler(cfg):
+    """The ``ops.FutureSampler`` of ``lta_sampling.mode=philox`` (stateless: nothing of it goes into a checkpoint); None with
+    ``mode: torch`` -- the validation loop then samples with torch's generator, as the reference does."""
+    ls = lta_sampling_config(cfg)
+    if ls["mode"] != "philox":
+        return None
+    from .ops import FutureSampler
+    return FutureSampler(ls["seed"])
+
+
 def build_task_weighting(cfg, enabled, device=None):
     """The models.TaskLogVariance of an ``uncertainty`` run over the enabled tasks (in the step's order), on ``device``; None in
     the other modes (nothing is built: the optimizer and the launches are the ones without the feature)."""

@@ -87,13 +87,19 @@ def validate(epoch, temporal_graph_model, dataloader, meter, primary_task, other
 
 @torch.no_grad()
 def validate_lta(temporal_graph_model, dataloader, meter, primary_task, other_tasks: Optional[List] = None, graphone=None,
-                 late_fusion: bool = False, device: str = "cuda"):
+                 late_fusion: bool = False, device: str = "cuda", sampler=None):
+    """``sampler`` (``ops.FutureSampler``, ``lta_sampling.mode=philox``): the K futures of a batch come from one seeded launch keyed
+    by the batch's ``ordinal`` (its index in the single-process batch order, stamped by data.BatchLoader), so every rank draws
+    what the single pass draws for that batch.  None: torch's generator."""
     other_tasks = other_tasks or []
     _eval_mode(temporal_graph_model, primary_task, other_tasks, graphone)
     for data in dataloader:
         data = data.to(device)
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
-        predictions, logits = primary_task.generate_from_logits(logits)
+        if sampler is not None:
+            predictions, logits = primary_task.generate_from_logits(logits, sampler=sampler, ordinal=getattr(data, "ordinal", None))
+        else:
+            predictions, logits = primary_task.generate_from_logits(logits)
         loss = primary_task.compute_loss(logits, data.y).mean()
         meter.update(logits, data.y, predictions, loss)
 

@@ -758,5 +758,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* the task factor of a head's backward seed read from device memory: adjustable and learned task weights (the _s head launches,
  * egk_task_scale_prepare / _grad, egk_fill_scaled_from) */
 #include "egopack_task_scale.h"
+/* K seeded categorical samples per logits row from the counter-based Philox stream, all heads in one launch: the futures of the LTA
+ * head (egk_categorical_sample) */
+#include "egopack_sample.h"
 
 #endif /* EGOPACK_HIP_H */

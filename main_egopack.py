@@ -35,8 +35,9 @@ AUX_ORDER = {"ar": ("lta", "oscc", "pnr"), "oscc": ("ar", "lta", "pnr"), "lta": 
 
 
 def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders, late_fusion=True, validate_all=False,
-                     device="cuda"):
-    """Task metrics with the GraphONE interaction for the novel task(s) (reference main_egopack.py:374-448)."""
+                     device="cuda", sampler=None):
+    """Task metrics with the GraphONE interaction for the novel task(s) (reference main_egopack.py:374-448).  ``sampler``: the
+    seeded sampler of the LTA futures (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator."""
     out = {}
     for t in ("ar", "oscc", "lta", "pnr"):
         if not (validate_all or weights.get(t, 0) > 0):
@@ -46,7 +47,7 @@ def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders,
         g1 = graphone if is_egopack else None
         meter = build_meter_for_dataset(dsets_val[t], device=device)
         if t == "lta":
-            validate_lta(model, loaders[t], meter, tasks[t], others, g1, late_fusion=late_fusion, device=device)
+            validate_lta(model, loaders[t], meter, tasks[t], others, g1, late_fusion=late_fusion, device=device, sampler=sampler)
         elif t == "pnr":
             validate_pnr(model, loaders[t], meter, tasks[t], others, g1, late_fusion=late_fusion, device=device)
         else:
@@ -164,13 +165,14 @@ def main(argv=None):
                               task_weighting=T.task_weighting_config(cfg)["mode"])  # (any mode but none: a ValueError that says why)
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))
+    sampler = T.build_lta_sampler(cfg)  # (lta_sampling.mode=philox: the LTA futures from the seeded launch; None: torch's generator)
     for epoch in range(1, cfg.num_epochs + 1):
         train(epoch, step, dl_train, weights, device, store=store)
         scheduler.step()
         T.log_validation_weights(logger, cfg, optimizer, epoch)
         with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
             validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, dl_val, late_fusion=cfg.late_fusion,
-                             validate_all=cfg.validate_all_tasks, device=device)  # all ranks: the split is sharded by batch
+                             validate_all=cfg.validate_all_tasks, device=device, sampler=sampler)  # all ranks: the split is sharded by batch
     if cfg.save_model and step.sync is not None:
         step.sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
     if cfg.save_model and rank == 0:

@@ -93,13 +93,14 @@ def validate_losses(step: engine.MTLStep, loaders, device="cuda"):
     return out
 
 
-def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="cuda"):
-    """Task metrics of every enabled task (reference main_temporal.py:340-400)."""
+def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="cuda", sampler=None):
+    """Task metrics of every enabled task (reference main_temporal.py:340-400).  ``sampler``: the seeded sampler of the LTA futures
+    (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator."""
     out = {}
     for t in enabled:
         meter = build_meter_for_dataset(dsets_val[t], device=device)
         if t == "lta":
-            validate_lta(model, loaders[t], meter, tasks[t], device=device)
+            validate_lta(model, loaders[t], meter, tasks[t], device=device, sampler=sampler)
         elif t == "pnr":
             validate_pnr(model, loaders[t], meter, tasks[t], device=device)
         else:
@@ -192,6 +193,7 @@ def main(argv=None):
         T.check_pnr_balance(logger, ck, cfg, pnr_balance)  # (likewise the PNR scalars)
         T.load_task_weighting(logger, ck, step)  # (log_var / the manual scales; without the entry: s = 0, one log line)
         logger.info("resumed from %s at epoch %d", cfg.resume_from, first_epoch)
+    sampler = T.build_lta_sampler(cfg)  # (lta_sampling.mode=philox: the LTA futures from the seeded launch; None: torch's generator)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
         train(epoch, step, dl_train, weights, device, store=store)
@@ -207,11 +209,11 @@ def main(argv=None):
             T.log_validation_weights(logger, cfg, optimizer, epoch)
             with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
                 logger.info("validation losses: %s", validate_losses(step, dl_val, device))
-                metrics = validate_metrics(epoch, model, tasks, step.enabled, dsets_val, dl_val, device)
+                metrics = validate_metrics(epoch, model, tasks, step.enabled, dsets_val, dl_val, device, sampler=sampler)
     if cfg.num_epochs < first_epoch and cfg.get("validate_untrained", False):  # (num_epochs=0: metrics of the initial state)
         T.log_validation_weights(logger, cfg, optimizer, 0)
         with T.ema_scope(cfg, optimizer):
-            metrics = validate_metrics(0, model, tasks, step.enabled, dsets_val, dl_val, device)
+            metrics = validate_metrics(0, model, tasks, step.enabled, dsets_val, dl_val, device, sampler=sampler)
     if cfg.save_model and sync is not None:
         sync.gather_moments(optimizer)
     if cfg.save_model and rank == 0:
