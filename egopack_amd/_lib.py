@@ -27,6 +27,7 @@ CE_BALANCED_HEADER = HERE.parent / "include" / "egopack_ce_balanced.h"  # likewi
 BCE_BALANCED_HEADER = HERE.parent / "include" / "egopack_bce_balanced.h"  # likewise; its symbols: BCE_BALANCED_SIGNATURES
 TASK_SCALE_HEADER = HERE.parent / "include" / "egopack_task_scale.h"  # likewise; its symbols: TASK_SCALE_SIGNATURES
 SAMPLE_HEADER = HERE.parent / "include" / "egopack_sample.h"  # likewise; its symbols: SAMPLE_SIGNATURES
+CLASS_REPORT_HEADER = HERE.parent / "include" / "egopack_class_report.h"  # likewise; its symbols: CLASS_REPORT_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -119,6 +120,13 @@ class SampleTask(C.Structure):
                 ("lo", vp), ("hi", vp), ("total", vp)]
 
 
+class ClassReportTask(C.Structure):
+    """struct egk_class_report_task (include/egopack_class_report.h): one head of a per-class report launch."""
+    _fields_ = [("logits", vp), ("ld", i64), ("labels", vp), ("label_stride", i64), ("rows", i32), ("C", i32),
+                ("confusion", vp), ("top2", vp), ("loss_q24", vp), ("counts", vp)]
+
+
+CLASS_REPORT_MAX_TASKS = 8  # EGK_CLASS_REPORT_MAX_TASKS (include/egopack_class_report.h)
 SAMPLE_MAX_TASKS, SAMPLE_MAX_K = 8, 1024  # EGK_SAMPLE_MAX_* (include/egopack_sample.h)
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
 
@@ -293,6 +301,12 @@ SAMPLE_SIGNATURES = {
 }
 
 
+# ... and include/egopack_class_report.h (the ninth ledger: tests/test_class_report_cpu.py over tests/test_gpu_bounds_class_report.py)
+CLASS_REPORT_SIGNATURES = {
+    "egk_class_report": (C.c_int, [vp, C.POINTER(ClassReportTask), i32]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -339,6 +353,11 @@ def sample_header_symbols() -> list:
     return _declared(SAMPLE_HEADER)
 
 
+def class_report_header_symbols() -> list:
+    """Every function name declared in include/egopack_class_report.h."""
+    return _declared(CLASS_REPORT_HEADER)
+
+
 _lib = None
 
 
@@ -354,7 +373,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
                               *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items(),
-                              *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items()]:
+                              *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items(), *CLASS_REPORT_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -111,6 +111,7 @@ enum KernelId {
     KID_BCE_BALANCED,      // egk_bce_w_fwd / _bwd, egk_rowdot_bce_w: BCE-with-logits with class factors and a focal exponent (loss.hip, norm_ops.hip)
     KID_TASK_SCALE,        // the entry points of include/egopack_task_scale.h: the _s head launches, prepare, grad, fill (loss.hip, norm_ops.hip, loss_optim.hip)
     KID_CATEGORICAL_SAMPLE, // egk_categorical_sample: K seeded categorical samples per logits row, all heads in one launch (sample.hip)
+    KID_CLASS_REPORT,      // egk_class_report: confusion, top-2 confusion and per-class loss sums of all heads in one launch (metrics.hip)
     KID_COUNT
 };
 

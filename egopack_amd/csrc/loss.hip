@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "bce_shaped.h"
+#include "ce_row.h"
 #include "common.h"
 
 namespace egk {
@@ -16,44 +17,7 @@ static inline int row_grid(int rows) {
 }
 
 // ---- cross entropy: one wave per row ------------------------------------------------------------
-// One row of one head, written once for the three kernels.  FWD: the wave reduces the row and returns its loss (lse_io = the
-// log-sum-exp it formed); !FWD: lse_io is the saved log-sum-exp.  GRAD: columns [0, pad) of ``dr`` are written -- the gradient
-// below C, 0 in [C, pad) and in ignored rows (t < 0 or t >= C), whose loss is 0.
-//
-// The plain arithmetic:   loss = lse - (1-eps)*x_t - eps/C * sum_c x_c,   dx_c = g * (exp(x_c - lse) - [c==t](1-eps) - eps/C)
-template <typename T, bool FWD, bool GRAD>
-__device__ __forceinline__ float ce_row_plain(const float* __restrict__ lr, int C, int pad, long long t, float smoothing, float g,
-                                              float& lse_io, T* __restrict__ dr, int lane) {
-    const bool live = t >= 0 && t < C;
-    float loss = 0.f, l;
-    if (FWD) {
-        float mx = -INFINITY;
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lr[c]);
-        mx = wave_max(mx);
-        float se = 0.f, sx = 0.f;
-        for (int c = lane; c < C; c += 64) {
-            const float v = lr[c];
-            se += expf(v - mx);
-            sx += v;
-        }
-        se = wave_sum(se);
-        sx = wave_sum(sx);
-        l = mx + logf(se);
-        lse_io = l;
-        if (live) loss = l - (1.f - smoothing) * lr[t] - (smoothing > 0.f ? smoothing / C * sx : 0.f);
-    } else {
-        l = lse_io;
-    }
-    if (GRAD) {
-        const float sm = smoothing > 0.f ? smoothing / C : 0.f;
-        for (int c = lane; c < pad; c += 64) {
-            float d = 0.f;
-            if (live && c < C) d = g * (expf(lr[c] - l) - (c == t ? 1.f - smoothing : 0.f) - sm);
-            st1t(dr + c, d);
-        }
-    }
-    return loss;
-}
+// (the plain row function, ce_row_plain, is in ce_row.h: the validation report of metrics.hip forms its loss with it too)
 
 // The balanced arithmetic (w: per-class weights, a: per-class logit offsets, either may be null): x'_c = x_c + a_c; FWD reduces
 // max, sum exp, W = sum w and sum w (x' - max) in one pass after the maximum; !FWD reduces only W (when smoothing needs it), lane

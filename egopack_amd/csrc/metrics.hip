@@ -4,6 +4,9 @@
 //                     rank < k: reference utils/meters/utils.py:6-28 topk_accuracy, torchmetrics MulticlassAccuracy)
 //   egk_edit_distance Levenshtein distance of K sampled label sequences against the ground truth
 //                     (reference utils/meters/ego4d.py:410-423 ``editdistance.eval(pred, label) / Z``, min over K on the host)
+//   egk_class_report  confusion matrix, top-2 confusion matrix and per-class fixed-point loss sums of all heads of a task in one
+//                     launch (include/egopack_class_report.h; reference utils/confusion.py, utils/meters/ego4d.py:125-170)
+#include "ce_row.h"
 #include "common.h"
 
 namespace egk {
@@ -58,6 +61,73 @@ __global__ __launch_bounds__(64) void edit_distance_kernel(const long long* __re
     out[idx] = prev[Z];
 }
 
+// ---- the per-class report: one wave per (task, row) ---------------------------------------------------------------------------
+// The order of label_rank_kernel as ONE integer per class: the f32 value as a monotone 32-bit key (NaN -> 0, below the key of -inf;
+// -0 and +0 share a key) above the complemented class index, so that the larger integer is the better class, no two classes of a
+// row share one, and 0 means "no class".  top1 / top2 are the largest and the second largest of the row.
+__device__ __forceinline__ unsigned long long rank_key(float v, int c) {
+    unsigned k;
+    if (v != v) {
+        k = 0u;
+    } else {
+        const unsigned b = __float_as_uint(v == 0.f ? 0.f : v);
+        k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    }
+    return ((unsigned long long)k << 32) | (unsigned long long)(0xffffffffu - (unsigned)c);
+}
+__device__ __forceinline__ void add_i64(long long* p, long long v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
+
+struct ClassReportTasks {
+    egk_class_report_task t[EGK_CLASS_REPORT_MAX_TASKS];
+};
+__global__ __launch_bounds__(256) void class_report_kernel(const ClassReportTasks P) {
+    const egk_class_report_task& t = P.t[blockIdx.y];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rows = t.rows, C = t.C;
+    const long long* __restrict__ labels = (const long long*)t.labels;
+    long long* __restrict__ counts = (long long*)t.counts;
+    for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+        const long long y = labels[(long long)row * t.label_stride];
+        if (y < 0 || y >= C) {
+            if (lane == 0) add_i64(counts + 1, 1);
+            continue;
+        }
+        const float* __restrict__ r = t.logits + (long long)row * t.ld;
+        unsigned long long a1 = 0, a2 = 0;  // this lane's best and second best; then the wave's
+        for (int c = lane; c < C; c += 64) {
+            const unsigned long long k = rank_key(r[c], c);
+            if (k > a1) {
+                a2 = a1;
+                a1 = k;
+            } else if (k > a2) {
+                a2 = k;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long b1 = __shfl_xor(a1, o, 64), b2 = __shfl_xor(a2, o, 64);
+            const unsigned long long lo = a1 < b1 ? a1 : b1, hi2 = a2 > b2 ? a2 : b2;
+            a1 = a1 > b1 ? a1 : b1;
+            a2 = lo > hi2 ? lo : hi2;
+        }
+        float lse;
+        const float loss = ce_row_plain<float, true, false>(r, C, 0, y, 0.f, 0.f, lse, nullptr, lane);
+        if (lane == 0) {
+            const long long top1 = (long long)(0xffffffffu - (unsigned)a1);
+            const long long top2 = a2 ? (long long)(0xffffffffu - (unsigned)a2) : -1;
+            add_i64(counts, 1);
+            add_i64((long long*)t.confusion + y * C + top1, 1);
+            if (t.top2 && top1 != y && top2 == y) add_i64((long long*)t.top2 + y * C + top1, 1);
+            const float q = loss * 16777216.f;  // (exact: a power of two)
+            if (fabsf(q) < 9.2233720368547758e18f) {  // finite, and llrint(q) fits: |q| < 2^63
+                if (t.loss_q24) add_i64((long long*)t.loss_q24 + y, llrintf(q));
+            } else {
+                add_i64(counts + 2, 1);
+            }
+        }
+    }
+}
+
 }  // namespace egk
 
 using namespace egk;
@@ -86,6 +156,34 @@ int egk_edit_distance(egk_stream_t stream, const int64_t* pred, int64_t p_sn, in
     hipLaunchKernelGGL(edit_distance_kernel, dim3(cdiv(N * K, 64)), dim3(64), 0, s, (const long long*)pred, (long long)p_sn,
                        (long long)p_sz, (long long)p_sk, (const long long*)label, (long long)l_sn, (long long)l_sz, out, N, Z, K);
     return check_launch("egk_edit_distance");
+}
+
+int egk_class_report(egk_stream_t stream, const egk_class_report_task* tasks, int32_t count) {
+    EGK_REQUIRE(tasks, "egk_class_report: null task list");
+    EGK_REQUIRE(count >= 1 && count <= EGK_CLASS_REPORT_MAX_TASKS, "egk_class_report: 1 .. %d tasks (got %d)",
+                EGK_CLASS_REPORT_MAX_TASKS, count);
+    ClassReportTasks P{};
+    int max_rows = 0;
+    double bytes = 0;
+    for (int i = 0; i < count; ++i) {
+        const egk_class_report_task& t = tasks[i];
+        EGK_REQUIRE(t.logits && t.labels && t.confusion && t.counts, "egk_class_report: null pointer (task %d)", i);
+        EGK_REQUIRE(t.C >= 1 && t.ld >= t.C, "egk_class_report: bad class count / leading dimension (task %d: C %d, ld %lld)", i, t.C,
+                    (long long)t.ld);
+        EGK_REQUIRE(t.rows >= 0, "egk_class_report: rows >= 0 (task %d: %d)", i, t.rows);
+        EGK_REQUIRE(aligned_to(4u, {t.logits}) && aligned_to(8u, {t.labels, t.confusion, t.top2, t.loss_q24, t.counts}),
+                    "egk_class_report: misaligned pointer (task %d: logits 4-byte, labels and the int64 accumulators 8-byte)", i);
+        P.t[i] = t;
+        if (t.rows > max_rows) max_rows = t.rows;
+        bytes += 8.0 * t.rows * t.C + 8.0 * t.rows;
+    }
+    if (max_rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_CLASS_REPORT, s, 0, bytes);
+    int grid = cdiv(max_rows, 4);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(class_report_kernel, dim3(grid, count), dim3(256), 0, s, P);
+    return check_launch("egk_class_report");
 }
 
 }  // extern "C"

@@ -12,7 +12,16 @@ it kept in small device tensors -- nothing is copied to the host before ``comput
     Ego4dOSCCMeter :292-318           OSCCMeter            accuracy, loss
     Ego4dPNRMeter :321-377            PNRMeter             accuracy, recall, auroc, localization_error, loss
     Ego4dLTAMeter :380-453            LTAMeter             verbs_ed, nouns_ed (+ verbs/nouns_top1), loss
-Dropped: confusion matrices, per-class loss tables, feature dumps (reporting only).
+    utils/confusion.py + ego4d.py:125-170   class_report=True   per head: *_confusion, *_top2_confusion, *_class_loss,
+                                                           *_class_precision / _recall / _f1, *_top_confusions,
+                                                           *_macro_precision / _recall / _f1, *_acc_many / _medium / _few
+Dropped: feature dumps, W&B tables and plots (reporting only).
+
+The per-class report (``class_report=True``; ``log_confusion_matrices`` of the config) is one ``egk_class_report`` launch per
+``update`` for all heads of the meter (include/egopack_class_report.h), beside the counting above, which it leaves as it is.  Its
+state is four int64 tensors per head -- confusion [C, C], top-2 confusion [C, C], per-class loss sums in 2^-24 fixed point [C],
+counts [4] -- that join ``_sums()``: integers only, so shards merge to the bits of the single pass.  With the report off a meter
+has the keys and values it had before.
 
 Several ranks (SURVEY §8(e) caveat 5): every meter is a set of SUMS (integer counts, float64 loss / distance sums) plus,
 for the PNR AUROC, a list of scores.  ``merge`` adds another meter's state, ``all_reduce`` does the same across the
@@ -59,6 +68,108 @@ def edit_distances(pred: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
                                           ops._p(label), label.stride(0), label.stride(1), ops._p(out), n, z, k),
             "egk_edit_distance")
     return out
+
+
+def class_report(heads) -> None:
+    """One ``egk_class_report`` launch for ``heads``, a list of ``(logits [N, C], labels [N] -- a column view is read through its
+    stride --, state)`` with ``state`` a ``_ClassReport`` of C classes: the state's tensors are added to.  f32 logits with unit
+    column stride are read where they lie; anything else is converted first."""
+    if not heads:
+        return
+    if len(heads) > _lib.CLASS_REPORT_MAX_TASKS:
+        raise ValueError(f"class_report: at most {_lib.CLASS_REPORT_MAX_TASKS} heads per launch, got {len(heads)}")
+    tasks = (_lib.ClassReportTask * len(heads))()
+    keep = []  # (converted tensors stay alive until the launch is issued)
+    for t, (logits, labels, state) in zip(tasks, heads):
+        ops._need_gpu(logits, labels)
+        logits = logits.detach()
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+            raise ValueError(f"class_report: logits {tuple(logits.shape)} / labels {tuple(labels.shape)}")
+        if (logits.shape[1] > 1 and logits.stride(1) != 1) or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+            logits = logits.contiguous()
+        if labels.dtype != torch.int64:
+            labels = labels.to(torch.int64)
+        if logits.shape[1] != state.C:
+            raise ValueError(f"class_report: {logits.shape[1]} logits per row, the state has {state.C} classes")
+        keep += [logits, labels]
+        t.logits, t.ld, t.labels, t.label_stride = logits.data_ptr(), max(logits.stride(0), logits.shape[1]), labels.data_ptr(), labels.stride(0)
+        t.rows, t.C = logits.shape[0], state.C
+        t.confusion, t.top2, t.loss_q24, t.counts = (x.data_ptr() for x in state.tensors())
+    ops._ck(_lib.load().egk_class_report(ops._stream(), tasks, len(heads)), "egk_class_report")
+
+
+Q24 = float(1 << 24)  # the fixed point of the per-class loss sums
+
+
+class _ClassReport:
+    """Confusion [C, C] (+1 at [label, top-1]), top-2 confusion [C, C] (+1 at [label, top-1] where the label was the runner-up),
+    per-class loss sums in 2^-24 fixed point [C] and counts [4] (valid, ignored, non-finite loss, 0) of one head: int64, on the
+    device, added to by ``class_report``."""
+
+    def __init__(self, n_classes: int, device):
+        self.C = int(n_classes)
+        self.confusion = torch.zeros((self.C, self.C), dtype=torch.int64, device=device)
+        self.top2 = torch.zeros((self.C, self.C), dtype=torch.int64, device=device)
+        self.loss_q24 = torch.zeros(self.C, dtype=torch.int64, device=device)
+        self.counts = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def tensors(self) -> List[torch.Tensor]:
+        return [self.confusion, self.top2, self.loss_q24, self.counts]
+
+
+def report_metrics(confusion, top2, loss_q24, names=None, train_counts=None, shots=(20, 100), top_confusions: int = 20) -> dict:
+    """What a head's report derives from its integer state, on the host in float64 (keys without the head's prefix).
+
+    support_c = row sum, predicted_c = column sum, tp_c = diagonal.  recall_c = tp / support (0 without support), precision_c =
+    tp / predicted (0 for a class never predicted), f1_c = 2 p r / (p + r) (0 when both are 0); the macro figures are means over
+    the classes with support > 0.  class_loss_c = loss_q24 / 2^24 / support (NaN without support).  top_confusions: the largest
+    non-zero off-diagonal cells of the top-2 matrix as (label name, confused-with name, count), ties by the lower flat index.
+    With ``train_counts`` (training labels per class) and shots = (lo, hi): top-1 accuracy over the validation samples whose
+    class has > hi (many), lo .. hi inclusive (medium), < lo (few) training labels, with each bucket's class and sample counts."""
+    conf, top2 = torch.as_tensor(confusion).cpu().to(torch.int64), torch.as_tensor(top2).cpu().to(torch.int64)
+    C = conf.shape[0]
+    names = list(names) if names is not None else [str(c) for c in range(C)]
+    tp, support, predicted = conf.diagonal(), conf.sum(1), conf.sum(0)
+    tpd = tp.double()
+    recall = torch.where(support > 0, tpd / support.clamp(min=1).double(), torch.zeros(C, dtype=torch.float64))
+    precision = torch.where(predicted > 0, tpd / predicted.clamp(min=1).double(), torch.zeros(C, dtype=torch.float64))
+    pr = precision + recall
+    f1 = torch.where(pr > 0, 2 * precision * recall / pr.clamp(min=1e-300), torch.zeros(C, dtype=torch.float64))
+    seen = support > 0
+    macro = (lambda v: float(v[seen].mean())) if bool(seen.any()) else (lambda v: 0.0)
+    loss = torch.as_tensor(loss_q24).cpu().double() / Q24
+    class_loss = torch.where(seen, loss / support.clamp(min=1).double(), torch.full((C,), float("nan"), dtype=torch.float64))
+    off = top2.clone()
+    off.fill_diagonal_(0)
+    flat = off.reshape(-1)
+    val, idx = torch.sort(flat, descending=True, stable=True)
+    pairs = [(names[i // C], names[i % C], v) for v, i in zip(val[:max(int(top_confusions), 0)].tolist(),
+                                                                 idx[:max(int(top_confusions), 0)].tolist()) if v > 0]
+    out = {"macro_precision": macro(precision), "macro_recall": macro(recall), "macro_f1": macro(f1),
+           "confusion": conf, "top2_confusion": top2, "class_loss": class_loss, "class_precision": precision,
+           "class_recall": recall, "class_f1": f1, "top_confusions": pairs}
+    if train_counts is not None:
+        n = torch.as_tensor(train_counts).cpu().to(torch.int64)
+        if n.shape != (C,):
+            raise ValueError(f"class_report: {tuple(n.shape)} training counts for {C} classes")
+        lo, hi = shots
+        for name, mask in (("many", n > hi), ("medium", (n >= lo) & (n <= hi)), ("few", n < lo)):
+            samples = int(support[mask].sum())
+            out[f"acc_{name}"] = int(tp[mask].sum()) / samples if samples else 0.0
+            out[f"classes_{name}"] = int(mask.sum())
+            out[f"samples_{name}"] = samples
+    return out
+
+
+def _report_line(name: str, m: dict, names) -> str:
+    """The report's line of ``print_logs``: macro F1, the bucket accuracies, the five classes with the lowest recall (support >= 1)."""
+    support = m["confusion"].sum(1)
+    order = sorted((c for c in range(len(support)) if int(support[c]) >= 1), key=lambda c: (float(m["class_recall"][c]), c))[:5]
+    worst = ", ".join(f"{names[c]} {float(m['class_recall'][c]) * 100:.1f} (n={int(support[c])})" for c in order)
+    shots = "".join(f", {b} {m[f'acc_{b}'] * 100:.2f}" for b in ("many", "medium", "few") if f"acc_{b}" in m)
+    return f"{name} macro F1: {m['macro_f1'] * 100:.2f}{shots}; lowest recall: {worst or '-'}"
 
 
 class _HeadCounts:
@@ -147,11 +258,47 @@ class _Calibration:
 class BaseMeter:
     """utils/meters/base.py: running mean of the per-batch loss + sample counter."""
 
-    def __init__(self, save_features: bool = False, device="cuda") -> None:
+    def __init__(self, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
+                 shots=(20, 100), top_confusions: int = 20) -> None:
         self.device = torch.device(device)
         self.loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         self.loss_n = 0
         self.counter = 0
+        # the per-class report (off: no state, no launch, no key); the meters that have heads fill ``reports``
+        self.class_report, self.train_counts = bool(class_report), train_counts
+        self.shots, self.top_confusions = (int(shots[0]), int(shots[1])), int(top_confusions)
+        self.reports: Dict[str, tuple] = {}  # key prefix -> (_ClassReport, class names, training counts of the head or None)
+
+    def _add_report(self, prefix: str, names, head: int) -> None:
+        if not self.class_report:
+            return
+        tc = self.train_counts
+        if tc is not None and not torch.is_tensor(tc):
+            tc = tc[head]  # (the per-head list of train.label_counts)
+        self.reports[prefix] = (_ClassReport(len(names), self.device), list(names), tc)
+
+    def _report_sums(self) -> List[torch.Tensor]:
+        return [t for st, _, _ in self.reports.values() for t in st.tensors()]
+
+    def _report_metrics(self) -> Dict[str, dict]:
+        return {p: report_metrics(st.confusion, st.top2, st.loss_q24, names, tc, self.shots, self.top_confusions)
+                for p, (st, names, tc) in self.reports.items()}
+
+    def _report_logs(self) -> dict:
+        return {f"{p}{k}": v for p, m in self._report_metrics().items() for k, v in m.items()}
+
+    def _report_lines(self) -> List[str]:
+        return [_report_line(p.rstrip("_") or "classes", m, self.reports[p][1]) for p, m in self._report_metrics().items()]
+
+    def report_tables(self) -> dict:
+        """The non-scalar entries of the report plus the class names and the counts: what ``class_report.save`` writes."""
+        out = {}
+        for p, (st, names, tc) in self.reports.items():
+            out.update({k: v for k, v in self._report_logs().items() if k.startswith(p) and not isinstance(v, (int, float))})
+            out[f"{p}class_names"], out[f"{p}counts"] = names, st.counts.cpu()
+            if tc is not None:
+                out[f"{p}train_counts"] = torch.as_tensor(tc).cpu()
+        return out
 
     def update(self, labels, loss, *args, **kwargs) -> None:
         loss = loss.detach().double()
@@ -170,7 +317,7 @@ class BaseMeter:
 
     def _sums(self) -> List[torch.Tensor]:
         """Device tensors that add across shards (updated in place)."""
-        return [self.loss_sum]
+        return [self.loss_sum, *self._report_sums()]
 
     def merge(self, other: "BaseMeter") -> "BaseMeter":
         """Add the state of a meter that saw another shard of the split."""
@@ -223,10 +370,10 @@ class BaseMeter:
         return torch.float32
 
     def print_logs(self) -> List[str]:
-        return [f"Loss: {self.loss():.4f}"]
+        return [*self._report_lines(), f"Loss: {self.loss():.4f}"]
 
     def get_logs(self, *args, **kwargs) -> Dict[str, float]:
-        return {"loss": self.loss()}
+        return {"loss": self.loss(), **self._report_logs()}
 
 
 class _VerbNounMeter(BaseMeter):
@@ -237,6 +384,9 @@ class _VerbNounMeter(BaseMeter):
         self.verb_labels, self.noun_labels = dataset.class_labels[self.idx_verbs], dataset.class_labels[self.idx_nouns]
         self.verbs = _HeadCounts(len(self.verb_labels), self.device)
         self.nouns = _HeadCounts(len(self.noun_labels), self.device)
+        # (the reference builds its noun table from the VERB matrix, utils/meters/ego4d.py:148; here the nouns get the nouns' matrix)
+        self._add_report("verbs_", self.verb_labels, self.idx_verbs)
+        self._add_report("nouns_", self.noun_labels, self.idx_nouns)
 
     def _sums(self):
         return [*super()._sums(), *self.verbs.tensors(), *self.nouns.tensors()]
@@ -245,6 +395,9 @@ class _VerbNounMeter(BaseMeter):
     def _count(self, logits, labels):
         self.verbs.update(logits[self.idx_verbs].detach(), labels[:, self.idx_verbs])
         self.nouns.update(logits[self.idx_nouns].detach(), labels[:, self.idx_nouns])
+        if self.class_report:  # both heads in one launch, beside the counting above
+            class_report([(logits[self.idx_verbs], labels[:, self.idx_verbs], self.reports["verbs_"][0]),
+                          (logits[self.idx_nouns], labels[:, self.idx_nouns], self.reports["nouns_"][0])])
 
 
 class RecognitionMeter(_VerbNounMeter):
@@ -300,7 +453,8 @@ class AnticipationMeter(_VerbNounMeter):
 
     def print_logs(self):
         logs = self.get_logs()
-        return [", ".join(f"{k}: {v * 100:.2f}" for k, v in logs.items() if k != "loss"), *super().print_logs()]
+        mine = [k for k in logs if k.startswith(("verbs_accuracy_top", "verbs_recall_top", "nouns_accuracy_top", "nouns_recall_top"))]
+        return [", ".join(f"{k}: {logs[k] * 100:.2f}" for k in mine), *super().print_logs()]
 
 
 class OSCCMeter(BaseMeter):
@@ -308,6 +462,11 @@ class OSCCMeter(BaseMeter):
         super().__init__(*args, **kwargs)
         self.dataset = dataset
         self.counts = _HeadCounts(2, self.device, ks=(1,))
+        if self.class_report:  # one head of two classes, keys without a prefix
+            tc = self.train_counts
+            if tc is not None and not torch.is_tensor(tc):
+                tc = tc[0]
+            self.reports[""] = (_ClassReport(2, self.device), list(getattr(dataset, "oscc_class_labels", ("no_change", "change"))), tc)
 
     def _sums(self):
         return [*super()._sums(), *self.counts.tensors()]
@@ -316,6 +475,8 @@ class OSCCMeter(BaseMeter):
     def update(self, logits, labels, *args, **kwargs) -> None:
         super().update(labels, *args, **kwargs)
         self.counts.update(logits.detach(), labels)
+        if self.class_report:
+            class_report([(logits, labels, self.reports[""][0])])
 
     def print_logs(self):
         return [f"Accuracy: {self.counts.accuracy(1) * 100:.2f}", *super().print_logs()]
@@ -437,17 +598,22 @@ class LTAMeter(_VerbNounMeter):
                 f"nouns_top1: {l['nouns_top1']:.4f}", *super().print_logs()]
 
 
-def build_meter_for_dataset(dataset, save_features: bool = False, device="cuda") -> BaseMeter:
-    """utils/meters/__init__.py:10-22, keyed on the dataset's ``task`` name (synthetic and Ego4D datasets alike)."""
+def build_meter_for_dataset(dataset, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
+                            shots=(20, 100), top_confusions: int = 20) -> BaseMeter:
+    """utils/meters/__init__.py:10-22, keyed on the dataset's ``task`` name (synthetic and Ego4D datasets alike).
+    ``class_report``: the per-class report of the verb / noun and OSCC meters (PNR is binary and reports tp / tn already: it
+    takes no report); ``train_counts``: per head the training labels of every class (``train.label_counts``) for the
+    many / medium / few-shot accuracies, ``shots`` their (lo, hi) borders, ``top_confusions`` the length of the confusion list."""
     kind = getattr(dataset, "task", None) or type(dataset).__name__.lower()
+    rep = dict(class_report=class_report, train_counts=train_counts, shots=shots, top_confusions=top_confusions)
     if "pnr" in kind:
         return PNRMeter(dataset, device=device)
     if "oscc" in kind:
-        return OSCCMeter(dataset, device=device)
+        return OSCCMeter(dataset, device=device, **rep)
     if "lta" in kind:
-        return LTAMeter(dataset, device=device)
+        return LTAMeter(dataset, device=device, **rep)
     if "anticipation" in kind:
-        return AnticipationMeter(dataset, device=device)
+        return AnticipationMeter(dataset, device=device, **rep)
     if "ar" in kind or "recognition" in kind:
-        return RecognitionMeter(dataset, save_features=save_features, device=device)
+        return RecognitionMeter(dataset, save_features=save_features, device=device, **rep)
     raise NotImplementedError(f"no meter for dataset {type(dataset).__name__}")

@@ -453,6 +453,79 @@ def lta_sampling_config(cfg) -> dict:
     return ls
 
 
+# ---- the per-class validation report (``log_confusion_matrices`` + ``class_report:`` of the config) ---------------------
+CLASS_REPORT_DEFAULTS = {"shots": [20, 100], "top_confusions": 20, "save": True}
+CLASS_REPORT_TASKS = ("ar", "lta", "oscc")  # (PNR is binary and reports tp / tn already)
+
+
+def class_report_config(cfg) -> dict:
+    """The ``class_report:`` block with its defaults filled in, plus ``enabled`` = ``log_confusion_matrices`` (the reference's
+    key); an unknown key is a ValueError naming it, and so are shots that are not two increasing integers >= 0."""
+    raw = cfg.get("class_report") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(CLASS_REPORT_DEFAULTS)
+    if unknown:
+        raise ValueError(f"class_report: unknown key(s) {sorted(unknown)} ({', '.join(CLASS_REPORT_DEFAULTS)})")
+    cr = {**CLASS_REPORT_DEFAULTS, **raw}
+    shots = list(cr["shots"]) if isinstance(cr["shots"], (list, tuple)) or hasattr(cr["shots"], "__iter__") else [cr["shots"]]
+    if len(shots) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in shots) or not 0 <= shots[0] < shots[1]:
+        raise ValueError(f"class_report.shots: {shots!r} is not [lo, hi] with integers 0 <= lo < hi")
+    cr["shots"] = (int(shots[0]), int(shots[1]))
+    if isinstance(cr["top_confusions"], bool) or not isinstance(cr["top_confusions"], int) or cr["top_confusions"] < 0:
+        raise ValueError(f"class_report.top_confusions: {cr['top_confusions']!r} is not an integer >= 0")
+    cr["save"] = bool(cr["save"])
+    cr["enabled"] = bool(cfg.get("log_confusion_matrices", False)) if hasattr(cfg, "get") else False
+    return cr
+
+
+def class_report_train_counts(cfg, dsets_train, tasks=None) -> dict:
+    """{task: per-head training label counts} for the many / medium / few-shot accuracies of the report -- {} with the report off
+    (nothing is counted).  AR / LTA: ``label_counts``; OSCC: its two classes over the labels of the split.  Counted once per run."""
+    if not class_report_config(cfg)["enabled"]:
+        return {}
+    out = {}
+    for t in CLASS_REPORT_TASKS:
+        if t not in dsets_train or (tasks is not None and t not in tasks):
+            continue
+        if t == "oscc":
+            ds = dsets_train[t]
+            if hasattr(ds, "_tables"):  # (as ``pnr_label_counts``: the label table of a dataset that holds one)
+                y = torch.as_tensor(ds._tables()["y"]).reshape(-1).to(torch.int64)
+            else:
+                ys = [torch.as_tensor(ds[i].y).reshape(-1) for i in range(len(ds))]
+                y = torch.cat(ys).to(torch.int64) if ys else torch.zeros(0, dtype=torch.int64)
+            out[t] = [torch.bincount(y[(y >= 0) & (y < 2)], minlength=2).to(torch.int64)]
+        else:
+            out[t] = label_counts(dsets_train[t])
+    return out
+
+
+def class_report_meter_args(cfg, train_counts, task: str) -> dict:
+    """The keyword arguments of ``build_meter_for_dataset`` for ``task``: {} with the report off."""
+    cr = class_report_config(cfg)
+    if not cr["enabled"] or task not in CLASS_REPORT_TASKS:
+        return {}
+    return dict(class_report=True, train_counts=(train_counts or {}).get(task), shots=cr["shots"], top_confusions=cr["top_confusions"])
+
+
+def save_class_reports(logger, cfg, directory: Path, reports: dict) -> list:
+    """``class_report.save``: one ``class_report_<task>.pt`` per task under ``directory`` with the non-scalar entries of the last
+    validation's report and the class names (``BaseMeter.report_tables``).  Returns the paths written."""
+    cr = class_report_config(cfg)
+    if not (cr["enabled"] and cr["save"]):
+        return []
+    paths = []
+    for t, tables in (reports or {}).items():
+        if not tables:
+            continue
+        directory.mkdir(parents=True, exist_ok=True)
+        path = directory / f"class_report_{t}.pt"
+        torch.save(tables, path)
+        logger.info("class report of %s -> %s", t, path)
+        paths.append(path)
+    return paths
+
+
 def build_lta_sampler(cfg):
     """The ``ops.FutureSampler`` of ``lta_sampling.mode=philox`` (stateless: nothing of it goes into a checkpoint); None with
     ``mode: torch`` -- the validation loop then samples with torch's generator, as the reference does."""

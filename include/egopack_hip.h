@@ -761,5 +761,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* K seeded categorical samples per logits row from the counter-based Philox stream, all heads in one launch: the futures of the LTA
  * head (egk_categorical_sample) */
 #include "egopack_sample.h"
+/* the per-class validation report: confusion, top-2 confusion and fixed-point per-class loss sums of all heads of a task in one
+ * launch, integer accumulators only (egk_class_report) */
+#include "egopack_class_report.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -35,9 +35,11 @@ AUX_ORDER = {"ar": ("lta", "oscc", "pnr"), "oscc": ("ar", "lta", "pnr"), "lta": 
 
 
 def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders, late_fusion=True, validate_all=False,
-                     device="cuda", sampler=None):
+                     device="cuda", sampler=None, report=None, reports=None):
     """Task metrics with the GraphONE interaction for the novel task(s) (reference main_egopack.py:374-448).  ``sampler``: the
-    seeded sampler of the LTA futures (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator."""
+    seeded sampler of the LTA futures (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``:
+    task -> the meter's per-class report arguments (``T.class_report_meter_args``, log_confusion_matrices); ``reports``: a dict
+    that receives every task's tables."""
     out = {}
     for t in ("ar", "oscc", "lta", "pnr"):
         if not (validate_all or weights.get(t, 0) > 0):
@@ -45,7 +47,7 @@ def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders,
         is_egopack = weights.get(t, 0) > 0
         others = [tasks[o] for o in AUX_ORDER[t] if o in graphone.task_labels] if is_egopack else []
         g1 = graphone if is_egopack else None
-        meter = build_meter_for_dataset(dsets_val[t], device=device)
+        meter = build_meter_for_dataset(dsets_val[t], device=device, **(report(t) if report else {}))
         if t == "lta":
             validate_lta(model, loaders[t], meter, tasks[t], others, g1, late_fusion=late_fusion, device=device, sampler=sampler)
         elif t == "pnr":
@@ -56,6 +58,8 @@ def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders,
         for line in meter.print_logs():
             logger.info("[val %s] %s", t, line)
         out[t] = {k: v for k, v in meter.get_logs().items() if isinstance(v, (int, float))}
+        if reports is not None and meter.reports:
+            reports[t] = meter.report_tables()
     return out
 
 
@@ -166,13 +170,21 @@ def main(argv=None):
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))
     sampler = T.build_lta_sampler(cfg)  # (lta_sampling.mode=philox: the LTA futures from the seeded launch; None: torch's generator)
+    # log_confusion_matrices: the per-class report of the validation meters; the training labels are counted once, here
+    validated = [t for t in ("ar", "oscc", "lta", "pnr") if cfg.validate_all_tasks or weights.get(t, 0) > 0]
+    train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=validated)
+    report, reports = (lambda t: T.class_report_meter_args(cfg, train_counts, t)), {}
     for epoch in range(1, cfg.num_epochs + 1):
         train(epoch, step, dl_train, weights, device, store=store)
         scheduler.step()
         T.log_validation_weights(logger, cfg, optimizer, epoch)
         with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
             validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, dl_val, late_fusion=cfg.late_fusion,
-                             validate_all=cfg.validate_all_tasks, device=device, sampler=sampler)  # all ranks: the split is sharded by batch
+                             validate_all=cfg.validate_all_tasks, device=device, sampler=sampler, report=report,
+                             reports=reports)  # all ranks: the split is sharded by batch
+    if rank == 0:  # (class_report.save: the tables of the last validation, beside the checkpoint)
+        T.save_class_reports(logger, cfg, Path(cfg.checkpoint_dir) / (f"{cfg.artifact_prefix}_egopack_" + "-".join(
+            sorted(t for t, w in weights.items() if w > 0))), reports)
     if cfg.save_model and step.sync is not None:
         step.sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
     if cfg.save_model and rank == 0:
