@@ -28,6 +28,7 @@ BCE_BALANCED_HEADER = HERE.parent / "include" / "egopack_bce_balanced.h"  # like
 TASK_SCALE_HEADER = HERE.parent / "include" / "egopack_task_scale.h"  # likewise; its symbols: TASK_SCALE_SIGNATURES
 SAMPLE_HEADER = HERE.parent / "include" / "egopack_sample.h"  # likewise; its symbols: SAMPLE_SIGNATURES
 CLASS_REPORT_HEADER = HERE.parent / "include" / "egopack_class_report.h"  # likewise; its symbols: CLASS_REPORT_SIGNATURES
+TOPK_HEADER = HERE.parent / "include" / "egopack_topk.h"  # likewise; its symbols: TOPK_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -126,6 +127,13 @@ class ClassReportTask(C.Structure):
                 ("confusion", vp), ("top2", vp), ("loss_q24", vp), ("counts", vp)]
 
 
+class TopkTask(C.Structure):
+    """struct egk_topk_task (include/egopack_topk.h): one head of a top-k softmax launch."""
+    _fields_ = [("logits", vp), ("ld", i64), ("C", i32), ("reserved", i32), ("idx", vp), ("idx_row_stride", i64),
+                ("prob", vp), ("prob_row_stride", i64), ("lse", vp)]
+
+
+TOPK_MAX_TASKS, TOPK_MAX_K = 8, 64  # EGK_TOPK_MAX_* (include/egopack_topk.h)
 CLASS_REPORT_MAX_TASKS = 8  # EGK_CLASS_REPORT_MAX_TASKS (include/egopack_class_report.h)
 SAMPLE_MAX_TASKS, SAMPLE_MAX_K = 8, 1024  # EGK_SAMPLE_MAX_* (include/egopack_sample.h)
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
@@ -307,6 +315,12 @@ CLASS_REPORT_SIGNATURES = {
 }
 
 
+# ... and include/egopack_topk.h (the tenth ledger: tests/test_topk_cpu.py over tests/test_gpu_bounds_topk.py)
+TOPK_SIGNATURES = {
+    "egk_topk_softmax": (C.c_int, [vp, C.POINTER(TopkTask), i32, i32, i32, i32]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -358,6 +372,11 @@ def class_report_header_symbols() -> list:
     return _declared(CLASS_REPORT_HEADER)
 
 
+def topk_header_symbols() -> list:
+    """Every function name declared in include/egopack_topk.h."""
+    return _declared(TOPK_HEADER)
+
+
 _lib = None
 
 
@@ -373,7 +392,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
                               *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items(),
-                              *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items(), *CLASS_REPORT_SIGNATURES.items()]:
+                              *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items(), *CLASS_REPORT_SIGNATURES.items(),
+                              *TOPK_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

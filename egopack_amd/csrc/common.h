@@ -112,6 +112,7 @@ enum KernelId {
     KID_TASK_SCALE,        // the entry points of include/egopack_task_scale.h: the _s head launches, prepare, grad, fill (loss.hip, norm_ops.hip, loss_optim.hip)
     KID_CATEGORICAL_SAMPLE, // egk_categorical_sample: K seeded categorical samples per logits row, all heads in one launch (sample.hip)
     KID_CLASS_REPORT,      // egk_class_report: confusion, top-2 confusion and per-class loss sums of all heads in one launch (metrics.hip)
+    KID_TOPK_SOFTMAX,      // egk_topk_softmax: the best k classes of every row of every head, their probabilities and the log-sum-exp (metrics.hip)
     KID_COUNT
 };
 

@@ -6,6 +6,8 @@
 //                     (reference utils/meters/ego4d.py:410-423 ``editdistance.eval(pred, label) / Z``, min over K on the host)
 //   egk_class_report  confusion matrix, top-2 confusion matrix and per-class fixed-point loss sums of all heads of a task in one
 //                     launch (include/egopack_class_report.h; reference utils/confusion.py, utils/meters/ego4d.py:125-170)
+//   egk_topk_softmax  the best k classes of every row of every head in that same order, with their softmax probabilities and the
+//                     row's log-sum-exp, in one launch (include/egopack_topk.h: what a prediction file holds)
 #include "ce_row.h"
 #include "common.h"
 
@@ -128,6 +130,81 @@ __global__ __launch_bounds__(256) void class_report_kernel(const ClassReportTask
     }
 }
 
+// ---- the best k classes of a row: one wave per (task, row) ---------------------------------------------------------------------
+// Entry j of a row is the class with the j-th largest rank_key: pass j takes the wave-wide maximum of the keys BELOW the winner of
+// pass j - 1 (no two classes of a row share a key, so "below" removes exactly the classes already taken) and lane j keeps it.  A
+// row of at most TOPK_RES classes (the workload's 2, 115 and 478) holds its keys in registers, TOPK_SLOTS per lane, class
+// c = lane + 64 * i in slot i (coalesced loads); a wider row forms the keys again from its logits in every pass.  k = 64 needs no
+// register per entry (lane j holds entry j), so the budget is the 2 * TOPK_SLOTS key registers whatever k is: 71 VGPRs, no scratch,
+// 7 of 8 waves per SIMD -- the passes are dependent wave reductions, so resident waves are what hides them.
+// No LDS, no workspace, no atomics; lanes j < k store the outputs.
+constexpr int TOPK_SLOTS = 8;
+constexpr int TOPK_RES = WAVE * TOPK_SLOTS;
+
+struct TopkTasks {
+    egk_topk_task t[EGK_TOPK_MAX_TASKS];
+};
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long b = __shfl_xor(v, o, 64);
+        v = v > b ? v : b;
+    }
+    return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void topk_softmax_kernel(const TopkTasks P, int count, int rows, int k) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long items = (long long)count * rows;
+    for (long long item = (long long)blockIdx.x * 4 + wave; item < items; item += (long long)gridDim.x * 4) {
+        const int ti = (int)(item / rows), row = (int)(item % rows);
+        const egk_topk_task& t = P.t[ti];
+        const int C = t.C;
+        const T* __restrict__ r = reinterpret_cast<const T*>(t.logits) + (long long)row * t.ld;
+        const bool res = C <= TOPK_RES;
+        unsigned long long key[TOPK_SLOTS];
+#pragma unroll
+        for (int i = 0; i < TOPK_SLOTS; ++i) {  // (0: "no class" -- below every key, never taken)
+            const int c = lane + WAVE * i;
+            key[i] = res && c < C ? rank_key(ld1t(r + c), c) : 0ull;
+        }
+        unsigned long long prev = ~0ull;  // (above every key: the value part of a key is at most that of +inf)
+        unsigned long long mine = 0ull;   // entry ``lane`` of the row
+        for (int j = 0; j < k; ++j) {
+            unsigned long long best = 0ull;
+            if (res) {
+#pragma unroll
+                for (int i = 0; i < TOPK_SLOTS; ++i)
+                    if (key[i] < prev && key[i] > best) best = key[i];
+            } else {
+                for (int c = lane; c < C; c += WAVE) {
+                    const unsigned long long q = rank_key(ld1t(r + c), c);
+                    if (q < prev && q > best) best = q;
+                }
+            }
+            best = wave_max_u64(best);
+            if (best == 0ull) break;  // the row has no more classes: entries j .. k - 1 stay "no class"
+            if (lane == j) mine = best;
+            prev = best;
+        }
+        float lse;
+        ce_row_plain<float, true, false, T>(r, C, 0, -1, 0.f, 0.f, lse, nullptr, lane);
+        if (lane < k) {
+            const long long c = mine ? (long long)(0xffffffffu - (unsigned)mine) : -1;
+            reinterpret_cast<long long*>(t.idx)[(long long)row * t.idx_row_stride + lane] = c;
+            if (t.prob) t.prob[(long long)row * t.prob_row_stride + lane] = mine ? expf(ld1t(r + (mine ? c : 0)) - lse) : 0.f;
+        }
+        if (t.lse && lane == 0) t.lse[row] = lse;
+    }
+}
+
+template <typename T>
+static void topk_launch(hipStream_t s, int grid, const TopkTasks& P, int count, int rows, int k) {
+    hipLaunchKernelGGL(topk_softmax_kernel<T>, dim3(grid), dim3(256), 0, s, P, count, rows, k);
+}
+
 }  // namespace egk
 
 using namespace egk;
@@ -184,6 +261,39 @@ int egk_class_report(egk_stream_t stream, const egk_class_report_task* tasks, in
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(class_report_kernel, dim3(grid, count), dim3(256), 0, s, P);
     return check_launch("egk_class_report");
+}
+
+int egk_topk_softmax(egk_stream_t stream, const egk_topk_task* tasks, int32_t count, int32_t rows, int32_t k, int32_t dtype) {
+    EGK_REQUIRE(tasks, "egk_topk_softmax: null task list");
+    EGK_REQUIRE(count >= 1 && count <= EGK_TOPK_MAX_TASKS, "egk_topk_softmax: 1 .. %d tasks (got %d)", EGK_TOPK_MAX_TASKS, count);
+    EGK_REQUIRE(rows >= 0, "egk_topk_softmax: rows >= 0 (got %d)", rows);
+    EGK_REQUIRE(k >= 1 && k <= EGK_TOPK_MAX_K, "egk_topk_softmax: k in 1 .. %d (got %d)", EGK_TOPK_MAX_K, k);
+    EGK_REQUIRE(dtype == EGK_F32 || dtype == EGK_BF16, "egk_topk_softmax: unknown logits dtype %d", dtype);
+    TopkTasks P{};
+    double bytes = 0;
+    for (int i = 0; i < count; ++i) {
+        const egk_topk_task& t = tasks[i];
+        EGK_REQUIRE(t.logits && t.idx, "egk_topk_softmax: null pointer (task %d)", i);
+        EGK_REQUIRE(t.C >= 1 && t.ld >= t.C, "egk_topk_softmax: bad class count / leading dimension (task %d: C %d, ld %lld)", i, t.C,
+                    (long long)t.ld);
+        EGK_REQUIRE(t.reserved == 0, "egk_topk_softmax: the reserved field is 0 (task %d: %d)", i, t.reserved);
+        EGK_REQUIRE(t.idx_row_stride >= k, "egk_topk_softmax: idx row stride >= k (task %d: %lld, k %d)", i, (long long)t.idx_row_stride, k);
+        EGK_REQUIRE(!t.prob || t.prob_row_stride >= k, "egk_topk_softmax: prob row stride >= k (task %d: %lld, k %d)", i,
+                    (long long)t.prob_row_stride, k);
+        EGK_REQUIRE(aligned_to(dtype == EGK_BF16 ? 2u : 4u, {t.logits}) && aligned_to(8u, {t.idx}) && aligned_to(4u, {t.prob, t.lse}),
+                    "egk_topk_softmax: misaligned pointer (task %d: logits to their element, idx 8-byte, prob and lse 4-byte)", i);
+        P.t[i] = t;
+        const double es = dtype == EGK_BF16 ? 2 : 4;
+        const double passes = t.C > TOPK_RES ? (double)(k < t.C ? k : t.C) + 2 : 3;  // (the keys -- once, or once per entry --, the maximum, the sum)
+        bytes += (double)rows * (t.C * es * passes + (t.prob ? (es + 4.0) * k : 0) + 8.0 * k + (t.lse ? 4 : 0));
+    }
+    if (rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_TOPK_SOFTMAX, s, 0, bytes);
+    int grid = cdiv((int64_t)count * rows, 4);
+    if (grid > 2048) grid = 2048;
+    EGK_DISPATCH_T(dtype, (topk_launch<T>(s, grid, P, (int)count, (int)rows, (int)k)));
+    return check_launch("egk_topk_softmax");
 }
 
 }  // extern "C"

@@ -3928,6 +3928,43 @@ class FutureSampler:
         return categorical_sample_multi(list(logits), K, self.seed, ordinal, row0)
 
 
+# ---- top-k softmax (include/egopack_topk.h) ---------------------------------------------------------------------------
+@torch.no_grad()
+def topk_softmax(logits_list, k: int, want_prob: bool = True, want_lse: bool = False):
+    """The best ``k`` classes of every row of every head of ``logits_list`` ([N, C_h] f32 or bf16, one N) in ONE launch: a list of
+    (idx int64 [N, k], prob f32 [N, k] | None, lse f32 [N] | None), one entry per head.  The order is the meters' (larger value
+    first, ties to the lower class index, a NaN below -inf); prob = exp(x - lse) with the log-sum-exp of the loss kernels; entries
+    beyond a head's class count are (-1, 0).  Views with a unit class stride are read in place through their row stride; heads of
+    mixed element types are widened to f32."""
+    if not 1 <= len(logits_list) <= _lib.TOPK_MAX_TASKS:
+        raise ValueError(f"topk_softmax: 1 .. {_lib.TOPK_MAX_TASKS} heads (got {len(logits_list)})")
+    _need_gpu(*logits_list)
+    if any(l.dim() != 2 or l.shape[0] != logits_list[0].shape[0] for l in logits_list):
+        raise ValueError(f"topk_softmax: heads of [N, C_h] with one N (got {[tuple(l.shape) for l in logits_list]})")
+    if len({l.dtype for l in logits_list}) > 1:  # (one element type per launch; a bf16 head and its widening give the same entries)
+        logits_list = [cast_raw(_c(l), torch.float32) for l in logits_list]
+    logits_list = [_rm(l) for l in logits_list]
+    N, dev = logits_list[0].shape[0], logits_list[0].device
+    if not 1 <= int(k) <= _lib.TOPK_MAX_K:
+        raise RuntimeError(f"topk_softmax: k in 1 .. {_lib.TOPK_MAX_K} (got {k})")
+    k = int(k)
+    outs = [(torch.empty((N, k), dtype=torch.int64, device=dev),
+             torch.empty((N, k), dtype=torch.float32, device=dev) if want_prob else None,
+             torch.empty((N,), dtype=torch.float32, device=dev) if want_lse else None) for _ in logits_list]
+    if N == 0:  # (no rows: nothing to launch, and an empty tensor has no pointer to hand over)
+        return outs
+    tasks = (_lib.TopkTask * len(logits_list))()
+    for t, l, (idx, prob, lse) in zip(tasks, logits_list, outs):
+        t.logits, t.ld, t.C, t.reserved = _p(l), max(l.stride(0), l.shape[1]), l.shape[1], 0  # (a one-row tensor's stride is arbitrary)
+        t.idx, t.idx_row_stride = _p(idx), k
+        if want_prob:
+            t.prob, t.prob_row_stride = _p(prob), k
+        if want_lse:
+            t.lse = _p(lse)
+    _ck(_lib.load().egk_topk_softmax(_stream(), tasks, len(logits_list), N, k, _dt(logits_list[0])), "egk_topk_softmax")
+    return outs
+
+
 # ---- phase stamps (development) ---------------------------------------------------------------------------------
 _stamps = {"buf": None, "names": []}
 

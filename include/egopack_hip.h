@@ -764,5 +764,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* the per-class validation report: confusion, top-2 confusion and fixed-point per-class loss sums of all heads of a task in one
  * launch, integer accumulators only (egk_class_report) */
 #include "egopack_class_report.h"
+/* the prediction export: the best k classes of every row of every head in the meters' order, their softmax probabilities and the
+ * log-sum-exp of the loss kernels, in one launch (egk_topk_softmax) */
+#include "egopack_topk.h"
 
 #endif /* EGOPACK_HIP_H */
