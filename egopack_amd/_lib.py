@@ -29,6 +29,7 @@ TASK_SCALE_HEADER = HERE.parent / "include" / "egopack_task_scale.h"  # likewise
 SAMPLE_HEADER = HERE.parent / "include" / "egopack_sample.h"  # likewise; its symbols: SAMPLE_SIGNATURES
 CLASS_REPORT_HEADER = HERE.parent / "include" / "egopack_class_report.h"  # likewise; its symbols: CLASS_REPORT_SIGNATURES
 TOPK_HEADER = HERE.parent / "include" / "egopack_topk.h"  # likewise; its symbols: TOPK_SIGNATURES
+RETRIEVAL_HEADER = HERE.parent / "include" / "egopack_retrieval.h"  # likewise; its symbols: RETRIEVAL_SIGNATURES
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -133,6 +134,13 @@ class TopkTask(C.Structure):
                 ("prob", vp), ("prob_row_stride", i64), ("lse", vp)]
 
 
+class RetrievalTask(C.Structure):
+    """struct egk_retrieval_task (include/egopack_retrieval.h): one auxiliary task of a retrieval report launch."""
+    _fields_ = [("f", vp), ("f_ld", i64), ("f_act", vp), ("f_act_ld", i64), ("bank", vp), ("bank_ld", i64), ("K", i32), ("reserved", i32),
+                ("nn", vp), ("nn_row_stride", i64), ("dist", vp), ("dist_row_stride", i64), ("wins", vp), ("wins_row_stride", i64)]
+
+
+RETRIEVAL_MAX_TASKS, RETRIEVAL_MAX_K = 8, 32  # EGK_RETRIEVAL_MAX_* (include/egopack_retrieval.h)
 TOPK_MAX_TASKS, TOPK_MAX_K = 8, 64  # EGK_TOPK_MAX_* (include/egopack_topk.h)
 CLASS_REPORT_MAX_TASKS = 8  # EGK_CLASS_REPORT_MAX_TASKS (include/egopack_class_report.h)
 SAMPLE_MAX_TASKS, SAMPLE_MAX_K = 8, 1024  # EGK_SAMPLE_MAX_* (include/egopack_sample.h)
@@ -321,6 +329,12 @@ TOPK_SIGNATURES = {
 }
 
 
+# ... and include/egopack_retrieval.h (the eleventh ledger: tests/test_retrieval_cpu.py over tests/test_gpu_bounds_retrieval.py)
+RETRIEVAL_SIGNATURES = {
+    "egk_retrieval_report": (C.c_int, [vp, C.POINTER(RetrievalTask), i32, i32, i32, i32, i32, i32]),
+}
+
+
 def _declared(header: Path) -> list:
     text = header.read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -377,6 +391,11 @@ def topk_header_symbols() -> list:
     return _declared(TOPK_HEADER)
 
 
+def retrieval_header_symbols() -> list:
+    """Every function name declared in include/egopack_retrieval.h."""
+    return _declared(RETRIEVAL_HEADER)
+
+
 _lib = None
 
 
@@ -393,7 +412,7 @@ def load() -> C.CDLL:
     for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
                               *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items(),
                               *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items(), *CLASS_REPORT_SIGNATURES.items(),
-                              *TOPK_SIGNATURES.items()]:
+                              *TOPK_SIGNATURES.items(), *RETRIEVAL_SIGNATURES.items()]:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

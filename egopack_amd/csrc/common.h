@@ -113,6 +113,7 @@ enum KernelId {
     KID_CATEGORICAL_SAMPLE, // egk_categorical_sample: K seeded categorical samples per logits row, all heads in one launch (sample.hip)
     KID_CLASS_REPORT,      // egk_class_report: confusion, top-2 confusion and per-class loss sums of all heads in one launch (metrics.hip)
     KID_TOPK_SOFTMAX,      // egk_topk_softmax: the best k classes of every row of every head, their probabilities and the log-sum-exp (metrics.hip)
+    KID_RETRIEVAL_REPORT,  // egk_retrieval_report: per node and auxiliary task the distances of its prototypes and their wins in the first gather-max (graph_ops.hip)
     KID_COUNT
 };
 

@@ -633,6 +633,91 @@ __global__ __launch_bounds__(256) void gather_max_fwd_kernel(const T* __restrict
     }
 }
 
+// ---- the retrieval report (include/egopack_retrieval.h): one wave per (task, row) -------------------------------------------------
+// Pass 1: the distance of every listed prototype, one prototype at a time -- three accumulators per lane (f.p, |f|^2, |p|^2; the
+// squared difference alone for l2), row_inv_norm_kernel's striding (four-term groups per lane in column order, then wave_sum), so a
+// value depends on its row, its prototype and H alone; lane j keeps entry j.  The node's f32 row is read again per prototype (4 KB at
+// H = 1024: it stays in the L1).  Pass 2: gather_max_fwd_kernel's comparisons in its order per 4-column group, then one ballot and
+// population count per (source, component) -- integers, no LDS, no atomics; lane j keeps the count of source j.  Tasks are
+// blockIdx.y; the rows of a task are walked like the rows of every other row kernel.
+struct RetrievalTasks {
+    egk_retrieval_task t[EGK_RETRIEVAL_MAX_TASKS];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void retrieval_report_kernel(const RetrievalTasks P, int rows, int cols, int k, int l2) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const egk_retrieval_task& t = P.t[blockIdx.y];
+    const T* __restrict__ fa = reinterpret_cast<const T*>(t.f_act);
+    const long long* __restrict__ nn = reinterpret_cast<const long long*>(t.nn);
+    // four elements at a time only where every row of the operand starts on such a group (the values read are the same either way)
+    const bool w4 = (cols & 3) == 0;
+    const bool vf = w4 && (t.f_ld & 3) == 0 && (reinterpret_cast<uintptr_t>(t.f) & 15) == 0;
+    const bool vb = w4 && (t.bank_ld & 3) == 0 && (reinterpret_cast<uintptr_t>(t.bank) & 15) == 0;
+    const bool va = w4 && (t.f_act_ld & 3) == 0 && (reinterpret_cast<uintptr_t>(fa) & (4 * sizeof(T) - 1)) == 0;
+    const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
+    for (int row = rw.first; row < rw.end; row += rw.step) {
+        const long long* __restrict__ list = nn + (long long)row * t.nn_row_stride;
+        if (t.dist) {
+            const float* __restrict__ fr = t.f + (long long)row * t.f_ld;
+            float mine = 0.f;  // entry ``lane`` of the row
+            for (int j = 0; j < k; ++j) {
+                const float* __restrict__ pr = t.bank + list[j] * t.bank_ld;
+                float d;
+                if (l2) {
+                    float s = 0.f;
+                    for (int c = lane * 4; c < cols; c += 256) {
+                        const float4 a = ld4(fr, c, cols, vf), b = ld4(pr, c, cols, vb);
+                        const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z, w = a.w - b.w;
+                        s += (x * x + y * y) + (z * z + w * w);
+                    }
+                    d = sqrtf(wave_sum(s)) / 4096.f;
+                } else {
+                    float dot = 0.f, ff = 0.f, pp = 0.f;
+                    for (int c = lane * 4; c < cols; c += 256) {
+                        const float4 a = ld4(fr, c, cols, vf), b = ld4(pr, c, cols, vb);
+                        dot += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+                        ff += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+                        pp += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
+                    }
+                    dot = wave_sum(dot);
+                    ff = wave_sum(ff);
+                    pp = wave_sum(pp);
+                    d = 1.f - dot / (sqrtf(ff) * sqrtf(pp));
+                }
+                if (lane == j) mine = d;
+            }
+            if (lane < k) t.dist[(long long)row * t.dist_row_stride + lane] = mine;
+        }
+        if (t.wins) {
+            const T* __restrict__ ar = fa + (long long)row * t.f_act_ld;
+            int count = 0;  // of source ``lane``
+            for (int c0 = 0; c0 < cols; c0 += 256) {  // (wave-uniform trip count: the ballots below need every lane)
+                const int c = c0 + lane * 4;
+                // message order of the reference: prototype edges first, the self loop appended last; first maximum wins on ties
+                float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+                int ax = 0, ay = 0, az = 0, aw = 0;
+                if (c < cols) {
+                    for (int j = 0; j <= k; ++j) {
+                        const float4 v = j < k ? ld4(t.bank + list[j] * t.bank_ld, c, cols, vb) : ld4(ar, c, cols, va);
+                        if (v.x > best.x) { best.x = v.x; ax = j; }
+                        if (v.y > best.y) { best.y = v.y; ay = j; }
+                        if (v.z > best.z) { best.z = v.z; az = j; }
+                        if (v.w > best.w) { best.w = v.w; aw = j; }
+                    }
+                }
+                const bool ox = c + 0 < cols, oy = c + 1 < cols, oz = c + 2 < cols, ow = c + 3 < cols;
+                for (int j = 0; j <= k; ++j) {
+                    const int n = __popcll(__ballot(ox && ax == j)) + __popcll(__ballot(oy && ay == j)) +
+                                  __popcll(__ballot(oz && az == j)) + __popcll(__ballot(ow && aw == j));
+                    if (lane == j) count += n;
+                }
+            }
+            if (lane <= k) t.wins[(long long)row * t.wins_row_stride + lane] = count;
+        }
+    }
+}
+
 // The same op with every load of a row requested up front: the generic kernel walks k + 1 sources x cols / 256 column steps as
 // a chain of dependent loads (one wave per row: ~15 us for 2048 rows whatever the bandwidth); here the k neighbour indices are
 // read first and then U column steps x (K + 1) sources are in flight together.  Same comparisons in the same order (prototype
@@ -1831,6 +1916,46 @@ int egk_gather_max_fwd(egk_stream_t stream, const void* f, const float* bank, co
     EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(gather_max_fwd_kernel<T>, dim3(row_grid(rows)), dim3(256), 0, s, (const T*)f, bank,
                                              (const long long*)nn, (T*)m, arg, rows, cols, k));
     return check_launch("egk_gather_max_fwd");
+}
+
+int egk_retrieval_report(egk_stream_t stream, const egk_retrieval_task* tasks, int32_t count, int32_t rows, int32_t H, int32_t k,
+                         int32_t distance, int32_t dtype) {
+    EGK_REQUIRE(tasks, "egk_retrieval_report: null task list");
+    EGK_REQUIRE(count >= 1 && count <= EGK_RETRIEVAL_MAX_TASKS, "egk_retrieval_report: 1 .. %d tasks (got %d)", EGK_RETRIEVAL_MAX_TASKS,
+                count);
+    EGK_REQUIRE(rows >= 0, "egk_retrieval_report: rows >= 0 (got %d)", rows);
+    EGK_REQUIRE(H >= 1, "egk_retrieval_report: H >= 1 (got %d)", H);
+    EGK_REQUIRE(k >= 1 && k <= EGK_RETRIEVAL_MAX_K, "egk_retrieval_report: k in 1 .. %d (got %d)", EGK_RETRIEVAL_MAX_K, k);
+    EGK_REQUIRE(distance == 0 || distance == 1, "egk_retrieval_report: unknown distance %d (0 cosine, 1 l2)", distance);
+    EGK_REQUIRE(dtype == EGK_F32 || dtype == EGK_BF16, "egk_retrieval_report: unknown f_act dtype %d", dtype);
+    RetrievalTasks P{};
+    double bytes = 0;
+    for (int i = 0; i < count; ++i) {
+        const egk_retrieval_task& t = tasks[i];
+        EGK_REQUIRE(t.f && t.f_act && t.bank && t.nn, "egk_retrieval_report: null pointer (task %d)", i);
+        EGK_REQUIRE(t.K >= 1, "egk_retrieval_report: bank rows K >= 1 (task %d: %d)", i, t.K);
+        EGK_REQUIRE(t.reserved == 0, "egk_retrieval_report: the reserved field is 0 (task %d: %d)", i, t.reserved);
+        EGK_REQUIRE(t.f_ld >= H && t.f_act_ld >= H && t.bank_ld >= H,
+                    "egk_retrieval_report: leading dimension >= H (task %d: f %lld, f_act %lld, bank %lld, H %d)", i, (long long)t.f_ld,
+                    (long long)t.f_act_ld, (long long)t.bank_ld, H);
+        EGK_REQUIRE(t.nn_row_stride >= k, "egk_retrieval_report: nn row stride >= k (task %d: %lld, k %d)", i, (long long)t.nn_row_stride, k);
+        EGK_REQUIRE(t.dist || t.wins, "egk_retrieval_report: dist and wins are both null (task %d): nothing to report", i);
+        EGK_REQUIRE(!t.dist || t.dist_row_stride >= k, "egk_retrieval_report: dist row stride >= k (task %d: %lld, k %d)", i,
+                    (long long)t.dist_row_stride, k);
+        EGK_REQUIRE(!t.wins || t.wins_row_stride >= k + 1, "egk_retrieval_report: wins row stride >= k + 1 (task %d: %lld, k %d)", i,
+                    (long long)t.wins_row_stride, k);
+        EGK_REQUIRE(aligned_to(4u, {t.f, t.bank, t.dist, t.wins}) && aligned_to(dtype == EGK_BF16 ? 2u : 4u, {t.f_act}) && aligned_to(8u, {t.nn}),
+                    "egk_retrieval_report: misaligned pointer (task %d: f, bank, dist and wins 4-byte, f_act to its element, nn 8-byte)", i);
+        P.t[i] = t;
+        const double es = dtype == EGK_BF16 ? 2 : 4;
+        bytes += (double)rows * ((t.dist ? 4.0 * H * (k + 1) + 4.0 * k : 0) + (t.wins ? 4.0 * H * k + es * H + 4.0 * (k + 1) : 0) + 8.0 * k);
+    }
+    if (rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(KID_RETRIEVAL_REPORT, s, 0, bytes);
+    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL(retrieval_report_kernel<T>, dim3(row_grid(rows), count), dim3(256), 0, s, P, (int)rows, (int)H,
+                                             (int)k, (int)distance));
+    return check_launch("egk_retrieval_report");
 }
 
 int egk_gather_max_bwd(egk_stream_t stream, const void* dm, const uint8_t* arg, void* df, int32_t rows, int32_t cols,

@@ -62,6 +62,20 @@ def finalise_banks(banks: Dict[str, torch.Tensor], count: torch.Tensor) -> Dict[
     return {name: (bank[seen] / cnt).float() for name, bank in banks.items()}
 
 
+def bank_labels(dataloader, n_classes) -> torch.Tensor:
+    """The label of every bank row: the ascending int64 [K] of ``verb * |nouns| + noun`` over the labelled nodes (``y[:, 0] != -1``)
+    of the loader's batches -- exactly the rows ``finalise_banks`` keeps (``count > 0``), in its order, so row i of every bank is the
+    mean over the nodes labelled (``out[i] // |nouns|``, ``out[i] % |nouns|``).  ``n_classes``: (|verbs|, |nouns|).  Integer work
+    on the host; only the labels of the batches are read."""
+    n_verbs, n_nouns = (int(c) for c in n_classes)
+    seen = torch.zeros(n_verbs * n_nouns, dtype=torch.bool)
+    for data in dataloader:
+        y = data.y.detach().cpu().to(torch.int64)
+        y = y[y[:, 0] != -1]
+        seen[y[:, 0] * n_nouns + y[:, 1]] = True
+    return torch.nonzero(seen).reshape(-1)
+
+
 @torch.no_grad()
 def build_graphone(model, ar_task, tasks: List, dataloader, device="cuda", group=None) -> Dict[str, torch.Tensor]:
     logger.info("Building graphONE from tasks: %s", ", ".join(t.name for t in tasks))

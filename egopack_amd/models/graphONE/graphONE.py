@@ -19,6 +19,7 @@ under no_grad) and is a deterministic gather over the edge list grouped by proto
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 from typing import Dict, List, Literal, Tuple
 
@@ -67,6 +68,22 @@ class GraphONE(nn.Module):
         self._task_streams: List[torch.cuda.Stream] = []
         self._searched: Dict[tuple, tuple] = {}  # results of ``search_ahead`` waiting for their ``interact``
         self._forked = False  # the last ``_search_all`` ran on the task streams
+        self._recording = False  # ``record_retrieval``
+        self.last_retrieval: Dict[str, Dict[str, torch.Tensor]] = {}
+
+    @contextlib.contextmanager
+    def record_retrieval(self):
+        """While open, every ``interact`` in eval mode under ``no_grad`` keeps, per task, what it searched and found in
+        ``last_retrieval[task]``: ``features`` (the f32 [N, H] rows the search read), ``nn`` (the full int64 [N, k] list the stages
+        consumed) and ``features_act`` (the activation-type rows the first stage's gather-max read) -- the interaction's own tensors,
+        not a second search; a later ``interact`` replaces them.  ``last_retrieval`` is cleared on entry and keeps the last
+        interaction's tensors after exit.  The outputs of ``interact`` do not depend on it; nothing is kept in training."""
+        self.last_retrieval = {}
+        prev, self._recording = self._recording, True
+        try:
+            yield self.last_retrieval
+        finally:
+            self._recording = prev
 
     def _bank_norm(self, task: str) -> torch.Tensor:
         """Per-prototype 1/||p|| (cosine) or ||p||^2 (l2): cached while the bank is frozen, recomputed per call otherwise
@@ -105,6 +122,8 @@ class GraphONE(nn.Module):
                 main.wait_stream(st)
                 output[task].record_stream(main)
                 for a in closest[task][:1]:
+                    a.record_stream(main)
+                for a in self.last_retrieval.get(task, {}).values() if self._keeps() else ():
                     a.record_stream(main)
             return output, closest
         for task, f in items:
@@ -212,14 +231,23 @@ class GraphONE(nn.Module):
             out += list(nn_idx.values()) + list(f_act if isinstance(f_act, (list, tuple)) else [f_act])
         return out
 
+    def _keeps(self) -> bool:
+        return self._recording and not self.training and not torch.is_grad_enabled()
+
     def _task_interaction(self, task: str, features: torch.Tensor):
         bank = self.embeddings[task].weight
+        keep = self._keeps()
+        searched = features.detach()
+        if keep and searched.dtype != torch.float32:
+            searched = ops.to_act_f32(searched)  # (the widening the search makes itself: made here so that it can be kept)
         # the search reads the features as they are handed in: callers that want index selection independent of the
         # activation storage type pass the f32 output of the producing contraction (engine.EgoPackStep does)
         # (the bank is handed over as the parameter itself: its bf16 halves for the search product are cached on it)
-        nn_idx = ops.nearest_prototypes(features.detach(), bank, self.k, self.distance_func, self._bank_norm(task))
+        nn_idx = ops.nearest_prototypes(searched, bank, self.k, self.distance_func, self._bank_norm(task))
         assignments = [nn_idx[:, 0]] * self.depth  # the reference recomputes identical edges per depth
         f = ops.to_act(features)
+        if keep:
+            self.last_retrieval[task] = {"features": searched, "nn": nn_idx, "features_act": f.detach()}
         for stage in self.conv_stages[task]:
             m = ops.gather_max(f, bank, nn_idx)
             h = stage.module_0.combine(m, f)

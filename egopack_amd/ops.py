@@ -3965,6 +3965,59 @@ def topk_softmax(logits_list, k: int, want_prob: bool = True, want_lse: bool = F
     return outs
 
 
+# ---- retrieval report (include/egopack_retrieval.h) -------------------------------------------------------------------
+@torch.no_grad()
+def retrieval_report(feats, feats_act, banks, nns, distance_func: str = "cosine", want_dist: bool = True, want_wins: bool = True):
+    """What every node retrieved, for every auxiliary task in ONE launch: a list of (dist f32 [N, k] | None, wins int32 [N, k + 1] |
+    None), one entry per task.  ``feats``: the f32 [N, H] features the search read; ``feats_act``: the [N, H] activation-type features
+    the first GraphONE stage's gather-max read (f32 or bf16, one type for all tasks); ``banks``: f32 [K_t, H]; ``nns``: int64 [N, k]
+    lists with entries in 0 .. K_t - 1 (``GraphONE.last_retrieval`` holds all three as the interaction used them).  dist[n, j]: the
+    reference's distance ('cosine': 1 - cos similarity; 'l2': cdist / 4096) between node n and prototype nns[n, j]; wins[n, j]: the
+    number of channels in which source j (prototypes in list order, the node itself last) supplies the gather-max's maximum.  Views
+    with a unit column stride are read in place through their row stride."""
+    if distance_func not in ("cosine", "l2"):
+        raise ValueError(f"Unknown distance function: {distance_func}")
+    n = len(feats)
+    if not 1 <= n <= _lib.RETRIEVAL_MAX_TASKS:
+        raise ValueError(f"retrieval_report: 1 .. {_lib.RETRIEVAL_MAX_TASKS} tasks (got {n})")
+    if not (len(feats_act) == len(banks) == len(nns) == n):
+        raise ValueError("retrieval_report: one feature matrix, one activation matrix, one bank and one index list per task")
+    if not (want_dist or want_wins):
+        raise ValueError("retrieval_report: nothing to report (want_dist and want_wins are both off)")
+    N, H = feats[0].shape
+    k = int(nns[0].shape[1])
+    if not 1 <= k <= _lib.RETRIEVAL_MAX_K:
+        raise ValueError(f"retrieval_report: k in 1 .. {_lib.RETRIEVAL_MAX_K} (got {k})")
+    _need_gpu(*feats, *feats_act, *banks, *nns)
+    if any(t.dim() != 2 or tuple(t.shape) != (N, H) for t in (*feats, *feats_act)) or any(b.dim() != 2 or b.shape[1] != H for b in banks):
+        raise ValueError(f"retrieval_report: features of one [N, H] and banks of [K, H] (got {[tuple(t.shape) for t in (*feats, *feats_act, *banks)]})")
+    if any(tuple(i.shape) != (N, k) or i.dtype != torch.int64 for i in nns):
+        raise ValueError(f"retrieval_report: int64 index lists of one [N, k] (got {[(tuple(i.shape), i.dtype) for i in nns]})")
+    if any(t.dtype != torch.float32 for t in (*feats, *banks)):
+        raise TypeError("retrieval_report: the searched features and the banks are float32")
+    if len({a.dtype for a in feats_act}) > 1:
+        raise TypeError(f"retrieval_report: one activation type per launch (got {[a.dtype for a in feats_act]})")
+    feats, feats_act, banks = [_rm(f) for f in feats], [_rm(a) for a in feats_act], [_rm(b) for b in banks]
+    nns = [i if i.stride(1) == 1 and i.stride(0) >= k else i.contiguous() for i in nns]
+    dev = feats[0].device
+    outs = [(torch.empty((N, k), dtype=torch.float32, device=dev) if want_dist else None,
+             torch.empty((N, k + 1), dtype=torch.int32, device=dev) if want_wins else None) for _ in range(n)]
+    if N == 0:  # (no rows: nothing to launch, and an empty tensor has no pointer to hand over)
+        return outs
+    tasks = (_lib.RetrievalTask * n)()
+    ld = lambda m: max(m.stride(0), m.shape[1])  # (a one-row tensor's stride is arbitrary)
+    for t, f, a, b, i, (dist, wins) in zip(tasks, feats, feats_act, banks, nns, outs):
+        t.f, t.f_ld, t.f_act, t.f_act_ld, t.bank, t.bank_ld = _p(f), ld(f), _p(a), ld(a), _p(b), ld(b)
+        t.K, t.reserved, t.nn, t.nn_row_stride = b.shape[0], 0, _p(i), ld(i)
+        if want_dist:
+            t.dist, t.dist_row_stride = _p(dist), k
+        if want_wins:
+            t.wins, t.wins_row_stride = _p(wins), k + 1
+    _ck(_lib.load().egk_retrieval_report(_stream(), tasks, n, N, H, k, int(distance_func == "l2"), _dt(feats_act[0])),
+        "egk_retrieval_report")
+    return outs
+
+
 # ---- phase stamps (development) ---------------------------------------------------------------------------------
 _stamps = {"buf": None, "names": []}
 

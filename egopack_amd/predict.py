@@ -217,7 +217,8 @@ def _by_sample(sample: torch.Tensor):
 def to_json(task: str, pred: dict, dataset) -> dict:
     """The JSON document of a task's predictions, keyed by ``dataset.sample_id(i)`` when the dataset has such a method, else
     ``str(i)``.  LTA: {"verb": K lists of Z ints, "noun": K lists of Z ints} (the challenge's shape); AR: the per-node top-k lists;
-    OSCC: {"state_change", "prob"}; PNR: {"pnr_frame", "node", "prob"}."""
+    OSCC: {"state_change", "prob"}; PNR: {"pnr_frame", "node", "prob"}.  A file with retrieval fields (predict_egopack.py) also gets
+    ``"retrieval"`` per sample: {"pos": its nodes, <aux task>: {"index", "dist", "wins"[, "label"]} per node}."""
     doc = {}
     if task == "lta":
         for s, v, n in zip(pred["futures_sample"].tolist(), pred["verb_futures"], pred["noun_futures"]):
@@ -234,6 +235,14 @@ def to_json(task: str, pred: dict, dataset) -> dict:
             doc[_key(dataset, s)] = {"pnr_frame": float(f), "node": int(n), "prob": float(p)}
     else:
         raise ValueError(f"to_json: unknown task {task!r}")
+    if "retrieval_sample" in pred:  # (a file of predict_egopack.py: what every node of the sample retrieved, per auxiliary task)
+        aux = sorted(f[len("retrieval_"):-len("_index")] for f in pred if f.startswith("retrieval_") and f.endswith("_index"))
+        for s, rows in _by_sample(pred["retrieval_sample"]).items():
+            entry = {"pos": pred["retrieval_pos"][rows].tolist()}
+            for a in aux:
+                entry[a] = {f: pred[f"retrieval_{a}_{f}"][rows].tolist() for f in ("index", "dist", "wins", "label")
+                            if f"retrieval_{a}_{f}" in pred}
+            doc.setdefault(_key(dataset, s), {})["retrieval"] = entry
     return doc
 
 
@@ -244,6 +253,38 @@ def _class_names(task: str, dataset):
     if task == "oscc" and getattr(dataset, "oscc_class_labels", None) is not None:
         return list(dataset.oscc_class_labels)
     return None
+
+
+def predict_task(t: str, model, dataloader, dataset, task, pc: dict, ls: dict, device, **fusion) -> dict:
+    """The loop of task ``t`` with the entry points' arguments (``pc``: ``predict_config``, ``ls``: ``train.lta_sampling_config``).
+    ``fusion``: ``other_tasks`` / ``graphone`` / ``late_fusion`` of the loops, for a model with a GraphONE."""
+    names = getattr(dataset, "label_names", None)
+    heads = (names.index("verbs"), names.index("nouns")) if names else (0, 1)
+    if t == "ar":
+        return predict_heads(model, dataloader, task, k=pc["topk"], device=device, head_index=heads, **fusion)
+    if t == "lta":
+        from .meters import LTAMeter
+        return predict_lta(model, dataloader, task, k=pc["topk"], seed=ls["seed"], n_nodes=int(getattr(dataset, "lta_nodes", LTAMeter.N_NODES)),
+                           n_futures=LTAMeter.N_SAMPLES, device=device, head_index=heads, **fusion)
+    if t == "oscc":
+        return predict_oscc(model, dataloader, task, device=device, **fusion)
+    return predict_pnr(model, dataloader, task, device=device, **fusion)
+
+
+def write_predictions(t: str, pred: dict, dataset, pc: dict, ls: dict, ck: dict, out_dir: Path, seconds: float, **extra):
+    """``predictions_<t>.pt`` (and ``.json``): (the saved document, its path).  ``extra``: further entries of the document."""
+    doc = {**pred, "topk": pc["topk"], "seed": ls["seed"], "split": pc["split"], "epoch": ck.get("epoch"), **extra}
+    names = _class_names(t, dataset)
+    if names is not None:
+        doc["class_names"] = names
+    path = out_dir / f"predictions_{t}.pt"
+    torch.save(doc, path)
+    if pc["json"]:
+        with open(out_dir / f"predictions_{t}.json", "w") as f:
+            json.dump(to_json(t, pred, dataset), f)
+    n = next(iter(pred.values())).shape[0] if pred else 0
+    logger.info("[predict %s] %d rows of split '%s' in %.1f ms -> %s", t, n, pc["split"], seconds * 1e3, path)
+    return doc, path
 
 
 def main(argv=None):
@@ -261,8 +302,8 @@ def main(argv=None):
     if not cfg.get("resume_from"):
         raise ValueError("predict: resume_from=<checkpoint> is required (there is nothing to predict with untrained weights)")
     if cfg.get("enable_graphone", False):
-        raise ValueError("predict: enable_graphone=True is not supported yet (the entry point builds no GraphONE; the loops of "
-                         "egopack_amd.predict take one as an argument)")
+        raise ValueError("predict: enable_graphone=True is not served here (this entry point builds no GraphONE): an EgoPack "
+                         "checkpoint is exported by predict_egopack.py")
     T.setup_logging(rank)
     T.cap_host_threads(int(cfg.get("host_threads", 8)))
     T.seed_everything(cfg, rank)
@@ -295,38 +336,13 @@ def main(argv=None):
     out_dir = Path(pc["out"]) if pc["out"] else Path(cfg.resume_from).resolve().parent / "predictions"
     out_dir.mkdir(parents=True, exist_ok=True)
 
-    def heads_of(ds):
-        names = getattr(ds, "label_names", None)
-        return (names.index("verbs"), names.index("nouns")) if names else (0, 1)
-
     results, paths, seconds = {}, {}, {}
     for t in enabled:
-        ds, dl = dsets[t], loaders[t]
         t0 = time.perf_counter()
-        if t == "ar":
-            pred = predict_heads(model, dl, tasks[t], k=pc["topk"], device=device, head_index=heads_of(ds))
-        elif t == "lta":
-            from .meters import LTAMeter
-            pred = predict_lta(model, dl, tasks[t], k=pc["topk"], seed=ls["seed"], n_nodes=int(getattr(ds, "lta_nodes", LTAMeter.N_NODES)),
-                               n_futures=LTAMeter.N_SAMPLES, device=device, head_index=heads_of(ds))
-        elif t == "oscc":
-            pred = predict_oscc(model, dl, tasks[t], device=device)
-        else:
-            pred = predict_pnr(model, dl, tasks[t], device=device)
+        pred = predict_task(t, model, loaders[t], dsets[t], tasks[t], pc, ls, device)
         torch.cuda.synchronize()
         seconds[t] = time.perf_counter() - t0
-        doc = {**pred, "topk": pc["topk"], "seed": ls["seed"], "split": pc["split"], "epoch": ck.get("epoch")}
-        names = _class_names(t, ds)
-        if names is not None:
-            doc["class_names"] = names
-        paths[t] = out_dir / f"predictions_{t}.pt"
-        torch.save(doc, paths[t])
-        if pc["json"]:
-            with open(out_dir / f"predictions_{t}.json", "w") as f:
-                json.dump(to_json(t, pred, ds), f)
-        n = next(iter(pred.values())).shape[0] if pred else 0
-        logger.info("[predict %s] %d rows of split '%s' in %.1f ms -> %s", t, n, pc["split"], seconds[t] * 1e3, paths[t])
-        results[t] = doc
+        results[t], paths[t] = write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t])
     return {"predictions": results, "paths": paths, "out": out_dir, "seconds": seconds, "model": model, "tasks": tasks,
             "datasets": dsets, "loaders": loaders}
 

@@ -1,1 +1,1 @@
-from egopack_amd.graphone import build_graphone  # noqa: F401
+from egopack_amd.graphone import bank_labels, build_graphone  # noqa: F401

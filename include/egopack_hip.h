@@ -767,5 +767,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* the prediction export: the best k classes of every row of every head in the meters' order, their softmax probabilities and the
  * log-sum-exp of the loss kernels, in one launch (egk_topk_softmax) */
 #include "egopack_topk.h"
+/* the retrieval report of a GraphONE prediction: per node and auxiliary task the distances of the prototypes it consulted and the
+ * number of channels each of them supplies to the first stage's max aggregation, in one launch (egk_retrieval_report) */
+#include "egopack_retrieval.h"
 
 #endif /* EGOPACK_HIP_H */
