@@ -6,6 +6,7 @@ kind (the CPU oracle under oracle/ is test infrastructure and is never imported 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import re
 from pathlib import Path
@@ -18,18 +19,10 @@ import torch  # noqa: F401
 
 HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["EGK_LIB_PATH"]) if os.environ.get("EGK_LIB_PATH") else HERE / "libegopack_hip.so"  # (env: development A/B of two builds)
-HEADER = HERE.parent / "include" / "egopack_hip.h"
-OPTIM_HEADER = HERE.parent / "include" / "egopack_optim.h"  # included by egopack_hip.h; its symbols: OPTIM_SIGNATURES
-OPTIM_GROUPS_HEADER = HERE.parent / "include" / "egopack_optim_groups.h"  # likewise; its symbols: OPTIM_GROUPS_SIGNATURES
-
-EMA_HEADER = HERE.parent / "include" / "egopack_ema.h"  # likewise; its symbols: EMA_SIGNATURES
-CE_BALANCED_HEADER = HERE.parent / "include" / "egopack_ce_balanced.h"  # likewise; its symbols: CE_BALANCED_SIGNATURES
-BCE_BALANCED_HEADER = HERE.parent / "include" / "egopack_bce_balanced.h"  # likewise; its symbols: BCE_BALANCED_SIGNATURES
-TASK_SCALE_HEADER = HERE.parent / "include" / "egopack_task_scale.h"  # likewise; its symbols: TASK_SCALE_SIGNATURES
-SAMPLE_HEADER = HERE.parent / "include" / "egopack_sample.h"  # likewise; its symbols: SAMPLE_SIGNATURES
-CLASS_REPORT_HEADER = HERE.parent / "include" / "egopack_class_report.h"  # likewise; its symbols: CLASS_REPORT_SIGNATURES
-TOPK_HEADER = HERE.parent / "include" / "egopack_topk.h"  # likewise; its symbols: TOPK_SIGNATURES
-RETRIEVAL_HEADER = HERE.parent / "include" / "egopack_retrieval.h"  # likewise; its symbols: RETRIEVAL_SIGNATURES
+# The headers ARE the table of the C ABI: load() binds every prototype they declare (signatures() below).  A C user includes
+# the first, which includes the others; a new header is one more key here.
+HEADERS = {key: HERE.parent / "include" / f"egopack_{key}.h" for key in (
+    "hip", "optim", "optim_groups", "ema", "ce_balanced", "bce_balanced", "task_scale", "sample", "class_report", "topk", "retrieval")}
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -146,254 +139,84 @@ CLASS_REPORT_MAX_TASKS = 8  # EGK_CLASS_REPORT_MAX_TASKS (include/egopack_class_
 SAMPLE_MAX_TASKS, SAMPLE_MAX_K = 8, 1024  # EGK_SAMPLE_MAX_* (include/egopack_sample.h)
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2  # EGK_OPT_* (include/egopack_optim.h)
 
-# name -> (restype, argtypes); mirrors include/egopack_hip.h one to one
-SIGNATURES = {
-    "egk_version": (C.c_int, []),
-    "egk_last_error": (C.c_char_p, []),
-    "egk_prof_enable": (C.c_int, [C.c_int]),
-    "egk_prof_reset": (C.c_int, []),
-    "egk_prof_count": (C.c_int, []),
-    "egk_prof_get": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(i64), C.POINTER(C.c_double),
-                               C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "egk_stamp": (C.c_int, [vp, vp, i32]),
-    "egk_tee_split_next": (C.c_int, [vp, vp, i64]),
-    "egk_gemm": (C.c_int, [vp, C.POINTER(GemmDesc)]),
-    "egk_gemm_stats_blocks": (C.c_int, [C.POINTER(GemmDesc)]),
-    "egk_gemm_grouped": (C.c_int, [vp, C.POINTER(GemmDesc), i32]),
-    "egk_gemm_ws_bytes": (i64, [C.POINTER(GemmDesc)]),
-    "egk_gemm_splitk": (C.c_int, [i32, i32, i32, i32]),
-    "egk_gemm_set_pipeline": (C.c_int, [i32]),
-    "egk_colsum_ws_len": (C.c_int, [i32, i32]),
-    "egk_colsum": (C.c_int, [vp, vp, i64, i32, i32, vp, i32, vp, i32]),
-    "egk_rowln_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, f32, u64, u64, vp, i32]),
-    "egk_rowln_bwd_ws_rows": (C.c_int, [i32]),
-    "egk_rowln_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
-    "egk_ln_bwd_reduce": (C.c_int, [vp, vp, vp, vp, i32, i32, i32]),
-    "egk_ln_bwd_reduce_multi": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32]),
-    "egk_rowln_group_fwd": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, i32, i32]),
-    "egk_rowln_group_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32]),
-    "egk_graphln_ws_bytes": (i64, [i32, i32, i32]),
-    "egk_graphln_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32]),
-    "egk_graphln_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32]),
-    "egk_rowdot_ws_rows": (i32, [i32]),
-    "egk_rowdot_bce": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32]),
-    "egk_rowdot_reduce": (C.c_int, [vp, vp, vp, vp, i32, i32]),
-    "egk_rowdot_ce2_max_rows": (i32, []),
-    "egk_rowdot_ce2": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32]),
-    "egk_rowdot_ce2_multi": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32]),
-    "egk_graphln_stats_blocks": (i32, [i32]),
-    "egk_graphln_stats": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, i32]),
-    "egk_graphln_bwd_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i32]),
-    "egk_graphln_bwd_finish": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, i32]),
-    "egk_graphln_fwd_apply": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, i32]),
-    "egk_graphln_bwd_apply": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, i32]),
-    "egk_pe_table": (C.c_int, [vp, vp, i64, i32, i32, vp]),
-    "egk_pe_add_table": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, i32, i32, i32]),
-    "egk_pe_add": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32]),
-    "egk_csr_gather": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, i32]),
-    "egk_csr_gather_banded": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, i32]),
-    "egk_csr_heavy_ws_bytes": (i64, [i32, i32]),
-    "egk_csr_heavy_threshold": (i32, []),
-    "egk_gather_max_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
-    "egk_gather_max_group_fwd": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32]),
-    "egk_gather_max_tune": (C.c_int, [i32]),
-    "egk_gather_max_bwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32]),
-    "egk_segment_max_fwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32]),
-    "egk_segment_max_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32]),
-    "egk_segment_max_multi_fwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32]),
-    "egk_segment_max_multi_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
-    "egk_row_inv_norm": (C.c_int, [vp, vp, vp, i32, i32, i32]),
-    "egk_cos_dist": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, i32]),
-    "egk_topk_smallest": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, i32, i32]),
-    "egk_row_sq_norm": (C.c_int, [vp, vp, vp, i32, i32, i32]),
-    "egk_topk_smallest_l2": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, i32, i32]),
-    "egk_topk_window": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
-    "egk_gemm_defer_reduce_next": (C.c_int, [i32]),
-    "egk_slab_input_next": (C.c_int, [vp, vp, vp]),
-    "egk_gemm_reduce_slabs": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i64]),
-    "egk_topk_window_group": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
-    "egk_topk_window_group16": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32]),
-    "egk_residual_ratio16": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, i32]),
-    "egk_cast_f16": (C.c_int, [vp, vp, vp, i64]),
-    "egk_row_inv_norm_cast": (C.c_int, [vp, vp, vp, vp, vp, i32, i32]),
-    "egk_bf16_residual_ratio": (C.c_int, [vp, vp, i64, vp, vp, i32, i32]),
-    "egk_gather_max_bank_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
-    "egk_segment_sum_rows_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32]),
-    "egk_onehot_sigmoid_loss_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, f32, f32]),
-    "egk_onehot_sigmoid_loss_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32]),
-    "egk_ce_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i32, i32, f32, i32]),
-    "egk_ce_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, f32, i32]),
-    "egk_ce_fused_multi": (C.c_int, [vp, vp, i32, f32, i32]),
-    "egk_ce_fused": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, i64, i32, f32, f32, i32]),
-    "egk_bce_fwd": (C.c_int, [vp, vp, vp, vp, i32]),
-    "egk_bce_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32]),
-    "egk_dropout_fwd": (C.c_int, [vp, vp, vp, vp, i64, f32, u64, u64, vp, i32]),
-    "egk_dropout_bwd": (C.c_int, [vp, vp, vp, vp, i64, f32, i32]),
-    "egk_relu_gate": (C.c_int, [vp, vp, vp, vp, i64, i32]),
-    "egk_cast": (C.c_int, [vp, vp, i32, vp, i32, i64]),
-    "egk_split_bf16": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, i64]),
-    "egk_host_bounded_draws": (i64, [vp, vp, vp, i64, i32, vp]),
-    "egk_host_window_rows": (i64, [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
-    "egk_host_build_batch": (i64, [C.POINTER(HostDataset), vp, vp, vp, i64, C.POINTER(HostBatch)]),
-    "egk_host_batch_sizes": (i64, [C.POINTER(HostDataset), vp, i64, vp]),
-    "egk_host_merge_batches": (i64, [C.POINTER(HostPart), i32, C.POINTER(HostMerged)]),
-    "egk_tune": (C.c_int, [i32, i32]),
-    "egk_weighted_sums": (C.c_int, [vp, vp, vp, vp, i32, vp]),
-    "egk_weighted_sums_acc": (C.c_int, [vp, vp, vp, vp, i32, vp, vp]),
-    "egk_fill_scaled_multi": (C.c_int, [vp, vp, vp, vp, vp, i32]),
-    "egk_copy_blocks": (C.c_int, [vp, vp, vp, vp, i32]),
-    "egk_gather_rows": (C.c_int, [vp, vp, i32, i64, i64, vp, vp, i32, i64, i32]),
-    "egk_gather_lerp_rows": (C.c_int, [vp, vp, i32, i64, i64, vp, vp, vp, vp, i32, i64, i32]),
-    "egk_label_rank": (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i32]),
-    "egk_edit_distance": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, vp, i32, i32, i32]),
-    "egk_cast_rows": (C.c_int, [vp, vp, i32, i64, vp, i32, i64, i32, i32, i32]),
-    "egk_axpby": (C.c_int, [vp, vp, vp, vp, i64, f32, f32]),
-    "egk_fill_scaled": (C.c_int, [vp, vp, f32, vp, i64]),
-    "egk_sum_scale": (C.c_int, [vp, vp, vp, i64, f32, i32]),
-    "egk_adam_step": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, f32, f32, f32, f32, vp]),
-    "egk_zero_fill": (C.c_int, [vp, vp, i64]),
-    "egk_zero_fill_ranges": (C.c_int, [vp, vp, vp, vp, i32]),
-    "egk_adam_step_bump": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, f32, f32, f32, f32, vp, vp, vp, i64]),
-    "egk_adam_hyper": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp]),
-    "egk_grad_sumsq_slots": (C.c_int, [i64]),
-    "egk_grad_sumsq": (C.c_int, [vp, vp, i32, i64, vp, i32]),
-    "egk_grad_norm_finalize": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp]),
-    "egk_adam_step_gated": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, f32, f32, f32, f32, vp, vp, vp, i64, vp]),
-}
+# C typedef name -> Structure: what a ``const egk_x*`` parameter binds to, and what tests/test_cabi.py compares with the header field by field
+STRUCTS = {"egk_gemm_desc": GemmDesc, "egk_host_dataset": HostDataset, "egk_host_batch": HostBatch, "egk_host_part": HostPart,
+           "egk_host_merged": HostMerged, "egk_ce_task": CETask, "egk_ce_w_task": CEWTask, "egk_optim_desc": OptimDesc,
+           "egk_optim_groups": OptimGroups, "egk_ema_desc": EmaDesc, "egk_sample_task": SampleTask,
+           "egk_class_report_task": ClassReportTask, "egk_topk_task": TopkTask, "egk_retrieval_task": RetrievalTask}
+
+# ---- the prototypes of the headers as ctypes signatures ---------------------------------------------------------------------------
+SCALARS = {"int": C.c_int, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32, "double": C.c_double, "egk_stream_t": vp}
+POINTEES = {"void", "float", "double", "int32_t", "int64_t", "uint8_t", "uint32_t", "uint64_t"}  # T*, T* const*, ... -> c_void_p
 
 
-# ... and include/egopack_optim.h, the header egopack_hip.h includes (its own table: the ledgers of the two headers are separate)
-OPTIM_SIGNATURES = {
-    "egk_optim_step": (C.c_int, [vp, C.POINTER(OptimDesc)]),
-}
+def strip_c(text: str) -> str:
+    """C text without its comments and preprocessor lines."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    return re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
 
 
-# ... and include/egopack_optim_groups.h (the third ledger: tests/test_param_groups_cpu.py over tests/test_gpu_bounds_param_groups.py)
-OPTIM_GROUPS_SIGNATURES = {
-    "egk_optim_step_groups": (C.c_int, [vp, C.POINTER(OptimDesc), C.POINTER(OptimGroups)]),
-}
+def ctype_of(decl: str, where: str):
+    """The ctypes type of one C parameter (its name dropped), return type or struct field type.  The rules are fixed: a scalar of
+    SCALARS; one pointer to a struct of STRUCTS -> POINTER(Structure); char* -> c_char_p; any other pointer, of any depth, to a
+    type of POINTEES -> c_void_p.  Everything else raises: a type nobody listed never becomes c_void_p silently."""
+    tokens = [t for t in re.findall(r"\w+|\S", decl) if t != "const"]
+    if len(tokens) > 1 and re.fullmatch(r"\w+", tokens[-1]):
+        tokens.pop()  # the parameter's name
+    base, depth = [t for t in tokens if t != "*"], tokens.count("*")
+    if len(base) == 1 and re.fullmatch(r"\w+", base[0]):
+        if depth == 0 and base[0] in SCALARS:
+            return SCALARS[base[0]]
+        if depth == 1 and base[0] in STRUCTS:
+            return C.POINTER(STRUCTS[base[0]])
+        if depth == 1 and base[0] == "char":
+            return C.c_char_p
+        if depth >= 1 and base[0] in POINTEES:
+            return vp
+    raise TypeError(f"{where}: no ctypes rule for '{decl.strip()}'")
 
 
-# ... and include/egopack_ema.h (the fourth ledger: tests/test_ema_cpu.py over tests/test_gpu_bounds_ema.py)
-EMA_SIGNATURES = {
-    "egk_optim_step_ema": (C.c_int, [vp, C.POINTER(OptimDesc), C.POINTER(OptimGroups), C.POINTER(EmaDesc)]),
-    "egk_ema_swap": (C.c_int, [vp, vp, vp, i64]),
-}
+def parse_prototypes(text: str, where: str = "<text>") -> dict:
+    """name -> (restype, argtypes) of every ``ret egk_name(args);`` of a header's text.  A statement with a parenthesis that is not
+    such a prototype, a type ctype_of() refuses and a name declared twice raise, naming ``where``, the function and the text."""
+    text = re.sub(r'extern\s*"C"\s*\{', " ", strip_c(text))
+    text = re.sub(r"\{[^{}]*\}", " ", text).replace("}", " ")  # struct and enum bodies; the closing brace of extern "C"
+    out = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if "(" not in stmt or stmt.startswith("typedef "):
+            continue
+        m = re.fullmatch(r"(.+?)\b(egk_\w+) ?\((.*)\)", stmt)
+        if m is None:
+            raise TypeError(f"{where}: not a prototype of an egk_ entry point: '{stmt}'")
+        ret, name, args = m.groups()
+        if name in out:
+            raise TypeError(f"{where}: {name} is declared twice")
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        out[name] = (ctype_of(ret + " ", f"{where}: return type of {name}"), [ctype_of(a, f"{where}: {name}") for a in args])
+    return out
 
 
-# ... and include/egopack_ce_balanced.h (the fifth ledger: tests/test_class_balance_cpu.py over tests/test_gpu_bounds_class_balance.py)
-CE_BALANCED_SIGNATURES = {
-    "egk_ce_w_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, i32, f32, i32]),
-    "egk_ce_w_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, f32, i32]),
-    "egk_ce_w_fused_multi": (C.c_int, [vp, C.POINTER(CEWTask), i32, f32, i32]),
-}
+@functools.lru_cache(maxsize=None)
+def signatures() -> dict:
+    """header key -> {name: (restype, argtypes)}, parsed from the files of HEADERS (once)."""
+    out, owner = {}, {}
+    for key, path in HEADERS.items():
+        if not path.exists():
+            raise RuntimeError(f"{path} is missing: it is header '{key}' of the C ABI, and the binding of libegopack_hip.so is "
+                               "read from the headers (there is no second table).")
+        out[key] = parse_prototypes(path.read_text(), path.name)
+        for name in out[key]:
+            if name in owner:
+                raise RuntimeError(f"{name} is declared in {HEADERS[owner[name]].name} and again in {path.name}")
+            owner[name] = key
+    return out
 
 
-# ... and include/egopack_bce_balanced.h (the sixth ledger: tests/test_pnr_balance_cpu.py over tests/test_gpu_bounds_pnr_balance.py)
-BCE_BALANCED_SIGNATURES = {
-    "egk_bce_w_fwd": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, f32]),
-    "egk_bce_w_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, f32, f32, f32, i32]),
-    "egk_rowdot_bce_w": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, i32]),
-}
-
-
-# ... and include/egopack_task_scale.h (the seventh ledger: tests/test_task_weighting_cpu.py over tests/test_gpu_bounds_task_weighting.py)
-TASK_SCALE_SIGNATURES = {
-    "egk_ce_fused_multi_s": (C.c_int, [vp, vp, vp, i32, f32, i32]),
-    "egk_ce_w_fused_multi_s": (C.c_int, [vp, C.POINTER(CEWTask), vp, i32, f32, i32]),
-    "egk_rowdot_bce_s": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, i32]),
-    "egk_rowdot_bce_w_s": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, f32, f32, f32, i32]),
-    "egk_rowdot_ce2_s": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, i32]),
-    "egk_rowdot_ce2_multi_s": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32]),
-    "egk_task_scale_prepare": (C.c_int, [vp, vp, vp, i32]),
-    "egk_task_scale_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]),
-    "egk_fill_scaled_from": (C.c_int, [vp, vp, i64, f32, vp]),
-}
-
-
-# ... and include/egopack_sample.h (the eighth ledger: tests/test_lta_sampling_cpu.py over tests/test_gpu_bounds_lta_sampling.py)
-SAMPLE_SIGNATURES = {
-    "egk_categorical_sample": (C.c_int, [vp, C.POINTER(SampleTask), i32, i32, i32, u64, i64, i64, i32]),
-}
-
-
-# ... and include/egopack_class_report.h (the ninth ledger: tests/test_class_report_cpu.py over tests/test_gpu_bounds_class_report.py)
-CLASS_REPORT_SIGNATURES = {
-    "egk_class_report": (C.c_int, [vp, C.POINTER(ClassReportTask), i32]),
-}
-
-
-# ... and include/egopack_topk.h (the tenth ledger: tests/test_topk_cpu.py over tests/test_gpu_bounds_topk.py)
-TOPK_SIGNATURES = {
-    "egk_topk_softmax": (C.c_int, [vp, C.POINTER(TopkTask), i32, i32, i32, i32]),
-}
-
-
-# ... and include/egopack_retrieval.h (the eleventh ledger: tests/test_retrieval_cpu.py over tests/test_gpu_bounds_retrieval.py)
-RETRIEVAL_SIGNATURES = {
-    "egk_retrieval_report": (C.c_int, [vp, C.POINTER(RetrievalTask), i32, i32, i32, i32, i32, i32]),
-}
-
-
-def _declared(header: Path) -> list:
-    text = header.read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(egk_[a-z0-9_]+)\s*\(", text)))
-
-
-def header_symbols() -> list:
-    """Every function name declared in include/egopack_hip.h."""
-    return _declared(HEADER)
-
-
-def optim_header_symbols() -> list:
-    """Every function name declared in include/egopack_optim.h."""
-    return _declared(OPTIM_HEADER)
-
-
-def optim_groups_header_symbols() -> list:
-    """Every function name declared in include/egopack_optim_groups.h."""
-    return _declared(OPTIM_GROUPS_HEADER)
-
-
-def ema_header_symbols() -> list:
-    """Every function name declared in include/egopack_ema.h."""
-    return _declared(EMA_HEADER)
-
-
-def ce_balanced_header_symbols() -> list:
-    """Every function name declared in include/egopack_ce_balanced.h."""
-    return _declared(CE_BALANCED_HEADER)
-
-
-def bce_balanced_header_symbols() -> list:
-    """Every function name declared in include/egopack_bce_balanced.h."""
-    return _declared(BCE_BALANCED_HEADER)
-
-
-def task_scale_header_symbols() -> list:
-    """Every function name declared in include/egopack_task_scale.h."""
-    return _declared(TASK_SCALE_HEADER)
-
-
-def sample_header_symbols() -> list:
-    """Every function name declared in include/egopack_sample.h."""
-    return _declared(SAMPLE_HEADER)
-
-
-def class_report_header_symbols() -> list:
-    """Every function name declared in include/egopack_class_report.h."""
-    return _declared(CLASS_REPORT_HEADER)
-
-
-def topk_header_symbols() -> list:
-    """Every function name declared in include/egopack_topk.h."""
-    return _declared(TOPK_HEADER)
-
-
-def retrieval_header_symbols() -> list:
-    """Every function name declared in include/egopack_retrieval.h."""
-    return _declared(RETRIEVAL_HEADER)
+def declared(key: str | None = None) -> list:
+    """The sorted entry-point names of one header, or those of all headers in the order of HEADERS."""
+    sigs = signatures()
+    return sorted(sigs[key]) if key is not None else [name for k in sigs for name in sorted(sigs[k])]
 
 
 _lib = None
@@ -409,13 +232,11 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m egopack_amd.build` "
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in [*SIGNATURES.items(), *OPTIM_SIGNATURES.items(), *OPTIM_GROUPS_SIGNATURES.items(),
-                              *EMA_SIGNATURES.items(), *CE_BALANCED_SIGNATURES.items(), *BCE_BALANCED_SIGNATURES.items(),
-                              *TASK_SCALE_SIGNATURES.items(), *SAMPLE_SIGNATURES.items(), *CLASS_REPORT_SIGNATURES.items(),
-                              *TOPK_SIGNATURES.items(), *RETRIEVAL_SIGNATURES.items()]:
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
+    for table in signatures().values():  # (raises for a missing header and for a name two headers declare)
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -24,8 +24,9 @@
  * egk_bce_fwd / _bwd with the loss expression switched by a template flag (csrc/loss.hip); the plain entry points compute what
  * they computed: a caller that passes no scalar runs them.
  *
- * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_pnr_balance.py and their ledger in
- * tests/test_pnr_balance_cpu.py, in the form of the five older ledgers.  Profile id "bce_balanced" counts all three.
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_pnr_balance.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "bce_balanced" (egopack_amd/_lib.py binds them from the prototypes below).
+ * Profile id "bce_balanced" counts all three.
  */
 #ifndef EGOPACK_BCE_BALANCED_H
 #define EGOPACK_BCE_BALANCED_H

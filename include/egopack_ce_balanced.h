@@ -20,8 +20,9 @@
  * grid of the plain entry points, whose kernels these are with the vectors switched on by a template flag (csrc/loss.hip); a
  * caller that passes no vector runs the plain instantiation and gets the bits it always got.
  *
- * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_class_balance.py and their ledger in
- * tests/test_class_balance_cpu.py, in the form of the four older ledgers.  Profile id "ce_balanced" counts all three.
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_class_balance.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "ce_balanced" (egopack_amd/_lib.py binds them from the prototypes below).
+ * Profile id "ce_balanced" counts all three.
  */
 #ifndef EGOPACK_CE_BALANCED_H
 #define EGOPACK_CE_BALANCED_H

@@ -27,8 +27,9 @@
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no workspace, no synchronisation, capturable; 0 = ok,
  * negative = EGK_E*, positive = hipError_t; a launch touches only what its arguments name).
  *
- * The entry point of THIS header has its guard-band cases in tests/test_gpu_bounds_class_report.py and its ledger in
- * tests/test_class_report_cpu.py, in the form of the eight older ledgers.  Profile id "class_report".
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_class_report.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "class_report" (egopack_amd/_lib.py binds them from the prototypes below).
+ * Profile id "class_report".
  */
 #ifndef EGOPACK_CLASS_REPORT_H
 #define EGOPACK_CLASS_REPORT_H

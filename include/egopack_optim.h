@@ -6,9 +6,8 @@
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no synchronisation, capturable; 0 = ok, negative =
  * EGK_E*, positive = hipError_t; a launch touches only what its arguments name).
  *
- * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_optim.py and their ledger in
- * tests/test_optim_rules_cpu.py (the ledger of egopack_hip.h is tests/test_cabi.py over tests/test_gpu_bounds.py), in the same
- * form: header and cases fold into the older files by moving text.
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_optim.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "optim" (egopack_amd/_lib.py binds them from the prototypes below).
  */
 #ifndef EGOPACK_OPTIM_H
 #define EGOPACK_OPTIM_H

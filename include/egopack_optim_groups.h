@@ -8,8 +8,8 @@
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no synchronisation, capturable; 0 = ok, negative =
  * EGK_E*, positive = hipError_t; a launch touches only what its arguments name).
  *
- * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_param_groups.py and their ledger in
- * tests/test_param_groups_cpu.py, in the form of the two older ledgers (tests/test_cabi.py, tests/test_optim_rules_cpu.py).
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_param_groups.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "optim_groups" (egopack_amd/_lib.py binds them from the prototypes below).
  */
 #ifndef EGOPACK_OPTIM_GROUPS_H
 #define EGOPACK_OPTIM_GROUPS_H

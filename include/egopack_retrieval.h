@@ -28,8 +28,9 @@
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no workspace, no synchronisation, capturable; 0 = ok,
  * negative = EGK_E*, positive = hipError_t; a launch touches only what its arguments name).
  *
- * The entry point of THIS header has its guard-band cases in tests/test_gpu_bounds_retrieval.py and its ledger in
- * tests/test_retrieval_cpu.py, in the form of the ten older ledgers.  Profile id "retrieval_report".
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_retrieval.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "retrieval" (egopack_amd/_lib.py binds them from the prototypes below).
+ * Profile id "retrieval_report".
  */
 #ifndef EGOPACK_RETRIEVAL_H
 #define EGOPACK_RETRIEVAL_H

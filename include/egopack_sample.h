@@ -37,8 +37,9 @@
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no workspace, no synchronisation, capturable; 0 = ok,
  * negative = EGK_E*, positive = hipError_t; a launch touches only what its arguments name).
  *
- * The entry point of THIS header has its guard-band cases in tests/test_gpu_bounds_lta_sampling.py and its ledger in
- * tests/test_lta_sampling_cpu.py, in the form of the seven older ledgers.  Profile id "categorical_sample".
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_lta_sampling.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "sample" (egopack_amd/_lib.py binds them from the prototypes below).
+ * Profile id "categorical_sample".
  */
 #ifndef EGOPACK_SAMPLE_H
 #define EGOPACK_SAMPLE_H

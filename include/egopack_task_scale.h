@@ -23,8 +23,9 @@
  * of egopack_hip.h hold here word for word (stream-ordered, no allocation, no synchronisation, capturable; 0 = ok, negative =
  * EGK_E*, positive = hipError_t; a launch touches only what its arguments name).  A scale pointer must be 4-byte aligned.
  *
- * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_task_weighting.py and their ledger in
- * tests/test_task_weighting_cpu.py, in the form of the six older ledgers.  Profile id "task_scale" counts all of them.
+ * The entry points of THIS header have their guard-band cases in tests/test_gpu_bounds_task_weighting.py; the one ledger of all
+ * headers, tests/test_cabi.py, holds them under the key "task_scale" (egopack_amd/_lib.py binds them from the prototypes below).
+ * Profile id "task_scale" counts all of them.
  */
 #ifndef EGOPACK_TASK_SCALE_H
 #define EGOPACK_TASK_SCALE_H

@@ -1,8 +1,11 @@
-"""The C-ABI library loads on a CPU-only box and exports every symbol include/egopack_hip.h declares
-(no compute calls without a GPU)."""
+"""The C-ABI library loads on a CPU-only box, exports every symbol the headers of include/ declare and is bound with the types they
+declare (no compute calls without a GPU): the one ledger of all headers, the struct layouts, and the prototype parser itself."""
 import ctypes
 
+import pytest
+
 from egopack_amd import _lib
+from tests import cabi_common as CC
 
 
 def test_library_is_built_and_loads():
@@ -11,29 +14,128 @@ def test_library_is_built_and_loads():
     assert isinstance(_lib.last_error(), str)
 
 
-def test_every_header_symbol_is_exported_and_bound():
-    lib = _lib.load()
-    declared = _lib.header_symbols()
-    assert len(declared) >= 35
+# ---- the one ledger of the C ABI: every header of _lib.HEADERS, in one form (tests/cabi_common.py holds what is pinned per header) ---
+KEYS = list(_lib.HEADERS)
+
+
+def test_every_header_has_its_ledger_entries():
+    assert KEYS == list(CC.NAMES) == list(CC.EXEMPT) == list(CC.BOUNDS)
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_every_header_symbol_is_exported_and_bound(key):
+    """The names of a header are the pinned ones, and each is exported and bound with the types its prototype declares."""
+    lib, header = _lib.load(), _lib.HEADERS[key].name
+    declared, sigs = _lib.declared(key), _lib.signatures()[key]
+    assert declared == CC.NAMES[key] == sorted(sigs), sorted(set(declared) ^ set(CC.NAMES[key]))
     for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_hip.h but not exported"
-    assert set(declared) == set(_lib.SIGNATURES), set(declared) ^ set(_lib.SIGNATURES)
+        assert hasattr(lib, name), f"{name} declared in include/{header} but not exported"
+        fn, (restype, argtypes) = getattr(lib, name), sigs[name]
+        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
+    if key != "hip":
+        assert f'#include "{header}"' in _lib.HEADERS["hip"].read_text()  # (a C user includes one file)
 
 
-def test_gemm_descriptor_layout_matches_header():
-    # field order / count of struct egk_gemm_desc as declared in the header
-    import re
-    text = _lib.HEADER.read_text()
-    body = re.search(r"typedef struct egk_gemm_desc \{(.*?)\} egk_gemm_desc;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.GemmDesc._fields_]
+def test_no_entry_point_is_declared_by_two_headers():
+    for i, a in enumerate(KEYS):
+        for b in KEYS[i + 1:]:
+            both = set(_lib.declared(a)) & set(_lib.declared(b))
+            assert not both, f"{sorted(both)} declared in {a} and in {b}"
+    assert len(_lib.declared()) == len(set(_lib.declared())) == sum(len(v) for v in CC.NAMES.values())
+
+
+def test_struct_layouts_match_the_headers():
+    """Every struct typedef of every header is registered in _lib.STRUCTS, and its Structure has the header's field names, types
+    and array lengths in the header's order."""
+    seen = {}
+    for key in KEYS:
+        for typedef in CC.struct_typedefs(key):
+            assert typedef not in seen, f"{typedef} declared in {seen[typedef]} and in {key}"
+            seen[typedef] = key
+    assert set(seen) == set(_lib.STRUCTS), set(seen) ^ set(_lib.STRUCTS)
+    for typedef, cls in _lib.STRUCTS.items():
+        want, have = CC.struct_fields(seen[typedef], typedef), [(f[0], f[1]) for f in cls._fields_]
+        assert [n for n, _ in have] == [n for n, _ in want], typedef
+        assert have == want, (typedef, [(h, w) for h, w in zip(have, want) if h != w])
+
+
+# ---- the prototype parser itself: fixed points written out by hand, and what it must refuse ---------------------------------------
+vp, i32, i64, u64, f32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
+P = ctypes.POINTER
+PINNED = {  # key, name: the prototype as the header spells it, (restype, argtypes) by hand
+    ("hip", "egk_last_error"): ("const char* egk_last_error(void);", (ctypes.c_char_p, [])),
+    ("hip", "egk_prof_get"): ("""int egk_prof_get(int id, char* name, int name_len, int64_t* launches, double* total_ms,
+                 double* alg_flops, double* alg_bytes);""", (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int, vp, vp, vp, vp])),
+    ("hip", "egk_gemm"): ("int egk_gemm(egk_stream_t s, const egk_gemm_desc* d);", (ctypes.c_int, [vp, P(_lib.GemmDesc)])),
+    ("hip", "egk_gemm_ws_bytes"): ("int64_t egk_gemm_ws_bytes(const egk_gemm_desc* d);", (i64, [P(_lib.GemmDesc)])),
+    ("hip", "egk_rowln_fwd"): ("""int egk_rowln_fwd(egk_stream_t s, const void* x, const float* w, const float* b, void* y, float* mean,
+                  float* rstd, uint8_t* mask, int32_t rows, int32_t cols, float eps, int32_t relu, float p,
+                  uint64_t seed, uint64_t offset, const uint64_t* dev_offset, int32_t dtype);""",
+                                (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, f32, u64, u64, vp, i32])),
+    ("hip", "egk_host_build_batch"): ("""int64_t egk_host_build_batch(const egk_host_dataset* ds, uint32_t* mt_key, int32_t* mt_pos, const int64_t* idx, int64_t B,
+                             egk_host_batch* out);""", (i64, [P(_lib.HostDataset), vp, vp, vp, i64, P(_lib.HostBatch)])),
+    ("hip", "egk_ln_bwd_reduce_multi"): ("""int egk_ln_bwd_reduce_multi(egk_stream_t s, const void* const* ws, float* const* dw, float* const* db, const int32_t* rows,
+                            const int32_t* cols, const int32_t* n_seg, int32_t count);""", (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i32])),
+    ("hip", "egk_adam_hyper"): ("int egk_adam_hyper(egk_stream_t s, const float* src, int64_t* t_dev, double beta1, double beta2, float* hyper);",
+                                 (ctypes.c_int, [vp, vp, vp, f64, f64, vp])),
+    ("hip", "egk_ce_fused_multi"): ("int egk_ce_fused_multi(egk_stream_t s, const egk_ce_task* tasks, int32_t count, float smoothing, int32_t dtype);",
+                                     (ctypes.c_int, [vp, P(_lib.CETask), i32, f32, i32])),
+    ("hip", "egk_rowdot_ws_rows"): ("int32_t egk_rowdot_ws_rows(int32_t rows);", (i32, [i32])),
+    ("sample", "egk_categorical_sample"): ("""int egk_categorical_sample(egk_stream_t s, const egk_sample_task* tasks, int32_t count, int32_t rows, int32_t K, uint64_t seed,
+                           int64_t ordinal, int64_t row0, int32_t dtype);""", (ctypes.c_int, [vp, P(_lib.SampleTask), i32, i32, i32, u64, i64, i64, i32])),
+    ("ema", "egk_optim_step_ema"): ("int egk_optim_step_ema(egk_stream_t s, const egk_optim_desc* d, const egk_optim_groups* g, const egk_ema_desc* e);",
+                                     (ctypes.c_int, [vp, P(_lib.OptimDesc), P(_lib.OptimGroups), P(_lib.EmaDesc)])),
+    ("task_scale", "egk_rowdot_bce_w_s"): ("""int egk_rowdot_bce_w_s(egk_stream_t s, const void* f, const void* w, const float* bias, const int64_t* y, float* logits, float* loss,
+                       void* df, float* ws, int32_t rows, int32_t cols, float seed, const float* scale, float pos, float neg,
+                       float gamma, int32_t dtype);""", (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, f32, f32, f32, i32])),
+}
+
+
+def test_hand_pinned_signatures_are_what_the_parser_reads():
+    """The fixed points that keep the parser honest: from the prototype's text alone, and from the header it was copied from."""
+    text = "/* a comment with egk_not_a_function(int) in it */\n#include <stdint.h>\n" + "\n// another\n".join(t for t, _ in PINNED.values())
+    parsed = _lib.parse_prototypes(text)
+    assert sorted(parsed) == sorted(name for _, name in PINNED)
+    for (key, name), (_, want) in PINNED.items():
+        assert parsed[name] == want, name
+        assert _lib.signatures()[key][name] == want, name
+    # struct and enum bodies, typedefs and the extern "C" braces declare no entry point; parameter names are optional
+    text = 'extern "C" {\ntypedef void* egk_stream_t;\nenum { EGK_A = 0 };\ntypedef struct egk_t { int32_t a, b; } egk_t;\nint egk_f(egk_stream_t, const float* const*, int32_t);\n}\n'
+    assert _lib.parse_prototypes(text) == {"egk_f": (ctypes.c_int, [vp, vp, i32])}
+
+
+@pytest.mark.parametrize("what, text, needle", [
+    ("an unknown base type", "int egk_f(egk_stream_t s, size_t n);", "size_t n"),
+    ("a pointer to an unknown base type", "int egk_f(const egk_unlisted_desc* d);", "egk_unlisted_desc"),
+    ("an unknown return type", "unsigned egk_f(void);", "unsigned"),
+    ("a function-pointer parameter", "int egk_f(egk_stream_t s, void (*done)(int32_t, void*), void* arg);", "(*done)"),
+    ("a by-value struct", "int egk_f(egk_stream_t s, egk_gemm_desc d);", "egk_gemm_desc d"),
+    ("a pointer to a pointer to a struct", "int egk_f(const egk_gemm_desc* const* d);", "egk_gemm_desc"),
+    ("a name declared twice", "int egk_f(int32_t a);\nint egk_f(int64_t a);", "declared twice"),
+    ("a prototype without the prefix", "int other_f(int32_t a);", "other_f"),
+])
+def test_the_parser_refuses(what, text, needle):
+    """A type the parser does not know never becomes c_void_p silently: it raises, naming the header, the function and the text."""
+    with pytest.raises(TypeError) as e:
+        _lib.parse_prototypes(text, "some_header.h")
+    assert "some_header.h" in str(e.value) and needle in str(e.value), (what, str(e.value))
+    if "egk_f" in text:
+        assert "egk_f" in str(e.value)
+
+
+def test_a_missing_header_and_a_name_in_two_headers_are_refused_by_the_loader(tmp_path, monkeypatch):
+    monkeypatch.setattr(_lib, "HEADERS", {**_lib.HEADERS, "absent": tmp_path / "egopack_absent.h"})
+    _lib.signatures.cache_clear()
+    try:
+        with pytest.raises(RuntimeError, match="egopack_absent.h is missing.*'absent'"):
+            _lib.signatures()
+        (tmp_path / "egopack_absent.h").write_text("int egk_version(void);\n")
+        with pytest.raises(RuntimeError, match="egk_version is declared in egopack_hip.h and again in egopack_absent.h"):
+            _lib.signatures()
+    finally:
+        monkeypatch.undo()
+        _lib.signatures.cache_clear()
+    assert list(_lib.signatures()) == KEYS
 
 
 def test_argument_errors_are_reported_without_a_gpu():
@@ -69,56 +171,31 @@ def test_heavy_row_threshold_is_shared_by_the_csr_builder_and_the_kernel():
     assert data.build_csr(ei, data.HEAVY_DEGREE + 1).t_heavy.numel() == 0  # exactly the threshold: not listed
 
 
-# ---- the guard-band ledger: every entry point of the header has a bounds case, or writes no device memory ---------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (queries, knobs, the one-shot arming calls -- whose effect
-# is covered by the launch they arm, listed in that case's ``covers`` -- and the egk_host_* helpers, which run on the CPU).
-EXEMPT = {
-    "egk_version": "query: writes no device memory",
-    "egk_last_error": "query: writes no device memory",
-    "egk_prof_enable": "host-side switch of the launch counters: writes no device memory",
-    "egk_prof_reset": "host-side counters: writes no device memory",
-    "egk_prof_count": "query: writes no device memory",
-    "egk_prof_get": "query (synchronises recorded events): writes no device memory",
-    "egk_gemm_ws_bytes": "query: writes no device memory",
-    "egk_gemm_splitk": "query: writes no device memory",
-    "egk_gemm_set_pipeline": "knob: writes no device memory",
-    "egk_tune": "knob: writes no device memory",
-    "egk_gather_max_tune": "knob: writes no device memory",
-    "egk_colsum_ws_len": "query: writes no device memory",
-    "egk_rowln_bwd_ws_rows": "query: writes no device memory",
-    "egk_graphln_ws_bytes": "query: writes no device memory",
-    "egk_graphln_stats_blocks": "query: writes no device memory",
-    "egk_rowdot_ws_rows": "query: writes no device memory",
-    "egk_rowdot_ce2_max_rows": "query: writes no device memory",
-    "egk_csr_heavy_ws_bytes": "query: writes no device memory",
-    "egk_csr_heavy_threshold": "query: writes no device memory",
-    "egk_grad_sumsq_slots": "query: writes no device memory",
-    "egk_host_bounded_draws": "runs on the CPU: writes no device memory",
-    "egk_host_window_rows": "runs on the CPU: writes no device memory",
-    "egk_host_build_batch": "runs on the CPU: writes no device memory",
-    "egk_host_batch_sizes": "runs on the CPU: writes no device memory",
-    "egk_host_merge_batches": "runs on the CPU: writes no device memory",
-}
-# covered by a case (they launch nothing themselves, the launch they arm writes device memory): must NOT be exempt
-ARMING = {"egk_tee_split_next", "egk_gemm_defer_reduce_next", "egk_slab_input_next"}
-# egk_gemm_stats_blocks is a query too, but the statistics case declares it: it sizes the guarded st_ws
-
-
-def test_every_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to the header later fails here until it gets a case in tests/test_gpu_bounds.py."""
-    from tests import test_gpu_bounds as B  # (importable without a GPU)
-    declared, covered = set(_lib.header_symbols()), set(B.covered())
+# ---- the guard-band ledger: every entry point of a header has a bounds case, or writes no device memory (tests/cabi_common.py) -------
+@pytest.mark.parametrize("key", KEYS)
+def test_every_entry_point_has_a_bounds_case_or_writes_no_device_memory(key):
+    """A kernel added to a header later fails here until it gets a case in the header's bounds module (cabi_common.BOUNDS)."""
+    B, exempt = CC.bounds(key), CC.EXEMPT[key]  # (importable without a GPU)
+    declared, covered = set(_lib.declared(key)), set(B.covered())
     assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared, f"exemptions of entry points the header does not declare: {sorted(set(EXEMPT) - declared)}"
-    both = covered & set(EXEMPT)
+    assert set(exempt) <= declared, f"exemptions of entry points the header does not declare: {sorted(set(exempt) - declared)}"
+    both = covered & set(exempt)
     assert not both, f"in exactly one of the two places: {sorted(both)}"
-    missing = declared - covered - set(EXEMPT)
+    missing = CC.uncovered(key)
     assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    assert all("writes no device memory" in why for why in EXEMPT.values())
-    assert ARMING <= covered
+    assert all("writes no device memory" in why for why in exempt.values())
+    assert CC.ARMING.get(key, set()) <= covered
     for name, fn, variant, covers, plain in B.CASES:
         assert covers and all(c.startswith("egk_") for c in covers), name
     assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
+
+
+def test_the_bounds_modules_hold_their_own_cases():
+    """The cases of a header live in their own list, and no entry point is covered from two modules."""
+    mods = [CC.bounds(key) for key in KEYS]
+    for i, a in enumerate(mods):
+        for b in mods[i + 1:]:
+            assert a.CASES is not b.CASES and not set(a.covered()) & set(b.covered()), (a.__name__, b.__name__)
 
 
 def test_unaligned_and_undersized_arguments_are_refused_before_any_launch():

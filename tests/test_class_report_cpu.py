@@ -1,8 +1,7 @@
-"""The per-class validation report without a GPU: the ledger of include/egopack_class_report.h (the form of
-tests/test_lta_sampling_cpu.py), the host-side refusals of its entry point, the host model's ranking, the derived metrics on
-hand-made matrices, the ``class_report:`` config block, and the keys of every meter with the report off."""
+"""The per-class validation report without a GPU: what include/egopack_class_report.h pins beyond the one ledger (tests/test_cabi.py),
+the host-side refusals of its entry point, the host model's ranking, the derived metrics on hand-made matrices, the
+``class_report:`` config block, and the keys of every meter with the report off."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -10,63 +9,19 @@ import torch
 
 from tests import class_report_common as CR
 
-# ---- 1. the ledger of include/egopack_class_report.h -----------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
-NAMES = ["egk_class_report"]
-
-
-def test_every_class_report_header_symbol_is_exported_and_bound():
-    from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.class_report_header_symbols()
-    assert sorted(declared) == NAMES
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_class_report.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.CLASS_REPORT_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.CLASS_REPORT_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.OPTIM_GROUPS_SIGNATURES)
-             | set(_lib.EMA_SIGNATURES) | set(_lib.CE_BALANCED_SIGNATURES) | set(_lib.BCE_BALANCED_SIGNATURES)
-             | set(_lib.TASK_SCALE_SIGNATURES) | set(_lib.SAMPLE_SIGNATURES) | set(_lib.sample_header_symbols()))
-    assert not set(declared) & older
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)  # (the oldest ledger stays closed over its own)
-    assert '#include "egopack_class_report.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
+# ---- 1. include/egopack_class_report.h beyond the common ledger ------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
 def test_class_report_task_struct_layout_matches_header():
     from egopack_amd import _lib
-    text = _lib.CLASS_REPORT_HEADER.read_text()
-    body = re.search(r"typedef struct egk_class_report_task \{(.*?)\} egk_class_report_task;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.ClassReportTask._fields_]
+    from tests import cabi_common as CC
+    text = _lib.HEADERS["class_report"].read_text()
+    names = [n for n, _ in CC.struct_fields("class_report", "egk_class_report_task")]
     assert names == ["logits", "ld", "labels", "label_stride", "rows", "C", "confusion", "top2", "loss_q24", "counts"]
     T = _lib.ClassReportTask
     assert ctypes.sizeof(T) == 72 and T.rows.offset == 32 and T.C.offset == 36 and T.confusion.offset == 40 and T.counts.offset == 64
     assert f"#define EGK_CLASS_REPORT_MAX_TASKS {_lib.CLASS_REPORT_MAX_TASKS}" in text and _lib.CLASS_REPORT_MAX_TASKS == 8
-
-
-def test_every_class_report_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_class_report.h later fails here until it gets a case in
-    tests/test_gpu_bounds_class_report.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_class_report as B  # (importable without a GPU)
-    declared, covered = set(_lib.class_report_header_symbols()), set(B.covered())
-    assert covered == declared - set(EXEMPT), (sorted(covered), sorted(declared))
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_lta_sampling as LSB
-    for other in (OLD, LSB):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
 
 
 def test_class_report_has_a_profile_id_of_its_own():

@@ -1,10 +1,9 @@
-"""The weight average of the flat optimizers without a GPU: the ledger of include/egopack_ema.h (the form of
-tests/test_optim_rules_cpu.py and tests/test_param_groups_cpu.py), the host-side refusals of its two entry points, the
-constructors' refusals, the configuration keys, the state dict of an optimizer whose flat buffers do not exist yet, the torch
-classes loading a state dict that carries an average, and the refusal under the sharded update."""
+"""The weight average of the flat optimizers without a GPU: what include/egopack_ema.h pins beyond the one ledger (tests/test_cabi.py),
+the host-side refusals of its two entry points, the constructors' refusals, the configuration keys, the state dict of an optimizer
+whose flat buffers do not exist yet, the torch classes loading a state dict that carries an average, and the refusal under the
+sharded update."""
 import ctypes
 import logging
-import re
 
 import pytest
 import torch
@@ -17,66 +16,20 @@ def _params(seed=0):
     return [torch.randn(s, generator=g).requires_grad_(True) for s in SHAPES]
 
 
-# ---- 1. the ledger of include/egopack_ema.h --------------------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
+# ---- 1. include/egopack_ema.h beyond the common ledger ---------------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
-def test_every_ema_header_symbol_is_exported_and_bound():
+def test_ema_header_includes_the_groups_header():
     from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.ema_header_symbols()
-    assert declared == ["egk_ema_swap", "egk_optim_step_ema"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_ema.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.EMA_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.EMA_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.optim_header_symbols())
-             | set(_lib.OPTIM_GROUPS_SIGNATURES) | set(_lib.optim_groups_header_symbols()))
-    assert not set(declared) & older
-    # the three older ledgers stay closed over their own
-    assert _lib.optim_header_symbols() == ["egk_optim_step"] == sorted(_lib.OPTIM_SIGNATURES)
-    assert _lib.optim_groups_header_symbols() == ["egk_optim_step_groups"] == sorted(_lib.OPTIM_GROUPS_SIGNATURES)
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)
-    assert '#include "egopack_ema.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
-    assert '#include "egopack_optim_groups.h"' in _lib.EMA_HEADER.read_text()
+    assert '#include "egopack_optim_groups.h"' in _lib.HEADERS["ema"].read_text()
 
 
 def test_ema_struct_layout_matches_header():
     from egopack_amd import _lib
-    text = _lib.EMA_HEADER.read_text()
-    body = re.search(r"typedef struct egk_ema_desc \{(.*?)\} egk_ema_desc;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.EmaDesc._fields_] == ["ema", "decay", "warmup"]
+    from tests import cabi_common as CC
+    assert [n for n, _ in CC.struct_fields("ema", "egk_ema_desc")] == [f[0] for f in _lib.EmaDesc._fields_] == ["ema", "decay", "warmup"]
     assert ctypes.sizeof(_lib.EmaDesc) == 24 and _lib.EmaDesc.decay.offset == 8 and _lib.EmaDesc.warmup.offset == 16
-
-
-def test_every_ema_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_ema.h later fails here until it gets a case in tests/test_gpu_bounds_ema.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_ema as B  # (importable without a GPU)
-    declared, covered = set(_lib.ema_header_symbols()), set(B.covered())
-    assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    missing = declared - covered - set(EXEMPT)
-    assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    assert all("writes no device memory" in why for why in EXEMPT.values())
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    # the cases of this header live in their own list: the three older ledgers stay closed over their own
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_optim as OPT
-    from tests import test_gpu_bounds_param_groups as GRP
-    for other in (OLD, OPT, GRP):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
 
 
 def test_optim_ema_has_a_profile_id_of_its_own():

@@ -1,9 +1,8 @@
-"""The seeded sampler of the LTA futures without a GPU: the ledger of include/egopack_sample.h (the form of
-tests/test_task_weighting_cpu.py), the host-side refusals of its entry point, the counter layout and the uniform conversion of the
-host model (tests/lta_sampling_common.py), the ``lta_sampling:`` config block, the batch ordinal of data.BatchLoader, and the
-chi-square test of the host model alone against the bounds the GPU test uses."""
+"""The seeded sampler of the LTA futures without a GPU: what include/egopack_sample.h pins beyond the one ledger (tests/test_cabi.py),
+the host-side refusals of its entry point, the counter layout and the uniform conversion of the host model
+(tests/lta_sampling_common.py), the ``lta_sampling:`` config block, the batch ordinal of data.BatchLoader, and the chi-square test
+of the host model alone against the bounds the GPU test uses."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -12,62 +11,15 @@ import torch
 from tests import lta_sampling_common as LS
 from tests import philox_ref as PR
 
-# ---- 1. the ledger of include/egopack_sample.h -----------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
-NAMES = ["egk_categorical_sample"]
+# ---- 1. include/egopack_sample.h beyond the common ledger ------------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
-def test_every_sample_header_symbol_is_exported_and_bound():
+def test_sample_task_struct_size_and_limits():
     from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.sample_header_symbols()
-    assert sorted(declared) == NAMES
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_sample.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.SAMPLE_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.SAMPLE_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.OPTIM_GROUPS_SIGNATURES)
-             | set(_lib.EMA_SIGNATURES) | set(_lib.CE_BALANCED_SIGNATURES) | set(_lib.BCE_BALANCED_SIGNATURES)
-             | set(_lib.TASK_SCALE_SIGNATURES) | set(_lib.task_scale_header_symbols()))
-    assert not set(declared) & older
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)  # (the oldest ledger stays closed over its own)
-    assert '#include "egopack_sample.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
-
-
-def test_sample_task_struct_layout_matches_header():
-    from egopack_amd import _lib
-    text = _lib.SAMPLE_HEADER.read_text()
-    body = re.search(r"typedef struct egk_sample_task \{(.*?)\} egk_sample_task;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.SampleTask._fields_]
+    text = _lib.HEADERS["sample"].read_text()
     assert ctypes.sizeof(_lib.SampleTask) == 72 and _lib.SampleTask.head.offset == 20 and _lib.SampleTask.out.offset == 24
     assert f"#define EGK_SAMPLE_MAX_TASKS {_lib.SAMPLE_MAX_TASKS}" in text and f"#define EGK_SAMPLE_MAX_K {_lib.SAMPLE_MAX_K}" in text
-
-
-def test_every_sample_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_sample.h later fails here until it gets a case in tests/test_gpu_bounds_lta_sampling.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_lta_sampling as B  # (importable without a GPU)
-    declared, covered = set(_lib.sample_header_symbols()), set(B.covered())
-    assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    missing = declared - covered - set(EXEMPT)
-    assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_task_weighting as TWB
-    for other in (OLD, TWB):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
 
 
 def test_categorical_sample_has_a_profile_id_of_its_own():

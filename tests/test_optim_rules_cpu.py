@@ -1,6 +1,6 @@
-"""The update rules behind one launch interface, without a GPU: the configuration targets, the state dicts against
-torch.optim.AdamW / torch.optim.SGD, the ledger of include/egopack_optim.h (the form of tests/test_cabi.py), the host-side refusals
-of egk_optim_step, and GradSync.gather_moments over an optimizer with one state buffer and with none."""
+"""The update rules behind one launch interface, without a GPU: the configuration targets, the state dicts against torch.optim.AdamW /
+torch.optim.SGD, what include/egopack_optim.h pins beyond the one ledger (tests/test_cabi.py), the host-side refusals of
+egk_optim_step, and GradSync.gather_moments over an optimizer with one state buffer and with none."""
 import ctypes
 import os
 import re
@@ -170,58 +170,16 @@ def test_a_state_of_another_rule_is_refused_by_name():
     assert opt.decoupled_weight_decay and opt.param_groups[0]["decoupled_weight_decay"] is True
 
 
-# ---- 3. the ledger of include/egopack_optim.h ----------------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
+# ---- 3. include/egopack_optim.h beyond the common ledger -------------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
-def test_every_optim_header_symbol_is_exported_and_bound():
+def test_optim_rule_codes_match_header():
     from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.optim_header_symbols()
-    assert declared == ["egk_optim_step"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_optim.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.OPTIM_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.OPTIM_SIGNATURES)
-    assert not set(declared) & set(_lib.SIGNATURES) and not set(declared) & set(_lib.header_symbols())
-    assert '#include "egopack_optim.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
-
-
-def test_optim_descriptor_layout_matches_header():
-    from egopack_amd import _lib
-    text = _lib.OPTIM_HEADER.read_text()
-    body = re.search(r"typedef struct egk_optim_desc \{(.*?)\} egk_optim_desc;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.OptimDesc._fields_]
+    text = _lib.HEADERS["optim"].read_text()
     codes = dict(re.findall(r"(EGK_OPT_[A-Z]+) = (\d)", text))
     assert codes == {"EGK_OPT_ADAM": "0", "EGK_OPT_ADAMW": "1", "EGK_OPT_SGD": "2"}
     assert (_lib.OPT_ADAM, _lib.OPT_ADAMW, _lib.OPT_SGD) == (0, 1, 2)
-
-
-def test_every_optim_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_optim.h later fails here until it gets a case in tests/test_gpu_bounds_optim.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_optim as B  # (importable without a GPU)
-    declared, covered = set(_lib.optim_header_symbols()), set(B.covered())
-    assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    missing = declared - covered - set(EXEMPT)
-    assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    assert all("writes no device memory" in why for why in EXEMPT.values())
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    # the cases of this header live in their own list: the ledger of egopack_hip.h stays closed over its own
-    from tests import test_gpu_bounds as OLD
-    assert not set(B.covered()) & set(OLD.covered()) and B.CASES is not OLD.CASES
 
 
 # ---- 4. host-side refusals of egk_optim_step ---------------------------------------------------------------------------------------------

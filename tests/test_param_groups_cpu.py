@@ -1,8 +1,7 @@
-"""Parameter groups without a GPU: train.build_param_groups, the constructors' refusals, the host-side segment table, the ledger
-of include/egopack_optim_groups.h (the form of tests/test_cabi.py and tests/test_optim_rules_cpu.py), the host-side refusals of
-egk_optim_step_groups, the state dicts against the torch classes over the same groups, schedulers over two groups."""
+"""Parameter groups without a GPU: train.build_param_groups, the constructors' refusals, the host-side segment table, what
+include/egopack_optim_groups.h pins beyond the one ledger (tests/test_cabi.py), the host-side refusals of egk_optim_step_groups, the
+state dicts against the torch classes over the same groups, schedulers over two groups."""
 import ctypes
-import re
 
 import pytest
 import torch
@@ -179,63 +178,20 @@ def test_group_segments_follow_the_slots():
         opt._check_segments([(0, 8, 0)], 16)
 
 
-# ---- 3. the ledger of include/egopack_optim_groups.h -----------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
+# ---- 3. include/egopack_optim_groups.h beyond the common ledger ------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
-def test_every_optim_groups_header_symbol_is_exported_and_bound():
+def test_optim_groups_header_includes_the_optim_header():
     from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.optim_groups_header_symbols()
-    assert declared == ["egk_optim_step_groups"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_optim_groups.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.OPTIM_GROUPS_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.OPTIM_GROUPS_SIGNATURES)
-    older = set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.optim_header_symbols())
-    assert not set(declared) & older
-    assert '#include "egopack_optim_groups.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
-    assert '#include "egopack_optim.h"' in _lib.OPTIM_GROUPS_HEADER.read_text()
+    assert '#include "egopack_optim.h"' in _lib.HEADERS["optim_groups"].read_text()
 
 
-def test_optim_groups_struct_layout_matches_header():
+def test_optim_groups_struct_size_and_limits():
     from egopack_amd import _lib
-    text = _lib.OPTIM_GROUPS_HEADER.read_text()
-    body = re.search(r"typedef struct egk_optim_groups \{(.*?)\} egk_optim_groups;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.OptimGroups._fields_]
     assert ctypes.sizeof(_lib.OptimGroups) == 40 and _lib.OptimGroups.seg_begin.offset == 16
     from egopack_amd import optim
-    assert (optim.MAX_SEGMENTS, optim.MAX_GROUPS) == (4096, 64) and "1..4096, 1..64" in text
-
-
-def test_every_optim_groups_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_optim_groups.h later fails here until it gets a case in
-    tests/test_gpu_bounds_param_groups.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_param_groups as B  # (importable without a GPU)
-    declared, covered = set(_lib.optim_groups_header_symbols()), set(B.covered())
-    assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    missing = declared - covered - set(EXEMPT)
-    assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    assert all("writes no device memory" in why for why in EXEMPT.values())
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    # the cases of this header live in their own list: the two older ledgers stay closed over their own
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_optim as OPT
-    assert not set(B.covered()) & set(OLD.covered()) and not set(B.covered()) & set(OPT.covered())
-    assert B.CASES is not OLD.CASES and B.CASES is not OPT.CASES
+    assert (optim.MAX_SEGMENTS, optim.MAX_GROUPS) == (4096, 64) and "1..4096, 1..64" in _lib.HEADERS["optim_groups"].read_text()
 
 
 def test_optim_groups_has_a_profile_id_of_its_own():

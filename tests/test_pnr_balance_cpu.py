@@ -1,6 +1,6 @@
-"""The shaped BCE of the PNR head without a GPU: the ledger of include/egopack_bce_balanced.h (the form of
-tests/test_class_balance_cpu.py), the host-side refusals of its three entry points, the host model of tests/pnr_balance_common.py
-against F.binary_cross_entropy_with_logits(pos_weight=) and the written-out focal formula in float64, the known answers of
+"""The shaped BCE of the PNR head without a GPU: what include/egopack_bce_balanced.h pins beyond the one ledger (tests/test_cabi.py),
+the host-side refusals of its three entry points, the host model of tests/pnr_balance_common.py against
+F.binary_cross_entropy_with_logits(pos_weight=) and the written-out focal formula in float64, the known answers of
 ``train.build_pnr_balance``, the configuration keys, and the state-dict keys of a task and a criterion that carry scalars."""
 import ctypes
 import logging
@@ -10,59 +10,13 @@ import torch
 
 from tests import pnr_balance_common as PB
 
-# ---- 1. the ledger of include/egopack_bce_balanced.h -----------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
-NAMES = ["egk_bce_w_bwd", "egk_bce_w_fwd", "egk_rowdot_bce_w"]
+# ---- 1. include/egopack_bce_balanced.h beyond the common ledger ------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
-def test_every_bce_balanced_header_symbol_is_exported_and_bound():
-    from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.bce_balanced_header_symbols()
-    assert sorted(declared) == NAMES
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_bce_balanced.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.BCE_BALANCED_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.BCE_BALANCED_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.optim_header_symbols())
-             | set(_lib.OPTIM_GROUPS_SIGNATURES) | set(_lib.optim_groups_header_symbols())
-             | set(_lib.EMA_SIGNATURES) | set(_lib.ema_header_symbols())
-             | set(_lib.CE_BALANCED_SIGNATURES) | set(_lib.ce_balanced_header_symbols()))
-    assert not set(declared) & older
-    # the five older ledgers stay closed over their own
-    assert _lib.optim_header_symbols() == ["egk_optim_step"] == sorted(_lib.OPTIM_SIGNATURES)
-    assert _lib.optim_groups_header_symbols() == ["egk_optim_step_groups"] == sorted(_lib.OPTIM_GROUPS_SIGNATURES)
-    assert _lib.ema_header_symbols() == ["egk_ema_swap", "egk_optim_step_ema"] == sorted(_lib.EMA_SIGNATURES)
-    assert sorted(_lib.ce_balanced_header_symbols()) == sorted(_lib.CE_BALANCED_SIGNATURES)
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)
-    assert '#include "egopack_bce_balanced.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
-
-
-def test_every_bce_balanced_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_bce_balanced.h later fails here until it gets a case in
-    tests/test_gpu_bounds_pnr_balance.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_pnr_balance as B  # (importable without a GPU)
-    declared, covered = set(_lib.bce_balanced_header_symbols()), set(B.covered())
-    assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    missing = declared - covered - set(EXEMPT)
-    assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    assert all("writes no device memory" in why for why in EXEMPT.values())
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    # the coverage check does fail for an entry point without a case
-    assert (declared | {"egk_bce_w_not_there"}) - covered - set(EXEMPT) == {"egk_bce_w_not_there"}
-    # the cases of this header live in their own list: the five older ledgers stay closed over their own
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_class_balance as CEB
-    from tests import test_gpu_bounds_ema as EMA
-    from tests import test_gpu_bounds_optim as OPT
-    from tests import test_gpu_bounds_param_groups as GRP
-    for other in (OLD, OPT, GRP, EMA, CEB):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
+def test_the_bce_balanced_coverage_check_fails_for_an_entry_point_without_a_case():
+    from tests import cabi_common as CC
+    assert CC.uncovered("bce_balanced") == set() and CC.uncovered("bce_balanced", {"egk_bce_w_not_there"}) == {"egk_bce_w_not_there"}
 
 
 def test_bce_balanced_has_a_profile_id_of_its_own():

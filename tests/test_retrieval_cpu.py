@@ -1,9 +1,8 @@
-"""The retrieval report and the EgoPack prediction entry point without a GPU: the ledger of include/egopack_retrieval.h (the form
-of tests/test_topk_cpu.py), the host-side refusals of its entry point, known answers of the host model
-(tests/retrieval_common.py), ``graphone.bank_labels`` against the reference's recipe, the ``predict_egopack:`` config block and the
-refusals of ``predict_egopack.main``."""
+"""The retrieval report and the EgoPack prediction entry point without a GPU: what include/egopack_retrieval.h pins beyond the one
+ledger (tests/test_cabi.py), the host-side refusals of its entry point, known answers of the host model (tests/retrieval_common.py),
+``graphone.bank_labels`` against the reference's recipe, the ``predict_egopack:`` config block and the refusals of
+``predict_egopack.main``."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -11,67 +10,21 @@ import torch
 
 from tests import retrieval_common as RC
 
-# ---- 1. the ledger of include/egopack_retrieval.h -----------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
-NAMES = ["egk_retrieval_report"]
-
-
-def test_every_retrieval_header_symbol_is_exported_and_bound():
-    from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.retrieval_header_symbols()
-    assert sorted(declared) == NAMES
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_retrieval.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.RETRIEVAL_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.RETRIEVAL_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.OPTIM_GROUPS_SIGNATURES)
-             | set(_lib.EMA_SIGNATURES) | set(_lib.CE_BALANCED_SIGNATURES) | set(_lib.BCE_BALANCED_SIGNATURES)
-             | set(_lib.TASK_SCALE_SIGNATURES) | set(_lib.SAMPLE_SIGNATURES) | set(_lib.CLASS_REPORT_SIGNATURES)
-             | set(_lib.TOPK_SIGNATURES) | set(_lib.topk_header_symbols()))
-    assert not set(declared) & older
-    # the older ledgers stay closed over their own symbols
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)
-    assert set(_lib.topk_header_symbols()) == set(_lib.TOPK_SIGNATURES)
-    assert '#include "egopack_retrieval.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
+# ---- 1. include/egopack_retrieval.h beyond the common ledger ---------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
 def test_retrieval_task_struct_layout_matches_header():
     from egopack_amd import _lib
-    text = _lib.RETRIEVAL_HEADER.read_text()
-    body = re.search(r"typedef struct egk_retrieval_task \{(.*?)\} egk_retrieval_task;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.RetrievalTask._fields_]
+    from tests import cabi_common as CC
+    text = _lib.HEADERS["retrieval"].read_text()
+    names = [n for n, _ in CC.struct_fields("retrieval", "egk_retrieval_task")]
     assert names == ["f", "f_ld", "f_act", "f_act_ld", "bank", "bank_ld", "K", "reserved", "nn", "nn_row_stride", "dist",
                      "dist_row_stride", "wins", "wins_row_stride"]
     T = _lib.RetrievalTask
     assert ctypes.sizeof(T) == 104 and T.K.offset == 48 and T.reserved.offset == 52 and T.nn.offset == 56 and T.wins.offset == 88
     assert f"#define EGK_RETRIEVAL_MAX_TASKS {_lib.RETRIEVAL_MAX_TASKS}" in text and _lib.RETRIEVAL_MAX_TASKS == 8
     assert f"#define EGK_RETRIEVAL_MAX_K {_lib.RETRIEVAL_MAX_K}" in text and _lib.RETRIEVAL_MAX_K == 32
-
-
-def test_every_retrieval_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_retrieval.h later fails here until it gets a case in tests/test_gpu_bounds_retrieval.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_retrieval as B  # (importable without a GPU)
-    declared, covered = set(_lib.retrieval_header_symbols()), set(B.covered())
-    assert covered == declared - set(EXEMPT), (sorted(covered), sorted(declared))
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_topk as TKB
-    for other in (OLD, TKB):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
 
 
 def test_retrieval_report_has_a_profile_id_of_its_own():

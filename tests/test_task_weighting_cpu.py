@@ -1,7 +1,7 @@
-"""Task weighting without a GPU: the ledger of include/egopack_task_scale.h (the form of tests/test_pnr_balance_cpu.py), the
-host-side refusals of its entry points, the ``task_weighting:`` config block, the float64 host model of
-tests/task_weighting_common.py against torch autograd, ``train.build_optimizer`` with the log-variances, the checkpoint entry, and
-the refusals of the EgoPack step and the sharded update."""
+"""Task weighting without a GPU: what include/egopack_task_scale.h pins beyond the one ledger (tests/test_cabi.py), the host-side
+refusals of its entry points, the ``task_weighting:`` config block, the float64 host model of tests/task_weighting_common.py against
+torch autograd, ``train.build_optimizer`` with the log-variances, the checkpoint entry, and the refusals of the EgoPack step and the
+sharded update."""
 import ctypes
 import logging
 
@@ -11,55 +11,20 @@ import torch
 
 from tests import task_weighting_common as TW
 
-# ---- 1. the ledger of include/egopack_task_scale.h ---------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
-NAMES = ["egk_ce_fused_multi_s", "egk_ce_w_fused_multi_s", "egk_fill_scaled_from", "egk_rowdot_bce_s", "egk_rowdot_bce_w_s",
-         "egk_rowdot_ce2_multi_s", "egk_rowdot_ce2_s", "egk_task_scale_grad", "egk_task_scale_prepare"]
+# ---- 1. include/egopack_task_scale.h beyond the common ledger --------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
-def test_every_task_scale_header_symbol_is_exported_and_bound():
+def test_every_seeded_sibling_has_its_s_form():
     from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.task_scale_header_symbols()
-    assert sorted(declared) == NAMES
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_task_scale.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.TASK_SCALE_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.TASK_SCALE_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.OPTIM_GROUPS_SIGNATURES)
-             | set(_lib.EMA_SIGNATURES) | set(_lib.CE_BALANCED_SIGNATURES) | set(_lib.BCE_BALANCED_SIGNATURES)
-             | set(_lib.bce_balanced_header_symbols()) | set(_lib.ce_balanced_header_symbols()))
-    assert not set(declared) & older
-    # the six older ledgers stay closed over their own
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)
-    assert sorted(_lib.ce_balanced_header_symbols()) == sorted(_lib.CE_BALANCED_SIGNATURES)
-    assert sorted(_lib.bce_balanced_header_symbols()) == sorted(_lib.BCE_BALANCED_SIGNATURES)
-    assert '#include "egopack_task_scale.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
-    # every seeded sibling has its _s form
+    lib, declared = _lib.load(), _lib.declared("task_scale")
     for sib in ("egk_ce_fused_multi", "egk_ce_w_fused_multi", "egk_rowdot_bce", "egk_rowdot_bce_w", "egk_rowdot_ce2", "egk_rowdot_ce2_multi"):
         assert sib + "_s" in declared and hasattr(lib, sib)
 
 
-def test_every_task_scale_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_task_scale.h later fails here until it gets a case in
-    tests/test_gpu_bounds_task_weighting.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_task_weighting as B  # (importable without a GPU)
-    declared, covered = set(_lib.task_scale_header_symbols()), set(B.covered())
-    assert covered <= declared, f"cases name entry points the header does not declare: {sorted(covered - declared)}"
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    missing = declared - covered - set(EXEMPT)
-    assert not missing, f"entry points with neither a bounds case nor an exemption: {sorted(missing)}"
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    assert (declared | {"egk_task_scale_not_there"}) - covered - set(EXEMPT) == {"egk_task_scale_not_there"}
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_class_balance as CEB
-    from tests import test_gpu_bounds_pnr_balance as PNRB
-    for other in (OLD, CEB, PNRB):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
+def test_the_task_scale_coverage_check_fails_for_an_entry_point_without_a_case():
+    from tests import cabi_common as CC
+    assert CC.uncovered("task_scale") == set() and CC.uncovered("task_scale", {"egk_task_scale_not_there"}) == {"egk_task_scale_not_there"}
 
 
 def test_task_scale_has_a_profile_id_of_its_own():

@@ -1,8 +1,7 @@
-"""The top-k softmax launch and the prediction entry point without a GPU: the ledger of include/egopack_topk.h (the form of
-tests/test_class_report_cpu.py), the host-side refusals of its entry point, the ``predict:`` config block, the refusals of
-``predict.main`` and the host model's order on tie and NaN rows."""
+"""The top-k softmax launch and the prediction entry point without a GPU: what include/egopack_topk.h pins beyond the one ledger
+(tests/test_cabi.py), the host-side refusals of its entry point, the ``predict:`` config block, the refusals of ``predict.main`` and
+the host model's order on tie and NaN rows."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -10,68 +9,20 @@ import pytest
 from tests import class_report_common as CR
 from tests import topk_common as TK
 
-# ---- 1. the ledger of include/egopack_topk.h --------------------------------------------------------------------------------------
-# The ONLY admissible reason for an exemption is "writes no device memory" (tests/test_cabi.py); this header has none.
-EXEMPT = {}
-NAMES = ["egk_topk_softmax"]
-
-
-def test_every_topk_header_symbol_is_exported_and_bound():
-    from egopack_amd import _lib
-    lib = _lib.load()
-    declared = _lib.topk_header_symbols()
-    assert sorted(declared) == NAMES
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/egopack_topk.h but not exported"
-        assert getattr(lib, name).argtypes == _lib.TOPK_SIGNATURES[name][1]
-    assert set(declared) == set(_lib.TOPK_SIGNATURES)
-    older = (set(_lib.SIGNATURES) | set(_lib.header_symbols()) | set(_lib.OPTIM_SIGNATURES) | set(_lib.OPTIM_GROUPS_SIGNATURES)
-             | set(_lib.EMA_SIGNATURES) | set(_lib.CE_BALANCED_SIGNATURES) | set(_lib.BCE_BALANCED_SIGNATURES)
-             | set(_lib.TASK_SCALE_SIGNATURES) | set(_lib.SAMPLE_SIGNATURES) | set(_lib.sample_header_symbols())
-             | set(_lib.CLASS_REPORT_SIGNATURES) | set(_lib.class_report_header_symbols()))
-    assert not set(declared) & older
-    # the older ledgers stay closed over their own symbols
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)
-    assert set(_lib.sample_header_symbols()) == set(_lib.SAMPLE_SIGNATURES)
-    assert set(_lib.class_report_header_symbols()) == set(_lib.CLASS_REPORT_SIGNATURES)
-    assert '#include "egopack_topk.h"' in _lib.HEADER.read_text()  # (a C user includes one file)
+# ---- 1. include/egopack_topk.h beyond the common ledger --------------------------------------------------------------------------
+# (names, exports, bound types, the bounds ledger and the struct fields of this header: the one ledger, tests/test_cabi.py)
 
 
 def test_topk_task_struct_layout_matches_header():
     from egopack_amd import _lib
-    text = _lib.TOPK_HEADER.read_text()
-    body = re.search(r"typedef struct egk_topk_task \{(.*?)\} egk_topk_task;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _lib.TopkTask._fields_]
+    from tests import cabi_common as CC
+    text = _lib.HEADERS["topk"].read_text()
+    names = [n for n, _ in CC.struct_fields("topk", "egk_topk_task")]
     assert names == ["logits", "ld", "C", "reserved", "idx", "idx_row_stride", "prob", "prob_row_stride", "lse"]
     T = _lib.TopkTask
     assert ctypes.sizeof(T) == 64 and T.C.offset == 16 and T.reserved.offset == 20 and T.idx.offset == 24 and T.lse.offset == 56
     assert f"#define EGK_TOPK_MAX_TASKS {_lib.TOPK_MAX_TASKS}" in text and _lib.TOPK_MAX_TASKS == 8
     assert f"#define EGK_TOPK_MAX_K {_lib.TOPK_MAX_K}" in text and _lib.TOPK_MAX_K == 64
-
-
-def test_every_topk_entry_point_has_a_bounds_case_or_writes_no_device_memory():
-    """A kernel added to include/egopack_topk.h later fails here until it gets a case in tests/test_gpu_bounds_topk.py."""
-    from egopack_amd import _lib
-    from tests import test_gpu_bounds_topk as B  # (importable without a GPU)
-    declared, covered = set(_lib.topk_header_symbols()), set(B.covered())
-    assert covered == declared - set(EXEMPT), (sorted(covered), sorted(declared))
-    assert set(EXEMPT) <= declared and not covered & set(EXEMPT)
-    for name, fn, variant, covers, plain in B.CASES:
-        assert covers and all(c.startswith("egk_") for c in covers), name
-    assert len({c[0] for c in B.CASES}) == len(B.CASES), "case ids must be unique"
-    from tests import test_gpu_bounds as OLD
-    from tests import test_gpu_bounds_class_report as CRB
-    from tests import test_gpu_bounds_lta_sampling as LSB
-    for other in (OLD, LSB, CRB):
-        assert not set(B.covered()) & set(other.covered()) and B.CASES is not other.CASES
 
 
 def test_topk_softmax_has_a_profile_id_of_its_own():
