@@ -1,6 +1,6 @@
-// Small elementwise helpers (dropout, ReLU gate, axpby, scaled and weighted sums, block copies, zero fills), the single-launch
-// Adam step over the flat parameter buffer and the global gradient norm.  All HBM-bound / latency-bound.  (The loss kernels are in
-// loss.hip.)
+// Small elementwise helpers (dropout, ReLU gate, axpby, scaled and weighted sums, block copies, zero fills), the step
+// constants of the flat-buffer optimizer and the global gradient norm.  All HBM-bound / latency-bound.  (The loss kernels are in
+// loss.hip, the optimizer's update kernels in optim_rules.hip.)
 #include <math.h>
 
 #include "common.h"
@@ -166,55 +166,6 @@ __global__ void adam_hyper_kernel(const float* __restrict__ src, long long* __re
         hyper[2] = (float)sqrt(1.0 - pow(b2, (double)t));
         hyper[3] = src[1];
     }
-}
-
-// ---- Adam (torch.optim.Adam single-tensor formulas, L2 weight decay) ----------------------------------------
-// the elements [0, n) of one span, grid-stride over ``nblk`` workgroups (adam_kernel: the whole slice)
-template <typename GT>
-__device__ __forceinline__ void adam_span(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                          long long n, const AdamConsts& ac, bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
-                                          int blk, int nblk) {
-    for (long long i = ((long long)blk * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)nblk * blockDim.x * 4) {
-        if (i + 4 <= n) {
-            float4 pv = *reinterpret_cast<float4*>(p + i);
-            const float4 gv = ld4t(g + i, 0, 4, true);
-            float4 mv = *reinterpret_cast<float4*>(m + i);
-            float4 vv = *reinterpret_cast<float4*>(v + i);
-            float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) adam_update(pp[t], gp[t], mp[t], vp[t], ac);
-            *reinterpret_cast<float4*>(p + i) = pv;
-            *reinterpret_cast<float4*>(m + i) = mv;
-            *reinterpret_cast<float4*>(v + i) = vv;
-            if (shadow) st4t(shadow + i, 0, 4, true, pv);
-            if (shadow_lo) {  // the LOW halves of the three-product contractions' weight operands: bf16(p - bf16(p)), egk_split_bf16's bits
-                const float lo4[4] = {pp[0] - bf2f(f2bf(pp[0])), pp[1] - bf2f(f2bf(pp[1])), pp[2] - bf2f(f2bf(pp[2])), pp[3] - bf2f(f2bf(pp[3]))};
-                st4t(shadow_lo + i, 0, 4, true, make_float4(lo4[0], lo4[1], lo4[2], lo4[3]));
-            }
-        } else {
-            for (long long j = i; j < n; ++j) {
-                adam_update(p[j], ld1t(g + j), m[j], v[j], ac);
-                if (shadow) shadow[j] = f2bf(p[j]);
-                if (shadow_lo) shadow_lo[j] = f2bf(p[j] - bf2f(f2bf(p[j])));
-            }
-        }
-    }
-}
-
-template <typename GT, bool GATED>  // GT: element type of the gradient buffer (f32, or bf16 after a compressed all-reduce)
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long long n, const float* __restrict__ hyper,
-                                                   float b1, float b2, float eps, float wd, bf16_t* __restrict__ shadow,
-                                                   bf16_t* __restrict__ shadow_lo, long long* __restrict__ bump_word, long long bump,
-                                                   const int* __restrict__ gate) {
-    // (egk_adam_step_bump: a device-side counter that moves on once per step -- the Philox offset word of the step's dropout
-    //  launches -- rides in this launch instead of costing one of its own)
-    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
-    // (egk_adam_step_gated: the step's gate word, written by egk_grad_norm_finalize -- 0 = the gradient norm was not finite, the
-    //  step is skipped: one wave-uniform load, nothing of p / m / v / the bf16 copies is touched; the offset word above still moved)
-    if (GATED && *gate == 0) return;
-    const AdamConsts ac{hyper[0] / hyper[1], hyper[2], hyper[3], b1, b2, eps, wd};
-    adam_span(p, g, m, v, n, ac, shadow, shadow_lo, blockIdx.x, gridDim.x);
 }
 
 // ---- global gradient norm (clipping inside the step) ---------------------------------------------------------------------
@@ -609,48 +560,6 @@ int egk_adam_hyper(egk_stream_t stream, const float* src, int64_t* t_dev, double
     EGK_REQUIRE(src && t_dev && hyper, "egk_adam_hyper: null pointer");
     hipLaunchKernelGGL(adam_hyper_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, (long long*)t_dev, beta1, beta2, hyper);
     return check_launch("egk_adam_hyper");
-}
-
-int egk_adam_step(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
-                  const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow) {
-    return egk_adam_step_bump(stream, p, g, g_dtype, m, v, n, hyper, beta1, beta2, eps, weight_decay, bf16_shadow, nullptr, nullptr, 0);
-}
-
-int egk_adam_step_bump(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
-                       const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
-                       void* bf16_lo_shadow, int64_t* bump_word, int64_t bump) {
-    return egk_adam_step_gated(stream, p, g, g_dtype, m, v, n, hyper, beta1, beta2, eps, weight_decay, bf16_shadow, bf16_lo_shadow,
-                               bump_word, bump, nullptr);
-}
-
-int egk_adam_step_gated(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
-                        const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
-                        void* bf16_lo_shadow, int64_t* bump_word, int64_t bump, const int32_t* gate) {
-    EGK_REQUIRE(p && g && m && v && hyper, "egk_adam_step: null pointer");
-    EGK_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
-                "egk_adam_step: buffers must be 16-byte aligned");
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    EGK_REQUIRE(!bf16_shadow || ((uintptr_t)bf16_shadow & 7) == 0, "egk_adam_step: shadow must be 8-byte aligned");
-    EGK_REQUIRE(!bf16_lo_shadow || ((uintptr_t)bf16_lo_shadow & 7) == 0, "egk_adam_step: low-half shadow must be 8-byte aligned");
-    ProfScope prof(KID_ADAM, s, 0, ((bf16_shadow ? 26.0 : 24.0) + (bf16_lo_shadow ? 2.0 : 0.0) + (g_dtype == EGK_BF16 ? 2.0 : 4.0)) * n);
-    // Workgroups: one 1024-element group per workgroup up to 32768 of them (egk_tune(6, n) sets the cap).  An optimizer slice runs
-    // BESIDE weight-gradient launches in every captured step's tail; round 5 first capped it at 4096 (a 8 us reduction queued beside
-    // it had waited 135 us for wave slots) and, once the gradient buffer was no longer cleared and read back, measured the wide grid
-    // ahead again: headline 1.365-1.379 against 1.374-1.386 ms, config 4 2.180-2.182 against 2.191-2.206, Hp = 4096 2.722 against
-    // 2.751 (narrower is clearly worse: 1024 workgroups 1.405-1.414, 512 1.447)
-    const long long want = (n / 4 + 255) / 256;
-    const long long cap = 32768;
-    const unsigned grid = (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
-    if (gate)
-        EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL((adam_kernel<T, true>), dim3(grid), dim3(256), 0, s, p, (const T*)g, m, v,
-                                                   (long long)n, hyper, beta1, beta2, eps, weight_decay, (bf16_t*)bf16_shadow,
-                                                   (bf16_t*)bf16_lo_shadow, (long long*)bump_word, (long long)bump, (const int*)gate));
-    else
-        EGK_DISPATCH_T(g_dtype, hipLaunchKernelGGL((adam_kernel<T, false>), dim3(grid), dim3(256), 0, s, p, (const T*)g, m, v,
-                                                   (long long)n, hyper, beta1, beta2, eps, weight_decay, (bf16_t*)bf16_shadow,
-                                                   (bf16_t*)bf16_lo_shadow, (long long*)bump_word, (long long)bump, (const int*)nullptr));
-    return check_launch("egk_adam_step");
 }
 
 int egk_grad_sumsq_slots(int64_t n) { return n > 0 ? sumsq_grid((long long)n) : 0; }

@@ -1,18 +1,32 @@
-// The update rules of the flat-buffer optimizer behind one launch interface (include/egopack_optim.h): Adam, AdamW and SGD, the
-// single-tensor formulas of torch 2.10.  ONE kernel family in the shape of adam_span / adam_kernel (loss_optim.hip): 16-byte
-// accesses on p, g and the state, a scalar tail for n % 4, the bf16 copy and the low half of the stored p, the offset word moved on
-// by workgroup 0, one wave-uniform load of the gate.  No atomics; every element has one writer.
-// The same family with an exponential moving average of the stored p kept beside it (include/egopack_ema.h): the bottom of the file.
+// The update rules of the flat-buffer optimizer: Adam, AdamW and SGD, the single-tensor formulas of torch 2.10, behind every
+// optimizer entry point of the ABI (egk_adam_step*, include/egopack_hip.h; egk_optim_step, include/egopack_optim.h; the segment
+// table of include/egopack_optim_groups.h; the moving average of include/egopack_ema.h).  ONE body (optim_body) and one kernel
+// family over it: 16-byte accesses on p, g and the state, a scalar tail for n % 4, the bf16 copy and the low half of the stored p,
+// the offset word moved on by workgroup 0, one wave-uniform load of the gate.  No atomics; every element has one writer.
+// ONE dispatcher (optim_dispatch) behind the entry points: the refusals, the grid, the bytes and the launch line.
 #include "common.h"
 
 namespace egk {
+
+// ---- Adam on one element (torch.optim.Adam single-tensor formulas, L2 weight decay) -------------------------------------------------
+struct AdamConsts {
+    float step, bc2s, gs, b1, b2, eps, wd;  // step = lr / (1 - b1^t), bc2s = sqrt(1 - b2^t), gs = gradient scale
+};
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamConsts& c) {
+#pragma clang fp contract(off)  // (no fused multiply-adds: which products the compiler fuses depends on the code around the inlined body)
+    const float gg = g * c.gs + c.wd * p;
+    m = m + (gg - m) * (1.f - c.b1);          // exp_avg.lerp_(grad, 1 - beta1)
+    v = v * c.b2 + (1.f - c.b2) * gg * gg;    // mul_(beta2).addcmul_(g, g, 1 - beta2)
+    const float denom = sqrtf(v) / c.bc2s + c.eps;
+    p = p - c.step * (m / denom);
+}
 
 // what a kernel of the family does per element; the rule codes of the ABI map onto these (SGD: by its momentum)
 enum { K_ADAM = 0, K_ADAMW, K_SGD, K_SGD_MOMENTUM };
 template <int KIND> struct StateCount { static constexpr int value = KIND == K_SGD ? 0 : KIND == K_SGD_MOMENTUM ? 1 : 2; };
 
 struct OptimConsts {
-    AdamConsts adam;    // (K_ADAM: adam_update itself, the shipped kernel's bits; K_ADAMW: its step, bc2s, gs, b2, eps; wd through ``decay``)
+    AdamConsts adam;    // (K_ADAM: adam_update itself; K_ADAMW: its step, bc2s, gs, b2, eps; wd through ``decay``)
     float lr, decay;    // decay = 1 - lr * wd
     float omb1, omb2;   // K_ADAMW: 1 - beta1, 1 - beta2 taken in double, rounded once (torch hands its kernels these scalars)
     float wd, gs, mu, damp1;  // damp1 = 1 - dampening
@@ -106,25 +120,12 @@ __device__ __forceinline__ void optim_tail(float* __restrict__ p, const GT* __re
     }
 }
 
-// the elements [0, n) of one span, grid-stride over ``nblk`` workgroups
-template <int KIND, typename GT, bool EMA = false>
-__device__ __forceinline__ void optim_span(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
-                                           long long n, const OptimConsts& c, bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
-                                           int blk, int nblk, float* __restrict__ ema = nullptr, float w = 0.f) {
-    for (long long i = ((long long)blk * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)nblk * blockDim.x * 4) {
-        if (i + 4 <= n)
-            optim_quad<KIND, GT, EMA>(p, g, s0, s1, i, [&]() -> const OptimConsts& { return c; }, shadow, shadow_lo, ema, w);
-        else
-            optim_tail<KIND, GT, EMA>(p, g, s0, s1, i, n, c, shadow, shadow_lo, ema, w);
-    }
-}
-
 struct OptimHyper {  // the host's scalars of a launch
     float b1, b2, omb1, omb2, eps, wd, mu, damp1;
     int nesterov;
 };
 
-// the constants of a launch from its learning rate and weight decay (of the launch: optim_kernel; of a group: optim_groups_kernel)
+// the constants of a launch from its learning rate and weight decay (of the launch, or of a group: group_consts)
 template <int KIND>
 __device__ __forceinline__ OptimConsts optim_consts(float lr, float wd, const float* __restrict__ hyper, const long long* __restrict__ t_dev,
                                                     const OptimHyper& h) {
@@ -142,32 +143,6 @@ __device__ __forceinline__ OptimConsts optim_consts(float lr, float wd, const fl
     c.nesterov = h.nesterov != 0;
     c.first = KIND == K_SGD_MOMENTUM ? *t_dev == 1 : false;  // (egk_adam_hyper has counted this step)
     return c;
-}
-
-template <int KIND, typename GT, bool GATED>  // GT: element type of the gradient buffer (f32, or bf16 after a compressed all-reduce)
-__global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0,
-                                                    float* __restrict__ s1, long long n, const float* __restrict__ hyper,
-                                                    const long long* __restrict__ t_dev, const OptimHyper h, bf16_t* __restrict__ shadow,
-                                                    bf16_t* __restrict__ shadow_lo, long long* __restrict__ bump_word, long long bump,
-                                                    const int* __restrict__ gate) {
-    // (the step's dropout offset word moves on inside this launch, whether the step happens or not: adam_kernel)
-    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
-    // (a closed gate -- the gradient norm was not finite -- skips the step: one wave-uniform load, nothing else is touched)
-    if (GATED && *gate == 0) return;
-    const OptimConsts c = optim_consts<KIND>(hyper[0], h.wd, hyper, t_dev, h);
-    optim_span<KIND, GT>(p, g, s0, s1, n, c, shadow, shadow_lo, blockIdx.x, gridDim.x);
-}
-
-template <int KIND, typename GT>
-static void optim_launch(hipStream_t s, unsigned grid, const egk_optim_desc& d, const OptimHyper& h) {
-    if (d.gate)
-        hipLaunchKernelGGL((optim_kernel<KIND, GT, true>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
-                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
-                           (long long*)d.bump_word, (long long)d.bump, (const int*)d.gate);
-    else
-        hipLaunchKernelGGL((optim_kernel<KIND, GT, false>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
-                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
-                           (long long*)d.bump_word, (long long)d.bump, (const int*)nullptr);
 }
 
 // ---- parameter groups: lr and weight decay per element from a segment table (include/egopack_optim_groups.h) ----------------------
@@ -188,7 +163,11 @@ __device__ __forceinline__ int seg_find(const long long* __restrict__ seg_begin,
     return lo;
 }
 
-// the constants of the group that holds element i of the 1024-element block at b0 (the lookup optim_groups_kernel describes)
+// The constants of the group that holds element i of the 1024-element block at b0.  The lookup: ONE search per workgroup and
+// 1024-element block for the segment of the block's first element -- workgroup-uniform, so it runs on the scalar unit while the
+// block's vector loads are in flight -- and one comparison that tells whether the block ends inside that segment.  Only the lanes of
+// a block that straddles a boundary search for themselves, over the at most 256 segments a block can touch.  A 16-byte group of
+// elements never straddles (boundaries and base are multiples of 4), so the scalar tail shares the segment of its first element.
 template <int KIND>
 __device__ __forceinline__ OptimConsts group_consts(const GroupTable& t, long long b0, long long i, long long n,
                                                     const float* __restrict__ hyper, const long long* __restrict__ t_dev,
@@ -203,43 +182,6 @@ __device__ __forceinline__ OptimConsts group_consts(const GroupTable& t, long lo
     grp = grp < 0 ? 0 : grp >= t.n_groups ? t.n_groups - 1 : grp;
     const float2 lw = *reinterpret_cast<const float2*>(t.group_hyper + 4 * grp);
     return optim_consts<KIND>(lw.x, lw.y, hyper, t_dev, h);
-}
-
-// optim_kernel with the constants of the group that holds the element.  The lookup: ONE search per workgroup and 1024-element block
-// for the segment of the block's first element -- workgroup-uniform, so it runs on the scalar unit while the block's vector loads are
-// in flight -- and one comparison that tells whether the block ends inside that segment.  Only the lanes of a block that straddles
-// a boundary search for themselves, over the at most 256 segments a block can touch.  A 16-byte group of elements never
-// straddles (boundaries and base are multiples of 4), so the scalar tail shares the segment of its first element.
-template <int KIND, typename GT, bool GATED>
-__global__ __launch_bounds__(256) void optim_groups_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0,
-                                                           float* __restrict__ s1, long long n, const float* __restrict__ hyper,
-                                                           const long long* __restrict__ t_dev, const OptimHyper h,
-                                                           bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
-                                                           long long* __restrict__ bump_word, long long bump, const int* __restrict__ gate,
-                                                           const GroupTable t) {
-    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
-    if (GATED && *gate == 0) return;
-    for (long long b0 = (long long)blockIdx.x * 1024; b0 < n; b0 += (long long)gridDim.x * 1024) {
-        const long long i = b0 + (long long)threadIdx.x * 4;
-        if (i >= n) continue;
-        auto consts = [&]() -> OptimConsts { return group_consts<KIND>(t, b0, i, n, hyper, t_dev, h); };
-        if (i + 4 <= n)
-            optim_quad<KIND, GT>(p, g, s0, s1, i, consts, shadow, shadow_lo);
-        else
-            optim_tail<KIND, GT>(p, g, s0, s1, i, n, consts(), shadow, shadow_lo);
-    }
-}
-
-template <int KIND, typename GT>
-static void optim_groups_launch(hipStream_t s, unsigned grid, const egk_optim_desc& d, const OptimHyper& h, const GroupTable& t) {
-    if (d.gate)
-        hipLaunchKernelGGL((optim_groups_kernel<KIND, GT, true>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
-                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
-                           (long long*)d.bump_word, (long long)d.bump, (const int*)d.gate, t);
-    else
-        hipLaunchKernelGGL((optim_groups_kernel<KIND, GT, false>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
-                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
-                           (long long*)d.bump_word, (long long)d.bump, (const int*)nullptr, t);
 }
 
 // ---- the moving average of the weights inside the launch (include/egopack_ema.h) ----------------------------------------------------
@@ -257,44 +199,72 @@ __device__ __forceinline__ float ema_weight(const EmaArgs& e, const long long* _
     return (float)(1.0 - (e.decay < ramp ? e.decay : ramp));
 }
 
-// optim_kernel (GROUPED = false) / optim_groups_kernel (GROUPED = true) with the average: optim_update, optim_quad and optim_tail
-// are theirs.  The gate pointer is tested at run time (wave-uniform), so the family has one kernel per (kind, gradient type, table).
-template <int KIND, typename GT, bool GROUPED>
-__global__ __launch_bounds__(256) void optim_ema_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0,
-                                                        float* __restrict__ s1, long long n, const float* __restrict__ hyper,
-                                                        const long long* __restrict__ t_dev, const OptimHyper h,
-                                                        bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
-                                                        long long* __restrict__ bump_word, long long bump, const int* __restrict__ gate,
-                                                        const GroupTable t, const EmaArgs e) {
-    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += bump;
-    if (gate && *gate == 0) return;  // (a closed gate: ema, p, the state and the copies stay as they are)
-    const float w = ema_weight(e, t_dev);
-    if constexpr (!GROUPED) {
-        const OptimConsts c = optim_consts<KIND>(hyper[0], h.wd, hyper, t_dev, h);
-        optim_span<KIND, GT, true>(p, g, s0, s1, n, c, shadow, shadow_lo, blockIdx.x, gridDim.x, e.ema, w);
-    } else {
-        for (long long b0 = (long long)blockIdx.x * 1024; b0 < n; b0 += (long long)gridDim.x * 1024) {
-            const long long i = b0 + (long long)threadIdx.x * 4;
-            if (i >= n) continue;
-            auto consts = [&]() -> OptimConsts { return group_consts<KIND>(t, b0, i, n, hyper, t_dev, h); };
-            if (i + 4 <= n)
-                optim_quad<KIND, GT, true>(p, g, s0, s1, i, consts, shadow, shadow_lo, e.ema, w);
-            else
-                optim_tail<KIND, GT, true>(p, g, s0, s1, i, n, consts(), shadow, shadow_lo, e.ema, w);
-        }
+// ---- the one body and the kernels over it --------------------------------------------------------------------------------------------
+struct OptimArgs {  // what a launch of the family is handed; ``t`` without a table and ``e`` without an average stay empty
+    float* p;
+    const void* g;  // f32, or bf16 after a compressed all-reduce (the kernel's GT)
+    float* s0;
+    float* s1;
+    long long n;
+    const float* hyper;
+    const long long* t_dev;
+    bf16_t* shadow;
+    bf16_t* shadow_lo;
+    long long* bump_word;
+    long long bump;
+    const int* gate;
+    OptimHyper h;
+    GroupTable t;
+    EmaArgs e;
+};
+
+// One launch over [0, n): workgroup b takes the 1024-element blocks b, b + gridDim.x, ... (256 threads x 4 elements).  The constants
+// come from the launch's lr and weight decay, formed once, or with GROUPED from the block's group (group_consts).
+// The buffers the launch writes arrive as __restrict__ PARAMETERS (optim_body unpacks them): a qualifier on a struct member tells
+// the compiler nothing, and without it every store may change hyper, the gate and the segment table, whose workgroup-uniform loads
+// then leave the scalar unit (the grouped kernel: 20 vector loads instead of 14).
+template <int KIND, typename GT, bool GROUPED, bool EMA>
+__device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                                           bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo, float* __restrict__ ema,
+                                           long long* __restrict__ bump_word, const OptimArgs& a) {
+    // (a device-side counter that moves on once per step -- the Philox offset word of the step's dropout launches -- rides in this
+    //  launch instead of costing one of its own, whether the step happens or not)
+    if (bump_word && blockIdx.x == 0 && threadIdx.x == 0) *bump_word += a.bump;
+    // (the step's gate word, written by egk_grad_norm_finalize -- 0 = the gradient norm was not finite, the step is skipped: one
+    //  wave-uniform load, nothing of p / the state / the average / the bf16 copies is touched)
+    if (a.gate && *a.gate == 0) return;
+    const float w = EMA ? ema_weight(a.e, a.t_dev) : 0.f;
+    OptimConsts launch{};
+    if constexpr (!GROUPED) launch = optim_consts<KIND>(a.hyper[0], a.h.wd, a.hyper, a.t_dev, a.h);
+    for (long long b0 = (long long)blockIdx.x * 1024; b0 < a.n; b0 += (long long)gridDim.x * 1024) {
+        const long long i = b0 + (long long)threadIdx.x * 4;
+        if (i >= a.n) continue;
+        auto consts = [&]() -> OptimConsts {
+            if constexpr (GROUPED) return group_consts<KIND>(a.t, b0, i, a.n, a.hyper, a.t_dev, a.h);
+            else return launch;
+        };
+        if (i + 4 <= a.n)
+            optim_quad<KIND, GT, EMA>(p, g, s0, s1, i, consts, shadow, shadow_lo, ema, w);
+        else
+            optim_tail<KIND, GT, EMA>(p, g, s0, s1, i, a.n, consts(), shadow, shadow_lo, ema, w);
     }
 }
 
-template <int KIND, typename GT>
-static void optim_ema_launch(hipStream_t s, unsigned grid, const egk_optim_desc& d, const OptimHyper& h, const GroupTable* t, const EmaArgs& e) {
-    if (t)
-        hipLaunchKernelGGL((optim_ema_kernel<KIND, GT, true>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
-                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
-                           (long long*)d.bump_word, (long long)d.bump, (const int*)d.gate, *t, e);
-    else
-        hipLaunchKernelGGL((optim_ema_kernel<KIND, GT, false>), dim3(grid), dim3(256), 0, s, d.p, (const GT*)d.g, d.state0, d.state1,
-                           (long long)d.n, d.hyper, (const long long*)d.t_dev, h, (bf16_t*)d.bf16_shadow, (bf16_t*)d.bf16_lo_shadow,
-                           (long long*)d.bump_word, (long long)d.bump, (const int*)d.gate, GroupTable{}, e);
+template <int KIND, typename GT, bool GROUPED, bool EMA>
+__device__ __forceinline__ void optim_body(const OptimArgs& a) {
+    optim_walk<KIND, GT, GROUPED, EMA>(a.p, static_cast<const GT*>(a.g), a.s0, a.s1, a.shadow, a.shadow_lo, a.e.ema, a.bump_word, a);
+}
+
+template <int KIND, typename GT, bool GROUPED, bool EMA>
+__global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
+    optim_body<KIND, GT, GROUPED, EMA>(a);
+}
+
+// what egk_adam_step* launch: the body for Adam under the name the profiles, bench.py and the timeline tools know the step's
+// optimizer launch by
+template <typename GT>
+__global__ __launch_bounds__(256) void adam_kernel(const OptimArgs a) {
+    optim_body<K_ADAM, GT, false, false>(a);
 }
 
 // p[i] <-> ema[i]: 16-byte accesses, a scalar tail for n % 4, grid-stride
@@ -314,7 +284,7 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, fl
     }
 }
 
-// what both entry points refuse, before any launch; ``a``: the descriptor without the state the rule does not have, ``kind``: its kernel
+// what every entry point refuses, before any launch; ``a``: the descriptor without the state the rule does not have, ``kind``: its kernel
 static int optim_check(const char* who, const egk_optim_desc* d, egk_optim_desc& a, int& kind) {
     EGK_REQUIRE(d, "%s: null descriptor", who);
     EGK_REQUIRE(d->rule == EGK_OPT_ADAM || d->rule == EGK_OPT_ADAMW || d->rule == EGK_OPT_SGD,
@@ -357,26 +327,73 @@ static int groups_check(const char* who, const egk_optim_groups* g) {
     return 0;
 }
 
-// bytes per parameter: p read + written, each state buffer read + written, the gradient read, the bf16 copies written
-static double optim_bytes(const egk_optim_desc& a, int kind) {
-    const double state_bytes = kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0;
-    return (8.0 + state_bytes + (a.g_dtype == EGK_BF16 ? 2.0 : 4.0) + (a.bf16_shadow ? 2.0 : 0.0) + (a.bf16_lo_shadow ? 2.0 : 0.0)) * (double)a.n;
+// what the entry point with the average refuses in its descriptor
+static int ema_check(const char* who, const egk_ema_desc* e, const egk_optim_desc& a) {
+    EGK_REQUIRE(e, "%s: null ema descriptor", who);
+    EGK_REQUIRE(e->ema, "%s: null ema pointer", who);
+    EGK_REQUIRE(((uintptr_t)e->ema & 15) == 0, "%s: ema must be 16-byte aligned", who);
+    EGK_REQUIRE(e->decay >= 0.0 && e->decay < 1.0, "%s: decay in [0, 1) (got %g)", who, e->decay);
+    EGK_REQUIRE(!e->warmup || a.t_dev, "%s: warmup needs t_dev (the device step counter)", who);
+    return 0;
 }
 
-// the grid of egk_adam_step*: one 1024-element group per workgroup up to 32768 of them (measured there)
+// bytes per parameter: p read + written, each state buffer read + written, the gradient read, the bf16 copies written, the average
+// read + written
+static double optim_bytes(const egk_optim_desc& a, int kind, bool ema) {
+    const double state_bytes = kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0;
+    return (8.0 + state_bytes + (a.g_dtype == EGK_BF16 ? 2.0 : 4.0) + (a.bf16_shadow ? 2.0 : 0.0) + (a.bf16_lo_shadow ? 2.0 : 0.0) +
+            (ema ? 8.0 : 0.0)) * (double)a.n;
+}
+
+// Workgroups: one 1024-element group per workgroup up to 32768 of them (egk_tune(6, n) sets the cap).  An optimizer slice runs
+// BESIDE weight-gradient launches in every captured step's tail; round 5 first capped it at 4096 (a 8 us reduction queued beside
+// it had waited 135 us for wave slots) and, once the gradient buffer was no longer cleared and read back, measured the wide grid
+// ahead again: headline 1.365-1.379 against 1.374-1.386 ms, config 4 2.180-2.182 against 2.191-2.206, Hp = 4096 2.722 against
+// 2.751 (narrower is clearly worse: 1024 workgroups 1.405-1.414, 512 1.447)
 static unsigned optim_grid(long long n) {
     const long long want = (n / 4 + 255) / 256;
     const long long cap = 32768;
     return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
-static GroupTable group_table(const egk_optim_groups& g) {
-    return GroupTable{(long long)g.base, (int)g.n_seg, (int)g.n_groups, (const long long*)g.seg_begin, (const int*)g.seg_group, g.group_hyper};
+// the kernel of a launch: adam_kernel for egk_adam_step* (KID_ADAM), otherwise the member of the family
+template <int KIND, typename GT>
+static auto optim_pick(int kid, bool grouped, bool ema) -> void (*)(OptimArgs) {
+    if (kid == KID_ADAM) return adam_kernel<GT>;
+    if (grouped) return ema ? optim_kernel<KIND, GT, true, true> : optim_kernel<KIND, GT, true, false>;
+    return ema ? optim_kernel<KIND, GT, false, true> : optim_kernel<KIND, GT, false, false>;
 }
 
-static OptimHyper optim_hyper(const egk_optim_desc& a) {
-    return OptimHyper{(float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), a.eps, a.weight_decay, a.momentum,
-                      (float)(1.0 - (double)a.dampening), a.nesterov ? 1 : 0};
+// Every optimizer entry point: the refusals, then one launch.  ``who``: the name the messages carry; ``kid``: the entry point's
+// profile id -- KID_OPTIM_GROUPS requires the table ``g``, KID_OPTIM_EMA the average ``e`` (and takes a table or none).
+static int optim_dispatch(const char* who, int kid, egk_stream_t stream, const egk_optim_desc* d, const egk_optim_groups* g,
+                          const egk_ema_desc* e) {
+    egk_optim_desc a;
+    int kind = 0;
+    if (const int rc = optim_check(who, d, a, kind)) return rc;
+    if (g || kid == KID_OPTIM_GROUPS)
+        if (const int rc = groups_check(who, g)) return rc;
+    if (kid == KID_OPTIM_EMA)
+        if (const int rc = ema_check(who, e, a)) return rc;
+    if (a.n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(kid, s, 0, optim_bytes(a, kind, e != nullptr));
+    OptimArgs k{a.p, a.g, a.state0, a.state1, (long long)a.n, a.hyper, (const long long*)a.t_dev, (bf16_t*)a.bf16_shadow,
+                (bf16_t*)a.bf16_lo_shadow, (long long*)a.bump_word, (long long)a.bump, (const int*)a.gate,
+                OptimHyper{(float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), a.eps, a.weight_decay,
+                           a.momentum, (float)(1.0 - (double)a.dampening), a.nesterov ? 1 : 0},
+                GroupTable{}, EmaArgs{}};
+    if (g) k.t = GroupTable{(long long)g->base, (int)g->n_seg, (int)g->n_groups, (const long long*)g->seg_begin, (const int*)g->seg_group, g->group_hyper};
+    if (e) k.e = EmaArgs{e->ema, e->decay, (float)(1.0 - e->decay), e->warmup ? 1 : 0};
+    void (*kernel)(OptimArgs) = nullptr;
+    switch (kind) {
+        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_ADAM, T>(kid, g, e))); break;
+        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_ADAMW, T>(kid, g, e))); break;
+        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_SGD, T>(kid, g, e))); break;
+        default: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_SGD_MOMENTUM, T>(kid, g, e))); break;
+    }
+    hipLaunchKernelGGL(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, k);
+    return check_launch(who);
 }
 
 }  // namespace egk
@@ -384,70 +401,39 @@ static OptimHyper optim_hyper(const egk_optim_desc& a) {
 using namespace egk;
 
 extern "C" int egk_optim_step(egk_stream_t stream, const egk_optim_desc* d) {
-    egk_optim_desc a;
-    int kind = 0;
-    if (const int rc = optim_check("egk_optim_step", d, a, kind)) return rc;
-    if (a.n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_OPTIM, s, 0, optim_bytes(a, kind));
-    const unsigned grid = optim_grid(a.n);
-    const OptimHyper h = optim_hyper(a);
-    switch (kind) {
-        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_ADAM, T>(s, grid, a, h))); break;
-        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_ADAMW, T>(s, grid, a, h))); break;
-        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_SGD, T>(s, grid, a, h))); break;
-        default: EGK_DISPATCH_T(a.g_dtype, (optim_launch<K_SGD_MOMENTUM, T>(s, grid, a, h))); break;
-    }
-    return check_launch("egk_optim_step");
+    return optim_dispatch("egk_optim_step", KID_OPTIM, stream, d, nullptr, nullptr);
 }
 
 extern "C" int egk_optim_step_groups(egk_stream_t stream, const egk_optim_desc* d, const egk_optim_groups* g) {
-    egk_optim_desc a;
-    int kind = 0;
-    if (const int rc = optim_check("egk_optim_step_groups", d, a, kind)) return rc;
-    if (const int rc = groups_check("egk_optim_step_groups", g)) return rc;
-    if (a.n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_OPTIM_GROUPS, s, 0, optim_bytes(a, kind));
-    const unsigned grid = optim_grid(a.n);
-    const OptimHyper h = optim_hyper(a);
-    const GroupTable t = group_table(*g);
-    switch (kind) {
-        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_ADAM, T>(s, grid, a, h, t))); break;
-        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_ADAMW, T>(s, grid, a, h, t))); break;
-        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_SGD, T>(s, grid, a, h, t))); break;
-        default: EGK_DISPATCH_T(a.g_dtype, (optim_groups_launch<K_SGD_MOMENTUM, T>(s, grid, a, h, t))); break;
-    }
-    return check_launch("egk_optim_step_groups");
+    return optim_dispatch("egk_optim_step_groups", KID_OPTIM_GROUPS, stream, d, g, nullptr);
 }
 
 extern "C" int egk_optim_step_ema(egk_stream_t stream, const egk_optim_desc* d, const egk_optim_groups* g, const egk_ema_desc* e) {
-    egk_optim_desc a;
-    int kind = 0;
-    if (const int rc = optim_check("egk_optim_step_ema", d, a, kind)) return rc;
-    if (g)
-        if (const int rc = groups_check("egk_optim_step_ema", g)) return rc;
-    EGK_REQUIRE(e, "egk_optim_step_ema: null ema descriptor");
-    EGK_REQUIRE(e->ema, "egk_optim_step_ema: null ema pointer");
-    EGK_REQUIRE(((uintptr_t)e->ema & 15) == 0, "egk_optim_step_ema: ema must be 16-byte aligned");
-    EGK_REQUIRE(e->decay >= 0.0 && e->decay < 1.0, "egk_optim_step_ema: decay in [0, 1) (got %g)", e->decay);
-    EGK_REQUIRE(!e->warmup || a.t_dev, "egk_optim_step_ema: warmup needs t_dev (the device step counter)");
-    if (a.n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_OPTIM_EMA, s, 0, optim_bytes(a, kind) + 8.0 * (double)a.n);
-    const unsigned grid = optim_grid(a.n);
-    const OptimHyper h = optim_hyper(a);
-    GroupTable table{};
-    if (g) table = group_table(*g);
-    const GroupTable* t = g ? &table : nullptr;
-    const EmaArgs ea{e->ema, e->decay, (float)(1.0 - e->decay), e->warmup ? 1 : 0};
-    switch (kind) {
-        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (optim_ema_launch<K_ADAM, T>(s, grid, a, h, t, ea))); break;
-        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (optim_ema_launch<K_ADAMW, T>(s, grid, a, h, t, ea))); break;
-        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (optim_ema_launch<K_SGD, T>(s, grid, a, h, t, ea))); break;
-        default: EGK_DISPATCH_T(a.g_dtype, (optim_ema_launch<K_SGD_MOMENTUM, T>(s, grid, a, h, t, ea))); break;
-    }
-    return check_launch("egk_optim_step_ema");
+    return optim_dispatch("egk_optim_step_ema", KID_OPTIM_EMA, stream, d, g, e);
+}
+
+// egk_adam_step*: EGK_OPT_ADAM from scalar arguments, under its own profile id and kernel name
+extern "C" int egk_adam_step_gated(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
+                                   const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
+                                   void* bf16_lo_shadow, int64_t* bump_word, int64_t bump, const int32_t* gate) {
+    egk_optim_desc d{};
+    d.rule = EGK_OPT_ADAM, d.g_dtype = g_dtype, d.n = n;
+    d.p = p, d.g = g, d.state0 = m, d.state1 = v, d.hyper = hyper;
+    d.beta1 = beta1, d.beta2 = beta2, d.eps = eps, d.weight_decay = weight_decay;
+    d.bf16_shadow = bf16_shadow, d.bf16_lo_shadow = bf16_lo_shadow, d.bump_word = bump_word, d.bump = bump, d.gate = gate;
+    return optim_dispatch("egk_adam_step", KID_ADAM, stream, &d, nullptr, nullptr);
+}
+
+extern "C" int egk_adam_step_bump(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
+                                  const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
+                                  void* bf16_lo_shadow, int64_t* bump_word, int64_t bump) {
+    return egk_adam_step_gated(stream, p, g, g_dtype, m, v, n, hyper, beta1, beta2, eps, weight_decay, bf16_shadow, bf16_lo_shadow,
+                               bump_word, bump, nullptr);
+}
+
+extern "C" int egk_adam_step(egk_stream_t stream, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
+                             const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow) {
+    return egk_adam_step_bump(stream, p, g, g_dtype, m, v, n, hyper, beta1, beta2, eps, weight_decay, bf16_shadow, nullptr, nullptr, 0);
 }
 
 extern "C" int egk_ema_swap(egk_stream_t stream, float* p, float* ema, int64_t n) {

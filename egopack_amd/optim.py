@@ -27,6 +27,7 @@ saving; the state dict carries it under a third top-level key, ``"ema"``."""
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import logging
 import math
 from typing import Iterable, List
@@ -674,7 +675,6 @@ class FlatOptimizer(torch.optim.Optimizer):
     def _zero_all_but_stored(self) -> bool:
         if not getattr(self, "_store_active", False):
             return False
-        import ctypes as C
         total, at, rest = self.flat_g.numel(), 0, []
         for off in sorted(self.store_slots):
             n = self.store_slots[off]
@@ -811,7 +811,6 @@ class FlatOptimizer(torch.optim.Optimizer):
         if bump is not None:
             d.bump_word, d.bump = bump[0].data_ptr(), int(bump[1])
         d.gate = gate.data_ptr() if gate is not None else None
-        import ctypes as C
         t = None
         if self.grouped:
             t = _lib.OptimGroups()
@@ -916,26 +915,13 @@ class FlatAdam(FlatOptimizer):
             self._optim_step(_lib.OPT_ADAMW if self.decoupled_weight_decay else _lib.OPT_ADAM, sl, grads, lo16, bump, gate,
                              beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"])
             return
-        if gate is not None:
-            _ck(_lib.load().egk_adam_step_gated(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
-                                                _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
-                                                g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
-                                                _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0,
-                                                _p(gate)),
-                "egk_adam_step_gated")
-            return
-        if bump is not None or lo16 is not None:
-            _ck(_lib.load().egk_adam_step_bump(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
-                                               _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
-                                               g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
-                                               _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0),
-                "egk_adam_step_bump")
-            return
-        _ck(_lib.load().egk_adam_step(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
-                                      _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
-                                      g["eps"], g["weight_decay"], _p(self.flat_w16[sl])),
-            "egk_adam_step")
-
+        # (no low halves, no offset word, no gate: null, which is what egk_adam_step / egk_adam_step_bump hand on)
+        _ck(_lib.load().egk_adam_step_gated(_stream(), _p(self.flat_p[sl]), _p(grads[sl]), 1 if grads.dtype == torch.bfloat16 else 0,
+                                            _p(self.flat_m[sl]), _p(self.flat_v[sl]), n, _p(self._hyper), b1, b2,
+                                            g["eps"], g["weight_decay"], _p(self.flat_w16[sl]), _p(lo16),
+                                            _p(bump[0]) if bump is not None else None, int(bump[1]) if bump is not None else 0,
+                                            _p(gate)),
+            "egk_adam_step_gated")
 
 
 class FlatAdamW(FlatAdam):

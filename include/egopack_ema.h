@@ -36,8 +36,8 @@ typedef struct egk_ema_desc {
  * in f32, three separately rounded operations (no fused multiply-add); w is formed in double and rounded once.  The update
  * itself is the instruction sequence of the launch without the average: p, the state and both bf16 copies come out with its
  * bits.  All four kernel kinds, f32 and bf16 gradients, plain and grouped.  One writer per element, vector stores, no atomics.
- * The gate: this family has ONE kernel per (kind, gradient type, plain | grouped); d->gate is tested for NULL at run time
- * (wave-uniform) instead of selecting a second instantiation, so no device word holding 1 is needed when clipping is off.
+ * The gate: as in every optimizer launch, d->gate is tested for NULL at run time (wave-uniform), there is no second
+ * instantiation, and no device word holding 1 is needed when clipping is off.
  * A closed gate (*d->gate == 0) returns after that one load: ema, p, the state and the copies untouched, *bump_word moved on.
  * Refused before any launch: e or e->ema NULL, ema not 16-byte aligned, decay outside [0, 1), warmup with d->t_dev NULL, and
  * everything egk_optim_step / egk_optim_step_groups refuse.  Profile id "optim_ema": the rule's bytes + 8 per element. */

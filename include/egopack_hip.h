@@ -696,7 +696,8 @@ int egk_grad_sumsq(egk_stream_t s, const void* g, int32_t g_dtype, int64_t n, do
 int egk_grad_norm_finalize(egk_stream_t s, const double* partials, int32_t n_slots, const float* src, float max_norm, float* hyper,
                            int64_t* t_dev, int32_t* gate, double* stats);
 /* egk_adam_step_bump behind a gate word (device int32, written by egk_grad_norm_finalize; NULL: no gate): when *gate == 0 the
- * launch leaves p, m, v and both bf16 copies untouched -- *bump_word still moves on. */
+ * launch leaves p, m, v and both bf16 copies untouched -- *bump_word still moves on.  The three egk_adam_step* are EGK_OPT_ADAM
+ * of egopack_optim.h from scalar arguments: the same kernel body, refusals and bits, under the profile id "adam". */
 int egk_adam_step_gated(egk_stream_t s, float* p, const void* g, int32_t g_dtype, float* m, float* v, int64_t n,
                         const float* hyper, float beta1, float beta2, float eps, float weight_decay, void* bf16_shadow,
                         void* bf16_lo_shadow, int64_t* bump_word, int64_t bump, const int32_t* gate);

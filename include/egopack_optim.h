@@ -26,7 +26,7 @@ enum { EGK_OPT_ADAM = 0, EGK_OPT_ADAMW = 1, EGK_OPT_SGD = 2 };
  *   EGK_OPT_ADAM   g' = g*s + wd*p; m = m + (g' - m)*(1-b1); v = v*b2 + (1-b2)*g'*g';
  *                  p -= (lr/hyper[1]) * m / (sqrt(v)/hyper[2] + eps)      -- egk_adam_step_gated's bits
  *   EGK_OPT_ADAMW  p *= 1 - lr*wd; then the lines above with g' = g*s; 1-b1, 1-b2 and 1 - lr*wd are taken in double and rounded
- *                  once, as torch rounds the scalars it hands its kernels (EGK_OPT_ADAM keeps the shipped kernel's f32 1.f - b)
+ *                  once, as torch rounds the scalars it hands its kernels (EGK_OPT_ADAM keeps egk_adam_step's f32 1.f - b)
  *   EGK_OPT_SGD    g' = g*s + wd*p; momentum != 0: buf = g' when *t_dev == 1 (the first step that happens: a skipped step is
  *                  taken back out of the counter), else buf = momentum*buf + (1-dampening)*g'; step = g' + momentum*buf
  *                  (nesterov) or buf; momentum == 0: step = g'.  p -= lr*step

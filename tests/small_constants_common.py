@@ -35,7 +35,7 @@ def rounded(t, dt):
 TOL_ROWLN = dict(y=5e-7, dx=6e-7, dw=9e-7, db=7e-7)
 TOL_GRAPHLN = dict(y=5e-7, dx=5e-7, dw=1e-6, db=6e-7)
 TOL_ADAM_P = 1e-6
-# exp_avg / exp_avg_sq span 20 decades: per ELEMENT, relative, atol = 0.  EGK_OPT_ADAM keeps the shipped kernel's f32 ``1.f - beta``
+# exp_avg / exp_avg_sq span 20 decades: per ELEMENT, relative, atol = 0.  EGK_OPT_ADAM keeps egk_adam_step's f32 ``1.f - beta``
 # (include/egopack_optim.h): fl32(1 - fl32(0.999)) is 1.3e-5 away from 0.001, and exp_avg_sq carries that; EGK_OPT_ADAMW rounds
 # 1 - beta once from double.
 TOL_ADAM_STATE = dict(adam=dict(m=2e-6, v=6e-5), adamw=dict(m=2e-6, v=2e-6))

@@ -70,7 +70,7 @@ def autograd_objective(L, w, s):
 
 
 def adam_first_step(g, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-    """The flat optimizer's Adam rule (csrc/common.h: adam_update; include/egopack_hip.h: egk_adam_hyper) for ONE element at step
+    """The flat optimizer's Adam rule (csrc/optim_rules.hip: adam_update; include/egopack_hip.h: egk_adam_hyper) for ONE element at step
     t = 1 from p = m = v = 0 with weight_decay 0 and gradient scale 1, in float64 -- with the hyperparameters at the precision the
     launch receives them: lr, beta1, beta2, eps and the bias corrections 1 - beta1^t and sqrt(1 - beta2^t) are f32 numbers (the last
     two formed in double and rounded once).  They are the rule's inputs, not its error: 1 - fl32(0.999) differs from 0.001 by

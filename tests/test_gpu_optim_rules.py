@@ -110,7 +110,12 @@ def _stream():
 @pytest.mark.parametrize("gate", [None, 1])
 def test_rule_zero_is_the_shipped_adam_kernel_bit_for_bit(gdt, gate):
     """EGK_OPT_ADAM through egk_optim_step against egk_adam_step_gated on the same inputs: n % 4 != 0 and a size with several
-    workgroups, with both bf16 copies and the offset word."""
+    workgroups, with both bf16 copies and the offset word.
+    Both entry points run ONE body (csrc/optim_rules.hip: optim_body; adam_kernel is a shell over it), so this compares two doors
+    to it -- the descriptor filled by the caller against the one egk_adam_step_gated fills, the two kernel names -- and no longer
+    pins Adam's bits independently.  What pins them: test_rule_matches_the_torch_class (this file; Adam itself:
+    tests/test_gpu_kernels.py::test_flat_adam_matches_torch_adam), tests/test_gpu_small_constants.py against the fp64 formulas, and
+    the comparison of every optimizer output against the build before the bodies were unified (profiles/optim_unified_cost.txt)."""
     from egopack_amd import _lib
     lib = _lib.load()
     for n in (1003, 300007):
@@ -252,3 +257,66 @@ def test_closed_gate_changes_nothing_but_the_offset_word(kind, kw):
     assert int(opt._t_dev.item()) == 1 and not torch.equal(opt.flat_p, p0)
     if kw.get("momentum") and not kw.get("weight_decay"):
         assert torch.equal(opt.state_buffers()[0], g1)  # buf = g' on the first step that happens
+
+
+# ---- 3. the capped grid: a workgroup that takes a second stride ----------------------------------------------------------------------
+GRID_CAP = 32768                    # workgroups (csrc/optim_rules.hip: optim_grid), 1024 elements each per stride
+N_CAPPED = GRID_CAP * 1024 + 1027   # the smallest size at which a workgroup takes a second stride, with a scalar tail (n % 4 == 3)
+CUT = 1024 * 1000                   # [CUT, N_CAPPED) alone is 31769 workgroups: under the cap
+
+
+@pytest.mark.parametrize("rule", ["adam", "sgd"])
+def test_second_stride_of_the_capped_grid_equals_two_launches_under_the_cap(rule):
+    """n = 32768 * 1024 + 1027, f32 gradient: Adam through egk_adam_step_gated, SGD without momentum through egk_optim_step.  One
+    launch over [0, n) -- workgroups 0 and 1 walk on to the blocks 32768 and 32769, the last one ends in a scalar tail -- equals
+    the launches over [0, CUT) and [CUT, n), neither of which reaches the cap, bit for bit in p, the state and both bf16 copies.
+    4096 elements around 32768 * 1024 are held to the fp64 formula at this file's tolerance, so the equal bits are the right ones."""
+    from egopack_amd import _lib
+    lib = _lib.load()
+    n = N_CAPPED
+    lr, b1, b2, eps, wd = 1e-2, 0.9, 0.999, 1e-8, 1e-3
+    g = torch.Generator(device=DEV).manual_seed(7)
+    p0, gr = torch.randn(n, device=DEV, generator=g), torch.randn(n, device=DEV, generator=g)
+    state0 = [torch.randn(n, device=DEV, generator=g) * 0.1, torch.rand(n, device=DEV, generator=g) * 0.01] if rule == "adam" else []
+    hyper = torch.tensor([lr, 1 - b1 ** 3, (1 - b2 ** 3) ** 0.5, 0.5], device=DEV)
+
+    def launch(bufs, lo, hi):
+        p, state, hi16, lo16 = bufs
+        if rule == "adam":
+            rc = lib.egk_adam_step_gated(_stream(), _p(p, 4 * lo), _p(gr, 4 * lo), 0, _p(state[0], 4 * lo), _p(state[1], 4 * lo), hi - lo,
+                                         _p(hyper), b1, b2, eps, wd, _p(hi16, 2 * lo), _p(lo16, 2 * lo), None, 0, None)
+        else:
+            d = _lib.OptimDesc()
+            d.rule, d.g_dtype, d.n = _lib.OPT_SGD, 0, hi - lo
+            d.p, d.g, d.hyper, d.weight_decay = p.data_ptr() + 4 * lo, gr.data_ptr() + 4 * lo, hyper.data_ptr(), wd
+            d.bf16_shadow, d.bf16_lo_shadow = hi16.data_ptr() + 2 * lo, lo16.data_ptr() + 2 * lo
+            rc = lib.egk_optim_step(_stream(), ctypes.byref(d))
+        assert rc == 0, _lib.last_error()
+
+    outs = []
+    for pieces in ([(0, n)], [(0, CUT), (CUT, n)]):
+        bufs = (p0.clone(), [s.clone() for s in state0], torch.zeros(n, dtype=BF, device=DEV), torch.zeros(n, dtype=BF, device=DEV))
+        for lo, hi in pieces:
+            launch(bufs, lo, hi)
+        torch.cuda.synchronize()
+        outs.append([bufs[0], *bufs[1], bufs[2].view(torch.int16), bufs[3].view(torch.int16)])
+    names = ["p", *(("exp_avg", "exp_avg_sq") if rule == "adam" else ()), "bf16 copy", "low half"]
+    assert not torch.equal(outs[0][0][-1027:], p0[-1027:])  # (the second stride and its tail were stepped)
+    for a, b, what in zip(outs[0], outs[1], names):
+        assert torch.equal(a, b), what
+
+    w = slice(GRID_CAP * 1024 - 2048, GRID_CAP * 1024 + 2048)
+    h = [float(x) for x in hyper.double().cpu()]
+    p, gg = p0[w].double().cpu(), gr[w].double().cpu() * h[3]
+    gg = gg + wd * p
+    if rule == "adam":
+        m, v = state0[0][w].double().cpu(), state0[1][w].double().cpu()
+        m = m + (gg - m) * (1 - b1)
+        v = v * b2 + (1 - b2) * gg * gg
+        want = [p - (h[0] / h[1]) * (m / (v.sqrt() / h[2] + eps)), m, v]
+    else:
+        want = [p - h[0] * gg]
+    for got, ref, what in zip(outs[0], want, names):
+        err = float(((got[w].double().cpu() - ref).abs() / (TOL["atol"] + TOL["rtol"] * ref.abs())).max())
+        print(f"{rule}: {what} around the second stride, largest |got - want| / (atol + rtol |want|) = {err:.4f}")
+        torch.testing.assert_close(got[w].cpu(), ref.float(), **TOL, msg=lambda s, what=what: f"{what}: {s}")
