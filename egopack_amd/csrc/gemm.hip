@@ -69,6 +69,9 @@ struct GemmArgs {
     const float* st_w;
     const float* st_b;
     float st_slope;
+    // rows epilogue: 1 = the descriptor-once, mode-specialised store loop (gemm_epilogue_rows_fast), which implies
+    // epilogue_rows_ok(g) -- set on the host; 0 = the branch-ladder loop (egk_gemm_set_pipeline(890 / 891))
+    int epi;
 };
 
 // Workgroup -> (slab z, tile row, tile column) for a 1-D launch of tiles_m * tiles_n * splitk workgroups.
@@ -546,6 +549,348 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmArgs& g, const f32x
     }
 }
 
+// ---- the rows epilogue, descriptor-once form (GemmArgs::epi) -------------------------------------------------------------------
+// gemm_epilogue_rows above reads every descriptor field it branches on from the kernarg segment again in each of its 2 * NI
+// unrolled iterations (kernarg loads are rematerialisable, so the compiler sinks them to their uses): about 13 dependent
+// scalar-cache round trips in front of the iteration's only store, and every global load of an iteration (C rows, residual
+// rows, st_x rows) is waited for with vmcnt(0), which also waits for the stores of the iteration before it.  This form
+//   * folds the descriptor into one wave-uniform mode word and reads the fields the loop needs ONCE, into scalar registers
+//     that an empty asm pins (not rematerialisable), before the staging barrier;
+//   * selects, by ONE uniform switch on the mode word outside the loop, a store loop compiled for that mode (the modes the
+//     training step issues; every other combination takes the general body, which branches on the pinned mode word);
+//   * runs the specialised loops in two phases: the LDS reads and the global row loads of ALL iterations first, then the
+//     arithmetic and the stores -- no load follows a store, so no wait covers a store;
+//   * takes the bias / st_mode 2 operands (bias, st_w, st_b, st_stats, the segment walk) from a RowsPre that the loader-wave
+//     kernels fill at kernel entry (their compute waves issue no other vector-memory instruction before the epilogue) and every
+//     other kernel fills in front of the staging barrier.
+// The operations on an element and their order are gemm_epilogue_rows' (alpha, + C, + bias, ReLU, + residual, round, statistics
+// of the rounded value), with the one contraction the compiler forms there written out (pre = fma(xh, w, b) of st_mode 2) and
+// contraction switched off otherwise: results, slabs and st_ws are the same bits.
+enum : unsigned { RM_ACC = 1, RM_BIAS = 2, RM_RELU = 4, RM_RES16 = 8, RM_RES32 = 16, RM_CB = 32, RM_ST1 = 64, RM_ST2 = 128, RM_SLAB = 256 };
+
+struct RowsPre {
+    unsigned mode;
+    int s0, s_split;
+    float mu[2], ri[2];
+    float bias[8], lw[8], lb[8];
+};
+
+// W = false leaves st_w / st_b (16 registers) to rows_prefetch_w: at the entry of the 192-row kernel they would not fit its budget
+template <bool ST, bool W = true>
+__device__ __forceinline__ void rows_prefetch(const GemmArgs& g, int m0, int n0, int tid, RowsPre& P) {
+    unsigned mode = RM_SLAB;
+    if (g.splitk == 1) {
+        mode = (g.accumulate ? RM_ACC : 0u) | (g.bias ? RM_BIAS : 0u) | (g.act == EGK_ACT_RELU ? RM_RELU : 0u) |
+               (g.residual ? (g.r_bf16 ? RM_RES16 : RM_RES32) : 0u) | (g.c_bf16 ? RM_CB : 0u);
+        if (ST && g.st_mode) mode |= g.st_mode == 2 ? RM_ST2 : RM_ST1;
+    }
+    P.mode = mode;
+    P.s0 = 0;
+    P.s_split = 0x7fffffff;
+    P.mu[0] = P.mu[1] = P.ri[0] = P.ri[1] = 0.f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) P.bias[t] = P.lw[t] = P.lb[t] = 0.f;
+    const int n = n0 + (tid & 15) * 8;
+    const bool cols = n < g.N;  // (N % 8 == 0: a group of 8 columns is all in or all out)
+    if ((mode & RM_BIAS) && cols) {
+        const float4 b0 = *reinterpret_cast<const float4*>(g.bias + n), b1 = *reinterpret_cast<const float4*>(g.bias + n + 4);
+        P.bias[0] = b0.x; P.bias[1] = b0.y; P.bias[2] = b0.z; P.bias[3] = b0.w; P.bias[4] = b1.x; P.bias[5] = b1.y; P.bias[6] = b1.z; P.bias[7] = b1.w;
+    }
+    if (mode & (RM_ST1 | RM_ST2)) {
+        int s0 = 0;
+        while (s0 + 1 < g.st_nseg && m0 >= g.st_seg_ptr[s0 + 1]) ++s0;
+        if (s0 + 1 < g.st_nseg) P.s_split = g.st_seg_ptr[s0 + 1];
+        P.s0 = s0;
+        if (mode & RM_ST2) {
+            P.mu[0] = g.st_stats[s0 * 2]; P.ri[0] = g.st_stats[s0 * 2 + 1];
+            if (s0 + 1 < g.st_nseg) { P.mu[1] = g.st_stats[s0 * 2 + 2]; P.ri[1] = g.st_stats[s0 * 2 + 3]; }
+            if (W && cols) {  // (st_w / st_b: 16-byte aligned, checked on the host)
+                const float4 w0 = *reinterpret_cast<const float4*>(g.st_w + n), w1 = *reinterpret_cast<const float4*>(g.st_w + n + 4);
+                const float4 c0 = *reinterpret_cast<const float4*>(g.st_b + n), c1 = *reinterpret_cast<const float4*>(g.st_b + n + 4);
+                P.lw[0] = w0.x; P.lw[1] = w0.y; P.lw[2] = w0.z; P.lw[3] = w0.w; P.lw[4] = w1.x; P.lw[5] = w1.y; P.lw[6] = w1.z; P.lw[7] = w1.w;
+                P.lb[0] = c0.x; P.lb[1] = c0.y; P.lb[2] = c0.z; P.lb[3] = c0.w; P.lb[4] = c1.x; P.lb[5] = c1.y; P.lb[6] = c1.z; P.lb[7] = c1.w;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void rows_prefetch_w(const GemmArgs& g, int n0, int tid, RowsPre& P) {
+    const int n = n0 + (tid & 15) * 8;
+    if ((P.mode & RM_ST2) && n < g.N) {
+        const float4 w0 = *reinterpret_cast<const float4*>(g.st_w + n), w1 = *reinterpret_cast<const float4*>(g.st_w + n + 4);
+        const float4 c0 = *reinterpret_cast<const float4*>(g.st_b + n), c1 = *reinterpret_cast<const float4*>(g.st_b + n + 4);
+        P.lw[0] = w0.x; P.lw[1] = w0.y; P.lw[2] = w0.z; P.lw[3] = w0.w; P.lw[4] = w1.x; P.lw[5] = w1.y; P.lw[6] = w1.z; P.lw[7] = w1.w;
+        P.lb[0] = c0.x; P.lb[1] = c0.y; P.lb[2] = c0.z; P.lb[3] = c0.w; P.lb[4] = c1.x; P.lb[5] = c1.y; P.lb[6] = c1.z; P.lb[7] = c1.w;
+    }
+}
+
+// the descriptor fields of the store loop, each in scalar registers of its own
+struct RowsDesc {
+    int M, N;
+    unsigned mode;
+    float alpha, slope;
+    char* C;
+    const char* R;
+    const char* X;
+    float* ws;
+    long long ldc, ldr, ldx;
+};
+
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+// (the pinned pointers have lost their address space: say it, or every access becomes a flat one, counted on both wait counters)
+typedef const __attribute__((address_space(1))) f32x4* gload_f32x4;
+typedef const __attribute__((address_space(1))) u32x4* gload_u32x4;
+typedef __attribute__((address_space(1))) f32x4* gstore_f32x4;
+typedef __attribute__((address_space(1))) u32x4* gstore_u32x4;
+
+__device__ __forceinline__ void unpack_bf16x8(const u32x4& r, float (&f)[8]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        f[2 * t] = __uint_as_float(r[t] << 16);
+        f[2 * t + 1] = __uint_as_float(r[t] & 0xffff0000u);
+    }
+}
+
+// the global rows one iteration reads (which of them depends on the mode)
+struct RowLoads {
+    f32x4 c0, c1, r0, r1, x0, x1;
+    u32x4 rh, xh;
+};
+
+__device__ __forceinline__ void rows_load(const RowsDesc& D, unsigned mode, long long mc, int n, RowLoads& L) {
+    if (mode & RM_ACC) {  // C is f32 when accumulating (checked on the host)
+        const gload_f32x4 cp = (gload_f32x4)(D.C + (mc * D.ldc + n) * 4);
+        L.c0 = cp[0]; L.c1 = cp[1];
+    }
+    if (mode & RM_RES16) L.rh = *(gload_u32x4)(D.R + (mc * D.ldr + n) * 2);
+    if (mode & RM_RES32) {
+        const gload_f32x4 rp = (gload_f32x4)(D.R + (mc * D.ldr + n) * 4);
+        L.r0 = rp[0]; L.r1 = rp[1];
+    }
+    if (mode & RM_ST2) {
+        if (mode & RM_CB) L.xh = *(gload_u32x4)(D.X + (mc * D.ldx + n) * 2);
+        else {
+            const gload_f32x4 xp = (gload_f32x4)(D.X + (mc * D.ldx + n) * 4);
+            L.x0 = xp[0]; L.x1 = xp[1];
+        }
+    }
+}
+
+// One row of 8 columns: gemm_epilogue_rows' arithmetic in its order, the store, the statistics.
+__device__ __forceinline__ void rows_finish(const RowsDesc& D, const RowsPre& P, unsigned mode, const f32x4& lo, const f32x4& hi,
+                                            const RowLoads& L, int m, int n, int z, float (&sa)[2][2]) {
+#pragma clang fp contract(off)
+    const bool ok = m < D.M;
+    float o[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    if (mode & RM_SLAB) {
+        if (ok) {
+            const gstore_f32x4 p = (gstore_f32x4)(reinterpret_cast<char*>(D.ws) + (((long long)z * D.M + m) * D.N + n) * 4);
+            p[0] = lo; p[1] = hi;
+        }
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) o[t] *= D.alpha;
+    if (mode & RM_ACC)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { o[t] += L.c0[t]; o[4 + t] += L.c1[t]; }
+    if (mode & RM_BIAS)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) o[t] += P.bias[t];
+    if (mode & RM_RELU)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) o[t] = fmaxf(o[t], 0.f);
+    if (mode & RM_RES16) {
+        float r[8];
+        unpack_bf16x8(L.rh, r);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) o[t] += r[t];
+    }
+    if (mode & RM_RES32)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { o[t] += L.r0[t]; o[4 + t] += L.r1[t]; }
+    if (mode & RM_CB) {
+        u32x4 pk;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) pk[t] = (unsigned)f32_to_bf16(o[2 * t]) | ((unsigned)f32_to_bf16(o[2 * t + 1]) << 16);
+        if (ok) *(gstore_u32x4)(D.C + ((long long)m * D.ldc + n) * 2) = pk;
+        if (mode & (RM_ST1 | RM_ST2)) unpack_bf16x8(pk, o);  // the sums are those of the values a reader of C would READ: the rounded ones
+    } else if (ok) {
+        const gstore_f32x4 cp = (gstore_f32x4)(D.C + ((long long)m * D.ldc + n) * 4);
+        cp[0] = f32x4{o[0], o[1], o[2], o[3]};
+        cp[1] = f32x4{o[4], o[5], o[6], o[7]};
+    }
+    if (!(mode & (RM_ST1 | RM_ST2))) return;
+    const bool rel = m >= P.s_split;
+    float a1 = 0.f, a2 = 0.f;
+    if (mode & RM_ST1) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            a1 += o[t];
+            a2 += o[t] * o[t];
+        }
+    } else {
+        const float mu = rel ? P.mu[1] : P.mu[0], ri = rel ? P.ri[1] : P.ri[0];
+        float xv[8];
+        if (mode & RM_CB) unpack_bf16x8(L.xh, xv);
+        else
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { xv[t] = L.x0[t]; xv[4 + t] = L.x1[t]; }
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {  // graphln_bwd_stats_kernel's arithmetic: dxhat = dy * lrelu'(pre) * w
+            const float xh = (xv[t] - mu) * ri;
+            const float pre = __builtin_fmaf(xh, P.lw[t], P.lb[t]);  // (the one contraction the ladder loop's build forms)
+            const float dxh = o[t] * (pre > 0.f ? 1.f : D.slope) * P.lw[t];
+            a1 += dxh;
+            a2 += dxh * xh;
+        }
+    }
+    // (sa[rel][k] += a_k for the rows below M, without an indexed register array)
+    sa[0][0] = (ok && !rel) ? sa[0][0] + a1 : sa[0][0];
+    sa[0][1] = (ok && !rel) ? sa[0][1] + a2 : sa[0][1];
+    sa[1][0] = (ok && rel) ? sa[1][0] + a1 : sa[1][0];
+    sa[1][1] = (ok && rel) ? sa[1][1] + a2 : sa[1][1];
+    // (the sums are due HERE: left to itself the compiler finishes the stores of every iteration first and keeps the rounded values
+    //  of the whole tile for the statistics behind them -- 48 registers the 192-row kernel does not have)
+    asm volatile("" : "+v"(sa[0][0]), "+v"(sa[0][1]), "+v"(sa[1][0]), "+v"(sa[1][1]));
+}
+
+// One store loop.  GEN = false: the mode is the compile-time word F and the loop is two-phase: the global rows of ALL iterations
+// are requested ahead of the first store, the staged values are read half a tile at a time (the staged values of a whole tile,
+// the global rows and the operands of RowsPre together do not fit the register budget of three waves per SIMD).  GEN = true: the
+// mode is D.mode (a pinned scalar) and each iteration of a rolled loop issues its own loads.  Rows at or past M are loaded from row M - 1 (a row
+// this tile owns: m0 < M) and neither stored nor counted; the caller has excluded the column groups at or past N.
+template <int NI, int MBW, bool GEN, unsigned F>
+__device__ __forceinline__ void rows_store_loop(const RowsDesc& D, const RowsPre& P, const float* stage, int m0, int n, int z, int tid,
+                                                float (&sa)[2][2]) {
+    constexpr int NIT = 2 * NI;
+    const int c8 = tid & 15, last = D.M - 1;
+    // (an opaque row index per loop: otherwise the row addresses that several loops of the switch have in common are formed in
+    //  front of the switch, for every iteration and operand, and stay live through whichever loop runs)
+    int r0 = tid >> 4;
+    asm volatile("; rows loop %1" : "+v"(r0) : "n"(GEN ? 0xfff : F));
+    if constexpr (GEN) {
+#pragma unroll 1
+        for (int it = 0; it < NIT; ++it) {  // (a real loop: unrolled, the row addresses of every iteration and operand are formed ahead)
+            const int row = it * (16 * MBW) + r0;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + row * 128 + (((2 * c8) ^ (row & 15)) << 2));
+            const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + row * 128 + (((2 * c8 + 1) ^ (row & 15)) << 2));
+            RowLoads L;
+            rows_load(D, D.mode, min(m0 + row, last), n, L);
+            rows_finish(D, P, D.mode, lo, hi, L, m0 + row, n, z, sa);
+        }
+    } else {
+        // CH: iterations per chunk of LDS reads (the st_mode 2 loop holds st_w / st_b and the st_x rows as well: one at a time)
+        constexpr int CH = (F & RM_ST2) ? 1 : NI;
+        RowLoads L[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) rows_load(D, F, min(m0 + it * (16 * MBW) + r0, last), n, L[it]);
+#pragma unroll
+        for (int c0 = 0; c0 < NIT; c0 += CH) {
+            __builtin_amdgcn_sched_barrier(0);  // (keeps the chunks' staged values from being live together)
+            f32x4 lo[CH], hi[CH];
+#pragma unroll
+            for (int k = 0; k < CH; ++k) {
+                const int row = (c0 + k) * (16 * MBW) + r0;
+                lo[k] = *reinterpret_cast<const f32x4*>(stage + row * 128 + (((2 * c8) ^ (row & 15)) << 2));
+                hi[k] = *reinterpret_cast<const f32x4*>(stage + row * 128 + (((2 * c8 + 1) ^ (row & 15)) << 2));
+            }
+            // Every global row is waited for in front of the FIRST store (vmcnt 0, the other counters untouched: the builtin, which
+            // the compiler's own wait insertion sees).  The stores sit in divergent branches (rows at or past M), so the counted
+            // waits the compiler would place for the later rows assume none was issued and end up waiting for the earlier stores.
+            if constexpr ((F & (RM_ACC | RM_RES16 | RM_RES32 | RM_ST2)) != 0)
+                if (c0 == 0) __builtin_amdgcn_s_waitcnt(0x0F70);
+#pragma unroll
+            for (int k = 0; k < CH; ++k)  // arithmetic and stores, in row order
+                rows_finish(D, P, F, lo[k], hi[k], L[c0 + k], m0 + (c0 + k) * (16 * MBW) + r0, n, z, sa);
+        }
+    }
+}
+
+// PRE: P was filled at kernel entry (loader-wave kernels).
+template <int NI, bool ST = true, int MBW = 1, bool PRE = false>
+__device__ __forceinline__ void gemm_epilogue_rows_fast(const GemmArgs& g, const f32x4 (&acc)[NI][4], unsigned char* lds, int m0, int n0,
+                                                        int wm, int wn, int lr, int lg, int z, int tid, int st_tile, RowsPre& P) {
+    RowsDesc D;
+    {
+        int M = g.M, N = g.N;
+        unsigned mode = PRE ? P.mode : 0u;
+        float alpha = g.alpha, slope = g.st_slope;
+        char* C = reinterpret_cast<char*>(g.C);
+        const char* R = reinterpret_cast<const char*>(g.residual);
+        const char* X = reinterpret_cast<const char*>(g.st_x);
+        float* ws = g.ws;
+        long long ldc = g.ldc, ldr = g.ldr, ldx = g.st_ldx;
+        asm volatile("" : "+s"(M), "+s"(N), "+s"(mode), "+s"(alpha), "+s"(slope));
+        asm volatile("" : "+s"(C), "+s"(R), "+s"(X), "+s"(ws));
+        asm volatile("" : "+s"(ldc), "+s"(ldr), "+s"(ldx));
+        D.M = M; D.N = N; D.mode = mode; D.alpha = alpha; D.slope = slope; D.C = C; D.R = R; D.X = X; D.ws = ws;
+        D.ldc = ldc; D.ldr = ldr; D.ldx = ldx;
+    }
+    __syncthreads();  // every wave is done with the ring (nothing is in flight: the last tiles were waited for)
+    float* stage = reinterpret_cast<float*>(lds);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int row = wm * 16 * NI + i * 16 + lr;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int slot = (wn * 16 + j * 4 + lg) ^ (row & 15);
+            *reinterpret_cast<f32x4*>(stage + row * 128 + slot * 4) = acc[i][j];
+        }
+    }
+    // (without loader waves: the operand loads go out here, where the accumulators are dead, and return during the barrier)
+    if constexpr (PRE) rows_prefetch_w(g, n0, tid, P);
+    else {
+        rows_prefetch<ST>(g, m0, n0, tid, P);
+        D.mode = P.mode;
+        asm volatile("" : "+s"(D.mode));
+    }
+    __syncthreads();
+    const int n = n0 + (tid & 15) * 8;
+    float sa[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+    if (n < D.N) {
+#define EGK_ROWS_CASE(F) case (F): rows_store_loop<NI, MBW, false, (F)>(D, P, stage, m0, n, z, tid, sa); break
+        switch (D.mode) {  // wave-uniform; the modes of the training step
+            EGK_ROWS_CASE(RM_CB);
+            EGK_ROWS_CASE(RM_CB | RM_BIAS);
+            EGK_ROWS_CASE(RM_CB | RM_BIAS | RM_RELU);
+            EGK_ROWS_CASE(RM_CB | RM_BIAS | RM_RES16);
+            EGK_ROWS_CASE(RM_CB | RM_BIAS | RM_ST1);
+            EGK_ROWS_CASE(RM_CB | RM_ST2);
+            EGK_ROWS_CASE(0u);
+            EGK_ROWS_CASE(RM_ACC);
+            EGK_ROWS_CASE(RM_SLAB);
+            default: rows_store_loop<NI, MBW, true, 0u>(D, P, stage, m0, n, z, tid, sa); break;
+        }
+#undef EGK_ROWS_CASE
+    }
+    if constexpr (ST) if (D.mode & (RM_ST1 | RM_ST2)) {  // block sums in gemm_epilogue_rows' order: lanes, then the waves in wave order
+        __shared__ double st_red_static[MBW == 1 ? 4 : 1][4];
+        double (*st_red)[4] = st_red_static;
+        if constexpr (MBW == 2) st_red = reinterpret_cast<double (*)[4]>(lds + 32 * NI * MBW * 512);
+        double v4[4] = {(double)sa[0][0], (double)sa[0][1], (double)sa[1][0], (double)sa[1][1]};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int o_ = 32; o_ > 0; o_ >>= 1) v4[q] += __shfl_xor(v4[q], o_, 64);
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) st_red[tid >> 6][q] = v4[q];
+        }
+        __syncthreads();
+        if (tid < g.st_nseg * 2) {
+            const int sg = tid >> 1, k = tid & 1, rel = sg - P.s0;
+            double t_ = 0.0;
+            if (rel == 0 || rel == 1) {
+                t_ = (st_red[0][rel * 2 + k] + st_red[1][rel * 2 + k]) + (st_red[2][rel * 2 + k] + st_red[3][rel * 2 + k]);
+                if constexpr (MBW == 2)
+                    t_ += (st_red[4][rel * 2 + k] + st_red[5][rel * 2 + k]) + (st_red[6][rel * 2 + k] + st_red[7][rel * 2 + k]);
+            }
+            g.st_ws[((long long)st_tile * g.st_nseg + sg) * 2 + k] = t_;
+        }
+    }
+}
+
 // BF16C: bf16 MFMA (else exact f32).  TA/TB: operand transposed in memory.  AT/BT: element type in memory.
 template <bool BF16C, bool TA, bool TB, typename AT, typename BT>
 __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmArgs g) {
@@ -822,6 +1167,14 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
         }
     }
 
+    // the rows epilogue's bias / statistics operands: with loader waves the compute waves issue no vector-memory instruction in the
+    // K loop (their vmcnt is free), so these loads are issued here and are in registers when the loop ends
+    constexpr bool PRE = LW > 0 && KG == 1 && (MB == 1 || NI == 3);
+    RowsPre pre;
+    if constexpr (PRE) {
+        if (g.epi) rows_prefetch<true, false>(g, m0, n0, tid, pre);
+    }
+
     f32x4 acc[NI][4];
 #pragma unroll
     for (int i = 0; i < NI; ++i)
@@ -1003,11 +1356,13 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
     }
     if constexpr (KG == 1) {
         if constexpr (MB == 1) {
-            if (epilogue_rows_ok(g)) gemm_epilogue_rows<NI>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn);
+            if (g.epi) gemm_epilogue_rows_fast<NI, true, 1, PRE>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn, pre);
+            else if (epilogue_rows_ok(g)) gemm_epilogue_rows<NI>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn);
             else gemm_epilogue<NI, 4>(g, acc, m0, n0, wm * 16 * NI, wn * 64, lr, lg, z);
         } else if constexpr (NI == 3) {  // 192 x 128: the staging image (96 KiB f32) fits the 3-stage ring
             static_assert(NSTAGE * STAGE >= 192 * 512 + 256, "the rows epilogue stages the whole tile (+ the wave partials) in the ring");
-            if (epilogue_rows_ok(g)) gemm_epilogue_rows<NI, true, 2>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn);
+            if (g.epi) gemm_epilogue_rows_fast<NI, true, 2, PRE>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn, pre);
+            else if (epilogue_rows_ok(g)) gemm_epilogue_rows<NI, true, 2>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn);
             else gemm_epilogue<NI, 4>(g, acc, m0, n0, wm * 16 * NI, wn * 64, lr, lg, z);
         } else {
             gemm_epilogue<NI, 4>(g, acc, m0, n0, wm * 16 * NI, wn * 64, lr, lg, z);
@@ -1102,8 +1457,13 @@ __device__ __forceinline__ void splitk_finish_group(const GemmArgs& g, int m, in
     }
 }
 
+// Waves per SIMD the register allocation has to leave room for (the second __launch_bounds__ argument): what the kernels had
+// when the rows epilogue was one loop -- two 4-wave workgroups per CU, three on 64-row tiles (a workgroup's LDS ring leaves room for
+// no more), three waves per SIMD of the 192-row tile with its loader waves.  Without it the scheduler, which sees one workgroup of
+// at most 256 threads, spends up to 512 registers on overlapping the specialised store loops of the rows epilogue.
+constexpr int pipe_min_waves(int KG, int MB, int NI, int LW) { return (KG == 1 && MB == 1) ? (NI == 2 ? 3 : 2) : (LW > 0 ? 3 : 1); }
 template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 = false, int LW = 0>
-__global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW) void gemm_pipe_kernel(const GemmArgs g) {
+__global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB, NI, LW)) void gemm_pipe_kernel(const GemmArgs g) {
     gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, false, F16, LW>(g, blockIdx.x);
 }
 
@@ -1121,7 +1481,7 @@ struct GemmGroup {
     int packed, count, total;  // packed placement (always 1): number of problems, total tile count
 };
 template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 = false, int LW = 0>
-__global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW) void gemm_pipe_group_kernel(const GemmGroup gg) {
+__global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB, NI, LW)) void gemm_pipe_group_kernel(const GemmGroup gg) {
     if (gg.packed) {
         const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
         const int q = gg.total >> 3, r = gg.total & 7;
@@ -1553,19 +1913,22 @@ __device__ __forceinline__ void gemm_pipe_f32_body(const GemmArgs& g, const int 
             __syncthreads();
         }
     }
-    if (epilogue_rows_ok(g)) gemm_epilogue_rows<NI>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn);
+    if (g.epi) {
+        RowsPre pre;
+        gemm_epilogue_rows_fast<NI>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn, pre);
+    } else if (epilogue_rows_ok(g)) gemm_epilogue_rows<NI>(g, acc, lds, m0, n0, wm, wn, lr, lg, z, tid, tm * g.tiles_n + tn);
     else gemm_epilogue<NI, 4>(g, acc, m0, n0, wm * 16 * NI, wn * 64, lr, lg, z);
 }
 
 template <bool TRA, bool TRB, int NI = 4>
-__global__ __launch_bounds__(NTHREADS) void gemm_pipe_f32_kernel(const GemmArgs g) {
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_pipe_f32_kernel(const GemmArgs g) {
     gemm_pipe_f32_body<TRA, TRB, NI, false>(g, blockIdx.x);
 }
 
 // grouped launch of exact-f32 contractions (the weight gradients of the reference-precision step): XCD-packed placement
 // as gemm_pipe_group_kernel -- the tiles of all problems form one list, XCD x takes a consecutive run of it
 template <bool TRA, bool TRB>
-__global__ __launch_bounds__(NTHREADS) void gemm_pipe_f32_group_kernel(const GemmGroup gg) {
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_pipe_f32_group_kernel(const GemmGroup gg) {
     const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
     const int q = gg.total >> 3, r = gg.total & 7;
     if (slot >= q + (xcd < r ? 1 : 0)) return;
@@ -1638,6 +2001,7 @@ static int g_use_pipe = 1;
 // in a replay).
 static constexpr double REDUCE_FIXED_US = 3.5;
 static int g_r192_loaders = 1;  // egk_gemm_set_pipeline(870 / 871): the 192 x 128 tile with four loader waves (variant 19) off / on
+static int g_rows_fast = 1;     // egk_gemm_set_pipeline(890 / 891): the rows epilogue's descriptor-once, mode-specialised store loop (GemmArgs::epi) off / on
 static int g_tt_tall = 1;       // egk_gemm_set_pipeline(850 / 851): 256 x 128 tiles for weight-gradient groups that leave the second workgroup slot of many CUs empty, off / on
 static bool g_lds_attr_set = false;
 template <int NS, bool TA, bool TB, int KG, int MB = 1>
@@ -1691,9 +2055,12 @@ static void ensure_lds_attr() {
     g_lds_attr_set = true;
 }
 // A/B runs in one process and the tests' forced variants: 0 routes every contraction through the generic kernel; 850 / 851 and
-// 870 / 871 switch one policy choice (g_tt_tall, g_r192_loaders).  Any other code outside 0 .. 19 changes nothing and returns -1.
+// 870 / 871 switch one policy choice (g_tt_tall, g_r192_loaders); 890 / 891 switch the store loop of the rows epilogue: 890 the
+// branch ladder that reads the descriptor in every iteration (gemm_epilogue_rows), 891 (default) the descriptor-once, mode-specialised
+// two-phase loop (gemm_epilogue_rows_fast) -- the same bits either way.  Any other code outside 0 .. 19 changes nothing and returns -1.
 extern "C" int egk_gemm_set_pipeline(int32_t on) {
     const int prev = g_use_pipe;
+    if (on == 890 || on == 891) { g_rows_fast = on - 890; return prev; }
     if (on == 870 || on == 871) { g_r192_loaders = on - 870; return prev; }
     if (on == 850 || on == 851) { g_tt_tall = on - 850; return prev; }
     if (on < 0 || on >= 20) return -1;
@@ -1858,6 +2225,7 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
         EGK_REQUIRE(d->st_nseg >= 1 && d->st_nseg <= 16 && d->st_seg_ptr && (query_blocks || d->st_ws), "egk_gemm: st_* segments / workspace");
         EGK_REQUIRE(d->st_mode == 1 || (d->st_x && d->st_stats && d->st_w && d->st_b), "egk_gemm: st_mode 2 needs x, stats, w, b");
     }
+    g.epi = g_rows_fast && epilogue_rows_ok(g);
     if (query_blocks) *query_blocks = 0;
     const long long K = src.k_total;
     const double flops = 2.0 * d->M * d->N * K;
@@ -2172,6 +2540,7 @@ static int fill_group_args(const egk_gemm_desc* d, GemmArgs& g) {
     g.st_mode = 0; g.st_nseg = 0; g.st_seg_ptr = nullptr; g.st_ws = nullptr; g.st_x = nullptr; g.st_ldx = 0;
     g.st_stats = nullptr; g.st_w = nullptr; g.st_b = nullptr; g.st_slope = 0.f;
     EGK_REQUIRE(d->st_mode == 0, "egk_gemm_grouped: no segment statistics in a grouped launch");
+    g.epi = g_rows_fast && epilogue_rows_ok(g);
     return 0;
 }
 

@@ -33,12 +33,14 @@ _lib.LIB_PATH = LIB
 from egopack_amd import ops
 
 if "--phases" in sys.argv:
-    # python tools/gemm_stamps.py --phases M N K tA tB splitk [variant]: entry -> first tile landed -> K loop -> epilogue,
+    # python tools/gemm_stamps.py --phases M N K tA tB splitk [variant [knob ...]]: entry -> first tile landed -> K loop -> epilogue,
     # per workgroup, of the 128-row pipelined kernels (the launch the policy would make unless a variant is forced)
     a = [v for v in sys.argv[1:] if not v.startswith("--")]
     M, N, K, tA, tB, sk = (int(v) for v in a[:6])
     lib = _lib.load()
     lib.egk_gemm_set_pipeline(int(a[6]) if len(a) > 6 else 1)
+    for v in a[7:]:  # further knob codes (850 / 851, 870 / 871, 890 / 891): an A/B of one build
+        lib.egk_gemm_set_pipeline(int(v))
     bf = torch.bfloat16
     A = torch.randn((K, M) if tA else (M, K), device="cuda").to(bf)
     B = torch.randn((K, N) if tB else (N, K), device="cuda").to(bf)
