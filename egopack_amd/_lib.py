@@ -96,7 +96,8 @@ class OptimDesc(C.Structure):
     """struct egk_optim_desc (include/egopack_optim.h)."""
     _fields_ = [("rule", i32), ("g_dtype", i32), ("n", i64), ("p", vp), ("g", vp), ("state0", vp), ("state1", vp), ("hyper", vp),
                 ("t_dev", vp), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", f32), ("weight_decay", f32), ("momentum", f32), ("dampening", f32),
-                ("nesterov", i32), ("bf16_shadow", vp), ("bf16_lo_shadow", vp), ("bump_word", vp), ("bump", i64), ("gate", vp)]
+                ("nesterov", i32), ("bf16_shadow", vp), ("bf16_lo_shadow", vp), ("bump_word", vp), ("bump", i64), ("gate", vp),
+                ("state_dtype", i32), ("state_round", i32), ("state_seed", u64), ("elem0", i64)]
 
 
 class OptimGroups(C.Structure):

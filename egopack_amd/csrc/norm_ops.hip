@@ -1038,6 +1038,7 @@ static inline int nv_for(int cols) { return cols <= 256 ? 1 : cols <= 1024 ? 4 :
 // >= 2 rows; in-step A/B of the headline workload, 200 steps x 3 rounds: 2048 -> 1.637, 512 -> 1.626, 768 -> 1.612 ms
 constexpr int CAP_PARTIAL = 512, CAP_WIDE = 768;
 extern int g_graph_rows_v2;  // (graph_ops.hip)
+extern int g_optim_grid_cap;  // (optim_rules.hip)
 static inline int row_grid(int rows) {  // kernels that emit per-workgroup partial rows: two workgroups per CU
     int g = cdiv(rows, WPB);
     return g < 1 ? 1 : (g > CAP_PARTIAL ? CAP_PARTIAL : g);
@@ -1206,10 +1207,11 @@ static inline bool wide_rows_ok(int cols, const void* in, const void* out, const
 
 extern "C" {
 
-// the tests' references: 3 = the rows1024.h graph-row kernels on / off, 7 = the workgroup-per-row LayerNorm kernels on / off;
-// any other key changes nothing and returns -1
+// the tests' references: 3 = the rows1024.h graph-row kernels on / off, 6 = the workgroup cap of the optimizer launches (1 .. 32768;
+// anything else leaves it), 7 = the workgroup-per-row LayerNorm kernels on / off; any other key changes nothing and returns -1
 int egk_tune(int32_t key, int32_t value) {
     if (key == 3) { const int p = g_graph_rows_v2; g_graph_rows_v2 = value; return p; }  // graph_ops.hip: the rows1024.h kernels
+    if (key == 6) { const int p = g_optim_grid_cap; if (value >= 1 && value <= 32768) g_optim_grid_cap = value; return p; }  // optim_rules.hip: optim_grid
     if (key == 7) { const int p = g_wide_rows; g_wide_rows = value; return p; }  // the workgroup-per-row LayerNorm kernels on / off
     return -1;
 }

@@ -64,20 +64,61 @@ __device__ __forceinline__ void ema_update(float& e, float p_new, float w) {
     e = e + move;
 }
 
-// the four elements [i, i + 4) of a span in 16-byte accesses; ``consts()`` is asked for the constants once the loads are issued.
+// ---- the state's element type (include/egopack_optim.h: state_dtype) ------------------------------------------------------------------
+// ST = float: the 16-byte loads and stores the family has always issued.  ST = bf16_t: one 8-byte access per buffer and quad, the
+// elements widened to f32 on the way in and rounded on the way out -- to nearest (f2bf), or by adding 16 random bits under the bits
+// that are dropped.  The body between the load and the store never sees which: it computes on f32 and uses the unrounded result.
+struct StateRound {      // wave-uniform: the launch's mode and what its Philox counters start from
+    int stochastic;      // state_round
+    uint64_t seed;       // state_seed, the key
+    uint64_t ctr_hi;     // (t & 0xFFFFFF) << 40, t = *t_dev, read once per workgroup
+    long long elem0;     // the absolute index of element 0 of the launch, a multiple of 4
+};
+
+// the four words of the 16-byte group that holds absolute element e = elem0 + i (i a multiple of 4): word k serves element e + k,
+// its high half state0, its low half state1
+__device__ __forceinline__ uint4 state_words(const StateRound& r, long long i) {
+    return philox4x32_10(r.ctr_hi | ((uint64_t)(r.elem0 + i) >> 2), r.seed);
+}
+
+// one f32 value to the bf16 bits that are stored; r16: 16 random bits, used when ``stochastic``
+__device__ __forceinline__ bf16_t round_state(float x, unsigned r16, bool stochastic) {
+    const unsigned b = __float_as_uint(x);
+    if (!stochastic || (b & 0x7f800000u) == 0x7f800000u) return f2bf(x);  // (inf / NaN keep f2bf's bits)
+    return (bf16_t)((b + r16) >> 16);  // (no carry into the sign: the exponent is not all ones)
+}
+
+__device__ __forceinline__ float4 ld_state4(const float* __restrict__ s) { return *reinterpret_cast<const float4*>(s); }
+__device__ __forceinline__ float4 ld_state4(const bf16_t* __restrict__ s) { return ld4t(s, 0, 4, true); }
+// ``high``: this buffer draws the high halves of the words (state0), otherwise the low halves (state1)
+__device__ __forceinline__ void st_state4(float* __restrict__ s, const float4& v, const uint4&, bool, bool) { *reinterpret_cast<float4*>(s) = v; }
+__device__ __forceinline__ void st_state4(bf16_t* __restrict__ s, const float4& v, const uint4& w, bool high, bool stochastic) {
+    const unsigned sh = high ? 16u : 0u;
+    uint2 pk;
+    pk.x = (unsigned)round_state(v.x, (w.x >> sh) & 0xffffu, stochastic) | ((unsigned)round_state(v.y, (w.y >> sh) & 0xffffu, stochastic) << 16);
+    pk.y = (unsigned)round_state(v.z, (w.z >> sh) & 0xffffu, stochastic) | ((unsigned)round_state(v.w, (w.w >> sh) & 0xffffu, stochastic) << 16);
+    *reinterpret_cast<uint2*>(s) = pk;
+}
+
+// the four elements [i, i + 4) of a span in 16-byte accesses (8-byte on a bf16 state); ``consts()`` is asked for the constants, and
+// the Philox call of a stochastic store issued, once the loads are on their way.
 // EMA: ``ema`` follows the new p with weight ``w`` before p is stored (read with the other loads, one 16-byte store).
-template <int KIND, typename GT, bool EMA = false, typename CF>
-__device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
-                                           long long i, CF consts, bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
-                                           float* __restrict__ ema = nullptr, float w = 0.f) {
+template <int KIND, typename GT, typename ST, bool EMA = false, typename CF>
+__device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __restrict__ g, ST* __restrict__ s0, ST* __restrict__ s1,
+                                           long long i, CF consts, const StateRound& sr, bf16_t* __restrict__ shadow,
+                                           bf16_t* __restrict__ shadow_lo, float* __restrict__ ema = nullptr, float w = 0.f) {
     constexpr int NS = StateCount<KIND>::value;
+    constexpr bool NARROW = !__is_same(ST, float);
     float4 pv = *reinterpret_cast<float4*>(p + i);
     const float4 gv = ld4t(g + i, 0, 4, true);
     float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, ev = av;
-    if constexpr (NS >= 1) av = *reinterpret_cast<float4*>(s0 + i);
-    if constexpr (NS >= 2) bv = *reinterpret_cast<float4*>(s1 + i);
+    if constexpr (NS >= 1) av = ld_state4(s0 + i);
+    if constexpr (NS >= 2) bv = ld_state4(s1 + i);
     if constexpr (EMA) ev = *reinterpret_cast<float4*>(ema + i);
     const OptimConsts c = consts();
+    uint4 rw = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (NARROW && NS >= 1)
+        if (sr.stochastic) rw = state_words(sr, i);
     float* pp = &pv.x; const float* gp = &gv.x; float* ap = &av.x; float* bp = &bv.x;
 #pragma unroll
     for (int t = 0; t < 4; ++t) optim_update<KIND>(pp[t], gp[t], ap[t], bp[t], c);
@@ -88,8 +129,8 @@ __device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __re
         *reinterpret_cast<float4*>(ema + i) = ev;
     }
     *reinterpret_cast<float4*>(p + i) = pv;
-    if constexpr (NS >= 1) *reinterpret_cast<float4*>(s0 + i) = av;
-    if constexpr (NS >= 2) *reinterpret_cast<float4*>(s1 + i) = bv;
+    if constexpr (NS >= 1) st_state4(s0 + i, av, rw, true, sr.stochastic != 0);
+    if constexpr (NS >= 2) st_state4(s1 + i, bv, rw, false, sr.stochastic != 0);
     if (shadow) st4t(shadow + i, 0, 4, true, pv);
     if (shadow_lo) {  // bf16(p - bf16(p)): egk_split_bf16's bits
         const float lo4[4] = {pp[0] - bf2f(f2bf(pp[0])), pp[1] - bf2f(f2bf(pp[1])), pp[2] - bf2f(f2bf(pp[2])), pp[3] - bf2f(f2bf(pp[3]))};
@@ -98,23 +139,35 @@ __device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __re
 }
 
 // the scalar tail [i, n) of a span (n - i < 4)
-template <int KIND, typename GT, bool EMA = false>
-__device__ __forceinline__ void optim_tail(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
-                                           long long i, long long n, const OptimConsts& c, bf16_t* __restrict__ shadow,
-                                           bf16_t* __restrict__ shadow_lo, float* __restrict__ ema = nullptr, float w = 0.f) {
+template <int KIND, typename GT, typename ST, bool EMA = false>
+__device__ __forceinline__ void optim_tail(float* __restrict__ p, const GT* __restrict__ g, ST* __restrict__ s0, ST* __restrict__ s1,
+                                           long long i, long long n, const OptimConsts& c, const StateRound& sr,
+                                           bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo, float* __restrict__ ema = nullptr,
+                                           float w = 0.f) {
     constexpr int NS = StateCount<KIND>::value;
+    constexpr bool NARROW = !__is_same(ST, float);
+    uint4 q = make_uint4(0u, 0u, 0u, 0u);  // (the tail's group starts at i, a multiple of 4: one call, word j - i for element j)
+    if constexpr (NARROW && NS >= 1)
+        if (sr.stochastic) q = state_words(sr, i);
     for (long long j = i; j < n; ++j) {
+        const unsigned rw = j == i ? q.x : j == i + 1 ? q.y : q.z;
+        (void)rw;
         float a = 0.f, b = 0.f;
-        if constexpr (NS >= 1) a = s0[j];
-        if constexpr (NS >= 2) b = s1[j];
+        if constexpr (NS >= 1) a = ld1t(s0 + j);
+        if constexpr (NS >= 2) b = ld1t(s1 + j);
         optim_update<KIND>(p[j], ld1t(g + j), a, b, c);
         if constexpr (EMA) {
             float e = ema[j];
             ema_update(e, p[j], w);
             ema[j] = e;
         }
-        if constexpr (NS >= 1) s0[j] = a;
-        if constexpr (NS >= 2) s1[j] = b;
+        if constexpr (NARROW) {
+            if constexpr (NS >= 1) s0[j] = round_state(a, rw >> 16, sr.stochastic != 0);
+            if constexpr (NS >= 2) s1[j] = round_state(b, rw & 0xffffu, sr.stochastic != 0);
+        } else {
+            if constexpr (NS >= 1) s0[j] = a;
+            if constexpr (NS >= 2) s1[j] = b;
+        }
         if (shadow) shadow[j] = f2bf(p[j]);
         if (shadow_lo) shadow_lo[j] = f2bf(p[j] - bf2f(f2bf(p[j])));
     }
@@ -203,8 +256,8 @@ __device__ __forceinline__ float ema_weight(const EmaArgs& e, const long long* _
 struct OptimArgs {  // what a launch of the family is handed; ``t`` without a table and ``e`` without an average stay empty
     float* p;
     const void* g;  // f32, or bf16 after a compressed all-reduce (the kernel's GT)
-    float* s0;
-    float* s1;
+    void* s0;       // f32, or bf16 with state_dtype == EGK_BF16 (the kernel's ST)
+    void* s1;
     long long n;
     const float* hyper;
     const long long* t_dev;
@@ -216,6 +269,9 @@ struct OptimArgs {  // what a launch of the family is handed; ``t`` without a ta
     OptimHyper h;
     GroupTable t;
     EmaArgs e;
+    int st_round;             // bf16 state: state_round, state_seed, elem0 of the descriptor
+    unsigned long long st_seed;
+    long long elem0;
 };
 
 // One launch over [0, n): workgroup b takes the 1024-element blocks b, b + gridDim.x, ... (256 threads x 4 elements).  The constants
@@ -223,8 +279,8 @@ struct OptimArgs {  // what a launch of the family is handed; ``t`` without a ta
 // The buffers the launch writes arrive as __restrict__ PARAMETERS (optim_body unpacks them): a qualifier on a struct member tells
 // the compiler nothing, and without it every store may change hyper, the gate and the segment table, whose workgroup-uniform loads
 // then leave the scalar unit (the grouped kernel: 20 vector loads instead of 14).
-template <int KIND, typename GT, bool GROUPED, bool EMA>
-__device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+template <int KIND, typename GT, typename ST, bool GROUPED, bool EMA>
+__device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __restrict__ g, ST* __restrict__ s0, ST* __restrict__ s1,
                                            bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo, float* __restrict__ ema,
                                            long long* __restrict__ bump_word, const OptimArgs& a) {
     // (a device-side counter that moves on once per step -- the Philox offset word of the step's dropout launches -- rides in this
@@ -234,6 +290,10 @@ __device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __re
     //  wave-uniform load, nothing of p / the state / the average / the bf16 copies is touched)
     if (a.gate && *a.gate == 0) return;
     const float w = EMA ? ema_weight(a.e, a.t_dev) : 0.f;
+    // (the counted step of a stochastic store: one wave-uniform load per workgroup, like the gate; the f32 state never asks)
+    StateRound sr{0, 0, 0, 0};
+    if constexpr (!__is_same(ST, float))
+        if (a.st_round) sr = StateRound{1, a.st_seed, ((uint64_t)*a.t_dev & 0xFFFFFFull) << 40, a.elem0};
     OptimConsts launch{};
     if constexpr (!GROUPED) launch = optim_consts<KIND>(a.hyper[0], a.h.wd, a.hyper, a.t_dev, a.h);
     for (long long b0 = (long long)blockIdx.x * 1024; b0 < a.n; b0 += (long long)gridDim.x * 1024) {
@@ -244,27 +304,36 @@ __device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __re
             else return launch;
         };
         if (i + 4 <= a.n)
-            optim_quad<KIND, GT, EMA>(p, g, s0, s1, i, consts, shadow, shadow_lo, ema, w);
+            optim_quad<KIND, GT, ST, EMA>(p, g, s0, s1, i, consts, sr, shadow, shadow_lo, ema, w);
         else
-            optim_tail<KIND, GT, EMA>(p, g, s0, s1, i, a.n, consts(), shadow, shadow_lo, ema, w);
+            optim_tail<KIND, GT, ST, EMA>(p, g, s0, s1, i, a.n, consts(), sr, shadow, shadow_lo, ema, w);
     }
 }
 
-template <int KIND, typename GT, bool GROUPED, bool EMA>
+template <int KIND, typename GT, typename ST, bool GROUPED, bool EMA>
 __device__ __forceinline__ void optim_body(const OptimArgs& a) {
-    optim_walk<KIND, GT, GROUPED, EMA>(a.p, static_cast<const GT*>(a.g), a.s0, a.s1, a.shadow, a.shadow_lo, a.e.ema, a.bump_word, a);
+    optim_walk<KIND, GT, ST, GROUPED, EMA>(a.p, static_cast<const GT*>(a.g), static_cast<ST*>(a.s0), static_cast<ST*>(a.s1), a.shadow,
+                                           a.shadow_lo, a.e.ema, a.bump_word, a);
 }
 
 template <int KIND, typename GT, bool GROUPED, bool EMA>
 __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
-    optim_body<KIND, GT, GROUPED, EMA>(a);
+    optim_body<KIND, GT, float, GROUPED, EMA>(a);
+}
+
+// The same body on a bf16 state.  Left alone the compiler keeps the ten round keys of the Philox call and the counter's uniform half
+// in scalar registers for the whole walk and ends at the scalar file's cap (106), which admits 7 waves per SIMD where the f32-state
+// kernels run 8; told to aim for 8 it keeps what does not fit in lanes of a vector register instead.
+template <int KIND, typename GT, bool GROUPED, bool EMA>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void optim_kernel_bf16_state(const OptimArgs a) {
+    optim_body<KIND, GT, bf16_t, GROUPED, EMA>(a);
 }
 
 // what egk_adam_step* launch: the body for Adam under the name the profiles, bench.py and the timeline tools know the step's
 // optimizer launch by
 template <typename GT>
 __global__ __launch_bounds__(256) void adam_kernel(const OptimArgs a) {
-    optim_body<K_ADAM, GT, false, false>(a);
+    optim_body<K_ADAM, GT, float, false, false>(a);
 }
 
 // p[i] <-> ema[i]: 16-byte accesses, a scalar tail for n % 4, grid-stride
@@ -308,10 +377,26 @@ static int optim_check(const char* who, const egk_optim_desc* d, egk_optim_desc&
     a = *d;
     if (kind == K_SGD) a.state0 = nullptr;
     if (kind == K_SGD || kind == K_SGD_MOMENTUM) a.state1 = nullptr;
-    EGK_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.state0 | (uintptr_t)a.state1) & 15) == 0,
-                "%s: buffers must be 16-byte aligned", who);
+    const bool narrow = a.state_dtype == EGK_BF16;  // (a bf16 state is accessed 8 bytes at a time: its own refusal, below)
+    const uintptr_t state_ptrs = narrow ? 0 : (uintptr_t)a.state0 | (uintptr_t)a.state1;
+    EGK_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | state_ptrs) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
     EGK_REQUIRE(((uintptr_t)a.bf16_shadow & 7) == 0, "%s: shadow must be 8-byte aligned", who);
     EGK_REQUIRE(((uintptr_t)a.bf16_lo_shadow & 7) == 0, "%s: low-half shadow must be 8-byte aligned", who);
+    return 0;
+}
+
+// what every entry point refuses in the four state fields at the descriptor's end, behind everything else it refuses (a zeroed
+// tail passes: the f32 launch)
+static int state_check(const char* who, const egk_optim_desc& a) {
+    EGK_REQUIRE(a.state_dtype == EGK_F32 || a.state_dtype == EGK_BF16, "%s: unknown state dtype %d (EGK_F32 = 0, EGK_BF16 = 1)", who,
+                (int)a.state_dtype);
+    EGK_REQUIRE(a.state_round == 0 || a.state_round == 1, "%s: state_round in {0 (nearest), 1 (stochastic)} (got %d)", who, (int)a.state_round);
+    EGK_REQUIRE(!a.state_round || a.state_dtype == EGK_BF16, "%s: stochastic rounding (state_round = 1) needs a bf16 state (state_dtype = EGK_BF16)", who);
+    EGK_REQUIRE(!a.state_round || a.t_dev,"%s: stochastic rounding (state_round = 1) needs t_dev (the device step counter)", who);
+    EGK_REQUIRE(a.elem0 >= 0 && a.elem0 % 4 == 0 && a.elem0 <= (1ll << 42) - a.n,
+                "%s: elem0 must be a non-negative multiple of 4 with elem0 + n <= 2^42 (got %lld)", who, (long long)a.elem0);
+    if (a.state_dtype == EGK_BF16)
+        EGK_REQUIRE((((uintptr_t)a.state0 | (uintptr_t)a.state1) & 7) == 0, "%s: bf16 state must be 8-byte aligned", who);
     return 0;
 }
 
@@ -337,31 +422,45 @@ static int ema_check(const char* who, const egk_ema_desc* e, const egk_optim_des
     return 0;
 }
 
-// bytes per parameter: p read + written, each state buffer read + written, the gradient read, the bf16 copies written, the average
-// read + written
+// bytes per parameter: p read + written, each state buffer read + written (4 B an access, 2 B on a bf16 state), the gradient read,
+// the bf16 copies written, the average read + written
 static double optim_bytes(const egk_optim_desc& a, int kind, bool ema) {
-    const double state_bytes = kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0;
+    const double state_bytes = (kind == K_SGD ? 0.0 : kind == K_SGD_MOMENTUM ? 8.0 : 16.0) * (a.state_dtype == EGK_BF16 ? 0.5 : 1.0);
     return (8.0 + state_bytes + (a.g_dtype == EGK_BF16 ? 2.0 : 4.0) + (a.bf16_shadow ? 2.0 : 0.0) + (a.bf16_lo_shadow ? 2.0 : 0.0) +
             (ema ? 8.0 : 0.0)) * (double)a.n;
 }
 
-// Workgroups: one 1024-element group per workgroup up to 32768 of them (egk_tune(6, n) sets the cap).  An optimizer slice runs
+// Workgroups: one 1024-element group per workgroup up to 32768 of them (egk_tune(6, n) sets the cap: the tests lower it so that a
+// small launch walks several laps).  An optimizer slice runs
 // BESIDE weight-gradient launches in every captured step's tail; round 5 first capped it at 4096 (a 8 us reduction queued beside
 // it had waited 135 us for wave slots) and, once the gradient buffer was no longer cleared and read back, measured the wide grid
 // ahead again: headline 1.365-1.379 against 1.374-1.386 ms, config 4 2.180-2.182 against 2.191-2.206, Hp = 4096 2.722 against
 // 2.751 (narrower is clearly worse: 1024 workgroups 1.405-1.414, 512 1.447)
+int g_optim_grid_cap = 32768;  // egk_tune 6 (norm_ops.hip)
 static unsigned optim_grid(long long n) {
     const long long want = (n / 4 + 255) / 256;
-    const long long cap = 32768;
+    const long long cap = g_optim_grid_cap;
     return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
 // the kernel of a launch: adam_kernel for egk_adam_step* (KID_ADAM), otherwise the member of the family
-template <int KIND, typename GT>
+template <int KIND, typename GT, typename ST>
 static auto optim_pick(int kid, bool grouped, bool ema) -> void (*)(OptimArgs) {
-    if (kid == KID_ADAM) return adam_kernel<GT>;
-    if (grouped) return ema ? optim_kernel<KIND, GT, true, true> : optim_kernel<KIND, GT, true, false>;
-    return ema ? optim_kernel<KIND, GT, false, true> : optim_kernel<KIND, GT, false, false>;
+    if constexpr (__is_same(ST, float)) {
+        if (kid == KID_ADAM) return adam_kernel<GT>;
+        if (grouped) return ema ? optim_kernel<KIND, GT, true, true> : optim_kernel<KIND, GT, true, false>;
+        return ema ? optim_kernel<KIND, GT, false, true> : optim_kernel<KIND, GT, false, false>;
+    } else {
+        if (grouped) return ema ? optim_kernel_bf16_state<KIND, GT, true, true> : optim_kernel_bf16_state<KIND, GT, true, false>;
+        return ema ? optim_kernel_bf16_state<KIND, GT, false, true> : optim_kernel_bf16_state<KIND, GT, false, false>;
+    }
+}
+// ... by the state's element type too (K_SGD has no state: its one instantiation serves either)
+template <int KIND, typename GT>
+static auto optim_pick(int kid, bool grouped, bool ema, bool narrow) -> void (*)(OptimArgs) {
+    if constexpr (StateCount<KIND>::value > 0)
+        if (narrow) return optim_pick<KIND, GT, bf16_t>(kid, grouped, ema);
+    return optim_pick<KIND, GT, float>(kid, grouped, ema);
 }
 
 // Every optimizer entry point: the refusals, then one launch.  ``who``: the name the messages carry; ``kid``: the entry point's
@@ -375,6 +474,7 @@ static int optim_dispatch(const char* who, int kid, egk_stream_t stream, const e
         if (const int rc = groups_check(who, g)) return rc;
     if (kid == KID_OPTIM_EMA)
         if (const int rc = ema_check(who, e, a)) return rc;
+    if (const int rc = state_check(who, a)) return rc;
     if (a.n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(kid, s, 0, optim_bytes(a, kind, e != nullptr));
@@ -382,15 +482,16 @@ static int optim_dispatch(const char* who, int kid, egk_stream_t stream, const e
                 (bf16_t*)a.bf16_lo_shadow, (long long*)a.bump_word, (long long)a.bump, (const int*)a.gate,
                 OptimHyper{(float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), a.eps, a.weight_decay,
                            a.momentum, (float)(1.0 - (double)a.dampening), a.nesterov ? 1 : 0},
-                GroupTable{}, EmaArgs{}};
+                GroupTable{}, EmaArgs{}, (int)a.state_round, (unsigned long long)a.state_seed, (long long)a.elem0};
     if (g) k.t = GroupTable{(long long)g->base, (int)g->n_seg, (int)g->n_groups, (const long long*)g->seg_begin, (const int*)g->seg_group, g->group_hyper};
     if (e) k.e = EmaArgs{e->ema, e->decay, (float)(1.0 - e->decay), e->warmup ? 1 : 0};
     void (*kernel)(OptimArgs) = nullptr;
+    const bool narrow = a.state_dtype == EGK_BF16;
     switch (kind) {
-        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_ADAM, T>(kid, g, e))); break;
-        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_ADAMW, T>(kid, g, e))); break;
-        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_SGD, T>(kid, g, e))); break;
-        default: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_SGD_MOMENTUM, T>(kid, g, e))); break;
+        case K_ADAM: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_ADAM, T>(kid, g, e, narrow))); break;
+        case K_ADAMW: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_ADAMW, T>(kid, g, e, narrow))); break;
+        case K_SGD: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_SGD, T>(kid, g, e, narrow))); break;
+        default: EGK_DISPATCH_T(a.g_dtype, (kernel = optim_pick<K_SGD_MOMENTUM, T>(kid, g, e, narrow))); break;
     }
     hipLaunchKernelGGL(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, k);
     return check_launch(who);

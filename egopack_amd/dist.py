@@ -348,6 +348,12 @@ class GradSync:
                              "rank steps 1 / world of the parameters, so the average would be sharded like the moments -- use the "
                              "all-reduce exchange (the default), where every rank runs the full launch")
 
+    def _refuse_bf16_state(self, opt) -> None:
+        if getattr(opt, "bf16_state", False):
+            raise ValueError("a bf16 optimizer state (state_dtype=torch.bfloat16 / optimizer_state.dtype: bf16) does not combine with the "
+                             "sharded update (sharded_update): the moments of a slice are kept, sliced and all-gathered as f32 buffers "
+                             "-- keep the state in f32, or use the all-reduce exchange (the default)")
+
     def _refuse_task_weighting(self, opt) -> None:
         if getattr(opt, "task_weighting", None) not in (None, "none"):
             raise ValueError(f"task weighting (task_weighting.mode: {opt.task_weighting}) does not combine with the sharded update "
@@ -358,6 +364,7 @@ class GradSync:
         self._refuse_clipping(opt)
         self._refuse_ema(opt)
         self._refuse_task_weighting(opt)
+        self._refuse_bf16_state(opt)
         flat_g = opt.flat_g
         gpu = flat_g.is_cuda
         compress = self.compress == "bf16" and gpu
@@ -443,6 +450,7 @@ class GradSync:
         self._refuse_clipping(opt)
         self._refuse_ema(opt)
         self._refuse_task_weighting(opt)
+        self._refuse_bf16_state(opt)
         flat_g, n = opt.flat_g, opt.flat_g.numel()
         per, lo, hi, body = self.shard_bounds(n)
         real = dist.get_world_size(self.group) if dist.is_initialized() else 1

@@ -3884,6 +3884,19 @@ def sampler_key(seed: int) -> int:
     return (int(seed) ^ SAMPLER_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
 
 
+# ---- the rounding bits of a bf16 optimizer state (include/egopack_optim.h) ------------------------------------------------
+# The Philox KEY of the stochastic rounding is the seed XOR this constant ("OPT_STAT" in ASCII).  The dropout kernels hold the
+# process seed itself as their key and the LTA sampler holds seed ^ SAMPLER_KEY_SALT: with one seed for all three, the three
+# consumers hold three different keys, so none of them ever draws a (key, counter) pair another one draws, whatever the counters are.
+OPTIM_STATE_KEY_SALT = 0x4F50545F53544154
+
+
+def optim_state_key(seed=None) -> int:
+    """The Philox key of the optimizer-state rounding for a user seed (None: the process seed of ``manual_seed``)."""
+    seed = _rng["seed"] if seed is None else int(seed)
+    return (seed ^ OPTIM_STATE_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
+
+
 @torch.no_grad()
 def categorical_sample_multi(logits_list, K: int, seed: int, ordinal: int, row0: int = 0, debug: bool = False):
     """K samples per row from softmax(logits[row]) for every head of ``logits_list`` ([N, C_h] f32 or bf16, one N) in ONE launch:

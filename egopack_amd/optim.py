@@ -34,7 +34,7 @@ from typing import Iterable, List
 
 import torch
 
-from . import _lib
+from . import _lib, ops, switches
 from .ops import _ck, _p, _stream
 
 logger = logging.getLogger("egopack")
@@ -83,6 +83,12 @@ def _unique(params):
     return uniq
 
 
+# the optimizer state's element type and the rounding of a bf16 state (include/egopack_optim.h): the names the config,
+# the keyword arguments and the state dict use, and the descriptor's codes
+STATE_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
+STATE_ROUNDINGS = {"nearest": 0, "stochastic": 1}
+
+
 # task weighting: the modes of ``task_weighting.mode`` and the name of the parameter group that holds the log-variances
 # -- the one definition engine.MTLStep, train and dist read
 TASK_WEIGHTING_MODES = ("none", "manual", "uncertainty")
@@ -91,7 +97,7 @@ TASK_WEIGHTING_GROUP = "task_weighting"
 
 class FlatOptimizer(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.Tensor], defaults: dict, state_keys=(), max_grad_norm=None, layout_order=None,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, state_dtype=torch.float32, state_rounding="stochastic", state_seed=None):
         """``layout_order``: the parameters in the order their slots take in the flat buffers (default: constructor order, groups one
         after the other).  A caller that splits one list into groups hands the list in here, and the layout -- backward order, the
         regions the step slices, the classifier banks -- stays what the ungrouped optimizer builds.
@@ -100,8 +106,25 @@ class FlatOptimizer(torch.optim.Optimizer):
         torch.nn.utils.clip_grad_norm_'s arithmetic, computed on the device inside the step (see ``norm_partials``).
         ``ema_decay`` (None or 0: off; otherwise inside (0, 1)): keep ``flat_ema``, the moving average of the weights, inside every
         launch: ema += (1 - d_t) * (p_new - ema) with d_t = ema_decay, or min(ema_decay, (1 + t) / (10 + t)) at step t with
-        ``ema_warmup``."""
+        ``ema_warmup``.
+        ``state_dtype`` (torch.float32, or torch.bfloat16): the element type of the state buffers.  A bf16 state is read widened,
+        the update runs in f32 as ever and only what is stored is rounded: ``state_rounding`` = "stochastic" (unbiased; every
+        rounding bit is a function of ``state_seed``, the counted step and the element's place in the flat buffers) or "nearest"
+        (which stalls exp_avg_sq: DESIGN 3.16).  ``state_seed`` (None: the process seed of ``ops.manual_seed`` when the optimizer is
+        built): the Philox key is ``ops.optim_state_key`` of it."""
         params = [p for p in params]
+        if isinstance(state_dtype, str):
+            state_dtype = STATE_DTYPES.get(state_dtype.lower(), state_dtype)
+        if state_dtype not in STATE_DTYPES.values():
+            raise ValueError(f"{type(self).__name__}: state_dtype must be torch.float32 or torch.bfloat16, got {state_dtype!r}")
+        if state_rounding not in STATE_ROUNDINGS:
+            raise ValueError(f"{type(self).__name__}: state_rounding must be one of {', '.join(STATE_ROUNDINGS)}, got {state_rounding!r}")
+        if state_seed is not None and (isinstance(state_seed, bool) or not isinstance(state_seed, int) or not 0 <= state_seed < 2 ** 64):
+            raise ValueError(f"{type(self).__name__}: state_seed must be None or an integer in [0, 2^64), got {state_seed!r}")
+        if state_dtype is torch.bfloat16 and switches.enabled("sharded_update"):
+            raise ValueError(f"{type(self).__name__}: state_dtype=torch.bfloat16 (optimizer_state.dtype: bf16) does not combine with the "
+                             "sharded update (EGK_ENABLE=sharded_update): dist.GradSync slices and all-gathers the moments as f32 "
+                             "buffers -- keep the state in f32, or use the all-reduce exchange (the default)")
         if ema_decay is not None and ema_decay != 0 and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError(f"{type(self).__name__}: ema_decay must be None, 0 (off) or inside (0, 1), got {ema_decay!r}")
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
@@ -120,7 +143,7 @@ class FlatOptimizer(torch.optim.Optimizer):
         self._group_host = None     # the per-group (lr, weight_decay) last uploaded
         self.flat_p = self.flat_g = self.flat_w16 = None
         self._state_keys = tuple(state_keys)
-        self._state_bufs: List[torch.Tensor] = []  # one flat f32 buffer per state key
+        self._state_bufs: List[torch.Tensor] = []  # one flat buffer of ``state_dtype`` per state key
         self.active: List[torch.Tensor] = []
         self.step_count = 0
         self.grad_scale = 1.0
@@ -138,6 +161,21 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.flat_ema = None        # the moving average of flat_p (same layout), with ``ema_decay`` only
         self._ema_swapped = False   # inside ``ema_weights()``: flat_p holds the average, flat_ema the raw weights
         self.task_weighting = "none"  # the step's task_weighting.mode (engine.MTLStep sets it; dist.GradSync reads it)
+        self.state_dtype = state_dtype
+        self.state_rounding = state_rounding
+        self.state_seed = int(ops._rng["seed"] if state_seed is None else state_seed)  # (the seed itself; the key: ops.optim_state_key)
+
+    @property
+    def bf16_state(self) -> bool:
+        """The state buffers hold bf16 (``state_dtype=torch.bfloat16``)."""
+        return self.state_dtype is torch.bfloat16
+
+    def _state_entries(self) -> dict:
+        """The three top-level keys the state dict of a bf16 state carries beside torch's (torch.optim ignores them).  An f32 state
+        writes the dict it always wrote: a dict without the keys IS an f32 state."""
+        if not self.bf16_state:
+            return {}
+        return {"state_dtype": "bf16", "state_rounding": self.state_rounding, "state_seed": self.state_seed}
 
     @property
     def ema(self) -> bool:
@@ -238,7 +276,7 @@ class FlatOptimizer(torch.optim.Optimizer):
         total = sum(sizes)
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        self._state_bufs = [torch.zeros(total, dtype=torch.float32, device=dev) for _ in self._state_keys]
+        self._state_bufs = [torch.zeros(total, dtype=self.state_dtype, device=dev) for _ in self._state_keys]
         self.flat_w16 = torch.zeros(total, dtype=torch.bfloat16, device=dev)  # bf16 operand copies of the weights
         off = 0
         with torch.no_grad():
@@ -341,7 +379,9 @@ class FlatOptimizer(torch.optim.Optimizer):
     def state_dict(self):
         """``{"state": {index: {"step", *state keys}}, "param_groups": [...]}`` with parameter indices in constructor order --
         loadable by the torch class of the rule over the same parameter list and vice versa.  (torch.optim.SGD keeps no
-        ``step``; the entry is harmless to it and tells a resumed run that its first step has happened.)"""
+        ``step``; the entry is harmless to it and tells a resumed run that its first step has happened.)  The buffers are f32
+        tensors whatever ``state_dtype`` is -- a bf16 state widened, which is exact -- and with a bf16 state ``state_dtype``,
+        ``state_rounding`` and ``state_seed`` travel as three more top-level keys."""
         if getattr(self, "_moments_sharded", False):
             raise RuntimeError(f"{type(self).__name__}.state_dict(): the moments are sharded over the ranks (dist.GradSync shard_update: "
                                "every rank holds its own 1 / world slice, zeros elsewhere) -- call GradSync.gather_moments(optimizer) "
@@ -355,13 +395,13 @@ class FlatOptimizer(torch.optim.Optimizer):
                 mv = self._moment_views.get(id(p))
                 if mv is not None:
                     state[i] = {"step": torch.tensor(float(self._steps_taken())),
-                                **{k: v.detach().clone() for k, v in zip(self._state_keys, mv)}}
+                                **{k: v.detach().float().clone() for k, v in zip(self._state_keys, mv)}}
                 i += 1
         if self._pending_state is not None and not state:
             # (the loaded state, with THIS optimizer's groups: a state loaded without the trailing task_weighting group must not
             #  be written back as if this optimizer had none)
-            return {**self._pending_state, "param_groups": groups}
-        out = {"state": state, "param_groups": groups}
+            return {**self._pending_state, "param_groups": groups, **self._state_entries()}
+        out = {"state": state, "param_groups": groups, **self._state_entries()}
         if self.ema:
             if self._ema_swapped:
                 raise RuntimeError(f"{type(self).__name__}.state_dict(): inside ema_weights() the parameters hold the average -- "
@@ -382,8 +422,15 @@ class FlatOptimizer(torch.optim.Optimizer):
         return self.flat_ema[off:off + p.numel()].view(p.shape)
 
     def load_state_dict(self, state_dict):
-        """Hyper-parameters now; the state now if the flat buffers exist, otherwise when the first step builds them."""
+        """Hyper-parameters now; the state now if the flat buffers exist, otherwise when the first step builds them.  With a bf16
+        state the incoming f32 buffers are rounded to nearest: exact for a dict a bf16 run wrote, a rounding (once, here) for one an
+        f32 run or a torch optimizer wrote.  ``state_dtype`` / ``state_rounding`` / ``state_seed`` stay the constructor's: a state
+        saved with another dtype loads, and one log line says so."""
         self._check_state_rule(state_dict)
+        held = state_dict.get("state_dtype", "f32")
+        if STATE_DTYPES.get(held) is not self.state_dtype and state_dict["state"]:
+            logger.info("%s: the loaded optimizer state was kept in %s, this run keeps it in %s%s", type(self).__name__, held,
+                        "bf16" if self.bf16_state else "f32", " (rounded to nearest once)" if self.bf16_state else " (widened, exact)")
         # A state saved WITHOUT learned task weights loads into an optimizer that has them: it lacks exactly the trailing
         # ``task_weighting`` group and its parameter (the last index), which then start with fresh moments -- an ``uncertainty`` run
         # warm-started from a fixed-weight run (train.load_task_weighting says so in its one log line).
@@ -406,7 +453,9 @@ class FlatOptimizer(torch.optim.Optimizer):
                     self.flat_ema.copy_(self.flat_p)
             self._apply_state(state_dict)
         else:  # snapshot: the caller may keep using (or another optimizer may step) the tensors it handed in
-            self._pending_state = {"state": {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
+            # (state buffers: as the flat buffers will hold them -- with a bf16 state rounded to nearest, f32 unchanged)
+            keep = lambda k, v: v.detach().clone().to(self.state_dtype).float() if k in self._state_keys else v.detach().clone()
+            self._pending_state = {"state": {i: {k: (keep(k, v) if torch.is_tensor(v) else v) for k, v in st.items()}
                                              for i, st in state_dict["state"].items()},
                                    "param_groups": state_dict["param_groups"]}
             if ema is not None:
@@ -811,6 +860,9 @@ class FlatOptimizer(torch.optim.Optimizer):
         if bump is not None:
             d.bump_word, d.bump = bump[0].data_ptr(), int(bump[1])
         d.gate = gate.data_ptr() if gate is not None else None
+        if self.bf16_state and self._state_bufs:  # (a zeroed tail: the f32 launch as it always was)
+            d.state_dtype, d.state_round = 1, STATE_ROUNDINGS[self.state_rounding]
+            d.state_seed, d.elem0 = ops.optim_state_key(self.state_seed), sl.start
         t = None
         if self.grouped:
             t = _lib.OptimGroups()
@@ -876,7 +928,8 @@ class FlatAdam(FlatOptimizer):
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, max_grad_norm=None, *, decoupled_weight_decay: bool = False, amsgrad: bool = False,
                  maximize: bool = False, foreach=None, fused=None, capturable: bool = False, differentiable: bool = False,
-                 layout_order=None, ema_decay=None, ema_warmup=False):
+                 layout_order=None, ema_decay=None, ema_warmup=False, state_dtype=torch.float32, state_rounding="stochastic",
+                 state_seed=None):
         _refuse_unbuilt(type(self).__name__, amsgrad, maximize)
         if not 0.0 <= lr:  # (torch.optim.Adam's checks and messages)
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -893,7 +946,8 @@ class FlatAdam(FlatOptimizer):
         if self.decoupled_weight_decay:  # (what torch.optim.Adam needs to read the saved group as AdamW's; plain Adam's group as it was)
             defaults["decoupled_weight_decay"] = True
         super().__init__(params, defaults, state_keys=("exp_avg", "exp_avg_sq"), max_grad_norm=max_grad_norm,
-                         layout_order=layout_order, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         layout_order=layout_order, ema_decay=ema_decay, ema_warmup=ema_warmup, state_dtype=state_dtype,
+                         state_rounding=state_rounding, state_seed=state_seed)
 
     _fixed_keys = ("decoupled_weight_decay",)
 
@@ -910,8 +964,8 @@ class FlatAdam(FlatOptimizer):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         n = sl.stop - sl.start
-        # (several groups, or the weight average: Adam's rule too goes through the descriptor, same bits)
-        if self.decoupled_weight_decay or self.grouped or self.ema:
+        # (several groups, the weight average, or a bf16 state: Adam's rule too goes through the descriptor, same bits)
+        if self.decoupled_weight_decay or self.grouped or self.ema or self.bf16_state:
             self._optim_step(_lib.OPT_ADAMW if self.decoupled_weight_decay else _lib.OPT_ADAM, sl, grads, lo16, bump, gate,
                              beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"])
             return
@@ -940,7 +994,7 @@ class FlatSGD(FlatOptimizer):
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm=None, *, maximize: bool = False, foreach=None,
                  fused=None, capturable: bool = False, differentiable: bool = False, layout_order=None, ema_decay=None,
-                 ema_warmup=False):
+                 ema_warmup=False, state_dtype=torch.float32, state_rounding="stochastic", state_seed=None):
         _refuse_unbuilt(type(self).__name__, False, maximize)
         if lr < 0.0:  # (torch.optim.SGD's checks and messages)
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -952,7 +1006,8 @@ class FlatSGD(FlatOptimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov))
         super().__init__(params, defaults, state_keys=("momentum_buffer",) if momentum != 0 else (), max_grad_norm=max_grad_norm,
-                         layout_order=layout_order, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         layout_order=layout_order, ema_decay=ema_decay, ema_warmup=ema_warmup, state_dtype=state_dtype,
+                         state_rounding=state_rounding, state_seed=state_seed)
 
     _fixed_keys = ("momentum",)  # (zero or not decides whether there is a buffer: the constructor's value stands)
 

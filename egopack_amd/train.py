@@ -13,7 +13,7 @@ from . import data as D
 from . import ops
 from .config import Cfg, compose, instantiate
 from .criterion import BCEWithLogitsNone, CrossEntropyNone, MetricSelectorWrapper
-from .optim import TASK_WEIGHTING_GROUP, TASK_WEIGHTING_MODES, FlatAdam, FlatAdamW, FlatSGD
+from .optim import STATE_DTYPES, STATE_ROUNDINGS, TASK_WEIGHTING_GROUP, TASK_WEIGHTING_MODES, FlatAdam, FlatAdamW, FlatSGD
 
 logger = logging.getLogger("egopack")
 TASKS = ("ar", "oscc", "lta", "pnr")
@@ -601,6 +601,37 @@ def load_task_weighting(logger, ckpt: dict, step) -> bool:
 
 OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
 
+# ---- the element type of the optimizer state (``optimizer_state:`` of the config; include/egopack_optim.h) ---------------
+OPTIMIZER_STATE_DEFAULTS = {"dtype": "f32", "rounding": "stochastic", "seed": None}
+
+
+def optimizer_state_config(cfg) -> dict:
+    """The ``optimizer_state:`` block with its defaults filled in (``dtype`` and ``rounding`` in lower case); an unknown key, dtype
+    or rounding is a ValueError that lists the known ones.  ``seed``: None (the run's seed) or an integer in [0, 2^64)."""
+    raw = cfg.get("optimizer_state") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(OPTIMIZER_STATE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"optimizer_state: unknown key(s) {sorted(unknown)} ({', '.join(OPTIMIZER_STATE_DEFAULTS)})")
+    st = {**OPTIMIZER_STATE_DEFAULTS, **raw}
+    st["dtype"], st["rounding"] = str(st["dtype"]).lower(), str(st["rounding"]).lower()
+    if st["dtype"] not in STATE_DTYPES:
+        raise ValueError(f"optimizer_state.dtype: unknown dtype '{st['dtype']}' ({' | '.join(STATE_DTYPES)})")
+    if st["rounding"] not in STATE_ROUNDINGS:
+        raise ValueError(f"optimizer_state.rounding: unknown rounding '{st['rounding']}' ({' | '.join(sorted(STATE_ROUNDINGS, reverse=True))})")
+    if st["seed"] is not None and (isinstance(st["seed"], bool) or not isinstance(st["seed"], int) or not 0 <= st["seed"] < 2 ** 64):
+        raise ValueError(f"optimizer_state.seed: {st['seed']!r} is neither null nor an integer in [0, 2^64)")
+    return st
+
+
+def log_optimizer_state(logger, optimizer) -> None:
+    """One line: which state the run keeps."""
+    if getattr(optimizer, "bf16_state", False):
+        logger.info("optimizer state: bf16, %s rounding%s (half the bytes of f32 moments)", optimizer.state_rounding,
+                    f", seed {optimizer.state_seed}" if optimizer.state_rounding == "stochastic" else "")
+    else:
+        logger.info("optimizer state: f32")
+
 
 PARAM_GROUP_MODULES = ("temporal_graph", "tasks", "graphone")  # the keys of ``param_groups.lr_scale``
 
@@ -684,6 +715,10 @@ def build_optimizer(cfg, params, layout_order=None, log_var=None):
     unknown = set(ema) - {"decay", "warmup", "validate", "save"}
     if unknown:
         raise ValueError(f"ema: unknown key(s) {sorted(unknown)} (decay, warmup, validate, save)")
+    # (``optimizer_state:`` likewise; the default block hands the constructors nothing they did not get before)
+    st = optimizer_state_config(cfg)
+    if st["dtype"] != "f32":
+        extra.update(state_dtype=STATE_DTYPES[st["dtype"]], state_rounding=st["rounding"], state_seed=st["seed"])
     return cls(params, **ocfg, max_grad_norm=float(cfg.get("grad_clip_norm", 0) or 0), ema_decay=float(ema.get("decay", 0) or 0),
                ema_warmup=bool(ema.get("warmup", False)), **extra)
 

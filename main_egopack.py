@@ -161,6 +161,7 @@ def main(argv=None):
             torch.distributed.broadcast(p.data, src=0)
     optimizer = T.build_optimizer(cfg, T.build_param_groups(cfg, model, tasks, graphone), layout_order=params)
     T.log_param_groups(logger, optimizer)
+    T.log_optimizer_state(logger, optimizer)
     scheduler = T.build_scheduler(cfg, optimizer)
     sync = edist.GradSync(world) if world > 1 else None
     step = engine.EgoPackStep(model, tasks, graphone, weights, optimizer,

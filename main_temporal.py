@@ -166,6 +166,7 @@ def main(argv=None):
         torch.distributed.broadcast(log_var.log_var.data, src=0)
     optimizer = T.build_optimizer(cfg, T.build_param_groups(cfg, model, tasks), layout_order=params, log_var=log_var)
     T.log_param_groups(logger, optimizer)
+    T.log_optimizer_state(logger, optimizer)
     scheduler = T.build_scheduler(cfg, optimizer)
     compress = str(cfg.get("grad_compress", "none"))  # element type of the gradient all-reduce: none (f32) | bf16
     sync = edist.GradSync(world, compress=compress) if world > 1 else None
