@@ -84,7 +84,8 @@ class HostMerged(C.Structure):
 class CETask(C.Structure):
     """struct egk_ce_task (include/egopack_hip.h)."""
     _fields_ = [("logits", vp * 4), ("ld", i64 * 4), ("C", i32 * 4), ("pad", i32 * 4), ("dcol", i64 * 4), ("n_heads", i32),
-                ("y", vp), ("y_stride", i64), ("loss", vp), ("dlogits", vp), ("ldd", i64), ("rows", i32), ("gscale", f32)]
+                ("y", vp), ("y_stride", i64), ("loss", vp), ("dlogits", vp), ("ldd", i64), ("rows", i32), ("gscale", f32),
+                ("margin", vp * 4), ("gloss", vp), ("focal_gamma", f32), ("loss_only", i32), ("reserved", i64)]
 
 
 class CEWTask(C.Structure):

@@ -21,22 +21,35 @@ def _class_vector(v, what: str) -> Optional[torch.Tensor]:
     return v.detach().to(torch.float32).contiguous().clone()
 
 
+def _focal_gamma(gamma, what: str) -> float:
+    gamma = 0.0 if gamma is None else float(gamma)
+    if not (gamma >= 0.0 and gamma != float("inf")):
+        raise ValueError(f"{what}: the focal exponent must be finite and >= 0, got {gamma}")
+    return gamma
+
+
 class CrossEntropyNone(torch.nn.Module):
     """nn.CrossEntropyLoss(reduction='none', ignore_index=-1[, label_smoothing][, weight]) on the HIP path.  ``offset``: a
     per-class vector added to the logits inside the loss only (logit adjustment).  Both are non-persistent buffers (single-head
-    use; ``MetricSelectorWrapper`` carries one pair per head)."""
+    use; ``MetricSelectorWrapper`` carries one pair per head).  ``margin`` / ``gamma``: the per-class margin subtracted from the
+    target's logit and the focal exponent (``ops.cross_entropy(margin=, gamma=)``), training mode only like the vectors."""
 
-    def __init__(self, ignore_index: int = -1, label_smoothing: float = 0.0, weight=None, offset=None):
+    def __init__(self, ignore_index: int = -1, label_smoothing: float = 0.0, weight=None, offset=None, margin=None, gamma: float = 0.0):
         super().__init__()
         if ignore_index != -1:
             raise ValueError("the hot path uses ignore_index=-1")
         self.label_smoothing = label_smoothing
         self.register_buffer("weight", _class_vector(weight, "CrossEntropyNone: weight"), persistent=False)
         self.register_buffer("offset", _class_vector(offset, "CrossEntropyNone: offset"), persistent=False)
+        self.register_buffer("margin", _class_vector(margin, "CrossEntropyNone: margin"), persistent=False)
+        self.gamma = _focal_gamma(gamma, "CrossEntropyNone")
 
     def forward(self, logits, target):
-        w, a = (self.weight, self.offset) if self.training else (None, None)  # (``eval()``: the plain cross entropy)
-        return ops.cross_entropy(logits, target, self.label_smoothing, weight=w, offset=a)  # (no vector: the plain launches)
+        if not self.training:  # (``eval()``: the plain cross entropy)
+            return ops.cross_entropy(logits, target, self.label_smoothing)
+        # (no vector, no margin, gamma 0: the plain launches)
+        return ops.cross_entropy(logits, target, self.label_smoothing, weight=self.weight, offset=self.offset, margin=self.margin,
+                                 gamma=self.gamma)
 
 
 class BCEWithLogitsNone(torch.nn.Module):
@@ -63,9 +76,12 @@ class MetricSelectorWrapper(torch.nn.Module):
     per-head loss vectors.  Needs only ``dataset.has_joint_label`` and ``dataset.num_labels``."""
 
     def __init__(self, criterion: torch.nn.Module, dataset, joint_label_training: bool = False, *,
-                 class_weights: Optional[Sequence] = None, class_offsets: Optional[Sequence] = None) -> None:
+                 class_weights: Optional[Sequence] = None, class_offsets: Optional[Sequence] = None,
+                 class_margins: Optional[Sequence] = None, focal_gamma: float = 0.0) -> None:
         """``class_weights`` / ``class_offsets``: one per-class vector or None per head of the task (label column), applied inside
-        the cross entropy of that head (``ops.cross_entropy(weight=, offset=)``); kept as non-persistent buffers."""
+        the cross entropy of that head (``ops.cross_entropy(weight=, offset=)``); kept as non-persistent buffers.
+        ``class_margins`` (one vector or None per head, buffers like them) / ``focal_gamma``: the LDAM margins and the focal
+        exponent of ``ops.cross_entropy(margin=, gamma=)``."""
         super().__init__()
         if not dataset.has_joint_label and joint_label_training:
             logger.warning("The flag join_labels is set to True but the dataset has no joint label")
@@ -79,6 +95,10 @@ class MetricSelectorWrapper(torch.nn.Module):
             self.n_balance = max(self.n_balance, len(vecs))
             for h, v in enumerate(vecs):
                 self.register_buffer(f"{name}_{h}", _class_vector(v, f"MetricSelectorWrapper: {name} of head {h}"), persistent=False)
+        self.n_margin = len(class_margins) if class_margins is not None else 0
+        for h, v in enumerate(class_margins or []):
+            self.register_buffer(f"class_margin_{h}", _class_vector(v, f"MetricSelectorWrapper: class_margin of head {h}"), persistent=False)
+        self.focal_gamma = _focal_gamma(focal_gamma, "MetricSelectorWrapper")
 
     def _heads(self, n_logits: int):
         if self.dataset.has_joint_label:
@@ -96,6 +116,20 @@ class MetricSelectorWrapper(torch.nn.Module):
         out = tuple(tuple(getattr(self, f"{name}_{h}", None) for h in heads) for name in ("class_weight", "class_offset"))
         return tuple(None if all(v is None for v in vecs) else vecs for vecs in out)
 
+    def select_shape(self, logits: Tuple[torch.Tensor, ...]):
+        """(margins, gamma) of the heads ``select`` chooses -- a tuple with one vector or None per chosen head (None when there is
+        none) and the focal exponent -- or (None, 0.0) in ``eval()`` mode: the terms shape the training loss only."""
+        if not self.training or (not self.n_margin and not self.focal_gamma):
+            return None, 0.0
+        margins = None
+        if self.n_margin:
+            heads = self._heads(len(logits))
+            if heads and max(heads) >= self.n_margin:
+                raise ValueError(f"MetricSelectorWrapper: margins for {self.n_margin} heads, head {max(heads)} is selected")
+            margins = tuple(getattr(self, f"class_margin_{h}", None) for h in heads)
+            margins = None if all(m is None for m in margins) else margins
+        return margins, self.focal_gamma
+
     def select(self, logits: Tuple[torch.Tensor, ...], ground_truths: torch.Tensor):
         """(logits of the heads that count, their label columns, label smoothing): what ``forward`` hands to the cross
         entropy (the engine batches the cross entropies of several tasks into one launch from these)."""
@@ -110,4 +144,6 @@ class MetricSelectorWrapper(torch.nn.Module):
     def forward(self, logits: Tuple[torch.Tensor, ...], ground_truths: torch.Tensor) -> torch.Tensor:
         sel, gt, smoothing = self.select(logits, ground_truths)
         weights, offsets = self.select_balance(logits)
-        return ops.cross_entropy(sel, gt, smoothing, weight=weights, offset=offsets)  # one fused per-row sum over the heads
+        margins, gamma = self.select_shape(logits)
+        # one fused per-row sum over the heads
+        return ops.cross_entropy(sel, gt, smoothing, weight=weights, offset=offsets, margin=margins, gamma=gamma)

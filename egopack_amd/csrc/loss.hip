@@ -78,6 +78,73 @@ __device__ __forceinline__ float ce_row_balanced(const float* __restrict__ lr, c
     return loss;
 }
 
+// The shaped arithmetic (egk_ce_task in egopack_hip.h; m: per-class margins, may be null; gamma: focal exponent >= 0):
+//   z_c = x_c + a_c - [c == t] m_t,  S = the balanced loss on z,  q = softmax(z)_t,  loss = (1 - q)^gamma S,
+//   dz_j = g [(1 - q)^gamma dS_j + S gamma q (1 - q)^(gamma - 1) (p_j - [j == t])].
+// S and dS_j are formed operation by operation as ce_row_balanced forms them (x - 0.f is x): with m null and gamma 0 the row
+// has the balanced row's bits.  1 - q = -expm1f(-(lse - z_t)), no cancellation; at q = 1 both factors are 0 by definition
+// (0 * inf otherwise).  Always the forward pass; ``grad`` = false writes no gradient (the forward-only form).
+template <typename T>
+__device__ __forceinline__ float ce_row_shaped(const float* __restrict__ lr, const float* __restrict__ w, const float* __restrict__ a,
+                                               const float* __restrict__ m, int C, int pad, long long t, float smoothing, float gamma,
+                                               float g, bool grad, T* __restrict__ dr, int lane) {
+#pragma clang fp contract(off)  // (the f32 and the bf16 instantiation form the same f32 value: no fusing that depends on the code around)
+    const bool live = t >= 0 && t < C;
+    const int tc = live ? (int)t : -1;
+    const float sm = smoothing > 0.f ? smoothing / C : 0.f;
+    const float mt = live && m ? m[tc] : 0.f;
+    auto z = [&](int c) {
+        const float v = lr[c] + (a ? a[c] : 0.f);
+        return c == tc ? v - mt : v;
+    };
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, z(c));
+    mx = wave_max(mx);
+    float se = 0.f, W = 0.f, swx = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float v = z(c) - mx;
+        const float wc = w ? w[c] : 1.f;
+        se += expf(v);
+        W += wc;
+        swx += wc * v;
+    }
+    se = wave_sum(se);
+    W = wave_sum(W);
+    swx = wave_sum(swx);
+    const float lg = logf(se);
+    const float l = mx + lg;
+    float loss = 0.f, fS = 1.f, cf = 0.f;
+    if (live) {
+        const float wt = w ? w[tc] : 1.f;
+        const float zt = z(tc);
+        const float S = (1.f - smoothing) * wt * (l - zt) + (smoothing > 0.f ? sm * (W * lg - swx) : 0.f);
+        loss = S;
+        if (gamma > 0.f) {
+            const float d = fmaxf(l - zt, 0.f);  // -log q (a rounding below 0 would hand powf a negative base)
+            const float q = expf(-d), u = -expm1f(-d);
+            fS = u > 0.f ? powf(u, gamma) : 0.f;
+            cf = u > 0.f ? S * gamma * q * powf(u, gamma - 1.f) : 0.f;
+            loss = fS * S;
+        }
+    }
+    if (grad) {
+        const float hard = live ? (1.f - smoothing) * (w ? w[tc] : 1.f) : 0.f;
+        for (int c = lane; c < pad; c += 64) {
+            float d = 0.f;
+            if (live && c < C) {
+                const float p = expf(z(c) - l);
+                const float e = p - (c == tc ? 1.f : 0.f);
+                d = hard * e;
+                if (sm > 0.f) d += sm * (W * p - (w ? w[c] : 1.f));
+                if (gamma > 0.f) d = fS * d + cf * e;
+                d *= g;
+            }
+            st1t(dr + c, d);
+        }
+    }
+    return loss;
+}
+
 // BAL = false never reads ``w`` / ``a``
 template <typename T, bool BAL, bool FWD, bool GRAD>
 __device__ __forceinline__ float ce_row(const float* __restrict__ lr, const float* __restrict__ w, const float* __restrict__ a, int C,
@@ -150,8 +217,16 @@ struct CETasks {
     float gscale[CE_MAX_TASKS];
     const float* scale[CE_MAX_TASKS];  // the task factor of gscale in device memory (egk_ce_fused_multi_s / egk_ce_w_fused_multi_s), or null
 };
-template <typename T, bool BAL>
-__global__ __launch_bounds__(256) void ce_fused_multi_kernel(const CETasks P, float smoothing) {
+// The tail of egk_ce_task (margins, focal exponent, per-row seeds, the forward-only flag): read by the SHAPED instantiation only.
+struct CEShape {
+    const float* m[CE_MAX_TASKS][CE_MAX_HEADS];
+    const float* gloss[CE_MAX_TASKS];  // null: every row's seed is the task's gscale
+    float gamma[CE_MAX_TASKS];
+    int loss_only[CE_MAX_TASKS];       // 1: no gradient is written (dlogits may be null)
+};
+// SHAPED: ce_row_shaped on every row (it takes the vectors of BAL, null or not); ``S`` is not read otherwise.
+template <typename T, bool BAL, bool SHAPED>
+__global__ __launch_bounds__(256) void ce_fused_multi_kernel(const CETasks P, const CEShape S, float smoothing) {
     const int k = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const CEHeads& H = P.H[k];
@@ -164,11 +239,20 @@ __global__ __launch_bounds__(256) void ce_fused_multi_kernel(const CETasks P, fl
     const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
     for (int row = rw.first; row < rw.end; row += rw.step) {
         float total = 0.f;
-        for (int h = 0; h < n_heads; ++h) {
-            float l;
-            total += ce_row<T, BAL, true, true>(H.logits[h] + (long long)row * H.ld[h], H.w[h], H.a[h], H.C[h], H.pad[h],
-                                                y[(long long)row * ys + h], smoothing, gscale, l,
-                                                dlogits + (long long)row * ldd + H.dcol[h], lane);
+        if constexpr (SHAPED) {
+            const float* __restrict__ gl = S.gloss[k];
+            const float g = gl ? scaled_seed(gscale, gl + row) : gscale;
+            for (int h = 0; h < n_heads; ++h)
+                total += ce_row_shaped<T>(H.logits[h] + (long long)row * H.ld[h], H.w[h], H.a[h], S.m[k][h], H.C[h], H.pad[h],
+                                          y[(long long)row * ys + h], smoothing, S.gamma[k], g, !S.loss_only[k],
+                                          dlogits + (long long)row * ldd + H.dcol[h], lane);
+        } else {
+            for (int h = 0; h < n_heads; ++h) {
+                float l;
+                total += ce_row<T, BAL, true, true>(H.logits[h] + (long long)row * H.ld[h], H.w[h], H.a[h], H.C[h], H.pad[h],
+                                                    y[(long long)row * ys + h], smoothing, gscale, l,
+                                                    dlogits + (long long)row * ldd + H.dcol[h], lane);
+            }
         }
         if (lane == 0) loss[row] = total;
     }
@@ -292,6 +376,8 @@ static int ce_bwd_launch(const char* who, int kid, egk_stream_t stream, const fl
 // (row_grid(longest task), count).  ``wtasks``: the tasks with their vectors (BAL), else ``tasks``.  The slots behind ``count``
 // repeat the last task with no rows: no wild pointers in the argument.  ``scales`` (the _s entry points of
 // include/egopack_task_scale.h; ``scaled``): one device float per task that multiplies the task's gscale inside the kernel.
+// The tail of egk_ce_task (margin, gloss, focal_gamma, loss_only) picks the SHAPED instantiation when any task sets any of it;
+// all zero: the instantiation and the bits of the launch without the tail.
 template <bool BAL>
 static int ce_fused_launch(const char* who, int kid, egk_stream_t stream, const egk_ce_task* tasks, const egk_ce_w_task* wtasks,
                            int32_t count, float smoothing, int32_t dtype, bool scaled = false, const float* const* scales = nullptr) {
@@ -300,14 +386,32 @@ static int ce_fused_launch(const char* who, int kid, egk_stream_t stream, const 
     EGK_REQUIRE(count >= 1 && count <= CE_MAX_TASKS, "%s: 1 .. %d tasks", who, CE_MAX_TASKS);
     EGK_REQUIRE(dtype == EGK_F32 || dtype == EGK_BF16, "%s: unknown activation dtype %d", who, (int)dtype);
     CETasks P;
+    CEShape S;
+    bool shaped = false;  // some task sets a field of the struct's tail: all zero is the launch without the tail
     double bytes = 0;
     int max_rows = 0;
     for (int i = 0; i < CE_MAX_TASKS; ++i) {
         const int j = i < count ? i : count - 1;
         const egk_ce_task& t = BAL ? wtasks[j].base : tasks[j];
         EGK_REQUIRE(t.n_heads >= 1 && t.n_heads <= CE_MAX_HEADS, "%s: 1 .. %d heads (task %d)", who, CE_MAX_HEADS, i);
-        EGK_REQUIRE(t.y && t.loss && t.dlogits, "%s: null pointer in task %d", who, i);
+        EGK_REQUIRE(t.loss_only == 0 || t.loss_only == 1, "%s: loss_only must be 0 or 1, got %d (task %d)", who, (int)t.loss_only, i);
+        EGK_REQUIRE(t.y && t.loss && (t.dlogits || t.loss_only), "%s: null pointer in task %d", who, i);
         EGK_REQUIRE(t.rows >= 0, "%s: rows must be >= 0 (task %d)", who, i);
+        EGK_REQUIRE(isfinite(t.focal_gamma) && t.focal_gamma >= 0.f, "%s: focal_gamma must be finite and >= 0, got %g (task %d)", who,
+                    (double)t.focal_gamma, i);
+        EGK_REQUIRE(!(t.loss_only && t.gloss), "%s: loss_only and gloss are both set (task %d) -- a forward-only pass takes no row seeds",
+                    who, i);
+        EGK_REQUIRE(t.reserved == 0, "%s: the reserved field of task %d is not 0", who, i);
+        EGK_REQUIRE(aligned_to(4, {t.gloss}), "%s: the row seeds (gloss) of task %d are not 4-byte aligned", who, i);
+        for (int h = 0; h < CE_MAX_HEADS; ++h) {
+            EGK_REQUIRE(h < t.n_heads || !t.margin[h], "%s: margin[%d] is set but task %d has %d heads", who, h, i, (int)t.n_heads);
+            EGK_REQUIRE(aligned_to(4, {t.margin[h]}), "%s: misaligned margin pointer -- margins are read one float at a time and must be "
+                        "4-byte aligned (head %d of task %d)", who, h, i);
+            S.m[i][h] = t.margin[h];
+            shaped = shaped || t.margin[h];
+        }
+        S.gloss[i] = t.gloss; S.gamma[i] = t.focal_gamma; S.loss_only[i] = t.loss_only;
+        shaped = shaped || t.gloss || t.loss_only || t.focal_gamma > 0.f;
         CEHeads& H = P.H[i];
         for (int h = 0; h < CE_MAX_HEADS; ++h) {
             const int k = h < t.n_heads ? h : t.n_heads - 1;
@@ -330,7 +434,10 @@ static int ce_fused_launch(const char* who, int kid, egk_stream_t stream, const 
     if (max_rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(kid, s, 0, bytes);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL((ce_fused_multi_kernel<T, BAL>), dim3(row_grid(max_rows), count), dim3(256), 0, s, P, smoothing));
+    if (shaped)  // (one shaped instantiation per element type: it takes the vectors, null or not)
+        EGK_DISPATCH_T(dtype, hipLaunchKernelGGL((ce_fused_multi_kernel<T, true, true>), dim3(row_grid(max_rows), count), dim3(256), 0, s, P, S, smoothing));
+    else
+        EGK_DISPATCH_T(dtype, hipLaunchKernelGGL((ce_fused_multi_kernel<T, BAL, false>), dim3(row_grid(max_rows), count), dim3(256), 0, s, P, S, smoothing));
     return check_launch(who);
 }
 

@@ -1776,11 +1776,14 @@ class MTLStep(StepBase):
             # the cross entropies of the banked tasks as ONE launch (each writes its own loss vector and gradient operand)
             sel = [self.criteria[t].select(logits, labels[t]) for t, logits in zip(banked, all_logits)]
             if len({s_[2] for s_ in sel}) == 1:
-                # (the criteria's class-balance vectors ride in the same launch; without any it is the launch it always was)
+                # (the criteria's class-balance vectors, margins and focal exponents ride in the same launch; without any it is the
+                #  launch it always was)
                 bal = [self.criteria[t].select_balance(logits) for t, logits in zip(banked, all_logits)]
+                shp = [self.criteria[t].select_shape(logits) for t, logits in zip(banked, all_logits)]
                 multi = ops.cross_entropy_multi([(s_[0], s_[1]) for s_ in sel], [self.weights[t] / n_loss[t] for t in banked],
                                                 sel[0][2], weights=[w for w, _ in bal], offsets=[a for _, a in bal],
-                                                scales=None if sc_vec is None else [sc[t] for t in banked])
+                                                scales=None if sc_vec is None else [sc[t] for t in banked],
+                                                margins=[m for m, _ in shp], gammas=[g for _, g in shp])
             for i, (t, logits) in enumerate(zip(banked, all_logits)):
                 if multi is not None:
                     v = multi[i]

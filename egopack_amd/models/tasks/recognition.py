@@ -68,6 +68,32 @@ class MultiHeadTask(ProjectionTask):
                 else:
                     self.register_buffer(key, v, persistent=False)
 
+    def set_ce_shape(self, margins=None, gamma: float = 0.0) -> None:
+        """The label-distribution-aware margins (one vector of ``heads[h]`` values or None per head, subtracted from the target's
+        logit inside the loss) and the focal exponent of the training loss (``ops.cross_entropy(margin=, gamma=)``).  The margins
+        are non-persistent buffers like the class-balance vectors.  None, 0 removes them."""
+        from ...criterion import _class_vector, _focal_gamma
+        vecs = list(margins) if margins is not None else [None] * len(self.heads)
+        if len(vecs) != len(self.heads):
+            raise ValueError(f"{self.name}: {len(vecs)} class_margin entries for {len(self.heads)} heads")
+        for h, v in enumerate(vecs):
+            v = _class_vector(v, f"{self.name}: class_margin of head {h}")
+            if v is not None and v.numel() != self.heads[h]:
+                raise ValueError(f"{self.name}: class_margin of head {h} has {v.numel()} entries, the head has {self.heads[h]} classes")
+            if v is not None:
+                v = v.to(self.classifiers[h][1].weight.device)
+            key = f"class_margin_{h}"
+            if key in self._buffers:
+                self._buffers[key] = v
+            else:
+                self.register_buffer(key, v, persistent=False)
+        self.focal_gamma = _focal_gamma(gamma, self.name)
+
+    def ce_shape(self):
+        """(margins, gamma) as ``ops.cross_entropy`` takes them: a tuple with one vector or None per head (or None), a float."""
+        vecs = tuple(getattr(self, f"class_margin_{h}", None) for h in range(len(self.heads)))
+        return (None if all(v is None for v in vecs) else vecs), getattr(self, "focal_gamma", 0.0)
+
     def class_balance(self):
         """(weights, offsets) as ``ops.cross_entropy`` takes them: a tuple with one vector or None per head, or None."""
         out = []
@@ -80,10 +106,13 @@ class MultiHeadTask(ProjectionTask):
         """sum over heads of CrossEntropy(reduction='none', ignore_index=-1).  While training, with the class-balance vectors of
         ``set_class_balance``; a validation loss (``eval()``) is always the plain cross entropy, so curves compare across runs."""
         weights, offsets = self.class_balance() if self.training else (None, None)
-        total = ops.cross_entropy(tuple(logits), targets, weight=weights, offset=offsets)  # (no vector: the plain launches)
+        margins, gamma = self.ce_shape() if self.training else (None, 0.0)  # (``set_ce_shape``; training loss only, like the vectors)
+        # (no vector, no margin, gamma 0: the plain launches)
+        total = ops.cross_entropy(tuple(logits), targets, weight=weights, offset=offsets, margin=margins, gamma=gamma)
         if return_separate_losses:
-            w, a = weights or [None] * len(logits), offsets or [None] * len(logits)
-            return total, tuple(ops.cross_entropy(l, targets[:, i].contiguous(), weight=w[i], offset=a[i]) for i, l in enumerate(logits))
+            w, a, m = weights or [None] * len(logits), offsets or [None] * len(logits), margins or [None] * len(logits)
+            return total, tuple(ops.cross_entropy(l, targets[:, i].contiguous(), weight=w[i], offset=a[i], margin=m[i], gamma=gamma)
+                                for i, l in enumerate(logits))
         return total
 
 

@@ -2817,35 +2817,62 @@ def _class_balance(weight, offset, logits, where="cross_entropy"):
     head -- or None when every vector is None (the caller then issues exactly the launches it issues without the arguments).
     Each argument: None, one tensor (a single head), or a tuple / list with one tensor or None per head.  The vectors are
     constants of the loss: no gradient reaches them."""
-    out = []
-    for name, arg in (("weight", weight), ("offset", offset)):
-        if arg is None:
-            vecs = [None] * len(logits)
-        elif torch.is_tensor(arg):
-            if len(logits) != 1:
-                raise ValueError(f"{where}: {name} is one tensor but there are {len(logits)} heads (pass one entry per head)")
-            vecs = [arg]
-        else:
-            vecs = list(arg)
-            if len(vecs) != len(logits):
-                raise ValueError(f"{where}: {name} has {len(vecs)} entries for {len(logits)} heads")
-        packed = []
-        for h, (v, l) in enumerate(zip(vecs, logits)):
-            if v is None:
-                packed.append(None)
-                continue
-            if not torch.is_tensor(v) or v.dtype != torch.float32:
-                raise ValueError(f"{where}: {name} of head {h} must be a float32 tensor, got "
-                                 f"{v.dtype if torch.is_tensor(v) else type(v).__name__}")
-            if v.device != l.device:
-                raise ValueError(f"{where}: {name} of head {h} is on {v.device}, the logits on {l.device}")
-            if v.dim() != 1 or v.shape[0] != l.shape[-1]:
-                raise ValueError(f"{where}: {name} of head {h} has shape {tuple(v.shape)}, the head has {l.shape[-1]} classes")
-            packed.append(_c(v.detach()))
-        out.append(tuple(packed))
+    out = tuple(_head_vectors(name, arg, logits, where) for name, arg in (("weight", weight), ("offset", offset)))
     if all(v is None for vecs in out for v in vecs):
         return None
-    return tuple(out)
+    return out
+
+
+def _head_vectors(name, arg, logits, where):
+    """One per-class argument of the cross entropies (``weight``, ``offset``, ``margin``) as a tuple with one packed f32 vector or
+    None per head."""
+    if arg is None:
+        vecs = [None] * len(logits)
+    elif torch.is_tensor(arg):
+        if len(logits) != 1:
+            raise ValueError(f"{where}: {name} is one tensor but there are {len(logits)} heads (pass one entry per head)")
+        vecs = [arg]
+    else:
+        vecs = list(arg)
+        if len(vecs) != len(logits):
+            raise ValueError(f"{where}: {name} has {len(vecs)} entries for {len(logits)} heads")
+    packed = []
+    for h, (v, l) in enumerate(zip(vecs, logits)):
+        if v is None:
+            packed.append(None)
+            continue
+        if not torch.is_tensor(v) or v.dtype != torch.float32:
+            raise ValueError(f"{where}: {name} of head {h} must be a float32 tensor, got "
+                             f"{v.dtype if torch.is_tensor(v) else type(v).__name__}")
+        if v.device != l.device:
+            raise ValueError(f"{where}: {name} of head {h} is on {v.device}, the logits on {l.device}")
+        if v.dim() != 1 or v.shape[0] != l.shape[-1]:
+            raise ValueError(f"{where}: {name} of head {h} has shape {tuple(v.shape)}, the head has {l.shape[-1]} classes")
+        packed.append(_c(v.detach()))
+    return tuple(packed)
+
+
+def _ce_shape(margin, gamma, logits, where="cross_entropy"):
+    """The ``margin`` / ``gamma`` arguments of the cross entropies as (margins, gamma) -- one packed f32 vector or None per head and
+    a Python float -- or None when every margin is None and gamma is 0 (the caller then issues exactly the launches it issues
+    without the arguments).  ``margin`` takes the forms of ``weight``; both are constants of the loss."""
+    margins = _head_vectors("margin", margin, logits, where)
+    gamma = 0.0 if gamma is None else float(gamma)
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"{where}: gamma must be finite and >= 0, got {gamma}")
+    if gamma == 0.0 and all(m is None for m in margins):
+        return None
+    return margins, gamma
+
+
+def _ce_tail(t, shape, n_heads, gloss=None, loss_only=False):
+    """The tail of one ``egk_ce_task`` (include/egopack_hip.h): the margins and the focal exponent of ``_ce_shape``, the row
+    seeds and the forward-only flag of the stand-alone form."""
+    for h in range(n_heads):
+        t.margin[h] = None if shape is None or shape[0][h] is None else shape[0][h].data_ptr()
+    t.focal_gamma = 0.0 if shape is None else shape[1]
+    t.gloss = None if gloss is None else gloss.data_ptr()
+    t.loss_only = int(loss_only)
 
 
 def _ce_task(t, logits, pads, starts, y, loss, gbuf, rows, coef):
@@ -2884,10 +2911,11 @@ def _ce_fused_plan(y, logits, from_col0):
     return gbuf, state, starts, [e - s0 for s0, e in zip(starts, ends)]
 
 
-def _ce_fused_launch(tasks, smoothing, bal, scales=None):
+def _ce_fused_launch(tasks, smoothing, bal, scales=None, shape=None):
     """ONE launch for the loss vectors AND the gradient operands of ``tasks`` = [(plan, logits, y, coef)]; ``bal``: None (the
     plain launch), or per task None / the (weights, offsets) of ``_class_balance``; ``scales``: None, or one task scale
-    (``_scale_arg``) per task -- the _s launches of include/egopack_task_scale.h.  Returns the loss vectors."""
+    (``_scale_arg``) per task -- the _s launches of include/egopack_task_scale.h; ``shape``: None, or per task None / the
+    (margins, gamma) of ``_ce_shape`` -- the tail of ``egk_ce_task``, in whichever of those launches.  Returns the loss vectors."""
     lib = _lib.load()
     arr = ((_lib.CETask if bal is None else _lib.CEWTask) * len(tasks))()
     losses = []
@@ -2898,6 +2926,8 @@ def _ce_fused_launch(tasks, smoothing, bal, scales=None):
             _ce_task(arr[i], logits, pads, starts, y, loss, gbuf, rows, coef)
         else:
             _ce_w_task(arr[i], logits, pads, starts, y, loss, gbuf, rows, coef, bal[i])
+        if shape is not None:
+            _ce_tail(arr[i] if bal is None else arr[i].base, shape[i], len(logits))
         losses.append(loss)
         state["filled"].update(starts)
         state["pads"] = True
@@ -2917,9 +2947,10 @@ def _ce_fused_launch(tasks, smoothing, bal, scales=None):
 
 class _CE(torch.autograd.Function):
     @staticmethod
-    def _fused(ctx, smoothing, y, logits, bal=None):
+    def _fused(ctx, smoothing, y, logits, bal=None, shape=None):
         """One launch for loss and gradient when the seed is known and every head's logits are blocks of ONE bank buffer
-        (``_ce_fused_plan``): the fused launch with one task.  ``bal``: the per-class vectors (``_class_balance``)."""
+        (``_ce_fused_plan``): the fused launch with one task.  ``bal``: the per-class vectors (``_class_balance``); ``shape``: the
+        margins and the focal exponent (``_ce_shape``)."""
         seed = _loss_seed["coef"]
         plan = None if seed is None else _ce_fused_plan(y, logits, from_col0=False)
         if plan is None:
@@ -2927,29 +2958,41 @@ class _CE(torch.autograd.Function):
         gbuf, starts = plan[0], plan[2]
         scale = _loss_seed["scale"]
         loss, = _ce_fused_launch([(plan, logits, y, seed)], smoothing, None if bal is None else [bal],
-                                 None if scale is None else [scale])
+                                 None if scale is None else [scale], None if shape is None else [shape])
         if starts[0] > 0:
             gbuf[:, :starts[0]].zero_()
         ctx.fused, ctx.shapes, ctx.seed = True, [tuple(l.shape) for l in logits], float(seed)
         return loss
 
     @staticmethod
-    def forward(ctx, smoothing, y, gdt, bal, *logits):
+    def forward(ctx, smoothing, y, gdt, bal, shape, *logits):
         # loss[n] = sum_h CE(logits[h][n], y[n, h]) with ignore_index -1 (y: [N] or [N, heads] int64)
         # bal: None, or (weights, offsets) with one packed f32 vector or None per head -- the launches of egopack_ce_balanced.h
+        # shape: None, or (margins, gamma) of ``_ce_shape`` -- the tail of egk_ce_task, in the fused launch or its stand-alone form
         _need_gpu(y, *logits)
         lib = _lib.load()
         rows = logits[0].shape[0]
         y = y.contiguous()
         ctx.fused = False
         ctx.bal = bal
-        fused = _CE._fused(ctx, smoothing, y, logits, bal)
+        ctx.shape = shape
+        fused = _CE._fused(ctx, smoothing, y, logits, bal, shape)
         if fused is not None:
             return fused
         loss = torch.empty(rows, dtype=torch.float32, device=logits[0].device)
         ystride = 1 if y.dim() == 1 else y.shape[1]
         saved = []
         ctx.dst = [getattr(l, "_egk_grad_dst", None) if _bank_handoff["on"] else None for l in logits]
+        if shape is not None:
+            # the stand-alone form of the shaped loss: the fused launch as a forward-only pass over all heads (loss_only); its
+            # backward is the same launch per head with the incoming gradient as row seeds (gloss).  No lse is kept.
+            if any(l.dtype != torch.float32 for l in logits):
+                raise TypeError("cross_entropy expects f32 logits")
+            ls = [_rm(l) for l in logits]
+            _CE._shaped_launch(ls, y, ystride, loss, None, None, bal, shape, smoothing, list(range(len(ls))))
+            ctx.smoothing, ctx.ystride, ctx.nh, ctx.gdt = smoothing, ystride, len(logits), gdt
+            ctx.save_for_backward(y, *ls)
+            return loss
         for h, l in enumerate(logits):
             if l.dtype != torch.float32:
                 raise TypeError("cross_entropy expects f32 logits")
@@ -2968,14 +3011,49 @@ class _CE(torch.autograd.Function):
         return loss
 
     @staticmethod
+    def _shaped_launch(ls, y, ystride, loss, gloss, out, bal, shape, smoothing, heads):
+        """The fused launch outside a step, on heads ``heads`` of row-major f32 logits ``ls`` (one task): ``gloss`` None -- forward
+        only, ``loss`` [rows] is written; else ``out`` ([rows, C] of one head, any row stride) takes the gradient under the row
+        seeds ``gloss`` and ``loss`` is scratch."""
+        if len(heads) > 4:
+            raise ValueError(f"cross_entropy: margin / gamma take at most 4 heads, got {len(heads)}")
+        lib = _lib.load()
+        arr = (_lib.CEWTask * 1)()
+        t, b = arr[0], arr[0].base
+        for k, h in enumerate(heads):
+            l = ls[h]
+            b.logits[k], b.ld[k], b.C[k], b.pad[k], b.dcol[k] = l.data_ptr(), l.stride(0), l.shape[1], l.shape[1], 0
+            t.weight[k] = None if bal is None or bal[0][h] is None else bal[0][h].data_ptr()
+            t.offset[k] = None if bal is None or bal[1][h] is None else bal[1][h].data_ptr()
+        b.n_heads, b.y_stride, b.loss, b.rows, b.gscale = len(heads), ystride, loss.data_ptr(), ls[0].shape[0], 1.0
+        b.y = y.data_ptr() + 8 * heads[0] if y.dim() == 2 else y.data_ptr()
+        b.dlogits, b.ldd = (None, 0) if out is None else (out.data_ptr(), out.stride(0))
+        _ce_tail(b, (tuple(shape[0][h] for h in heads), shape[1]), len(heads), gloss, loss_only=gloss is None)
+        _ck(lib.egk_ce_w_fused_multi(_stream(), arr, 1, float(smoothing), 0 if out is None else _dt(out)), "egk_ce_w_fused_multi")
+
+    @staticmethod
     def backward(ctx, gloss):
         lib = _lib.load()
         if ctx.fused:  # the gradient is already in the bank's operand buffer: placeholders for autograd
-            return (None, None, None, None, *[torch.empty(s_, dtype=torch.float32, device=gloss.device) for s_ in ctx.shapes])
+            return (None, None, None, None, None, *[torch.empty(s_, dtype=torch.float32, device=gloss.device) for s_ in ctx.shapes])
         y, *saved = ctx.saved_tensors
         gloss = _f32c(gloss)
         grads = []
         bal = ctx.bal
+        if ctx.shape is not None:
+            scratch = torch.empty(saved[0].shape[0], dtype=torch.float32, device=gloss.device)
+            for h, l in enumerate(saved):
+                rows, Cn = l.shape
+                d = torch.empty((rows, Cn), dtype=torch.float32, device=l.device)
+                dst = ctx.dst[h]
+                if dst is not None and dst[1] not in dst[2]["filled"]:
+                    gbuf, c0, state = dst
+                    _CE._shaped_launch(saved, y, ctx.ystride, scratch, gloss, gbuf[:, c0:c0 + Cn], bal, ctx.shape, ctx.smoothing, [h])
+                    state["filled"].add(c0)
+                else:
+                    _CE._shaped_launch(saved, y, ctx.ystride, scratch, gloss, d, bal, ctx.shape, ctx.smoothing, [h])
+                grads.append(d)
+            return (None, None, None, None, None, *grads)
 
         def bwd(h, l, yh, lse, out, ldd, Cn, dt):
             if bal is None:
@@ -2999,7 +3077,7 @@ class _CE(torch.autograd.Function):
             else:
                 bwd(h, l, yh, lse, d, d.stride(0), Cn, _dt(d))
             grads.append(d)
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, None, *grads)
 
 
 class _CEMulti(torch.autograd.Function):
@@ -3007,7 +3085,8 @@ class _CEMulti(torch.autograd.Function):
     as ONE launch, ``egk_ce_fused_multi``."""
 
     @staticmethod
-    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, scales, *tensors):
+    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, scales, shape, *tensors):
+        # shape: None, or one entry per task -- None or the (margins, gamma) of ``_ce_shape`` -- the tail of egk_ce_task
         # bal: None, or one entry per task -- None or the (weights, offsets) of ``_class_balance`` -- the launch with the vectors
         # scales: None, or one task scale per task -- the launch that multiplies each coef by its scale inside (egk_ce_*_fused_multi_s)
         tasks, shapes, k = [], [], 0
@@ -3017,14 +3096,14 @@ class _CEMulti(torch.autograd.Function):
             k += 1 + heads_per_task[i]
             tasks.append((plans[i], logits, y, coef))
             shapes.append([tuple(l.shape) for l in logits])
-        losses = _ce_fused_launch(tasks, smoothing, bal, scales)
+        losses = _ce_fused_launch(tasks, smoothing, bal, scales, shape)
         ctx.shapes, ctx.heads, ctx.fused = shapes, heads_per_task, True
         ctx.set_materialize_grads(False)
         return tuple(losses)
 
     @staticmethod
     def backward(ctx, *glosses):
-        out = [None, None, None, None, None, None]
+        out = [None, None, None, None, None, None, None]
         dev = next(g.device for g in glosses if g is not None)
         for shp in ctx.shapes:  # placeholders: the gradients are already in the banks' operand buffers
             out.append(None)  # y
@@ -3032,30 +3111,34 @@ class _CEMulti(torch.autograd.Function):
         return tuple(out)
 
 
-def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None, scales=None):
+def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None, scales=None, margins=None, gammas=None):
     """[loss_t] of ``cross_entropy(logits_t, y_t, smoothing)`` for several tasks whose backward seeds ``coefs`` are known, in ONE
     launch that also writes every task's gradient operand -- or None when some task does not qualify for the fused form
     (the caller then takes them one by one).  ``tasks``: [(logits tuple, y [N, heads] int64)].
     ``weights`` / ``offsets``: None, or one entry per task, each what ``cross_entropy`` takes as ``weight`` / ``offset``; with
     every vector None the launch is the one without the arguments.
     ``scales``: None, or one one-element f32 device tensor per task: task i's seed is fl32(coefs[i] * scales[i][0]), formed inside
-    the launch (include/egopack_task_scale.h).  None: exactly the launch without the argument."""
+    the launch (include/egopack_task_scale.h).  None: exactly the launch without the argument.
+    ``margins`` / ``gammas``: None, or one entry per task, each what ``cross_entropy`` takes as ``margin`` / ``gamma`` (the tail of
+    ``egk_ce_task``, include/egopack_hip.h); with every margin None and every gamma 0 the launch is the one without them."""
     if scales is not None:
         if any(sc is None for sc in scales):
             raise ValueError("cross_entropy_multi: scales has a None entry (every task needs its scale, or pass scales=None)")
         scales = [_scale_arg(sc, f"cross_entropy_multi (task {i})") for i, sc in enumerate(scales)]
-    for name, arg in (("weights", weights), ("offsets", offsets), ("scales", scales)):
+    for name, arg in (("weights", weights), ("offsets", offsets), ("scales", scales), ("margins", margins), ("gammas", gammas)):
         if arg is not None and len(arg) != len(tasks):
             raise ValueError(f"cross_entropy_multi: {name} has {len(arg)} entries for {len(tasks)} tasks")
     if not (2 <= len(tasks) <= 4) or not torch.is_grad_enabled():
         return None
-    plans, flat, heads, bal = [], [], [], []
+    plans, flat, heads, bal, shape = [], [], [], [], []
     dt = None
     for i, (logits, y) in enumerate(tasks):
         if torch.is_tensor(logits):
             logits = (logits,)
         bal.append(_class_balance(weights[i] if weights is not None else None, offsets[i] if offsets is not None else None,
                                   logits, f"cross_entropy_multi (task {i})"))
+        shape.append(_ce_shape(margins[i] if margins is not None else None, gammas[i] if gammas is not None else 0.0,
+                               logits, f"cross_entropy_multi (task {i})"))
         y = y.contiguous()
         plan = _ce_fused_plan(y, logits, from_col0=True)
         if plan is None or (dt is not None and plan[0].dtype != dt):
@@ -3066,19 +3149,27 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
         flat += [y, *logits]
     if all(b is None for b in bal):
         bal = None
-    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, scales, *flat))
+    if all(sh is None for sh in shape):
+        shape = None
+    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, scales, shape, *flat))
 
 
-def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None):
+def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None, margin=None, gamma=0.0):
     """Per-row CrossEntropy(reduction='none', ignore_index=-1), summed over heads when ``logits`` is
     a tuple and y is [N, heads].  Logits are f32; their gradient is emitted in the element type the
     producing contraction wants (bf16 in 'bf16' mode).
     ``weight`` / ``offset``: per-class f32 vectors of length C on the logits' device -- None, one tensor (a single head), or a
     tuple with one tensor or None per head: F.cross_entropy(x + offset, y, weight=weight, ...) per head, computed inside the
-    row pass (include/egopack_ce_balanced.h).  Constants: no gradient reaches them.  All None: the plain launches."""
+    row pass (include/egopack_ce_balanced.h).  Constants: no gradient reaches them.  All None: the plain launches.
+    ``margin`` (the forms of ``weight``) / ``gamma`` (one float >= 0): the label-distribution-aware margin, subtracted from the
+    target's logit only, and the focal exponent -- loss = (1 - q)^gamma * CE(z), z = x + offset - onehot(y) * margin, q =
+    softmax(z)[y] (the tail of ``egk_ce_task``, include/egopack_hip.h; at most 4 heads).  Under an announced seed on bank logits the
+    step's one fused launch carries them; elsewhere the same launch runs forward-only and, in backward, with the incoming gradient
+    as row seeds.  Constants.  All None / 0: exactly the launches without the arguments."""
     if torch.is_tensor(logits):
         logits = (logits,)
-    return _CE.apply(float(smoothing), y, _state["act"], _class_balance(weight, offset, logits), *logits)
+    return _CE.apply(float(smoothing), y, _state["act"], _class_balance(weight, offset, logits),
+                     _ce_shape(margin, gamma, logits), *logits)
 
 
 def bce_shape(pos, neg, gamma, where="bce_with_logits"):

@@ -3,6 +3,7 @@ and loader construction, checkpoints with the reference's key layout, schedulers
 from __future__ import annotations
 
 import logging
+import math
 import sys
 from pathlib import Path
 from typing import Dict, Optional
@@ -138,11 +139,15 @@ def start_loader_workers(loaders) -> None:
             dl.start_workers()
 
 
-def build_criteria(dsets, class_balance=None, pnr_balance=None):
+def build_criteria(dsets, class_balance=None, pnr_balance=None, ce_shape=None):
     """``class_balance``: what ``build_class_balance`` returns -- the AR / LTA wrappers then carry its per-class vectors.
-    ``pnr_balance``: what ``build_pnr_balance`` returns -- the PNR criterion then carries its pos / neg / gamma."""
-    cb = class_balance or {}
+    ``pnr_balance``: what ``build_pnr_balance`` returns -- the PNR criterion then carries its pos / neg / gamma.
+    ``ce_shape``: what ``build_ce_shape`` returns -- the AR / LTA wrappers then carry its margins and focal exponent."""
+    cb, sh = class_balance or {}, ce_shape or {}
     kw = {t: dict(class_weights=cb[t]["weights"], class_offsets=cb[t]["offsets"]) if t in cb else {} for t in ("ar", "lta")}
+    for t in ("ar", "lta"):
+        if t in sh:
+            kw[t].update(class_margins=sh[t]["margins"], focal_gamma=sh[t]["gamma"])
     pb = {k: pnr_balance[k] for k in ("pos", "neg", "gamma")} if pnr_balance else {}
     return {"ar": MetricSelectorWrapper(CrossEntropyNone(), dsets["ar"], **kw["ar"]),
             "lta": MetricSelectorWrapper(CrossEntropyNone(), dsets["lta"], **kw["lta"]),
@@ -302,6 +307,106 @@ def check_class_balance(logger, ckpt: dict, cfg, class_balance) -> bool:
                        "the run continues with the ones built now", class_balance_config(cfg),
                        None if stored is None else stored.get("config"))
     return same
+
+
+# ---- shaped cross entropy of the AR / LTA heads (``ce_shape:`` of the config): LDAM margin, focal term, deferred re-weighting -------
+# The terms ride in the tail of the fused launch's task argument (egk_ce_task, include/egopack_hip.h) next to the vectors of
+# ``class_balance``.  Training loss only, like them.
+CE_SHAPE_MARGINS = ("none", "ldam")
+CE_SHAPE_DEFAULTS = {"margin": "none", "max_margin": 0.5, "power": 0.25, "gamma": 0.0, "tasks": ["ar", "lta"], "reweight_after": 0}
+
+
+def ce_shape_config(cfg) -> dict:
+    """The ``ce_shape:`` block with its defaults filled in; an unknown key, margin mode or task is a ValueError naming it."""
+    raw = cfg.get("ce_shape") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(CE_SHAPE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"ce_shape: unknown key(s) {sorted(unknown)} ({', '.join(CE_SHAPE_DEFAULTS)})")
+    sh = {**CE_SHAPE_DEFAULTS, **raw}
+    sh["margin"] = str(sh["margin"]).lower()
+    if sh["margin"] not in CE_SHAPE_MARGINS:
+        raise ValueError(f"ce_shape.margin: unknown mode '{sh['margin']}' ({' | '.join(CE_SHAPE_MARGINS)})")
+    sh["tasks"] = [str(t) for t in (sh["tasks"] or [])]
+    unknown = set(sh["tasks"]) - set(CLASS_BALANCE_TASKS)
+    if unknown:
+        raise ValueError(f"ce_shape.tasks: unknown task(s) {sorted(unknown)} ({', '.join(CLASS_BALANCE_TASKS)})")
+    sh["max_margin"], sh["power"], sh["gamma"] = float(sh["max_margin"]), float(sh["power"]), float(sh["gamma"])
+    for k in ("max_margin", "power", "gamma"):
+        if not (math.isfinite(sh[k]) and sh[k] >= 0.0):
+            raise ValueError(f"ce_shape.{k}: {sh[k]} is not a finite value >= 0")
+    if isinstance(sh["reweight_after"], bool) or int(sh["reweight_after"]) != sh["reweight_after"] or int(sh["reweight_after"]) < 0:
+        raise ValueError(f"ce_shape.reweight_after: {sh['reweight_after']} is not an epoch number >= 0")
+    sh["reweight_after"] = int(sh["reweight_after"])
+    return sh
+
+
+def ldam_margins(counts, max_margin: float = 0.5, power: float = 0.25) -> torch.Tensor:
+    """Label-distribution-aware margins (Cao et al. 2019) from label counts, float64: m_c = max_margin * n'_c^-power /
+    max_c(n'_c^-power), n' = max(n, 1) -- the class with the fewest labels (a class without one counts as one) gets max_margin."""
+    n1 = torch.as_tensor(counts).to(torch.float64).clamp(min=1.0)
+    r = torch.pow(n1, -power)
+    return max_margin * (r / r.max())
+
+
+def build_ce_shape(cfg, dsets_train, device=None, tasks=None, class_balance=None) -> dict:
+    """{task: {"margins": [f32 vector per head] | None, "gamma": float, "counts": [...] | None}} for the tasks of
+    ``ce_shape.tasks`` -- {} when the block asks for nothing (no margin, gamma 0: nothing is counted, the criteria and the launches
+    are the ones without the feature).  The labels of the WHOLE training split are counted as ``class_balance`` counts them
+    (``label_counts``; its counts are reused when it has them).  ``reweight_after`` > 0 needs ``class_balance.mode=weight``."""
+    sh = ce_shape_config(cfg)
+    if sh["reweight_after"] > 0 and class_balance_config(cfg)["mode"] != "weight":
+        raise ValueError("ce_shape.reweight_after defers the class weights: it needs class_balance.mode=weight")
+    if sh["margin"] == "none" and sh["gamma"] == 0.0:
+        return {}
+    out = {}
+    for t in CLASS_BALANCE_TASKS:
+        if t not in sh["tasks"] or t not in dsets_train or (tasks is not None and t not in tasks):
+            continue
+        margins = counts = None
+        if sh["margin"] == "ldam":
+            counts = class_balance[t]["counts"] if class_balance and t in class_balance else label_counts(dsets_train[t])
+            margins = [ldam_margins(c, sh["max_margin"], sh["power"]).to(torch.float32) for c in counts]
+            margins = margins if device is None else [m.to(device) for m in margins]
+        out[t] = {"margins": margins, "gamma": sh["gamma"], "counts": counts}
+    return out
+
+
+def log_ce_shape(logger, cfg, ce_shape) -> None:
+    """The mode, once: one line per task (margin range per head, focal exponent, the epoch the class weights start at)."""
+    sh = ce_shape_config(cfg)
+    if sh["reweight_after"] > 0:
+        logger.info("ce shape: deferred re-weighting -- the class weights are all ones before epoch %d", sh["reweight_after"])
+    for t, e in (ce_shape or {}).items():
+        rng = "none" if e["margins"] is None else ", ".join(f"head {h} in [{float(m.min()):.6g}, {float(m.max()):.6g}]"
+                                                              for h, m in enumerate(e["margins"]))
+        logger.info("ce shape %s: margin %s (%s), focal gamma %.6g", t, sh["margin"], rng, e["gamma"])
+
+
+def reweight_side(cfg, epoch: int) -> str:
+    """Deferred re-weighting: which class weights epoch ``epoch`` (1-based, as the epoch loops and the checkpoints count) trains
+    with -- "ones" before ``ce_shape.reweight_after``, "weights" from it on (and always with ``reweight_after: 0``)."""
+    return "ones" if int(epoch) < ce_shape_config(cfg)["reweight_after"] else "weights"
+
+
+def apply_reweight(logger, cfg, class_balance, holders, epoch: int) -> Optional[str]:
+    """At an epoch boundary: rewrite the class-weight buffers of ``holders`` (task -> the wrapper or task module that carries
+    ``class_weight_<h>``) IN PLACE to the side of ``reweight_side`` -- the pointers a captured step holds stand, no new capture.
+    The vectors of ``class_balance`` themselves (what a checkpoint stores) stay the full weights.  None with the feature off."""
+    if ce_shape_config(cfg)["reweight_after"] <= 0 or not class_balance:
+        return None
+    side = reweight_side(cfg, epoch)
+    for t, e in class_balance.items():
+        if e.get("weights") is None or t not in holders:
+            continue
+        for h, w in enumerate(e["weights"]):
+            buf = getattr(holders[t], f"class_weight_{h}", None)
+            if buf is not None:
+                with torch.no_grad():
+                    buf.copy_(torch.ones_like(w) if side == "ones" else w)
+    if epoch == ce_shape_config(cfg)["reweight_after"]:  # (the switch, once; ``log_ce_shape`` announced it at start-up)
+        logger.info("ce shape: from epoch %d on the class weights apply", epoch)
+    return side
 
 
 # ---- positive-class weighting / focal loss of the PNR head (``pnr_balance:`` of the config) ---------------------------------------

@@ -592,7 +592,28 @@ int egk_ce_fused(egk_stream_t s, const float* const* logits, const int64_t* ld, 
                  int32_t rows, float smoothing, float gscale, int32_t dtype);
 /* The same for up to 4 TASKS in one launch (the AR and LTA heads of a multi-task step, main_temporal.py:93-126: one cross
  * entropy per task over its own logits, labels, loss vector and gradient operand).  Per task the arithmetic of
- * egk_ce_fused: bit-identical results. */
+ * egk_ce_fused: bit-identical results.
+ *
+ * The fields behind ``gscale`` SHAPE the loss of the task (the long-tail remedies next to the vectors of egopack_ce_balanced.h;
+ * every launch that takes this struct honours them: egk_ce_fused_multi, egk_ce_w_fused_multi and their _s forms).  For a live
+ * row (label t in [0, C)) of head h with logits x, weights w and offsets a (egk_ce_w_task; 1 and 0 elsewhere), smoothing eps,
+ * m = margin[h] (NULL: 0), gamma = focal_gamma and the row's seed g:
+ *     z_c  = x_c + a_c - [c == t] * m_t                     (LDAM, Cao et al. 2019: the margin touches the target's logit only)
+ *     p    = softmax(z),  q = p_t
+ *     S    = F.cross_entropy(z, t, weight=w, label_smoothing=eps, reduction='none')   (the arithmetic of egopack_ce_balanced.h on z)
+ *     loss = (1 - q)^gamma * S                              (focal term, Lin et al. 2017)
+ *     dz_j = g * [ (1 - q)^gamma * dS_j  +  S * gamma * q * (1 - q)^(gamma - 1) * (p_j - [j == t]) ]
+ * 1 - q is formed as -expm1f(-(lse - z_t)); with q == 1 and gamma > 0 both terms are 0; gamma == 0 drops the second term and
+ * the factor.  Ignored rows give loss 0 and gradient 0, pad columns are zero-filled.  Margins and gamma are constants.
+ *     margin[h]    device, [C[h]] f32, 4-byte aligned, or NULL; must be NULL for h >= n_heads
+ *     gloss        device, [rows] f32, 4-byte aligned, or NULL: row n's seed is fl32(gscale' * gloss[n]) instead of gscale'
+ *                  (gscale' = gscale, times the task scale in the _s forms) -- a backward pass for a caller whose seed is a vector
+ *     focal_gamma  finite and >= 0; 0 = off
+ *     loss_only    1: a forward-only pass -- ``loss`` is written, no gradient is, ``dlogits`` may be NULL (with 0 a NULL dlogits
+ *                  is refused); gloss must then be NULL
+ * ALL OF THEM ZERO is the launch without them: the same kernel instantiation, the same bits.  Refused before any launch, each
+ * with its own message: a misaligned margin or gloss pointer, gamma negative or not finite, loss_only outside {0, 1}, loss_only
+ * with gloss, a margin behind the task's heads. */
 typedef struct {
     const float* logits[4];
     int64_t ld[4];
@@ -607,6 +628,11 @@ typedef struct {
     int64_t ldd;
     int32_t rows;
     float gscale;
+    const float* margin[4];
+    const float* gloss;
+    float focal_gamma;
+    int32_t loss_only;
+    int64_t reserved; /* explicit tail padding: sizeof is a multiple of 8 on every ABI; must be 0 */
 } egk_ce_task;
 int egk_ce_fused_multi(egk_stream_t s, const egk_ce_task* tasks, int32_t count, float smoothing, int32_t dtype);
 /* nn.BCEWithLogitsLoss(reduction='none') on y.float()  main_temporal.py:123,298; pnr.py:82-83 */

@@ -130,6 +130,11 @@ def main(argv=None):
     T.log_class_balance(logger, cfg, balance)
     for t, e in balance.items():
         tasks[t].set_class_balance(e["weights"], e["offsets"])
+    # ce_shape: the enabled AR / LTA task trains with LDAM margins / the focal exponent; reweight_after defers its class weights
+    shape = T.build_ce_shape(cfg, dsets_train, device=device, tasks=[t for t, w in weights.items() if w > 0], class_balance=balance)
+    T.log_ce_shape(logger, cfg, shape)
+    for t, e in shape.items():
+        tasks[t].set_ce_shape(e["margins"], e["gamma"])
     # pnr_balance: an enabled PNR task trains with pos / neg / gamma inside its BCE (its ``compute_loss`` while training)
     pnr_balance = T.build_pnr_balance(cfg, dsets_train, tasks=[t for t, w in weights.items() if w > 0])
     T.log_pnr_balance(logger, cfg, pnr_balance)
@@ -176,6 +181,7 @@ def main(argv=None):
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=validated)
     report, reports = (lambda t: T.class_report_meter_args(cfg, train_counts, t)), {}
     for epoch in range(1, cfg.num_epochs + 1):
+        T.apply_reweight(logger, cfg, balance, tasks, epoch)  # (in place: a captured step keeps its pointers)
         train(epoch, step, dl_train, weights, device, store=store)
         scheduler.step()
         T.log_validation_weights(logger, cfg, optimizer, epoch)

@@ -179,10 +179,13 @@ def main(argv=None):
     # class_balance: per-class weights / logit offsets of the AR and LTA heads from the label counts of the whole training split
     balance = T.build_class_balance(cfg, dsets_train, device=device)
     T.log_class_balance(logger, cfg, balance)
+    # ce_shape: LDAM margins from the same counts, the focal exponent, deferred re-weighting of the class weights
+    shape = T.build_ce_shape(cfg, dsets_train, device=device, class_balance=balance)
+    T.log_ce_shape(logger, cfg, shape)
     # pnr_balance: pos / neg / gamma of the PNR head's BCE from the positive and negative node counts of the whole training split
     pnr_balance = T.build_pnr_balance(cfg, dsets_train, tasks=[t for t, w in weights.items() if w > 0])
     T.log_pnr_balance(logger, cfg, pnr_balance)
-    step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train, balance, pnr_balance), weights, optimizer,
+    step = engine.MTLStep(model, tasks, T.build_criteria(dsets_train, balance, pnr_balance, shape), weights, optimizer,
                           fused_backbone=cfg.fused_backbone, sync=sync, task_weighting=tw_mode, log_var=log_var)
     step.use_graph = bool(cfg.get("use_graph", True))
     step.exact_graph_ln = bool(cfg.get("exact_graph_ln", False))  # several ranks: graph-LN statistics over the GLOBAL batch
@@ -203,6 +206,9 @@ def main(argv=None):
     report, reports = (lambda t: T.class_report_meter_args(cfg, train_counts, t)), {}
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
+        # (ce_shape.reweight_after: the class-weight buffers are rewritten in place -- a captured step keeps its pointers; after a
+        #  resume the side follows the checkpoint's epoch)
+        T.apply_reweight(logger, cfg, balance, step.criteria, epoch)
         train(epoch, step, dl_train, weights, device, store=store)
         scheduler.step()
         logger.info("learning rate -> %.6g", scheduler.get_last_lr()[0])
