@@ -1039,6 +1039,8 @@ static inline int nv_for(int cols) { return cols <= 256 ? 1 : cols <= 1024 ? 4 :
 constexpr int CAP_PARTIAL = 512, CAP_WIDE = 768;
 extern int g_graph_rows_v2;  // (graph_ops.hip)
 extern int g_optim_grid_cap;  // (optim_rules.hip)
+extern int g_optim_stream_policy;
+bool optim_stream_policy_ok(int mask);
 static inline int row_grid(int rows) {  // kernels that emit per-workgroup partial rows: two workgroups per CU
     int g = cdiv(rows, WPB);
     return g < 1 ? 1 : (g > CAP_PARTIAL ? CAP_PARTIAL : g);
@@ -1208,11 +1210,13 @@ static inline bool wide_rows_ok(int cols, const void* in, const void* out, const
 extern "C" {
 
 // the tests' references: 3 = the rows1024.h graph-row kernels on / off, 6 = the workgroup cap of the optimizer launches (1 .. 32768;
-// anything else leaves it), 7 = the workgroup-per-row LayerNorm kernels on / off; any other key changes nothing and returns -1
+// anything else leaves it), 7 = the workgroup-per-row LayerNorm kernels on / off, 9 = the cache policy of the optimizer launches'
+// streams (an instantiated NT_* mask, optim_rules.hip; anything else leaves it); any other key changes nothing and returns -1
 int egk_tune(int32_t key, int32_t value) {
     if (key == 3) { const int p = g_graph_rows_v2; g_graph_rows_v2 = value; return p; }  // graph_ops.hip: the rows1024.h kernels
     if (key == 6) { const int p = g_optim_grid_cap; if (value >= 1 && value <= 32768) g_optim_grid_cap = value; return p; }  // optim_rules.hip: optim_grid
     if (key == 7) { const int p = g_wide_rows; g_wide_rows = value; return p; }  // the workgroup-per-row LayerNorm kernels on / off
+    if (key == 9) { const int p = g_optim_stream_policy; if (optim_stream_policy_ok(value)) g_optim_stream_policy = value; return p; }  // optim_rules.hip: NT_*
     return -1;
 }
 

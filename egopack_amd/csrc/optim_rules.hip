@@ -88,33 +88,78 @@ __device__ __forceinline__ bf16_t round_state(float x, unsigned r16, bool stocha
     return (bf16_t)((b + r16) >> 16);  // (no carry into the sign: the exponent is not all ones)
 }
 
-__device__ __forceinline__ float4 ld_state4(const float* __restrict__ s) { return *reinterpret_cast<const float4*>(s); }
-__device__ __forceinline__ float4 ld_state4(const bf16_t* __restrict__ s) { return ld4t(s, 0, 4, true); }
+// ---- cache policy of the single-use streams (egk_tune 9) ---------------------------------------------------------------------------
+// A launch reads g, p and the state and writes p and the state once per step; nothing reads those lines again before the next
+// step's launch, while the bf16 copies it writes are the next step's contraction operands.  A mask, the kernels' template argument NT,
+// marks accesses as non-temporal, per stream; the copies always keep the default policy.  The policy changes no arithmetic.
+enum { NT_G = 1, NT_LOAD = 2, NT_STORE = 4, NT_EMA = 8 };  // loads of g | loads of p and the state | their stores | the average, both ways
+typedef float nt_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned nt_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 ld_quad(const float* __restrict__ p, bool nt) {
+    if (nt) {
+        const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    }
+    return *reinterpret_cast<const float4*>(p);
+}
+__device__ __forceinline__ float4 ld_quad(const bf16_t* __restrict__ p, bool nt) {
+    if (nt) {
+        const nt_u2 r = __builtin_nontemporal_load(reinterpret_cast<const nt_u2*>(p));
+        return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
+                           __uint_as_float(r.y & 0xffff0000u));
+    }
+    return ld4t(p, 0, 4, true);
+}
+__device__ __forceinline__ void st_quad(float* __restrict__ p, const float4& v, bool nt) {
+    if (nt) {
+        const nt_f4 w = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(w, reinterpret_cast<nt_f4*>(p));
+        return;
+    }
+    *reinterpret_cast<float4*>(p) = v;
+}
+template <typename T> __device__ __forceinline__ T ld_one(const T* p, bool nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
+template <typename T> __device__ __forceinline__ void st_one(T* p, T v, bool nt) {
+    if (nt) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+__device__ __forceinline__ float ld_one_f(const float* p, bool nt) { return ld_one(p, nt); }
+__device__ __forceinline__ float ld_one_f(const bf16_t* p, bool nt) { return bf2f(ld_one(p, nt)); }
+
+__device__ __forceinline__ float4 ld_state4(const float* __restrict__ s, bool nt) { return ld_quad(s, nt); }
+__device__ __forceinline__ float4 ld_state4(const bf16_t* __restrict__ s, bool nt) { return ld_quad(s, nt); }
 // ``high``: this buffer draws the high halves of the words (state0), otherwise the low halves (state1)
-__device__ __forceinline__ void st_state4(float* __restrict__ s, const float4& v, const uint4&, bool, bool) { *reinterpret_cast<float4*>(s) = v; }
-__device__ __forceinline__ void st_state4(bf16_t* __restrict__ s, const float4& v, const uint4& w, bool high, bool stochastic) {
+__device__ __forceinline__ void st_state4(float* __restrict__ s, const float4& v, const uint4&, bool, bool, bool nt) { st_quad(s, v, nt); }
+__device__ __forceinline__ void st_state4(bf16_t* __restrict__ s, const float4& v, const uint4& w, bool high, bool stochastic, bool nt) {
     const unsigned sh = high ? 16u : 0u;
     uint2 pk;
     pk.x = (unsigned)round_state(v.x, (w.x >> sh) & 0xffffu, stochastic) | ((unsigned)round_state(v.y, (w.y >> sh) & 0xffffu, stochastic) << 16);
     pk.y = (unsigned)round_state(v.z, (w.z >> sh) & 0xffffu, stochastic) | ((unsigned)round_state(v.w, (w.w >> sh) & 0xffffu, stochastic) << 16);
+    if (nt) {
+        const nt_u2 q = {pk.x, pk.y};
+        __builtin_nontemporal_store(q, reinterpret_cast<nt_u2*>(s));
+        return;
+    }
     *reinterpret_cast<uint2*>(s) = pk;
 }
 
 // the four elements [i, i + 4) of a span in 16-byte accesses (8-byte on a bf16 state); ``consts()`` is asked for the constants, and
 // the Philox call of a stochastic store issued, once the loads are on their way.
 // EMA: ``ema`` follows the new p with weight ``w`` before p is stored (read with the other loads, one 16-byte store).
-template <int KIND, typename GT, typename ST, bool EMA = false, typename CF>
+// NT: the launch's cache policy, an NT_* mask (0: the default policy on every stream, the accesses the family has always issued).
+template <int KIND, typename GT, typename ST, bool EMA = false, int NT = 0, typename CF>
 __device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __restrict__ g, ST* __restrict__ s0, ST* __restrict__ s1,
                                            long long i, CF consts, const StateRound& sr, bf16_t* __restrict__ shadow,
                                            bf16_t* __restrict__ shadow_lo, float* __restrict__ ema = nullptr, float w = 0.f) {
     constexpr int NS = StateCount<KIND>::value;
     constexpr bool NARROW = !__is_same(ST, float);
-    float4 pv = *reinterpret_cast<float4*>(p + i);
-    const float4 gv = ld4t(g + i, 0, 4, true);
+    constexpr bool nt_ld = NT & NT_LOAD, nt_st = NT & NT_STORE, nt_ema = NT & NT_EMA;
+    float4 pv = ld_quad(p + i, nt_ld);
+    const float4 gv = ld_quad(g + i, NT & NT_G);
     float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, ev = av;
-    if constexpr (NS >= 1) av = ld_state4(s0 + i);
-    if constexpr (NS >= 2) bv = ld_state4(s1 + i);
-    if constexpr (EMA) ev = *reinterpret_cast<float4*>(ema + i);
+    if constexpr (NS >= 1) av = ld_state4(s0 + i, nt_ld);
+    if constexpr (NS >= 2) bv = ld_state4(s1 + i, nt_ld);
+    if constexpr (EMA) ev = ld_quad(ema + i, nt_ema);
     const OptimConsts c = consts();
     uint4 rw = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (NARROW && NS >= 1)
@@ -126,11 +171,11 @@ __device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __re
         float* ep = &ev.x;
 #pragma unroll
         for (int t = 0; t < 4; ++t) ema_update(ep[t], pp[t], w);
-        *reinterpret_cast<float4*>(ema + i) = ev;
+        st_quad(ema + i, ev, nt_ema);
     }
-    *reinterpret_cast<float4*>(p + i) = pv;
-    if constexpr (NS >= 1) st_state4(s0 + i, av, rw, true, sr.stochastic != 0);
-    if constexpr (NS >= 2) st_state4(s1 + i, bv, rw, false, sr.stochastic != 0);
+    st_quad(p + i, pv, nt_st);
+    if constexpr (NS >= 1) st_state4(s0 + i, av, rw, true, sr.stochastic != 0, nt_st);
+    if constexpr (NS >= 2) st_state4(s1 + i, bv, rw, false, sr.stochastic != 0, nt_st);
     if (shadow) st4t(shadow + i, 0, 4, true, pv);
     if (shadow_lo) {  // bf16(p - bf16(p)): egk_split_bf16's bits
         const float lo4[4] = {pp[0] - bf2f(f2bf(pp[0])), pp[1] - bf2f(f2bf(pp[1])), pp[2] - bf2f(f2bf(pp[2])), pp[3] - bf2f(f2bf(pp[3]))};
@@ -139,13 +184,14 @@ __device__ __forceinline__ void optim_quad(float* __restrict__ p, const GT* __re
 }
 
 // the scalar tail [i, n) of a span (n - i < 4)
-template <int KIND, typename GT, typename ST, bool EMA = false>
+template <int KIND, typename GT, typename ST, bool EMA = false, int NT = 0>
 __device__ __forceinline__ void optim_tail(float* __restrict__ p, const GT* __restrict__ g, ST* __restrict__ s0, ST* __restrict__ s1,
                                            long long i, long long n, const OptimConsts& c, const StateRound& sr,
-                                           bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo, float* __restrict__ ema = nullptr,
-                                           float w = 0.f) {
+                                           bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo,
+                                           float* __restrict__ ema = nullptr, float w = 0.f) {
     constexpr int NS = StateCount<KIND>::value;
     constexpr bool NARROW = !__is_same(ST, float);
+    constexpr bool nt_ld = NT & NT_LOAD, nt_st = NT & NT_STORE, nt_ema = NT & NT_EMA;
     uint4 q = make_uint4(0u, 0u, 0u, 0u);  // (the tail's group starts at i, a multiple of 4: one call, word j - i for element j)
     if constexpr (NARROW && NS >= 1)
         if (sr.stochastic) q = state_words(sr, i);
@@ -153,23 +199,25 @@ __device__ __forceinline__ void optim_tail(float* __restrict__ p, const GT* __re
         const unsigned rw = j == i ? q.x : j == i + 1 ? q.y : q.z;
         (void)rw;
         float a = 0.f, b = 0.f;
-        if constexpr (NS >= 1) a = ld1t(s0 + j);
-        if constexpr (NS >= 2) b = ld1t(s1 + j);
-        optim_update<KIND>(p[j], ld1t(g + j), a, b, c);
+        if constexpr (NS >= 1) a = ld_one_f(s0 + j, nt_ld);
+        if constexpr (NS >= 2) b = ld_one_f(s1 + j, nt_ld);
+        float pj = ld_one(p + j, nt_ld);
+        optim_update<KIND>(pj, ld_one_f(g + j, NT & NT_G), a, b, c);
         if constexpr (EMA) {
-            float e = ema[j];
-            ema_update(e, p[j], w);
-            ema[j] = e;
+            float e = ld_one(ema + j, nt_ema);
+            ema_update(e, pj, w);
+            st_one(ema + j, e, nt_ema);
         }
+        st_one(p + j, pj, nt_st);
         if constexpr (NARROW) {
-            if constexpr (NS >= 1) s0[j] = round_state(a, rw >> 16, sr.stochastic != 0);
-            if constexpr (NS >= 2) s1[j] = round_state(b, rw & 0xffffu, sr.stochastic != 0);
+            if constexpr (NS >= 1) st_one(s0 + j, round_state(a, rw >> 16, sr.stochastic != 0), nt_st);
+            if constexpr (NS >= 2) st_one(s1 + j, round_state(b, rw & 0xffffu, sr.stochastic != 0), nt_st);
         } else {
-            if constexpr (NS >= 1) s0[j] = a;
-            if constexpr (NS >= 2) s1[j] = b;
+            if constexpr (NS >= 1) st_one(s0 + j, a, nt_st);
+            if constexpr (NS >= 2) st_one(s1 + j, b, nt_st);
         }
-        if (shadow) shadow[j] = f2bf(p[j]);
-        if (shadow_lo) shadow_lo[j] = f2bf(p[j] - bf2f(f2bf(p[j])));
+        if (shadow) shadow[j] = f2bf(pj);
+        if (shadow_lo) shadow_lo[j] = f2bf(pj - bf2f(f2bf(pj)));
     }
 }
 
@@ -279,7 +327,7 @@ struct OptimArgs {  // what a launch of the family is handed; ``t`` without a ta
 // The buffers the launch writes arrive as __restrict__ PARAMETERS (optim_body unpacks them): a qualifier on a struct member tells
 // the compiler nothing, and without it every store may change hyper, the gate and the segment table, whose workgroup-uniform loads
 // then leave the scalar unit (the grouped kernel: 20 vector loads instead of 14).
-template <int KIND, typename GT, typename ST, bool GROUPED, bool EMA>
+template <int KIND, typename GT, typename ST, bool GROUPED, bool EMA, int NT>
 __device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __restrict__ g, ST* __restrict__ s0, ST* __restrict__ s1,
                                            bf16_t* __restrict__ shadow, bf16_t* __restrict__ shadow_lo, float* __restrict__ ema,
                                            long long* __restrict__ bump_word, const OptimArgs& a) {
@@ -304,36 +352,36 @@ __device__ __forceinline__ void optim_walk(float* __restrict__ p, const GT* __re
             else return launch;
         };
         if (i + 4 <= a.n)
-            optim_quad<KIND, GT, ST, EMA>(p, g, s0, s1, i, consts, sr, shadow, shadow_lo, ema, w);
+            optim_quad<KIND, GT, ST, EMA, NT>(p, g, s0, s1, i, consts, sr, shadow, shadow_lo, ema, w);
         else
-            optim_tail<KIND, GT, ST, EMA>(p, g, s0, s1, i, a.n, consts(), sr, shadow, shadow_lo, ema, w);
+            optim_tail<KIND, GT, ST, EMA, NT>(p, g, s0, s1, i, a.n, consts(), sr, shadow, shadow_lo, ema, w);
     }
 }
 
-template <int KIND, typename GT, typename ST, bool GROUPED, bool EMA>
+template <int KIND, typename GT, typename ST, bool GROUPED, bool EMA, int NT>
 __device__ __forceinline__ void optim_body(const OptimArgs& a) {
-    optim_walk<KIND, GT, ST, GROUPED, EMA>(a.p, static_cast<const GT*>(a.g), static_cast<ST*>(a.s0), static_cast<ST*>(a.s1), a.shadow,
-                                           a.shadow_lo, a.e.ema, a.bump_word, a);
+    optim_walk<KIND, GT, ST, GROUPED, EMA, NT>(a.p, static_cast<const GT*>(a.g), static_cast<ST*>(a.s0), static_cast<ST*>(a.s1), a.shadow,
+                                               a.shadow_lo, a.e.ema, a.bump_word, a);
 }
 
-template <int KIND, typename GT, bool GROUPED, bool EMA>
+template <int KIND, typename GT, bool GROUPED, bool EMA, int NT = 0>
 __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
-    optim_body<KIND, GT, float, GROUPED, EMA>(a);
+    optim_body<KIND, GT, float, GROUPED, EMA, NT>(a);
 }
 
 // The same body on a bf16 state.  Left alone the compiler keeps the ten round keys of the Philox call and the counter's uniform half
 // in scalar registers for the whole walk and ends at the scalar file's cap (106), which admits 7 waves per SIMD where the f32-state
 // kernels run 8; told to aim for 8 it keeps what does not fit in lanes of a vector register instead.
-template <int KIND, typename GT, bool GROUPED, bool EMA>
+template <int KIND, typename GT, bool GROUPED, bool EMA, int NT = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void optim_kernel_bf16_state(const OptimArgs a) {
-    optim_body<KIND, GT, bf16_t, GROUPED, EMA>(a);
+    optim_body<KIND, GT, bf16_t, GROUPED, EMA, NT>(a);
 }
 
 // what egk_adam_step* launch: the body for Adam under the name the profiles, bench.py and the timeline tools know the step's
 // optimizer launch by
-template <typename GT>
+template <typename GT, int NT = 0>
 __global__ __launch_bounds__(256) void adam_kernel(const OptimArgs a) {
-    optim_body<K_ADAM, GT, float, false, false>(a);
+    optim_body<K_ADAM, GT, float, false, false, NT>(a);
 }
 
 // p[i] <-> ema[i]: 16-byte accesses, a scalar tail for n % 4, grid-stride
@@ -444,23 +492,41 @@ static unsigned optim_grid(long long n) {
 }
 
 // the kernel of a launch: adam_kernel for egk_adam_step* (KID_ADAM), otherwise the member of the family
-template <int KIND, typename GT, typename ST>
+template <int KIND, typename GT, typename ST, int NT>
 static auto optim_pick(int kid, bool grouped, bool ema) -> void (*)(OptimArgs) {
     if constexpr (__is_same(ST, float)) {
-        if (kid == KID_ADAM) return adam_kernel<GT>;
-        if (grouped) return ema ? optim_kernel<KIND, GT, true, true> : optim_kernel<KIND, GT, true, false>;
-        return ema ? optim_kernel<KIND, GT, false, true> : optim_kernel<KIND, GT, false, false>;
+        if (kid == KID_ADAM) return adam_kernel<GT, NT>;
+        if (grouped) return ema ? optim_kernel<KIND, GT, true, true, NT> : optim_kernel<KIND, GT, true, false, NT>;
+        return ema ? optim_kernel<KIND, GT, false, true, NT> : optim_kernel<KIND, GT, false, false, NT>;
     } else {
-        if (grouped) return ema ? optim_kernel_bf16_state<KIND, GT, true, true> : optim_kernel_bf16_state<KIND, GT, true, false>;
-        return ema ? optim_kernel_bf16_state<KIND, GT, false, true> : optim_kernel_bf16_state<KIND, GT, false, false>;
+        if (grouped) return ema ? optim_kernel_bf16_state<KIND, GT, true, true, NT> : optim_kernel_bf16_state<KIND, GT, true, false, NT>;
+        return ema ? optim_kernel_bf16_state<KIND, GT, false, true, NT> : optim_kernel_bf16_state<KIND, GT, false, false, NT>;
     }
 }
 // ... by the state's element type too (K_SGD has no state: its one instantiation serves either)
-template <int KIND, typename GT>
+template <int KIND, typename GT, int NT>
 static auto optim_pick(int kid, bool grouped, bool ema, bool narrow) -> void (*)(OptimArgs) {
     if constexpr (StateCount<KIND>::value > 0)
-        if (narrow) return optim_pick<KIND, GT, bf16_t>(kid, grouped, ema);
-    return optim_pick<KIND, GT, float>(kid, grouped, ema);
+        if (narrow) return optim_pick<KIND, GT, bf16_t, NT>(kid, grouped, ema);
+    return optim_pick<KIND, GT, float, NT>(kid, grouped, ema);
+}
+// ... and by the cache policy of the launch's streams (egk_tune 9): the masks that are instantiated
+// Default: the three stores and every load non-temporal, the average left alone (NT_G | NT_LOAD | NT_STORE).  Same box, alternating
+// runs of the headline step: masks 0 / 1 / 3 within noise of each other, 7 ahead in every round (HISTORY.md section 21).
+int g_optim_stream_policy = NT_G | NT_LOAD | NT_STORE;
+bool optim_stream_policy_ok(int mask) { return mask == 0 || mask == 1 || mask == 2 || mask == 3 || mask == 4 || mask == 7 || mask == 8 || mask == 15; }
+template <int KIND, typename GT>
+static auto optim_pick(int kid, bool grouped, bool ema, bool narrow) -> void (*)(OptimArgs) {
+    switch (g_optim_stream_policy) {
+        case 1: return optim_pick<KIND, GT, 1>(kid, grouped, ema, narrow);
+        case 2: return optim_pick<KIND, GT, 2>(kid, grouped, ema, narrow);
+        case 3: return optim_pick<KIND, GT, 3>(kid, grouped, ema, narrow);
+        case 4: return optim_pick<KIND, GT, 4>(kid, grouped, ema, narrow);
+        case 7: return optim_pick<KIND, GT, 7>(kid, grouped, ema, narrow);
+        case 8: return optim_pick<KIND, GT, 8>(kid, grouped, ema, narrow);
+        case 15: return optim_pick<KIND, GT, 15>(kid, grouped, ema, narrow);
+        default: return optim_pick<KIND, GT, 0>(kid, grouped, ema, narrow);
+    }
 }
 
 // Every optimizer entry point: the refusals, then one launch.  ``who``: the name the messages carry; ``kid``: the entry point's
