@@ -24,6 +24,11 @@ LIB_PATH = Path(os.environ["EGK_LIB_PATH"]) if os.environ.get("EGK_LIB_PATH") el
 HEADERS = {key: HERE.parent / "include" / f"egopack_{key}.h" for key in (
     "hip", "optim", "optim_groups", "ema", "ce_balanced", "bce_balanced", "task_scale", "sample", "class_report", "topk", "retrieval")}
 
+# Headers bound from a SECOND table: the same parser, the same rules, their own ledger (tests/test_cabi_lamb.py).  Their prototypes take
+# scalars and pointers only, so STRUCTS stays the set the first ledger pins.  HEADERS, signatures() and declared() do not see them.
+EXTRA_HEADERS = {"lamb": HERE.parent / "include" / "egopack_lamb.h"}
+LAMB_PIECE = 4096  # EGK_LAMB_PIECE (include/egopack_lamb.h)
+
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
 
@@ -221,6 +226,23 @@ def declared(key: str | None = None) -> list:
     return sorted(sigs[key]) if key is not None else [name for k in sigs for name in sorted(sigs[k])]
 
 
+@functools.lru_cache(maxsize=None)
+def extra_signatures() -> dict:
+    """header key -> {name: (restype, argtypes)} of the files of EXTRA_HEADERS (once); a name a header of HEADERS declares too is
+    refused."""
+    owner = {name: key for key, table in signatures().items() for name in table}
+    out = {}
+    for key, path in EXTRA_HEADERS.items():
+        if not path.exists():
+            raise RuntimeError(f"{path} is missing: it is header '{key}' of the C ABI (EXTRA_HEADERS)")
+        out[key] = parse_prototypes(path.read_text(), path.name)
+        for name in out[key]:
+            if name in owner:
+                raise RuntimeError(f"{name} is declared in {path.name} and again under the key '{owner[name]}'")
+            owner[name] = key
+    return out
+
+
 _lib = None
 
 
@@ -234,7 +256,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m egopack_amd.build` "
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for table in signatures().values():  # (raises for a missing header and for a name two headers declare)
+    for table in (*signatures().values(), *extra_signatures().values()):  # (raises for a missing header and for a name two headers declare)
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res

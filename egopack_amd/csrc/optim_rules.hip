@@ -5,6 +5,7 @@
 // the offset word moved on by workgroup 0, one wave-uniform load of the gate.  No atomics; every element has one writer.
 // ONE dispatcher (optim_dispatch) behind the entry points: the refusals, the grid, the bytes and the launch line.
 #include "common.h"
+#include "optim_stream.h"  // ema_update, ema_weight, the NT_* cache policy and its loads and stores
 
 namespace egk {
 
@@ -56,14 +57,6 @@ __device__ __forceinline__ void optim_update(float& p, float g, float& a, float&
     }
 }
 
-// the moving average of the weights (include/egopack_ema.h): e += w * (p_new - e), three separately rounded f32 operations
-__device__ __forceinline__ void ema_update(float& e, float p_new, float w) {
-#pragma clang fp contract(off)
-    const float diff = p_new - e;
-    const float move = w * diff;
-    e = e + move;
-}
-
 // ---- the state's element type (include/egopack_optim.h: state_dtype) ------------------------------------------------------------------
 // ST = float: the 16-byte loads and stores the family has always issued.  ST = bf16_t: one 8-byte access per buffer and quad, the
 // elements widened to f32 on the way in and rounded on the way out -- to nearest (f2bf), or by adding 16 random bits under the bits
@@ -87,44 +80,6 @@ __device__ __forceinline__ bf16_t round_state(float x, unsigned r16, bool stocha
     if (!stochastic || (b & 0x7f800000u) == 0x7f800000u) return f2bf(x);  // (inf / NaN keep f2bf's bits)
     return (bf16_t)((b + r16) >> 16);  // (no carry into the sign: the exponent is not all ones)
 }
-
-// ---- cache policy of the single-use streams (egk_tune 9) ---------------------------------------------------------------------------
-// A launch reads g, p and the state and writes p and the state once per step; nothing reads those lines again before the next
-// step's launch, while the bf16 copies it writes are the next step's contraction operands.  A mask, the kernels' template argument NT,
-// marks accesses as non-temporal, per stream; the copies always keep the default policy.  The policy changes no arithmetic.
-enum { NT_G = 1, NT_LOAD = 2, NT_STORE = 4, NT_EMA = 8 };  // loads of g | loads of p and the state | their stores | the average, both ways
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned nt_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float4 ld_quad(const float* __restrict__ p, bool nt) {
-    if (nt) {
-        const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *reinterpret_cast<const float4*>(p);
-}
-__device__ __forceinline__ float4 ld_quad(const bf16_t* __restrict__ p, bool nt) {
-    if (nt) {
-        const nt_u2 r = __builtin_nontemporal_load(reinterpret_cast<const nt_u2*>(p));
-        return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
-                           __uint_as_float(r.y & 0xffff0000u));
-    }
-    return ld4t(p, 0, 4, true);
-}
-__device__ __forceinline__ void st_quad(float* __restrict__ p, const float4& v, bool nt) {
-    if (nt) {
-        const nt_f4 w = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(w, reinterpret_cast<nt_f4*>(p));
-        return;
-    }
-    *reinterpret_cast<float4*>(p) = v;
-}
-template <typename T> __device__ __forceinline__ T ld_one(const T* p, bool nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
-template <typename T> __device__ __forceinline__ void st_one(T* p, T v, bool nt) {
-    if (nt) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-__device__ __forceinline__ float ld_one_f(const float* p, bool nt) { return ld_one(p, nt); }
-__device__ __forceinline__ float ld_one_f(const bf16_t* p, bool nt) { return bf2f(ld_one(p, nt)); }
 
 __device__ __forceinline__ float4 ld_state4(const float* __restrict__ s, bool nt) { return ld_quad(s, nt); }
 __device__ __forceinline__ float4 ld_state4(const bf16_t* __restrict__ s, bool nt) { return ld_quad(s, nt); }
@@ -283,21 +238,6 @@ __device__ __forceinline__ OptimConsts group_consts(const GroupTable& t, long lo
     grp = grp < 0 ? 0 : grp >= t.n_groups ? t.n_groups - 1 : grp;
     const float2 lw = *reinterpret_cast<const float2*>(t.group_hyper + 4 * grp);
     return optim_consts<KIND>(lw.x, lw.y, hyper, t_dev, h);
-}
-
-// ---- the moving average of the weights inside the launch (include/egopack_ema.h) ----------------------------------------------------
-struct EmaArgs {
-    float* __restrict__ ema;
-    double decay;   // warmup: d_t = min(decay, (1 + t) / (10 + t)) from the device step counter
-    float w;        // no warmup: (float)(1.0 - decay), rounded on the host
-    int warmup;
-};
-
-__device__ __forceinline__ float ema_weight(const EmaArgs& e, const long long* __restrict__ t_dev) {
-    if (!e.warmup) return e.w;
-    const double t = (double)*t_dev;  // (egk_adam_hyper has counted this step)
-    const double ramp = (1.0 + t) / (10.0 + t);
-    return (float)(1.0 - (e.decay < ramp ? e.decay : ramp));
 }
 
 // ---- the one body and the kernels over it --------------------------------------------------------------------------------------------

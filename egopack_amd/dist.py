@@ -354,6 +354,12 @@ class GradSync:
                              "sharded update (sharded_update): the moments of a slice are kept, sliced and all-gathered as f32 buffers "
                              "-- keep the state in f32, or use the all-reduce exchange (the default)")
 
+    def _refuse_lamb(self, opt) -> None:
+        if hasattr(opt, "trust_ratios"):
+            raise ValueError(f"{type(opt).__name__} does not combine with the sharded update (sharded_update): the trust ratio needs the "
+                             "norms of a whole parameter slot, and a rank's shard of the flat buffers does not see whole slots -- use "
+                             "the all-reduce exchange (the default), where every rank runs the full launches")
+
     def _refuse_task_weighting(self, opt) -> None:
         if getattr(opt, "task_weighting", None) not in (None, "none"):
             raise ValueError(f"task weighting (task_weighting.mode: {opt.task_weighting}) does not combine with the sharded update "
@@ -365,6 +371,7 @@ class GradSync:
         self._refuse_ema(opt)
         self._refuse_task_weighting(opt)
         self._refuse_bf16_state(opt)
+        self._refuse_lamb(opt)
         flat_g = opt.flat_g
         gpu = flat_g.is_cuda
         compress = self.compress == "bf16" and gpu
@@ -451,6 +458,7 @@ class GradSync:
         self._refuse_ema(opt)
         self._refuse_task_weighting(opt)
         self._refuse_bf16_state(opt)
+        self._refuse_lamb(opt)
         flat_g, n = opt.flat_g, opt.flat_g.numel()
         per, lo, hi, body = self.shard_bounds(n)
         real = dist.get_world_size(self.group) if dist.is_initialized() else 1

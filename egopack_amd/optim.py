@@ -26,6 +26,7 @@ no launch.  ``ema_weights()`` swaps the average into the parameters (bf16 copies
 saving; the state dict carries it under a third top-level key, ``"ema"``."""
 from __future__ import annotations
 
+import bisect
 import contextlib
 import ctypes as C
 import logging
@@ -303,7 +304,7 @@ class FlatOptimizer(torch.optim.Optimizer):
         self._hyper_src = torch.zeros(2, dtype=torch.float32, device=dev)  # {lr, grad_scale}: uploaded when they change
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)        # optimizer steps taken (device-side counter)
         self._src_host, self._t_mirror = None, 0
-        if self.grouped:  # the tables every launch resolves lr / weight_decay from (group_hyper: uploaded by sync_hyper_source)
+        if self.grouped or self._group_table_always:  # the tables every launch resolves lr / weight_decay from (group_hyper: uploaded by sync_hyper_source)
             segs = self._segments
             self._seg_begin = torch.tensor([b for b, _, _ in segs] + [segs[-1][1]], dtype=torch.int64, device=dev)
             self._seg_group = torch.tensor([gi for _, _, gi in segs], dtype=torch.int32, device=dev)
@@ -498,6 +499,10 @@ class FlatOptimizer(torch.optim.Optimizer):
 
     # keys of a parameter group that select the kernel (the rule itself, the number of state buffers): a loaded state leaves them
     _fixed_keys = ()
+    # a rule that resolves lr / weight_decay from the group table even with one group (FlatLAMB: per slot)
+    _group_table_always = False
+    # the keys only a LAMB state's parameter groups carry: what tells it from an Adam state, whose buffers have the same names
+    _LAMB_KEYS = ("trust_clip", "always_adapt")
 
     @staticmethod
     def _entry_steps(st) -> float:
@@ -516,6 +521,12 @@ class FlatOptimizer(torch.optim.Optimizer):
             name = lambda keys: _STATE_NAMES.get(keys, "per-parameter state (" + ", ".join(sorted(keys)) + ")")
             raise RuntimeError(f"{type(self).__name__}.load_state_dict(): the checkpoint holds {name(held)}, the configured optimizer "
                                f"is {type(self).__name__} and keeps {name(want)}")
+        held_lamb = any(k in pg for pg in state_dict.get("param_groups", ()) for k in self._LAMB_KEYS)
+        if held == want and held_lamb != isinstance(self, FlatLAMB):  # (Adam's and LAMB's buffers have the same names)
+            raise RuntimeError(f"{type(self).__name__}.load_state_dict(): the checkpoint holds {'LAMB' if held_lamb else 'Adam / AdamW'} "
+                               f"state (exp_avg, exp_avg_sq, {'with' if held_lamb else 'without'} the group keys "
+                               f"{', '.join(self._LAMB_KEYS)}), the configured optimizer is {type(self).__name__}: the moments of one "
+                               "rule do not continue the other")
 
     def _apply_state(self, state_dict):
         params = self._all_params()
@@ -635,7 +646,7 @@ class FlatOptimizer(torch.optim.Optimizer):
             host[0], host[1] = src
             self._hyper_src.copy_(host, non_blocking=True)
             self._src_host = src
-        if self.grouped:  # the per-group {lr, weight_decay, 0, 0} rows the grouped launch reads: uploaded when any of them changes
+        if self.grouped or self._group_table_always:  # the per-group {lr, weight_decay, 0, 0} rows the grouped launch reads: uploaded when any of them changes
             rows = tuple((float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups)
             if rows != self._group_host:
                 host = torch.zeros(len(rows), 4, dtype=torch.float32, pin_memory=True)
@@ -1015,3 +1026,128 @@ class FlatSGD(FlatOptimizer):
         g = self.param_groups[0]
         self._optim_step(_lib.OPT_SGD, sl, grads, lo16, bump, gate, weight_decay=g["weight_decay"], momentum=g["momentum"],
                          dampening=g["dampening"], nesterov=int(bool(g["nesterov"])))
+
+
+class FlatLAMB(FlatAdam):
+    """LAMB (You et al. 2020; include/egopack_lamb.h): Adam's moments, the update u = m_hat / (sqrt(v_hat) + eps) + wd * p
+    and, per slot of the flat layout (one parameter with its alignment and 64-row padding), p -= lr * trust * u with trust = ||p|| / ||u||.
+    Three launches: ``launch`` issues egk_lamb_moments over its slice; the call that completes the coverage of the buffers issues
+    egk_lamb_trust and egk_lamb_apply over everything.  ``trust_clip``: trust <= 1.  ``always_adapt``: the ratio also where
+    weight_decay is 0 (default: trust 1 there).  lr and weight_decay come per slot from the parameter-group table, with one group too."""
+
+    _fixed_keys = ("decoupled_weight_decay", *FlatOptimizer._LAMB_KEYS)
+    _group_table_always = True
+
+    def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, max_grad_norm=None, *, trust_clip: bool = False, always_adapt: bool = False, **hints):
+        name = type(self).__name__
+        if hints.pop("decoupled_weight_decay", False):
+            raise ValueError(f"{name}: decoupled_weight_decay=True is not built -- LAMB's weight decay is part of the update whose norm "
+                             "the trust ratio divides by")
+        dt = hints.get("state_dtype", torch.float32)
+        if (STATE_DTYPES.get(dt.lower(), dt) if isinstance(dt, str) else dt) is torch.bfloat16:
+            raise ValueError(f"{name}: state_dtype=torch.bfloat16 (optimizer_state.dtype: bf16) is not built -- the norm launch and the "
+                             "apply launch would have to agree on the rounded moments; keep the state in f32")
+        if not eps > 0.0:
+            raise ValueError(f"{name}: eps must be positive (got {eps}): the zero padding of a slot has exp_avg_sq = 0")
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, **hints)
+        self.trust_clip, self.always_adapt = bool(trust_clip), bool(always_adapt)
+        for g in (self.defaults, *self.param_groups):  # (the state dict's groups carry them: what tells a LAMB state from Adam's)
+            g.setdefault("trust_clip", self.trust_clip)
+            g.setdefault("always_adapt", self.always_adapt)
+        self._check_groups()
+        self._lamb_covered, self._lamb_events = 0, []
+
+    @staticmethod
+    def piece_table(sizes) -> tuple:
+        """(slot_begin [n + 1], slot_piece0 [n + 1], piece_begin [pieces + 1]) of slots of ``sizes`` elements: every slot cut into
+        pieces of at most ``_lib.LAMB_PIECE`` elements, the last one shorter; a piece never crosses a slot boundary."""
+        begin, piece0, pieces = [0], [0], [0]
+        for sz in sizes:
+            if sz <= 0 or sz % 8:
+                raise ValueError(f"FlatLAMB.piece_table(): a slot of {sz} elements (slots are positive multiples of 8)")
+            b = begin[-1]
+            pieces.extend(min(b + k + _lib.LAMB_PIECE, b + sz) for k in range(0, sz, _lib.LAMB_PIECE))
+            begin.append(b + sz)
+            piece0.append(len(pieces) - 1)
+        return begin, piece0, pieces
+
+    def _materialise(self):
+        super()._materialise()
+        dev = self.flat_p.device
+        slots = sorted(self._slot_of[id(p)] for p in self.active)
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+        by_off = {self._slot_of[id(p)][0]: p for p in self.active}
+        begin, piece0, self._piece_begin = self.piece_table([sz for _, sz in slots])
+        if [off for off, _ in slots] != begin[:-1] or begin[-1] != self.flat_p.numel():
+            raise RuntimeError(f"{type(self).__name__}: the slots do not tile the flat buffers")
+        self._slot_params = [by_off[off] for off, _ in slots]
+        self._slot_begin = torch.tensor(begin, dtype=torch.int64, device=dev)
+        self._slot_piece0 = torch.tensor(piece0, dtype=torch.int32, device=dev)
+        self._slot_group = torch.tensor([group_of[id(p)] for p in self._slot_params], dtype=torch.int32, device=dev)
+        self._lamb_part = torch.zeros(piece0[-1], 2, 2, dtype=torch.float64, device=dev)
+        self._lamb_trust = torch.ones(len(slots), dtype=torch.float32, device=dev)
+        self._lamb_norms = torch.zeros(len(slots), 2, dtype=torch.float64, device=dev)
+        self._lamb_covered, self._lamb_events = 0, []
+
+    def prepare_hyper(self, in_capture: bool = False):
+        super().prepare_hyper(in_capture)
+        self._lamb_covered, self._lamb_events = 0, []  # (a step abandoned between two slices leaves nothing behind)
+
+    def _piece_range(self, lo: int, hi: int) -> tuple:
+        """(first piece that meets [lo, hi), how many do) from the host copy of the piece table; a range strictly inside one piece
+        is refused."""
+        pb = self._piece_begin
+        q0, q1 = bisect.bisect_right(pb, lo) - 1, bisect.bisect_right(pb, hi - 1) - 1
+        if lo % 8 or hi % 8 or lo < 0 or hi > pb[-1]:
+            raise ValueError(f"{type(self).__name__}.launch(): [{lo}, {hi}) must be multiples of 8 inside [0, {pb[-1]})")
+        if q0 == q1 and pb[q0] < lo and hi < pb[q0 + 1]:
+            raise ValueError(f"{type(self).__name__}.launch(): [{lo}, {hi}) lies strictly inside the piece [{pb[q0]}, {pb[q0 + 1]}) of a "
+                             f"parameter's slot -- the per-slot norms take a piece cut at most once per step: a gradient-exchange chunk "
+                             f"(chunk_mb) must hold at least {_lib.LAMB_PIECE} elements")
+        return q0, q1 - q0 + 1
+
+    def _launch_rule(self, sl, grads, lo16, bump, gate) -> None:
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        lib, lo, hi, total = _lib.load(), sl.start, sl.stop, self.flat_p.numel()
+        q0, nq = self._piece_range(lo, hi)  # (not strictly inside a piece: [lo, hi] holds a piece boundary)
+        if self._lamb_covered + (hi - lo) > total:
+            raise RuntimeError(f"{type(self).__name__}.launch(): the slices of this step cover more than the {total} elements of the "
+                               "flat buffers (prepare_hyper starts a step)")
+        n_slots, n_groups = self._slot_group.numel(), len(self.param_groups)
+        tables = (_p(self._slot_piece0), _p(self._slot_group), n_slots, _p(self._group_hyper), n_groups)
+        _ck(lib.egk_lamb_moments(_stream(), _p(self.flat_p), _p(grads), 1 if grads.dtype == torch.bfloat16 else 0, _p(self.flat_m),
+                                 _p(self.flat_v), lo, hi, q0, nq, 1, _p(self._slot_begin), *tables, _p(self._hyper),
+                                 b1, b2, g["eps"], _p(self._lamb_part), _p(gate), _p(bump[0]) if bump is not None else None,
+                                 int(bump[1]) if bump is not None else 0), "egk_lamb_moments")
+        self._lamb_covered += hi - lo
+        if self._lamb_covered < total:  # (more slices to come, maybe on other streams: the completing call waits for this one)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._lamb_events.append(ev)
+            return
+        for ev in self._lamb_events:
+            torch.cuda.current_stream().wait_event(ev)
+        self._lamb_covered, self._lamb_events = 0, []
+        _ck(lib.egk_lamb_trust(_stream(), _p(self._lamb_part), *tables, int(self.trust_clip), int(self.always_adapt),
+                               _p(self._lamb_trust), _p(self._lamb_norms), _p(gate)), "egk_lamb_trust")
+        lo_all = self.flat_w16lo if lo16 is not None else None
+        _ck(lib.egk_lamb_apply(_stream(), _p(self.flat_p), _p(self.flat_m), _p(self.flat_v), total, len(self._piece_begin) - 1,
+                               _p(self._slot_begin), *tables, _p(self._hyper), g["eps"], _p(self._lamb_trust), _p(self.flat_w16),
+                               _p(lo_all), _p(self.flat_ema) if self.ema else None, self.ema_decay, int(self.ema_warmup),
+                               _p(self._t_dev), _p(gate)), "egk_lamb_apply")
+        if lo_all is not None:
+            self._lo_fresh = [(0, total)]
+
+    def trust_ratios(self, names=None) -> dict:
+        """``{name or index: (trust, ||p||, ||u||)}`` of the last step that happened, per parameter that has a slot (one device
+        synchronisation).  ``names``: ``{parameter: name}`` (e.g. from ``named_parameters``); otherwise the parameter's index in
+        constructor order, the state dict's."""
+        if not self.materialised:
+            return {}
+        vals = torch.cat([self._lamb_trust.double(), self._lamb_norms.reshape(-1)]).tolist()
+        n = len(self._slot_params)
+        index = {id(p): i for i, p in enumerate(self._all_params())}
+        names = {id(p): nm for p, nm in (names or {}).items()}
+        return {names.get(id(p), index[id(p)]): (vals[s], vals[n + 2 * s], vals[n + 2 * s + 1]) for s, p in enumerate(self._slot_params)}

@@ -14,7 +14,7 @@ from . import data as D
 from . import ops
 from .config import Cfg, compose, instantiate
 from .criterion import BCEWithLogitsNone, CrossEntropyNone, MetricSelectorWrapper
-from .optim import STATE_DTYPES, STATE_ROUNDINGS, TASK_WEIGHTING_GROUP, TASK_WEIGHTING_MODES, FlatAdam, FlatAdamW, FlatSGD
+from .optim import STATE_DTYPES, STATE_ROUNDINGS, TASK_WEIGHTING_GROUP, TASK_WEIGHTING_MODES, FlatAdam, FlatAdamW, FlatLAMB, FlatSGD
 
 logger = logging.getLogger("egopack")
 TASKS = ("ar", "oscc", "lta", "pnr")
@@ -704,7 +704,8 @@ def load_task_weighting(logger, ckpt: dict, step) -> bool:
     return True
 
 
-OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD}
+OPTIMIZERS = {"torch.optim.Adam": FlatAdam, "torch.optim.AdamW": FlatAdamW, "torch.optim.SGD": FlatSGD,
+              "egopack_amd.optim.FlatLAMB": FlatLAMB}  # (LAMB has no torch class: the config names the flat-buffer one)
 
 # ---- the element type of the optimizer state (``optimizer_state:`` of the config; include/egopack_optim.h) ---------------
 OPTIMIZER_STATE_DEFAULTS = {"dtype": "f32", "rounding": "stochastic", "seed": None}
@@ -861,6 +862,17 @@ def log_grad_norms(logger, epoch: int, step) -> None:
     st = step.grad_norm_stats()
     logger.info("epoch %d: gradient norm mean %.9g, largest %.9g, clipped %d of %d steps (max norm %g), skipped %d (norm not finite)",
                 epoch, st["mean_norm"], st["max_norm"], st["clipped"], st["steps"], step.optimizer.max_grad_norm, st["skipped"])
+
+
+def log_trust_ratios(logger, epoch: int, step) -> None:
+    """With LAMB: the smallest, median and largest trust ratio of the epoch's last step, next to the task losses (nothing otherwise)."""
+    opt = step.optimizer
+    if not hasattr(opt, "trust_ratios") or not getattr(opt, "materialised", False):
+        return
+    trust = sorted(t for t, _, _ in opt.trust_ratios().values())
+    if trust:
+        logger.info("epoch %d: trust ratio min %.6g, median %.6g, max %.6g over %d parameter tensors", epoch, trust[0],
+                    trust[len(trust) // 2], trust[-1], len(trust))
 
 
 def build_scheduler(cfg, optimizer):

@@ -797,5 +797,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* the retrieval report of a GraphONE prediction: per node and auxiliary task the distances of the prototypes it consulted and the
  * number of channels each of them supplies to the first stage's max aggregation, in one launch (egk_retrieval_report) */
 #include "egopack_retrieval.h"
+/* LAMB, the layer-wise adaptive rule: per-slot norms of the parameters and of the update in a reduce launch, a trust ratio per slot,
+ * and the apply launch (egk_lamb_moments, egk_lamb_trust, egk_lamb_apply) */
+#include "egopack_lamb.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -84,6 +84,7 @@ def train(epoch, step: engine.EgoPackStep, loaders, weights, device="cuda", stor
                     it - mark[0], mark[0], torch.cuda.memory_allocated() / 2 ** 20, torch.cuda.memory_reserved() / 2 ** 20)
     logger.info("epoch %d: %d iterations, last objective %.4f", epoch, it, float(total))
     T.log_grad_norms(logger, epoch, step)  # (grad_clip_norm: mean / largest gradient norm, clipped and skipped steps of the epoch)
+    T.log_trust_ratios(logger, epoch, step)  # (LAMB: min / median / max trust ratio)
     lc = getattr(step, "loop_counts", None)
     if lc is not None:  # how many steps replayed the captured graph and how many ran eagerly (shape changes, warm-up)
         logger.info("epoch %d: %d steps replayed the captured step, %d ran eagerly", epoch, lc["replayed"], lc["eager"])

@@ -63,6 +63,7 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
     logger.info("epoch %d: %d iterations, train loss %s", epoch, it,
                 {t: round(s_ / max(n_, 1), 4) for t, (s_, n_) in step.loss_sums().items() if n_})
     T.log_grad_norms(logger, epoch, step)
+    T.log_trust_ratios(logger, epoch, step)  # (LAMB: min / median / max trust ratio)
     T.log_task_weighting(logger, epoch, step)  # (s_t and w_t exp(-s_t), or the manual scales; nothing with the feature off)
     lc = getattr(step, "loop_counts", None)
     if lc is not None:  # how many steps replayed the captured graph and how many ran eagerly (shape changes, warm-up)
