@@ -20,7 +20,7 @@ from typing import Dict, Mapping, Optional, Sequence
 
 import torch
 
-from . import ops, switches
+from . import ops, sched, switches
 from .data import Data, merge_batches
 from .criterion import MetricSelectorWrapper
 from .dist import GradSync
@@ -555,7 +555,7 @@ class StepBase:
                 return 8
         return None
     # forked launches (weight gradients, early Adam) issued one launch late so that the dX chain keeps its hardware queue under
-    # capture (ops.defer_after_next_launch): -4 % on the multi-task steps, -1.6 % on the single-task step; the EgoPack step,
+    # capture (sched.defer_after_next_launch): -4 % on the multi-task steps, -1.6 % on the single-task step; the EgoPack step,
     # whose GraphONE chains already occupy three queues, measured 4.04 vs 3.51 ms with it and leaves it off
     deferred_forks_default = True
 
@@ -609,7 +609,7 @@ class StepBase:
         # weight-gradient launches of the backbone on a side stream (they feed nothing but the optimizer): 2-4 % on the
         # multi-task steps, 1.8 % on the single-task step (1.236 -> 1.214 ms), neutral on the EgoPack step
         self.wgrad_side_streams = bool(parallel_heads)
-        # H x H weight gradients parked and issued four at a time as ONE grouped launch of 256 workgroups (ops._wgrad_defer):
+        # H x H weight gradients parked and issued four at a time as ONE grouped launch of 256 workgroups (sched._wgrad_defer):
         # -4 % on the 3-task step, -12 % on the single-task step; the EgoPack step measured 3.59 vs 3.46-3.52 ms with it in round 1
         # and left it off until round 4 (EgoPackStep.wgrad_grouping_default)
         self.wgrad_grouping = type(self).wgrad_grouping_default
@@ -649,7 +649,7 @@ class StepBase:
             n_streams = min(len(feats), self.max_head_streams or len(feats))
             while len(self._head_streams) < n_streams:
                 self._head_streams.append(torch.cuda.Stream())
-                ops.exclude_wgrad_streams(self._head_streams[-1:])
+                sched.exclude_wgrad_streams(self._head_streams[-1:])
             used = self._head_streams[:n_streams]
             for st in used:
                 st.wait_event(fork)
@@ -686,8 +686,8 @@ class StepBase:
         return list(self._head_streams)
 
     def _scope_streams(self) -> None:
-        """This step's own head / task / side streams are the excluded ones from here on (ops.scope_excluded_streams)."""
-        ops.scope_excluded_streams(self._branch_streams())
+        """This step's own head / task / side streams are the excluded ones from here on (sched.scope_excluded_streams)."""
+        sched.scope_excluded_streams(self._branch_streams())
 
     # ---- running per-task loss sums (what a training loop logs per epoch: reference main_temporal.py:129-134) -----------------------
     # The reference keeps them with ``.item()`` per step; kept as ``sum()`` + ``add_`` launches between two replays of the captured
@@ -710,8 +710,8 @@ class StepBase:
             return
         acc, order = self._loss_acc_for(live[0].device), list(self.enabled)
         src = {t: v.detach() for t, v in vectors.items()}
-        ops.park_rider(lambda: ops.weighted_mean_sum_into(self._loss_scratch, [src.get(t) for t in order], [0.0] * len(order), acc=acc),
-                       tuple(src.values()))
+        sched.park_rider(lambda: ops.weighted_mean_sum_into(self._loss_scratch, [src.get(t) for t in order], [0.0] * len(order), acc=acc),
+                         tuple(src.values()))
 
     def _count_losses(self, vectors) -> None:
         cnt = self._loss_counts
@@ -782,11 +782,11 @@ class StepBase:
         return [t for t in self.enabled if batches.get(t) is not None]
 
     # ---- the one way into issuing a step: eager (one piece, staged) and captured (one rank, exchange graph, staged graphs) ----------
-    # ops.step_schedule keeps three rules for every one of them: nothing parked or deferred survives a step that was abandoned by an
+    # sched.step_schedule keeps three rules for every one of them: nothing parked or deferred survives a step that was abandoned by an
     # exception, no hook outlives its step, and the settings of whoever issued before come back.
     @contextlib.contextmanager
     def _issuing(self, batches, merged, *, handoff: bool = False, store: bool = False):
-        """Issue one step inside: this step's streams are the excluded ones, the weight-gradient / fork scheduler of ``ops`` runs
+        """Issue one step inside: this step's streams are the excluded ones, the weight-gradient / fork scheduler (``sched``) runs
         with this step's settings.  ``handoff``: the side streams are handed to the gradient exchange at the end of every backward
         stage (``_exchange_region``) instead of joined.  ``store`` (captures): gradient slots learnt to have one writer per step
         (``_learn_single_writers``) are stored, not cleared + accumulated -- the provider is installed for the body (not at all:
@@ -796,8 +796,8 @@ class StepBase:
         self._scope_streams()
         prev_handoff, stored, ok = self._handoff, None, False
         try:
-            with ops.step_schedule(self.wgrad_side_streams, self.wgrad_grouping, self._wgrad_count(batches, merged), self.deferred_forks,
-                                   handoff):
+            with sched.step_schedule(self.wgrad_side_streams, self.wgrad_grouping, self._wgrad_count(batches, merged), self.deferred_forks,
+                                     handoff):
                 self._handoff = handoff
                 if store and not self._grad_store_off and hasattr(opt, "store_begin") and switches.enabled("grad_store"):
                     provider = opt.store_begin()
@@ -823,7 +823,7 @@ class StepBase:
             self._install_tail(self._tail_only_plan(self._live(batches)))
             with self._ln_exchange_scope():
                 total, vectors = self._backward_pass(batches, merged)
-            ops.join_wgrad(force=True)
+            sched.join_wgrad(force=True)
         return total, vectors
 
     def step(self, batches: Mapping[str, Data], merged: Optional[Data] = None):
@@ -857,7 +857,7 @@ class StepBase:
 
     def _fork_grad_clear(self, hyper: bool) -> None:
         """Captured steps clear the gradient buffer BESIDE the forward pass (nothing writes a gradient before the first backward
-        launch): 100 MB of memset off the chain's head, forked behind the forward pass's first launch (ops.defer_after_next_launch)
+        launch): 100 MB of memset off the chain's head, forked behind the forward pass's first launch (sched.defer_after_next_launch)
         and joined by ``_join_zero`` before backward starts.  ``hyper``: the step's Adam constants (one thread, from the device-side
         step counter) ride along."""
         opt, side = self.optimizer, self._own_stream("_zero_stream")
@@ -869,7 +869,7 @@ class StepBase:
                 if hyper:
                     opt.prepare_hyper(in_capture=True)
                 self._task_scale_head()  # (uncertainty: scale = exp(-log_var), joined with the clear before the heads read it)
-        ops.defer_after_next_launch(issue_zero)
+        sched.defer_after_next_launch(issue_zero)
         self._zero_pending = True
 
     def _task_scale_head(self) -> None:
@@ -882,7 +882,7 @@ class StepBase:
     def _join_zero(self):
         """Wait for the gradient clear forked by ``_fork_grad_clear`` before the first launch that writes a gradient."""
         if self._zero_pending:
-            ops.drain_deferred()
+            sched.drain_deferred()
             torch.cuda.current_stream().wait_stream(self._zero_stream)
             self._zero_pending = False
 
@@ -922,13 +922,13 @@ class StepBase:
         if self.sync is not None and self.sync.world > 1:
             # (handoff: the region's weight gradients may still be running on their side streams -- the communication stream
             #  waits for them, the backward stream goes straight on with the next stage)
-            after = ops.take_wgrad_streams() if self._handoff else ()
+            after = sched.take_wgrad_streams() if self._handoff else ()
             self.sync.start(self.optimizer, *region, after=after)
 
     def _stage_join(self):
         """End of a backward stage: the stage's gradients are complete once the weight-gradient side streams are joined."""
         if not self._handoff:
-            ops.join_wgrad(force=True)
+            sched.join_wgrad(force=True)
 
     def _finish_staged(self):
         if self.sync is not None and self.sync.world > 1:
@@ -1161,7 +1161,7 @@ class StepBase:
             merged = merge_batches([batches[t] for t in live]).to(batches[live[0]].pos.device)
         if warmup > 0 or not getattr(opt, "materialised", True):
             self._scope_streams()
-            side = ops.unexcluded_stream()  # (a pooled handle that is not one of this step's head / task streams)
+            side = sched.unexcluded_stream()  # (a pooled handle that is not one of this step's head / task streams)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(max(warmup, 1)):  # also materialises the flat buffers
@@ -1196,7 +1196,7 @@ class StepBase:
             clip = fuse_adam and self._clip_on()
             if clip and early is not None:
                 early["clip"], early["normed"] = True, []  # (its hooks take partial sums of the norm where they would start Adam slices)
-            with torch.cuda.graph(g, stream=ops.unexcluded_stream(), capture_error_mode=CAPTURE_MODE):
+            with torch.cuda.graph(g, stream=sched.unexcluded_stream(), capture_error_mode=CAPTURE_MODE):
                 ops.stamp("step_start")
                 self._hyper_in_graph = fuse_adam
                 self._fork_grad_clear(hyper=fuse_adam)  # (with the step's Adam constants when the optimizer is in the graph)
@@ -1206,17 +1206,17 @@ class StepBase:
                 if early is None and not fuse_adam:
                     self._install_tail(self._tail_only_plan(live))
                 if early is not None:
-                    ops.set_last_wgrad_hook(early["param"], early["hook"], pre=self._join_gradient_branches)
-                    ops.set_graphone_backward_hook(early.get("graphone_hook"))
+                    sched.set_last_wgrad_hook(early["param"], early["hook"], pre=self._join_gradient_branches)
+                    sched.set_graphone_backward_hook(early.get("graphone_hook"))
                     if early["tail"]:
                         g0 = opt.flat_g.data_ptr()
-                        ops.set_last_wgrad_tail(g0 + 4 * early["lo"], g0 + 4 * early["hi"])
+                        sched.set_last_wgrad_tail(g0 + 4 * early["lo"], g0 + 4 * early["hi"])
                 # (no join with the weight-gradient side stream when a backward() call returns: the gradients are read below, behind
-                #  ``join_wgrad(force=True)``)
+                #  ``sched.join_wgrad(force=True)``)
                 total, vectors = self._backward_pass(batches, merged)
                 self._join_zero()  # (a backward path that did not: the memset must at least precede the optimizer)
-                ops.set_last_wgrad_hook(None, None)
-                ops.join_wgrad(force=True)
+                sched.set_last_wgrad_hook(None, None)
+                sched.join_wgrad(force=True)
                 ops.stamp("backward_done")
                 # the Philox offset word of the dropout launches moves on INSIDE the graph (beside nothing that reads it: every
                 # dropout launch of the step is done when the optimizer starts): replay k draws the masks of offset base + k * stride
@@ -1267,7 +1267,7 @@ class StepBase:
 
     def _tail_only_plan(self, live):
         """(first TRN weight, flat range of the temporal pooling's slots) when the step can end with ONE grouped launch of the
-        pooling's weight gradients (ops.set_last_wgrad_tail) although no optimizer slice runs beside it -- the steps whose
+        pooling's weight gradients (sched.set_last_wgrad_tail) although no optimizer slice runs beside it -- the steps whose
         Adam follows a gradient exchange.  None when the layout does not allow it."""
         opt = self.optimizer
         tp = getattr(self.model, "temporal_pooling", None)
@@ -1290,8 +1290,8 @@ class StepBase:
         if plan is None:
             return
         g0 = self.optimizer.flat_g.data_ptr()
-        ops.set_last_wgrad_hook(plan[0], hook or (lambda: None))
-        ops.set_last_wgrad_tail(g0 + 4 * plan[1], g0 + 4 * plan[2])
+        sched.set_last_wgrad_hook(plan[0], hook or (lambda: None))
+        sched.set_last_wgrad_tail(g0 + 4 * plan[1], g0 + 4 * plan[2])
 
     def _early_adam_plan(self, live):
         """The step ends with two launches that have the chip to themselves one after the other: the weight gradient of
@@ -1312,7 +1312,7 @@ class StepBase:
             ok = hi > lo and lo % 8 == 0 and hi % 8 == 0 and sum(n for _, n in slots) == hi - lo  # (adjacent slots)
             return (lo, hi) if ok else None
         # the late Adam slice: the whole temporal pooling when its slots are one block (then the step's tail is ONE grouped
-        # launch of its weight gradients, ops.set_last_wgrad_tail), else the first linear alone
+        # launch of its weight gradients, sched.set_last_wgrad_tail), else the first linear alone
         # (a first linear whose weight gradient alone is >= 512 tiles of 128 x 128 -- the shipped pooling width 4096: 1152 -- fills
         #  the chip by itself: its launch stays alone and the late slice is that layer's, so that Adam over the rest of the pooling
         #  runs beside it; Hp = 4096 step 2.785-2.796 -> 2.770-2.772 ms.  At Hp = 1024 (288 tiles) the pooling's three weight
@@ -1332,8 +1332,8 @@ class StepBase:
 
             def issue(ev):
                 # (issued AFTER the last weight gradient's own launch, behind an event recorded here: see
-                #  ops.defer_after_next_launch -- the launch created first keeps the backward stream's hardware queue)
-                side = ops.wgrad_side_stream(main)
+                #  sched.defer_after_next_launch -- the launch created first keeps the backward stream's hardware queue)
+                side = sched.wgrad_side_stream(main)
                 plan["stream"].wait_event(ev)
                 if side is not None:
                     plan["stream"].wait_stream(side)
@@ -1352,7 +1352,7 @@ class StepBase:
                     if bump is not None:  # (no slice left to step here: the word still moves on)
                         ops.advance_rng_device(opt.flat_p.device)
             plan["rng_done"] = not plan.get("clip")  # (every dropout launch of the step has been issued: this is backward's end)
-            ops.defer_after_next_launch(issue)
+            sched.defer_after_next_launch(issue)
             plan["fired"] = True
         plan["hook"] = hook
         return plan
@@ -1368,7 +1368,7 @@ class StepBase:
         return []
 
     def _join_gradient_branches(self) -> None:
-        """Called on the backward stream right before the step's last weight gradient (ops.set_last_wgrad_hook ``pre``): the
+        """Called on the backward stream right before the step's last weight gradient (sched.set_last_wgrad_hook ``pre``): the
         branches of a one-call backward that run on other streams are joined HERE -- what they parked for the grouped
         weight-gradient launches (operands made on their streams) is issued next, and the optimizer slice that starts beside the
         last weight gradient reads every gradient they wrote.  (Autograd itself joins them only when backward() returns.)"""
@@ -1414,7 +1414,7 @@ class StepBase:
             # (handoff: every stage's side streams go to its region's collectives; single-writer gradient slots are stored: the
             #  collectives read final values either way)
             with (self._issuing(batches, merged, handoff=True, store=True),
-                  torch.cuda.graph(g, stream=ops.unexcluded_stream(), capture_error_mode=CAPTURE_MODE)):
+                  torch.cuda.graph(g, stream=sched.unexcluded_stream(), capture_error_mode=CAPTURE_MODE)):
                 ops.stamp("step_start")
                 # (the gradient buffer is cleared beside the forward pass, as in the one-rank capture: joined by _join_zero()
                 #  before the heads' backward writes the first gradient)
@@ -1441,7 +1441,7 @@ class StepBase:
                         def issue(ev):
                             side.wait_event(ev)
                             sync.step_started_chunks(opt, side)
-                        ops.defer_after_next_launch(issue)
+                        sched.defer_after_next_launch(issue)
                     self._install_tail(self._tail_only_plan(live), early_adam_hook if self._early_adam_ok() else None)
                     self._stage_b()
                     ops.stamp("stack_done")
@@ -1473,7 +1473,7 @@ class StepBase:
         # (``store``: one provider over the three captures -- every learnt slot is written in exactly one of them)
         with self._issuing(batches, merged, store=True):
             live = self._live(batches)
-            cap = ops.unexcluded_stream()  # (one capture stream for the three graphs, never a registered head / task stream)
+            cap = sched.unexcluded_stream()  # (one capture stream for the three graphs, never a registered head / task stream)
             with torch.cuda.graph(gs[0], stream=cap, capture_error_mode=CAPTURE_MODE):
                 # the gradient buffer is cleared BESIDE the forward pass, as in the one-rank capture (a fork and a join inside
                 # the first graph; _stage_a joins it before the heads' backward writes the first gradient)
@@ -1701,7 +1701,7 @@ class MTLStep(StepBase):
             compact_v[t] = v.detach()
             out = torch.empty(n_full[t], dtype=v.dtype, device=v.device)
             inv, src = live[t].live_inv, compact_v[t]
-            ops.park_rider(lambda: ops.expand_rows(src, inv, out=out), (src, inv, out))
+            sched.park_rider(lambda: ops.expand_rows(src, inv, out=out), (src, inv, out))
             return out
         # (a task whose labelled rows are an arithmetic progression -- one labelled node per sequence -- hands the grouped
         #  projection its full-height features and a row spec: a strided view stands for the gathered rows, no launch)
@@ -1825,9 +1825,9 @@ class MTLStep(StepBase):
                 total = torch.empty((), dtype=torch.float32, device=next(iter(src.values())).device)
                 acc = self._loss_acc_for(total.device)
                 if sc_vec is None:
-                    ops.park_rider(lambda: ops.weighted_mean_sum_into(total, [src.get(t) for t in order], [self.weights[t] for t in order],
-                                                                      [cnt.get(t) for t in order], acc=acc),
-                                   (total, *[src[t] for t in order if t in src]))
+                    sched.park_rider(lambda: ops.weighted_mean_sum_into(total, [src.get(t) for t in order], [self.weights[t] for t in order],
+                                                                        [cnt.get(t) for t in order], acc=acc),
+                                     (total, *[src[t] for t in order if t in src]))
                 else:
                     # with task scales the rider is egk_task_scale_grad: the objective under the scales, the RAW loss sums, and in the
                     # uncertainty mode d J / d log_var stored into the parameter's gradient slot (its one writer: final with the
@@ -1839,9 +1839,9 @@ class MTLStep(StepBase):
                         if ds is None:  # (the first step, before the flat buffers exist: an ordinary .grad)
                             ds = p.grad = torch.zeros_like(p)
                     out1 = total.view(1)
-                    ops.park_rider(lambda: ops.task_scale_grad_into(out1, [src.get(t) for t in order], [self.weights[t] for t in order],
-                                                                    sc_vec, [cnt.get(t) for t in order], log_var=lv, ds=ds, acc=acc),
-                                   (total, *[src[t] for t in order if t in src]))
+                    sched.park_rider(lambda: ops.task_scale_grad_into(out1, [src.get(t) for t in order], [self.weights[t] for t in order],
+                                                                      sc_vec, [cnt.get(t) for t in order], log_var=lv, ds=ds, acc=acc),
+                                     (total, *[src[t] for t in order if t in src]))
         return total, vectors, leaves
 
     compact_heads = True  # heads on the labelled rows only (data.live_label_rows); False: every row
@@ -1888,7 +1888,7 @@ class MTLStep(StepBase):
         # the heads' parked weight gradients (classifier banks, projections) go out as one launch NOW, beside the first
         # links of the backbone's dX chain; left parked, the backbone's first weight gradient would flush nine problems
         # as 8 + 1
-        ops.flush_wgrad(in_backward=False, force=True)
+        sched.flush_wgrad(in_backward=False, force=True)
         order = [t for t in feats if leaves[t].grad is not None]
         torch.autograd.backward([feats[t] for t in order], [leaves[t].grad for t in order])
         return total, vectors
@@ -2020,7 +2020,7 @@ class EgoPackStep(StepBase):
 
     def _early_adam_plan(self, live):
         """+ GraphONE's own slice (``graphone_adam`` off: none): its stage parameters (half of the step's parameters in config
-        4) have their final gradients when the grouped GraphONE backward returns (ops.set_graphone_backward_hook) -- Adam over
+        4) have their final gradients when the grouped GraphONE backward returns (sched.set_graphone_backward_hook) -- Adam over
         that slice then runs beside the backbone's backward instead of in the step's tail.  Round 4: the tail shrank from 275 to
         114 us and the backbone's backward grew by as much (2.746-2.751 against 2.72-2.80 ms, HISTORY.md: the
         memory-bound launch slows the chain it runs beside) -- opt-in then.  Round 5, with the searches grouped and the precise pass
@@ -2043,11 +2043,11 @@ class EgoPackStep(StepBase):
         def graphone_done():
             if plan["fired"] or plan["done"]:
                 return
-            ops.flush_wgrad(force=True)  # (what the interaction left parked; issued behind the backward stream's next launch)
+            sched.flush_wgrad(force=True)  # (what the interaction left parked; issued behind the backward stream's next launch)
             main = torch.cuda.current_stream()
 
             def issue(ev):
-                side = ops.wgrad_side_stream(main)
+                side = sched.wgrad_side_stream(main)
                 plan["stream"].wait_event(ev)
                 if side is not None:
                     plan["stream"].wait_stream(side)
@@ -2057,7 +2057,7 @@ class EgoPackStep(StepBase):
                         plan["normed"].append((g0, g1))
                     else:
                         opt.launch(None, g0, g1)
-            ops.defer_after_next_launch(issue)
+            sched.defer_after_next_launch(issue)
             plan["done"].append((g0, g1))
         plan["graphone_hook"] = graphone_done
         return plan
@@ -2168,7 +2168,7 @@ class EgoPackStep(StepBase):
                 # forked onto its own stream, the two chains run side by side (each alone leaves most of the chip idle)
                 main = torch.cuda.current_stream()
                 if self._precise_side is None:  # (a high-priority stream: 5.05-5.26 against 2.53-2.55 ms in the captured step)
-                    ops.exclude_wgrad_streams([self._own_stream("_precise_side")])
+                    sched.exclude_wgrad_streams([self._own_stream("_precise_side")])
                 side = self._precise_side
                 side.wait_stream(main)
                 tape = [] if self._one_pass_ok(batches, merged) else None

@@ -26,7 +26,7 @@ from typing import Dict, List, Literal, Tuple
 import torch
 import torch.nn as nn
 
-from ... import ops
+from ... import ops, sched
 from ..layers import LayerNorm, Linear, SAGEConv
 
 logger = logging.getLogger(__name__)
@@ -111,7 +111,7 @@ class GraphONE(nn.Module):
             fork.record(main)
             while len(self._task_streams) < len(items):
                 self._task_streams.append(torch.cuda.Stream())
-                ops.exclude_wgrad_streams(self._task_streams[-1:])
+                sched.exclude_wgrad_streams(self._task_streams[-1:])
             self.stream_of = {task: st for st, (task, _) in zip(self._task_streams, items)}  # (the stream each output was made on)
             for st, (task, f) in zip(self._task_streams, items):
                 st.wait_event(fork)
@@ -173,7 +173,7 @@ class GraphONE(nn.Module):
             fork.record(main)
             while len(self._task_streams) < len(items):
                 self._task_streams.append(torch.cuda.Stream())
-                ops.exclude_wgrad_streams(self._task_streams[-1:])
+                sched.exclude_wgrad_streams(self._task_streams[-1:])
             for st, (task, f) in zip(self._task_streams, items):
                 st.wait_event(fork)
                 f.record_stream(st)

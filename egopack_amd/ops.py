@@ -26,7 +26,8 @@ from typing import Optional
 
 import torch
 
-from . import _lib, switches
+from . import _lib, sched, switches
+from .sched import _last_wgrad, _wgrad_ln, join_wgrad  # noqa: F401  (bench.py's ``inline`` / ``side`` switches; the join after backward())
 
 F32, BF16 = 0, 1  # EGK_COMPUTE_* and EGK_F32 / EGK_BF16 element types
 X3 = 2            # host-side pseudo compute type: f32 values contracted as three bf16 products per K source (``_x3_expand``)
@@ -152,51 +153,10 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-# Launches forked to another stream are ISSUED one launch late: after the forking stream's NEXT library launch, behind an
-# event recorded at the fork point.  Same dependencies, same work -- but under hipGraph capture the order in which the two
-# children of a fork are created decides which of them stays on the parent's hardware queue (the first one), and the
-# other pays a cross-queue hand-off.  A backward pass naturally issues the forked weight gradient first, so the dX CHAIN
-# was the child that hopped, at every fork (tools/exp/fork_order.py: 12 links with a forked weight-gradient launch each,
-# 601 us per replay side-launch-first, 500 us chain-first).
-# ``on``: switched per step (``step_schedule``).
-_deferred = {"items": [], "busy": False, "on": True}
-
-
-def defer_after_next_launch(fn) -> None:
-    """Run ``fn(event)`` right after the current stream's next library launch (``event``: recorded on the current stream now);
-    immediately if the mechanism is off.  ``fn`` issues work on OTHER streams behind ``event``."""
-    cur = torch.cuda.current_stream()
-    ev = torch.cuda.Event()
-    ev.record(cur)
-    if not _deferred["on"]:
-        fn(ev)
-        return
-    _deferred["items"].append(((cur.device.index, cur.cuda_stream), ev, fn))
-
-
-def drain_deferred(all_streams: bool = True) -> None:
-    """Issue the deferred side launches now (every join point calls this first)."""
-    if _deferred["busy"] or not _deferred["items"]:
-        return
-    cur = torch.cuda.current_stream()
-    key = (cur.device.index, cur.cuda_stream)
-    take = [it for it in _deferred["items"] if all_streams or it[0] == key]
-    if not take:
-        return
-    _deferred["items"] = [it for it in _deferred["items"] if not (all_streams or it[0] == key)]
-    _deferred["busy"] = True
-    try:
-        for _, ev, fn in take:
-            fn(ev)
-    finally:
-        _deferred["busy"] = False
-
-
 def _ck(rc: int, what: str):
     if rc != 0:
         raise RuntimeError(f"{what} failed (code {rc}): {_lib.last_error()}")
-    if _deferred["items"] and not _deferred["busy"]:
-        drain_deferred(all_streams=False)
+    sched.drain_deferred(False)  # (this stream's late forks go out behind the launch)
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -753,350 +713,19 @@ def _grad_slot(param: Optional[torch.Tensor]):
     return None
 
 
-# ---- weight-gradient side streams --------------------------------------------------------------------------------
-# A dW contraction (64 tiles of 128 x 128, walked as <= 256 workgroups) feeds nothing but the optimizer, while the
-# dX chain it would sit in is a strict dependency chain of launches, many of them small.  When the gradient lands in
-# the flat buffer (no tensor goes back to autograd) the launch is put on a side stream that forks from the
-# backward stream at that point; ``join_wgrad()`` (queued as an end-of-backward callback of the autograd engine) joins
-# every side stream with the stream that called backward() before the gradients can be consumed.
-# Off by default: measured on MI355X it gains 3-4 % on the multi-task steps (M = 6144 backbone rows, heads on their
-# own streams) and loses 3-5 % on single-task steps (M = 2048: every launch is already a partial-chip launch);
-# egopack_amd.engine turns it on for steps with more than one enabled task (``step_schedule``).
-# ``handoff``: while on, the end of a backward() call does NOT make the backward stream wait for the side streams: the engine takes
-# them over with ``take_wgrad_streams`` and orders its gradient exchange behind them instead, so the next backward stage's dX chain
-# starts beside the weight gradients of the stage before.
-_wgrad = {"enabled": False, "streams": {}, "pending": [], "queued": False, "exclude": set(), "handoff": False}
-
-
-def exclude_wgrad_streams(streams) -> None:
-    """Backward work running on these streams keeps its weight-gradient launches (the task-head streams of the
-    engine already overlap each other; forking each of them again oversubscribes the hardware queues)."""
-    for st in streams:
-        _wgrad["exclude"].add((st.device.index, st.cuda_stream))
-
-
-
-def scope_excluded_streams(streams) -> None:
-    """The excluded set becomes exactly ``streams`` (a step calls this with ITS head / task / side streams when it starts issuing:
-    stream handles are pooled and handed out round-robin, so in a process that builds many steps -- a test suite -- the handles
-    excluded by steps long gone would otherwise pile up until every stream of the pool, the backward stream of the next step
-    included, counts as a head stream and its weight gradients take other launch paths than the same step in a fresh process)."""
-    _wgrad["exclude"] = {(st.device.index, st.cuda_stream) for st in streams if st is not None}
-
-
-def unexcluded_stream() -> torch.cuda.Stream:
-    """A stream from the pool whose handle is not registered as a head / task stream (torch hands pooled handles out
-    round-robin: a fresh ``torch.cuda.Stream()`` may alias one an earlier step excluded) -- for graph captures."""
-    keep = []
-    for _ in range(64):
-        st = torch.cuda.Stream()
-        if (st.device.index, st.cuda_stream) not in _wgrad["exclude"]:
-            return st
-        keep.append(st)
-    return keep[-1]
-
-
-def _wgrad_launch(in_place: bool, tensors, launch, in_backward: bool = True):
-    """Run ``launch()`` (weight / bias gradient kernels that only write persistent gradient slots) on the side
-    stream of the current stream; ``tensors`` are the temporaries it reads (kept alive for that stream).
-    ``in_backward`` False: called from ``join_wgrad`` itself (possibly after backward has returned): no end-of-backward
-    callback is installed, the caller joins right away."""
-    if not (_wgrad["enabled"] and in_place and tensors and tensors[0].is_cuda):
-        launch()
-        return
-    main = torch.cuda.current_stream()
-    key = (main.device.index, main.cuda_stream)
-    if key in _wgrad["exclude"]:
-        launch()
-        return
-    side = _wgrad["streams"].get(key)
-    if side is None:
-        side = _wgrad["streams"][key] = torch.cuda.Stream(device=main.device)
-
-    def issue(ev):
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            launch()
-        for t in tensors:
-            if t is not None:
-                t.record_stream(side)
-    defer_after_next_launch(issue)  # (the closure keeps the operands alive until then)
-    if side not in _wgrad["pending"]:
-        _wgrad["pending"].append(side)
-    if in_backward and not _wgrad["queued"]:  # join at the end of THIS backward pass, on the stream of the thread that called it
-        _wgrad["queued"] = True
-        torch.autograd.Variable._execution_engine.queue_callback(join_wgrad)
-
-
-# ---- deferred, grouped weight gradients ------------------------------------------------------------------------------------
-# A weight gradient of an H x H layer is a 64-tile contraction over K = all nodes: alone it fills a quarter of the chip,
-# and split-K to fill it costs slabs plus a second launch (measured: 23 us + 8.7 us per launch, 12 of them in the headline
-# step, all competing with the dX chain for the CUs).  With the queue on, such launches are PARKED (operands kept alive)
-# and issued SIX AT A TIME as one grouped launch on the side stream: 384 workgroups, no slabs, no reduce launch, a sixth
-# of the forks.  ``flush_wgrad`` issues what is parked (fewer than four at the end of backward).
-# ``count``: bf16 problems per grouped launch for the step being issued (None: WGRAD_GROUP_COUNT).
-_wq = {"on": False, "count": None, "items": [], "tiles": 0, "hold": [], "extra": [], "riders": []}
-# Six per launch: alone, six H x H problems in one launch of two 4-wave workgroups per CU run at 900 TF/s against 740 for
-# four on one 8-wave workgroup per CU (tools/gemm_group_bench.py: x4 70 us, x6 85 us, x8 133 us at K = 6144).  Inside the
-# step: 4 / 5 / 6 / 7 / 8 -> 1.558 / 1.60 / 1.538 / 1.60 / 1.595 ms (three alternating rounds of 200 steps; 12 H x H weight
-# gradients = two full launches of six).  Before the dX chain kept its hardware queue at the forks (defer_after_next_launch)
-# six measured WORSE than four (1.75 vs 1.68): the chain was the child that paid the queue hand-off behind every larger
-# launch.  The library takes up to 8 per launch.
-# Issued as soon as a group is full, on the side stream, beside whatever the dX chain does next.  Measured against issuing them on
-# the backward stream itself (1.598-1.604 ms) and against issuing them right before a backward row kernel and joining behind it
-# (1.774-1.782) in round 4: free-running groups 1.474-1.477 ms (HISTORY.md).
-WGRAD_GROUP_COUNT = 6
-WGRAD_GROUP_TILES = 64 * WGRAD_GROUP_COUNT
-F32_WGRAD_GROUP_COUNT = 8
-
-
-def park_rider(fn, hold=()) -> None:
-    """``fn()`` -- a launch that feeds nothing on the backward chain (a reported vector, say) -- rides with the next flush of the
-    parked weight gradients: issued on their side stream, in front of the grouped launch.  Run at once when nothing can be parked
-    (queue or side streams off, or on a task-head stream, whose parked work is issued by another stream)."""
-    if not (_wq["on"] and _wgrad["enabled"]) or _on_excluded_stream():
-        fn()
-        return
-    _wq["riders"].append(fn)
-    _wq["hold"].extend(t for t in hold if t is not None)
-
-
-def _wgrad_groupable(M, N, A, lda, B, ldb, K, compute=None) -> bool:
-    if not (_wq["on"] and _wgrad["enabled"]) or A.dtype != B.dtype:
-        return False
-    if A.dtype == torch.bfloat16:
-        ok = K % 64 == 0 and lda % 8 == 0 and ldb % 8 == 0
-    elif A.dtype == torch.float32 and compute == F32:
-        ok = K % 32 == 0 and lda % 4 == 0 and ldb % 4 == 0  # exact-f32 problems: the grouped f32 kernel (egk_gemm_grouped)
-    else:
-        return False
-    return (ok and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0 and ((M + 127) // 128) * ((N + 127) // 128) <= 128)
-
-
-def _on_excluded_stream() -> bool:
-    cur = torch.cuda.current_stream()
-    return (cur.device.index, cur.cuda_stream) in _wgrad["exclude"]
-
-
-def _wgrad_defer(args, kw, tensors, park_on_excluded: bool = False, park_only: bool = False) -> bool:
-    """Park the dW contraction ``gemm(*args, **kw)`` (transA, transB, accumulate into a gradient slot) for the next grouped
-    launch.  False: not eligible (the caller launches it itself).  On an excluded stream (the task-head streams of the
-    engine) nothing is parked unless ``park_on_excluded``: such a problem is only PARKED there -- it is issued by a later
-    flush from the backward stream, which by then has joined the head streams (engine._run_heads), never from the head
-    stream itself, where the operands parked by the OTHER head streams would be raced."""
-    M, N, A, lda, B, ldb, K = args[:7]
-    excluded = _on_excluded_stream()
-    if not _wgrad_groupable(M, N, A, lda, B, ldb, K, kw.get("compute")) or (excluded and not park_on_excluded):
-        return False
-    _wq["items"].append((args, kw))
-    _wq["hold"].extend(t for t in tensors if t is not None)
-    _wq["tiles"] += ((M + 127) // 128) * ((N + 127) // 128)
-    if excluded or park_only:  # (park_only: a later weight-gradient launch of the same step takes it along, see _take_parked)
-        return True
-    # exact-f32 problems are matrix-pipe bound: a launch lasts as long as the workgroups on its fullest CU, so EIGHT H x H
-    # problems (512 tiles = two per CU everywhere) where the bf16 launches take six
-    count = F32_WGRAD_GROUP_COUNT if A.dtype == torch.float32 else (_wq["count"] or WGRAD_GROUP_COUNT)
-    if len(_wq["items"]) >= count or _wq["tiles"] >= 64 * count:
-        flush_wgrad()
-    # (no end-of-backward join is scheduled for a parked problem: whoever switched the queue on -- engine.StepBase -- ends the
-    #  step's LAST backward() call with ``join_wgrad(force=True)``, which issues what is parked.  A join after every
-    #  backward() call of a step made the next call's dX chain wait for weight gradients that feed only the optimizer:
-    #  single-task step 0.915 -> 0.880 ms, multi-task steps neutral -- their heads' gradients were already parked this way)
-    return True
-
-
-def _take_parked(max_items: int):
-    """Remove and return up to ``max_items`` parked weight-gradient problems (all of them or none: a partial take would
-    reorder accumulations into one slot) for a caller that is about to issue a grouped launch of the same layout."""
-    items = _wq["items"]
-    if not items or len(items) > max_items:
-        return []
-    _wq["items"], _wq["tiles"] = [], 0
-    return items
-
-
-def _wgrad_defer_reduce(ws, dw, db, rows, cols, n_seg):
-    """Park a norm layer's dw / db reduction (egk_ln_bwd_reduce arguments) with the next grouped launch: the parked
-    reductions are issued as ONE launch (egk_ln_bwd_reduce_multi)."""
-    _wq["extra"].append((ws, dw, db, rows, cols, n_seg))
-    _wq["hold"].append(ws)
-
-
 def _launch_reductions(reds):
+    """The norm layers' dw / db reductions ``reds`` (sched.Reduction records): one launch per batch of ``sched.reduction_batches``."""
     lib = _lib.load()
-    # batches of at most 8 reductions with DISTINCT targets: a parameter used several times in one step (per-task backbone
-    # passes) has several reductions accumulating into the same dw / db -- those stay in separate, ordered launches
-    chunks, cur, seen = [], [], set()
-    for r in reds:
-        key = (r[1].data_ptr(), r[2].data_ptr())
-        if len(cur) == 8 or key[0] in seen or key[1] in seen:
-            chunks.append(cur)
-            cur, seen = [], set()
-        cur.append(r)
-        seen.update(key)
-    if cur:
-        chunks.append(cur)
-    for chunk in chunks:
-        n = len(chunk)
+    for batch in sched.reduction_batches(reds):
+        n = len(batch)
         if n == 1:
-            ws, dw, db, rows, cols, n_seg = chunk[0]
-            _ck(lib.egk_ln_bwd_reduce(_stream(), _p(ws), _p(dw), _p(db), rows, cols, n_seg), "egk_ln_bwd_reduce")
+            r = batch[0]
+            _ck(lib.egk_ln_bwd_reduce(_stream(), _p(r.ws), _p(r.dw), _p(r.db), r.rows, r.cols, r.n_seg), "egk_ln_bwd_reduce")
             continue
-        _ck(lib.egk_ln_bwd_reduce_multi(_stream(), _ptr_array([c[0] for c in chunk]), _ptr_array([c[1] for c in chunk]),
-                                        _ptr_array([c[2] for c in chunk]), (C.c_int32 * n)(*[c[3] for c in chunk]),
-                                        (C.c_int32 * n)(*[c[4] for c in chunk]), (C.c_int32 * n)(*[c[5] for c in chunk]), n),
+        _ck(lib.egk_ln_bwd_reduce_multi(_stream(), _ptr_array([r.ws for r in batch]), _ptr_array([r.dw for r in batch]),
+                                        _ptr_array([r.db for r in batch]), (C.c_int32 * n)(*[r.rows for r in batch]),
+                                        (C.c_int32 * n)(*[r.cols for r in batch]), (C.c_int32 * n)(*[r.n_seg for r in batch]), n),
             "egk_ln_bwd_reduce_multi")
-
-
-def flush_wgrad(in_backward: bool = True, force: bool = False):
-    """Issue what is parked.  On an excluded (task-head) stream nothing is issued -- unless ``force``: the engine's own
-    calls from the backward stream (end of a step's backward, the last-weight-gradient hook) must never leave parked work
-    behind, whatever stream handle the backward stream happens to have (a capture stream may alias a pooled handle that an
-    earlier step registered as excluded)."""
-    items, hold, extra, riders = _wq["items"], _wq["hold"], _wq["extra"], _wq["riders"]
-    if (not items and not extra and not riders) or (_on_excluded_stream() and not force):  # (a head stream never issues what others parked)
-        return
-    _wq["items"], _wq["hold"], _wq["extra"], _wq["tiles"], _wq["riders"] = [], [], [], 0, []
-    rng = _last_wgrad["tail"]
-    if rng is not None and (any(rng[0] <= it[0][7].data_ptr() < rng[1] for it in items)
-                            or any(rng[0] <= e[1].data_ptr() < rng[1] or rng[0] <= e[2].data_ptr() < rng[1] for e in extra)):
-        _last_wgrad["leaked"] = True  # (a gradient of the tail range leaves for the side stream: see last_wgrad_tail_on_backward_stream)
-
-    def launch():
-        stamp("wgrad_flush", seq=True)  # (on the side stream: when this flush's launches can start)
-        for fn in riders:
-            fn()
-        for i in range(0, len(items), 8):
-            chunk = items[i:i + 8]
-            stamp("wgrad_group", seq=True)
-            if len(chunk) == 1:
-                gemm(*chunk[0][0], **chunk[0][1])
-            else:
-                # beside the dX chain a group runs on 4-WAVE workgroups also when it has <= 256 tiles (alone the 8-wave
-                # two-wave-group variant is faster there: 70 vs 85 us for four H x H problems): an 8-wave workgroup takes
-                # 2 x 208 VGPRs of every SIMD of its CU and the chain's row kernels (96-193 VGPRs) wait for it to leave --
-                # a 13 us row-LayerNorm backward took 82 us behind such a launch; 4 waves leave 304.  Step 1.511 -> 1.498 ms
-                # (six alternating runs of 300 steps, every pair)
-                gemm_grouped(chunk, four_wave=len(chunk) <= 4)
-        if extra:
-            _launch_reductions(extra)
-        stamp("wgrad_flush_end", seq=True)
-    _wgrad_launch(True, hold, launch, in_backward)
-
-
-_last_wgrad = {"param": None, "hook": None, "pre": None, "inline": True, "tail": None, "leaked": False}
-
-
-def set_last_wgrad_tail(lo_ptr: int, hi_ptr: int) -> None:
-    """With a last-weight-gradient hook installed: parked weight gradients and norm reductions whose gradient slots lie in
-    the address range [lo_ptr, hi_ptr) are issued TOGETHER WITH the last weight gradient as one grouped launch on the
-    backward stream (the caller's hook starts the optimizer on everything OUTSIDE that range meanwhile and steps the range
-    after the launch).  Stand-alone, the first TRN linear's weight gradient alone takes 120 us and the two other TRN weight
-    gradients as a group of their own 66 us; the three in one launch 123 us (tools/exp/tail_group_bench.py).
-    (0, 0): only the last weight gradient itself (the default)."""
-    _last_wgrad["tail"] = (int(lo_ptr), int(hi_ptr)) if hi_ptr > lo_ptr else None
-    _last_wgrad["leaked"] = False
-
-
-def last_wgrad_tail_on_backward_stream() -> bool:
-    """Every gradient of the tail range (``set_last_wgrad_tail``) was issued on the BACKWARD stream: no parked problem or reduction
-    of the range left with an earlier flush for the side stream, no weight gradient of the range was launched there directly.  The
-    optimizer slice over the range may then follow the last weight gradient on the backward stream without waiting for the side
-    stream's queue (engine.StepBase: the step's tail)."""
-    return _last_wgrad["tail"] is not None and not _last_wgrad["leaked"]
-
-
-def _take_tail_items():
-    """Split what is parked by gradient-slot address: (contractions, reductions) inside the tail range are returned and
-    removed from the queue; the rest stays parked."""
-    rng = _last_wgrad["tail"]
-    if rng is None:
-        return [], []
-    inside = lambda t: rng[0] <= t.data_ptr() < rng[1]
-    items = [it for it in _wq["items"] if inside(it[0][7])]
-    _wq["items"] = [it for it in _wq["items"] if not inside(it[0][7])]
-    extra = [e for e in _wq["extra"] if inside(e[1]) and inside(e[2])]
-    _wq["extra"] = [e for e in _wq["extra"] if not (inside(e[1]) and inside(e[2]))]
-    _wq["tiles"] = sum(((it[0][0] + 127) // 128) * ((it[0][1] + 127) // 128) for it in _wq["items"])
-    return items, extra
-
-
-def set_last_wgrad_hook(param, hook, pre=None) -> None:
-    """``hook()`` is called (on the backward stream) just before the weight-gradient launch of ``param`` -- the engine
-    marks the LAST weight gradient of the step with it to start the optimizer on everything else meanwhile.  ``pre()`` runs
-    first, before what is parked is issued: a step whose backward has branches on other streams that nothing has joined yet
-    joins them there (parked problems of those branches read operands made on their streams)."""
-    _last_wgrad["param"], _last_wgrad["hook"], _last_wgrad["pre"] = param, hook, pre
-    if hook is None:
-        _last_wgrad["tail"] = None
-
-
-def wgrad_side_stream(main) -> Optional[torch.cuda.Stream]:
-    """The weight-gradient side stream of ``main`` if one has been created."""
-    return _wgrad["streams"].get((main.device.index, main.cuda_stream))
-
-
-def _ln_reduce_on_side(slot_w, slot_b, x) -> bool:
-    """The norm layers' dw / db reduction moves to the weight-gradient side stream when there is one for this stream
-    (side streams on, stream not one of the excluded head / task streams) and both gradients accumulate in place."""
-    if not (_wgrad["enabled"] and _wgrad_ln["side"] and slot_w is not None and slot_b is not None and x.is_cuda):
-        return False
-    main = torch.cuda.current_stream()
-    return (main.device.index, main.cuda_stream) not in _wgrad["exclude"]
-
-
-_wgrad_ln = {"side": True}  # (bench.py --ln-reduce-inline: False)
-
-
-def join_wgrad(force: bool = False):
-    """The current stream waits for every weight-gradient side stream with work in flight (call after backward,
-    before the gradients are read: optimizer step, gradient exchange, or the end of a hipGraph capture).  ``force``: the
-    caller IS the step's backward stream (see flush_wgrad)."""
-    if _wgrad["handoff"] and not force:
-        return  # (end-of-backward callback while the engine hands the side streams to its exchange: take_wgrad_streams)
-    flush_wgrad(in_backward=False, force=force)
-    drain_deferred()
-    cur = torch.cuda.current_stream() if _wgrad["pending"] else None
-    for side in _wgrad["pending"]:
-        cur.wait_stream(side)
-    _wgrad["pending"].clear()
-    _wgrad["queued"] = False
-
-
-def take_wgrad_streams() -> list:
-    """Issue whatever is parked, then hand over the side streams with weight-gradient work in flight: the CALLER orders its
-    consumer of the gradients behind them (and eventually joins that consumer into the backward stream)."""
-    flush_wgrad(in_backward=False, force=True)
-    drain_deferred()
-    streams = list(_wgrad["pending"])
-    _wgrad["pending"].clear()
-    _wgrad["queued"] = False
-    return streams
-
-
-@contextlib.contextmanager
-def step_schedule(side_streams: bool, grouping: bool, count: Optional[int] = None, deferred_forks: bool = True, handoff: bool = False):
-    """The scheduler's settings for ONE step being issued (egopack_amd.engine: every eager step and every capture runs inside one):
-    weight gradients on side streams, the parking queue with ``count`` bf16 problems per grouped launch (None: WGRAD_GROUP_COUNT),
-    the late issue of forked launches, the hand-over of the side streams to a gradient exchange.
-    Entering and leaving both drop whatever is parked or deferred: a step ends with ``join_wgrad`` (which issues it), so something
-    is left only when a step was abandoned by an exception -- its launches must not surface in, and its weight gradients must not
-    be accumulated by, the next step.  Leaving -- normally or through an exception -- also clears the hooks a step installs while
-    it runs (``set_last_wgrad_hook`` with its ``pre`` and tail range, ``set_graphone_backward_hook``): no hook outlives its step.
-    Scopes nest: the inner one hands the outer one's settings back."""
-    def install(enabled, on, per_launch, late, hand):
-        _wgrad["enabled"], _wgrad["handoff"] = bool(enabled), bool(hand)
-        _wq["on"], _wq["count"] = bool(on), None if per_launch is None else int(per_launch)
-        _wq["items"], _wq["hold"], _wq["extra"], _wq["tiles"], _wq["riders"] = [], [], [], 0, []
-        _deferred["on"], _deferred["items"] = bool(late), []
-    prev = (_wgrad["enabled"], _wq["on"], _wq["count"], _deferred["on"], _wgrad["handoff"])
-    install(side_streams, grouping, count, deferred_forks, handoff)
-    try:
-        yield
-    finally:
-        set_last_wgrad_hook(None, None)
-        set_graphone_backward_hook(None)
-        install(*prev)
 
 
 def _operand_layout_ok(g: torch.Tensor, esize: int) -> bool:
@@ -1316,38 +945,11 @@ class _Linear(torch.autograd.Function):
         if needs[1]:
             slot = _grad_slot(Wp)
             out = slot if slot is not None else torch.zeros(W.shape, dtype=torch.float32, device=g.device)
-            last = Wp is _last_wgrad["param"] and _last_wgrad["hook"] is not None
-            tail_items, tail_extra = [], []
-            if last:
-                if _last_wgrad["pre"] is not None:
-                    _last_wgrad["pre"]()
-                tail_items, tail_extra = _take_tail_items()  # (issued below; the argument tuples keep their operands alive)
-                flush_wgrad(force=True)  # (the hook starts the optimizer on every other slot: their gradients must be issued)
-                _last_wgrad["hook"]()
-            # the bias gradient colsum(dY) rides on the dW launch (summed from the dY^T tile already in LDS).  The LAST
-            # weight gradient of the step stays on the backward stream: nothing is left to overlap it with there, and the
-            # hop to the side stream and back costs two cross-queue hand-offs (~10 us each) on the step's tail.
+            # the bias gradient colsum(dY) rides on the dW launch (summed from the dY^T tile already in LDS)
             in_place = slot is not None and (db_out is None or db is None)
             dw_args = (N, K1, g, g.stride(0), x, K1, M, out, K1)
             dw_kw = dict(transA=True, transB=True, accumulate=True, compute=ctx.compute, dbias=db_out)
-            if last and (tail_items or tail_extra) and in_place and ctx.compute in (BF16, F32):
-                # the step's tail as ONE grouped launch on the backward stream: the parked weight gradients of the tail range
-                # + this one (the largest last), then the norm reductions of the range
-                if tail_items:
-                    gemm_grouped(tail_items + [(dw_args, dw_kw)])
-                else:
-                    gemm(*dw_args, **dw_kw)
-                if tail_extra:
-                    _launch_reductions(tail_extra)
-            elif not (in_place and not last and ctx.compute in (BF16, F32) and _wgrad_defer(dw_args, dw_kw, (g, x))):
-                rng = _last_wgrad["tail"]
-                if rng is not None and not last and rng[0] <= out.data_ptr() < rng[1]:
-                    _last_wgrad["leaked"] = True  # (launched below on the side stream)
-                for it in tail_items:  # (not eligible after all: issue what was taken, in order)
-                    gemm(*it[0], **it[1])
-                if tail_extra:
-                    _launch_reductions(tail_extra)
-                _wgrad_launch(in_place and not (last and _last_wgrad["inline"]), (g, x), lambda: gemm(*dw_args, **dw_kw))
+            sched.issue_last_or_wgrad(Wp, out, dw_args, dw_kw, (g, x), in_place, ctx.compute in (BF16, F32))
             dW = None if slot is not None else out
         elif db_out is not None:
             _colsum_into(g, db_out, True)
@@ -1355,9 +957,9 @@ class _Linear(torch.autograd.Function):
             K2 = x2.shape[1]
             slot = _grad_slot(W2p)
             out2 = slot if slot is not None else torch.zeros(W2.shape, dtype=torch.float32, device=g.device)
-            _wgrad_launch(slot is not None, (g, x2),
-                          lambda: gemm(N, K2, g, g.stride(0), x2, x2.stride(0), M, out2, K2, transA=True, transB=True,
-                                       accumulate=True, compute=ctx.compute))
+            sched._wgrad_launch(slot is not None, (g, x2),
+                                lambda: gemm(N, K2, g, g.stride(0), x2, x2.stride(0), M, out2, K2, transA=True, transB=True,
+                                             accumulate=True, compute=ctx.compute))
             dW2 = None if slot is not None else out2
         dres = _match(dy, ctx.res_dtype) if (has_res and needs[5]) else None
         if dres is not None and ctx.res_sink is not None:
@@ -1439,8 +1041,7 @@ class _ClassifierBank(torch.autograd.Function):
             gemm(M, K, gbuf, N, Wop, K, N, dx, K, transB=True, compute=ctx.compute)
         w_args = (N, K, gbuf, N, x, K, M, views["wg"], K)
         w_kw = dict(transA=True, transB=True, accumulate=True, compute=ctx.compute, dbias=views["bg"])
-        if not (ctx.compute == BF16 and _wgrad_defer(w_args, w_kw, (gbuf, x), park_on_excluded=True)):
-            _wgrad_launch(True, (gbuf, x), lambda: gemm(*w_args, **w_kw))
+        sched.issue_wgrad(w_args, w_kw, (gbuf, x), park_on_excluded=True, eligible=ctx.compute == BF16)
         return dx, None, None, None, None, None
 
 
@@ -1507,8 +1108,7 @@ class _GroupedBanks(torch.autograd.Function):
         for w_args, w_kw, hold in parked:
             # parked WITHOUT a join of their own: the projection heads' backward, which follows in the same step, takes them
             # along in its first grouped weight-gradient launch (one launch and one end-of-backward join fewer in the chain)
-            if not _wgrad_defer(w_args, w_kw, hold, park_on_excluded=True, park_only=True):
-                _wgrad_launch(True, hold, lambda a=w_args, kw=w_kw: gemm(*a, **kw))
+            sched.issue_wgrad(w_args, w_kw, hold, park_on_excluded=True, park_only=True)
         return (None, None, None, None, *dxs)
 
 
@@ -1611,12 +1211,12 @@ class _MultiLinear(torch.autograd.Function):
                     gemm(N, K, dy[off:off + m], ldy, x, K, m, out, K, transA=True, transB=True, accumulate=True,
                          compute=ctx.compute, slot_final=len(xs) == 1)  # (several launches add up one gradient: not final in any of them)
                     off += m
-            _wgrad_launch(slot is not None, (dy, *xs), launch_dw)
+            sched._wgrad_launch(slot is not None, (dy, *xs), launch_dw)
             dW = None if slot is not None else out
         if bp is not None and needs[1]:
             slot = _grad_slot(bp)
             outb = slot if slot is not None else torch.zeros(N, dtype=torch.float32, device=dy.device)
-            _wgrad_launch(slot is not None, (dy,), lambda: _colsum_into(dy, outb, True))
+            sched._wgrad_launch(slot is not None, (dy,), lambda: _colsum_into(dy, outb, True))
             db = None if slot is not None else outb
         return (dW, db, None, *dxs)
 
@@ -1693,14 +1293,14 @@ class _GroupedProjection(torch.autograd.Function):
                        dict(transB=True, compute=cmp)) for g in range(G)])
         dw2 = [((H2, H1, dfs[g], dfs[g].stride(0), a[ptr[g]:ptr[g + 1]], H1, rows[g], slots[g][4], H1),
                 dict(transA=True, transB=True, accumulate=True, compute=cmp, dbias=slots[g][5])) for g in range(G)]
-        proj_park = all(_wgrad_groupable(*pa[:7]) for pa, _ in dw2)  # (the parking queue must be on and take them)
+        proj_park = all(sched._wgrad_groupable(*pa[:7]) for pa, _ in dw2)  # (the parking queue must be on and take them)
         if proj_park:
             for g, (pa, pk) in enumerate(dw2):
-                if not _wgrad_defer(pa, pk, (dfs[g], a), park_on_excluded=True, park_only=True):
+                if not sched._wgrad_defer(pa, pk, (dfs[g], a), park_on_excluded=True, park_only=True):
                     raise RuntimeError("grouped_projection: a weight gradient announced as parkable was refused")
         else:
-            riders = _take_parked(8 - G)  # (the classifier banks' weight gradients, parked by their backward)
-            _wgrad_launch(True, (a, *dfs), lambda: gemm_grouped(riders + dw2))
+            riders = sched._take_parked(8 - G)  # (the classifier banks' weight gradients, parked by their backward)
+            sched._wgrad_launch(True, (a, *dfs), lambda: gemm_grouped(riders + dw2))
         dh1 = torch.empty_like(h1)
         grid = lib.egk_rowln_bwd_ws_rows(max(rows))
         ws = torch.empty(G * grid * 2 * H1 * 4, dtype=torch.uint8, device=dev)  # (own buffer: reduced on the side stream)
@@ -1708,12 +1308,12 @@ class _GroupedProjection(torch.autograd.Function):
         _ck(lib.egk_rowln_group_bwd(_stream(), _p(da), _p(h1), _ptr_array(lw), _ptr_array(lb), row_ptr, G, _p(mean), _p(rstd),
                                     _p(dh1), _p(ws), H1, 1, _dt(h1)), "egk_rowln_group_bwd")
 
-        reds = [(ws[g * grid * 2 * H1 * 4:], slots[g][2], slots[g][3], max(rows), H1, 0) for g in range(G)]
+        reds = [sched.Reduction(ws[g * grid * 2 * H1 * 4:], slots[g][2], slots[g][3], max(rows), H1, 0) for g in range(G)]
         if proj_park:
             for r in reds:
-                _wgrad_defer_reduce(*r)
+                sched.issue_ln_reduce(*r)  # (parked: the queue is on)
         else:
-            _wgrad_launch(True, (ws,), lambda: _launch_reductions(reds))
+            sched._wgrad_launch(True, (ws,), lambda: _launch_reductions(reds))
         dxs = [None] * G
         if any(ctx.needs_input_grad[4:4 + G]):
             # ONE buffer for the feature gradients of all groups at their FULL heights, consecutive (the fused backbone pass takes
@@ -1738,12 +1338,12 @@ class _GroupedProjection(torch.autograd.Function):
             dxs = [dx[fptr[g]:fptr[g + 1]] for g in range(G)]
         dw1 = [((H1, H, dh1[ptr[g]:ptr[g + 1]], H1, xs[g], xs[g].stride(0), rows[g], slots[g][0], H),
                 dict(transA=True, transB=True, accumulate=True, compute=cmp, dbias=slots[g][1])) for g in range(G)]
-        if proj_park and all(_wgrad_groupable(*pa[:7]) for pa, _ in dw1):
+        if proj_park and all(sched._wgrad_groupable(*pa[:7]) for pa, _ in dw1):
             for g, (pa, pk) in enumerate(dw1):
-                if not _wgrad_defer(pa, pk, (dh1, xs[g]), park_on_excluded=True, park_only=True):
+                if not sched._wgrad_defer(pa, pk, (dh1, xs[g]), park_on_excluded=True, park_only=True):
                     raise RuntimeError("grouped_projection: a weight gradient announced as parkable was refused")
         else:
-            _wgrad_launch(True, (dh1, *xs), lambda: gemm_grouped(dw1))
+            sched._wgrad_launch(True, (dh1, *xs), lambda: gemm_grouped(dw1))
         return (None, None, None, None, *dxs, *([None] * (6 * G)))
 
 
@@ -1859,15 +1459,6 @@ def grouped_projection(xs, nets, compute=None, specs=None):
 
 
 # ---- GraphONE: the stages of several auxiliary tasks as ONE chain of grouped launches --------------------------------------
-_g1_hook = {"fn": None}
-
-
-def set_graphone_backward_hook(fn) -> None:
-    """``fn()`` is called on the backward stream at the end of the grouped GraphONE backward (``_GraphOneStages``), when every
-    gradient of the stage parameters is either issued or parked -- the engine starts the optimizer on that region there."""
-    _g1_hook["fn"] = fn
-
-
 class _GraphOneStages(torch.autograd.Function):
     """The D stages of G auxiliary tasks' GraphONE interaction (reference models/graphONE/graphONE.py:94-115, the N feature
     rows only -- see models/graphONE/graphONE.py here) as one chain of launches over all tasks: per stage G max aggregations,
@@ -1935,12 +1526,12 @@ class _GraphOneStages(torch.autograd.Function):
             raise RuntimeError("graphone_stages: the parameters need in-place gradient slots (optim.FlatAdam materialised)")
         need_f0 = ctx.needs_input_grad[0]
         a0, m0 = saved[4], saved[1]
-        park = (_wgrad_groupable(H, H1, dy[0], dy[0].stride(0), a0, H1, N, cmp) and _wgrad_groupable(H1, H, a0, H1, m0, H, N, cmp)
+        park = (sched._wgrad_groupable(H, H1, dy[0], dy[0].stride(0), a0, H1, N, cmp) and sched._wgrad_groupable(H1, H, a0, H1, m0, H, N, cmp)
                 and all(d.stride(0) % 8 == 0 and d.data_ptr() % 16 == 0 for d in dy))
         pending, reds = [], []  # without the parking queue: grouped launches of <= 8 on the side stream, below
 
         def wgrad(pa, pk, keep):
-            if not (park and _wgrad_defer(pa, pk, keep, park_on_excluded=True)):
+            if not (park and sched._wgrad_defer(pa, pk, keep, park_on_excluded=True)):
                 pending.append((pa, pk, keep))
         df = None
         for s in reversed(range(D)):
@@ -1958,9 +1549,9 @@ class _GraphOneStages(torch.autograd.Function):
             _ck(lib.egk_rowln_group_bwd(_stream(), _p(da), _p(h), _ptr_array(lw), _ptr_array(lb), row_ptr, G, _p(mean), _p(rstd),
                                         _p(dh), _p(ws), H1, 1, _dt(h)), "egk_rowln_group_bwd")
             for g in range(G):
-                red = (ws[g * grid * 2 * H1 * 4:], slots[s][g][2], slots[s][g][3], N, H1, 0)
+                red = sched.Reduction(ws[g * grid * 2 * H1 * 4:], slots[s][g][2], slots[s][g][3], N, H1, 0)
                 if park:
-                    _wgrad_defer_reduce(*red)
+                    sched.issue_ln_reduce(*red)  # (parked: the queue is on)
                 else:
                     reds.append(red)
             if s > 0 or need_f0:
@@ -1978,14 +1569,14 @@ class _GraphOneStages(torch.autograd.Function):
                       dict(transA=True, transB=True, accumulate=True, compute=cmp), (dh, f))
             if s > 0:
                 dy = [sl(df, g) for g in range(G)]
-        if park and _g1_hook["fn"] is not None:
-            _g1_hook["fn"]()  # (every gradient of the interaction's parameters has been issued or parked: engine.EgoPackStep)
+        if park and sched._g1_hook["fn"] is not None:
+            sched._g1_hook["fn"]()  # (every gradient of the interaction's parameters has been issued or parked: engine.EgoPackStep)
         for i in range(0, len(pending), 8):
             chunk = pending[i:i + 8]
             keep = tuple(t for _, _, kp in chunk for t in kp)
-            _wgrad_launch(True, keep, lambda chunk=chunk: gemm_grouped([(pa, pk) for pa, pk, _ in chunk]))
+            sched._wgrad_launch(True, keep, lambda chunk=chunk: gemm_grouped([(pa, pk) for pa, pk, _ in chunk]))
         if reds:
-            _wgrad_launch(True, tuple(r[0] for r in reds), lambda: _launch_reductions(reds))
+            sched._wgrad_launch(True, tuple(r.ws for r in reds), lambda: _launch_reductions(reds))
         return (df if need_f0 else None, *([None] * (8 + 6 * G * D)))
 
 
@@ -2108,21 +1699,14 @@ class _RowLN(torch.autograd.Function):
         dw = slot_w if slot_w is not None else torch.zeros_like(w)
         db = slot_b if slot_b is not None else torch.zeros_like(b)
         nbytes = 2 * lib.egk_rowln_bwd_ws_rows(rows) * cols * 4
-        if _ln_reduce_on_side(slot_w, slot_b, x):
-            # dw / db feed nothing but the optimizer: their reduction goes to the weight-gradient side stream, from a
-            # workspace of its own (the shared one may be rewritten by the next launch of this stream)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            _ck(lib.egk_rowln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(mean), _p(rstd), _p(mask), _p(dx), None, None,
-                                  _p(ws), rows, cols, int(ctx.relu), ctx.p, _dt(x)), "egk_rowln_bwd")
-            if _wq["on"] and _wgrad["enabled"]:
-                _wgrad_defer_reduce(ws, dw, db, rows, cols, 0)
-            else:
-                _wgrad_launch(True, (ws,), lambda: _ck(lib.egk_ln_bwd_reduce(_stream(), _p(ws), _p(dw), _p(db), rows, cols, 0),
-                                                       "egk_ln_bwd_reduce"))
-            return dx, None, None, None, None, None, None
-        ws = workspace(nbytes, x.device)
-        _ck(lib.egk_rowln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(mean), _p(rstd), _p(mask), _p(dx), _p(dw), _p(db),
-                              _p(ws), rows, cols, int(ctx.relu), ctx.p, _dt(x)), "egk_rowln_bwd")
+        # dw / db feed nothing but the optimizer: their reduction goes to the weight-gradient side stream when there is one, from a
+        # workspace of its own (the shared one may be rewritten by the next launch of this stream)
+        side = sched._ln_reduce_on_side(slot_w, slot_b, x)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if side else workspace(nbytes, x.device)
+        _ck(lib.egk_rowln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(mean), _p(rstd), _p(mask), _p(dx), None if side else _p(dw),
+                              None if side else _p(db), _p(ws), rows, cols, int(ctx.relu), ctx.p, _dt(x)), "egk_rowln_bwd")
+        if side:
+            sched.issue_ln_reduce(ws, dw, db, rows, cols, 0)
         return dx, (None if slot_w is not None else dw), (None if slot_b is not None else db), None, None, None, None
 
 
@@ -2287,29 +1871,18 @@ class _GraphLN(torch.autograd.Function):
             ws_col = torch.empty(lib.egk_rowln_bwd_ws_rows(rows) * 2 * cols, dtype=torch.float32, device=x.device)
             _ck(lib.egk_graphln_bwd_apply(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(stats), _p(dx), _p(seg_ptr), n_seg, rows,
                                           cols, ctx.eps, ctx.slope, _p(pre[0]), pre[1], _p(ws_col), _dt(x)), "egk_graphln_bwd_apply")
-            if _ln_reduce_on_side(slot_w, slot_b, x):
-                if _wq["on"] and _wgrad["enabled"]:
-                    _wgrad_defer_reduce(ws_col, dw, db, rows, cols, 0)
-                else:
-                    _wgrad_launch(True, (ws_col,), lambda: _ck(lib.egk_ln_bwd_reduce(_stream(), _p(ws_col), _p(dw), _p(db), rows, cols, 0),
-                                                               "egk_ln_bwd_reduce"))
-                return dx, None, None, None, None, None, None, None
-            _ck(lib.egk_ln_bwd_reduce(_stream(), _p(ws_col), _p(dw), _p(db), rows, cols, 0), "egk_ln_bwd_reduce")
+            if sched._ln_reduce_on_side(slot_w, slot_b, x):
+                sched.issue_ln_reduce(ws_col, dw, db, rows, cols, 0)
+            else:
+                _ck(lib.egk_ln_bwd_reduce(_stream(), _p(ws_col), _p(dw), _p(db), rows, cols, 0), "egk_ln_bwd_reduce")
             return dx, (None if slot_w is not None else dw), (None if slot_b is not None else db), None, None, None, None, None
         nbytes = lib.egk_graphln_ws_bytes(rows, cols, n_seg)
-        if _ln_reduce_on_side(slot_w, slot_b, x):  # (see _RowLN.backward)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            _ck(lib.egk_graphln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(stats), _p(dx), None, None, _p(seg_ptr),
-                                    n_seg, rows, cols, ctx.eps, ctx.slope, _p(ws), _dt(x)), "egk_graphln_bwd")
-            if _wq["on"] and _wgrad["enabled"]:
-                _wgrad_defer_reduce(ws, dw, db, rows, cols, n_seg)
-            else:
-                _wgrad_launch(True, (ws,), lambda: _ck(lib.egk_ln_bwd_reduce(_stream(), _p(ws), _p(dw), _p(db), rows, cols, n_seg),
-                                                       "egk_ln_bwd_reduce"))
-            return dx, None, None, None, None, None, None, None
-        ws = workspace(nbytes, x.device)
-        _ck(lib.egk_graphln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(stats), _p(dx), _p(dw), _p(db), _p(seg_ptr),
-                                n_seg, rows, cols, ctx.eps, ctx.slope, _p(ws), _dt(x)), "egk_graphln_bwd")
+        side = sched._ln_reduce_on_side(slot_w, slot_b, x)  # (see _RowLN.backward)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if side else workspace(nbytes, x.device)
+        _ck(lib.egk_graphln_bwd(_stream(), _p(dy), _p(x), _p(w), _p(b), _p(stats), _p(dx), None if side else _p(dw),
+                                None if side else _p(db), _p(seg_ptr), n_seg, rows, cols, ctx.eps, ctx.slope, _p(ws), _dt(x)), "egk_graphln_bwd")
+        if side:
+            sched.issue_ln_reduce(ws, dw, db, rows, cols, n_seg)
         return dx, (None if slot_w is not None else dw), (None if slot_b is not None else db), None, None, None, None, None
 
 
@@ -2541,17 +2114,17 @@ class _SageMean(torch.autograd.Function):
             gemm(*r_args, **r_kw)
         # eligibility is decided ONCE for both problems (same shapes; both operand pairs checked, and the stream): a pair of which
         # only the first was parked would be accumulated twice by the fallback below
-        park = (in_place and ctx.compute in (BF16, F32) and not _on_excluded_stream()
-                and _wgrad_groupable(Ho, H, g, g.stride(0), agg, H, N, ctx.compute)
-                and _wgrad_groupable(Ho, H, g, g.stride(0), h, H, N, ctx.compute))
+        park = (in_place and ctx.compute in (BF16, F32) and not sched._on_excluded_stream()
+                and sched._wgrad_groupable(Ho, H, g, g.stride(0), agg, H, N, ctx.compute)
+                and sched._wgrad_groupable(Ho, H, g, g.stride(0), h, H, N, ctx.compute))
         if park:
             # one at a time: the first may flush a full group
-            if not _wgrad_defer(l_args, l_kw, (g, agg)):
+            if not sched._wgrad_defer(l_args, l_kw, (g, agg)):
                 raise RuntimeError("sage_mean_layer: a weight gradient announced as parkable was refused")
-            if not _wgrad_defer(r_args, r_kw, (g, h)):
+            if not sched._wgrad_defer(r_args, r_kw, (g, h)):
                 raise RuntimeError("sage_mean_layer: a weight gradient announced as parkable was refused")
         else:
-            _wgrad_launch(in_place, (g, agg, h), launch_out_grads)
+            sched._wgrad_launch(in_place, (g, agg, h), launch_out_grads)
         d_agg = torch.empty_like(h)
         d_pre = torch.empty_like(h)  # gradient at the projection's pre-activation: transposed gather gated by xp > 0
         a_args, a_kw = (N, H, g, g.stride(0), Wl_o, H, Ho, d_agg, H), dict(transB=True, compute=ctx.compute)
@@ -2573,12 +2146,12 @@ class _SageMean(torch.autograd.Function):
                 gemm(*h_args, **h_kw)
         p_args, p_kw = (H, H, d_pre, H, h, H, N, dWp, H), dict(transA=True, transB=True, accumulate=True, compute=ctx.compute,
                                                                dbias=dbp)
-        if not (rWp is None and rbp is None and ctx.compute in (BF16, F32) and _wgrad_defer(p_args, p_kw, (d_pre, h))):
-            _wgrad_launch(rWp is None and rbp is None, (d_pre, h), lambda: gemm(*p_args, **p_kw))
-        if ctx.res_src is not None and _last_wgrad["tail"] is not None:
+        p_in_place = rWp is None and rbp is None
+        sched.issue_wgrad(p_args, p_kw, (d_pre, h), eligible=p_in_place and ctx.compute in (BF16, F32), in_place=p_in_place)
+        if ctx.res_src is not None:
             # the FIRST layer of the stack (its backward is the stack's last): what is parked goes out now, beside the temporal
             # pooling's backward chain -- the step's tail launch then holds the temporal pooling's weight gradients only
-            flush_wgrad()
+            sched.flush_wgrad(before_tail=True)
         return (d_h, rWp, rbp, rWl, rbl, rWr, None, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
@@ -3371,9 +2944,9 @@ class _RowDotCE2Multi(torch.autograd.Function):
         if in_slots and any(d is not None for d in (*dws, *dbs)):
             # the classifiers' gradients feed nothing on the chain and land in the optimizer's slots: their launch (27 us on the
             # critical chain of BASELINE config 4 between the head and backward) rides with the next flush of the parked weight
-            # gradients (``park_rider``: at once when nothing can be parked)
+            # gradients (``sched.park_rider``: at once when nothing can be parked)
             launch(1)
-            park_rider(lambda: launch(2), hold=(*fs, gws, *w_ops))
+            sched.park_rider(lambda: launch(2), hold=(*fs, gws, *w_ops))
         else:
             launch(0)
         ctx.keep = (fs, w_ops, biases, gws)

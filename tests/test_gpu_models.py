@@ -31,6 +31,7 @@ def A():
     import egopack_amd.data as data
     import egopack_amd.engine as engine
     import egopack_amd.ops as ops
+    import egopack_amd.sched as sched
     from egopack_amd.criterion import BCEWithLogitsNone, CrossEntropyNone, MetricSelectorWrapper
     from egopack_amd.graphone import build_graphone
     from egopack_amd.models import Graph
@@ -670,7 +671,7 @@ def test_onehot_sigmoid_focal_kernel_vs_autograd(A, gamma, alpha):
 @pytest.mark.parametrize("what", ["grouped_heads", "wgrad_grouping"])
 def test_grouped_launches_equal_the_per_problem_launches(A, what):
     """engine.MTLStep with (a) the task heads' projections as ONE chain of grouped launches (ops.grouped_projection) and (b) the
-    H x H weight gradients parked and issued four at a time as one grouped launch (ops._wgrad_defer), each against the same
+    H x H weight gradients parked and issued four at a time as one grouped launch (sched._wgrad_defer), each against the same
     step without it: objective, loss vectors and every parameter after 3 Adam steps (bf16 mode: the paths run the same
     kernel bodies with other tile variants / no split-K -> fp32 accumulation-order noise, then bf16 rounding)."""
     import argparse
@@ -805,9 +806,9 @@ def test_parked_weight_gradients_survive_an_aliased_backward_stream(A):
         opt = A.FlatAdam(params, lr=1e-3, weight_decay=1e-5)
         step = A.engine.MTLStep(model, tasks, crit, weights, opt, fused_backbone=True)
         st = torch.cuda.Stream()
-        key = (st.device.index, st.cuda_stream)
+        key = A.sched.stream_key(st)
         if alias:
-            A.ops._wgrad["exclude"].add(key)
+            A.sched._wgrad.exclude.add(key)
         try:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
@@ -816,7 +817,7 @@ def test_parked_weight_gradients_survive_an_aliased_backward_stream(A):
             torch.cuda.current_stream().wait_stream(st)
             torch.cuda.synchronize()
         finally:
-            A.ops._wgrad["exclude"].discard(key)
+            A.sched._wgrad.exclude.discard(key)
         return opt.flat_p.clone()
 
     try:

@@ -632,63 +632,201 @@ def test_dual_replay_refuses_a_tape_that_was_not_consumed():
 
 
 def test_step_schedule_installs_its_settings_and_leaves_nothing_behind():
-    """ops.step_schedule (every step of the engine is issued inside one): the four settings hold inside and come back on the way
+    """sched.step_schedule (every step of the engine is issued inside one): the five settings hold inside and come back on the way
     out, a nested scope hands the outer one's settings back, and whichever way the scope is left -- normally or by an exception
     in the body -- nothing parked or deferred and no hook survives it."""
     import pytest
-    from egopack_amd import ops
+    from egopack_amd import sched
+    q, side, forks, last = sched._wq, sched._wgrad, sched._deferred, sched._last_wgrad
 
     def settings():
-        return ops._wgrad["enabled"], ops._wq["on"], ops._wq["count"], ops._deferred["on"], ops._wgrad["handoff"]
+        return side.enabled, q.on, q.count, forks.on, side.handoff
 
     def assert_clean():
-        assert all(ops._wq[k] == [] for k in ("items", "hold", "extra", "riders")) and ops._wq["tiles"] == 0
-        assert ops._deferred["items"] == []
-        assert ops._last_wgrad["param"] is None and ops._last_wgrad["hook"] is None and ops._last_wgrad["pre"] is None
-        assert ops._last_wgrad["tail"] is None and ops._g1_hook["fn"] is None
+        assert q.items == [] and q.hold == [] and q.reds == [] and q.riders == [] and q.tiles == 0
+        assert forks.items == []
+        assert last["param"] is None and last["hook"] is None and last["pre"] is None
+        assert last["tail"] is None and sched._g1_hook["fn"] is None
 
     def litter():  # (what a step leaves when it is abandoned half-way)
-        ops._wq["items"].append((("args",), {}))
-        ops._wq["hold"].append(torch.zeros(1))
-        ops._wq["extra"].append(("reduction",))
-        ops._wq["riders"].append(lambda: None)
-        ops._wq["tiles"] += 3
-        ops._deferred["items"].append(((0, 0), None, lambda ev: None))
-        ops.set_last_wgrad_hook(torch.zeros(1), lambda: None, pre=lambda: None)
-        ops.set_last_wgrad_tail(64, 128)
-        ops.set_graphone_backward_hook(lambda: None)
+        buf = torch.zeros(128 * 128)
+        sched._park((128, 128, buf, 128, buf, 128, 64, buf, 128), {}, (buf,))
+        q.reds.append(sched.Reduction(buf, buf[:4], buf[4:8], 1, 4, 0))  # (as issue_ln_reduce parks it when the queue is on)
+        q.hold.append(buf)
+        q.riders.append(lambda: None)
+        forks.items.append(sched.Fork((0, 0), None, lambda ev: None))
+        sched.set_last_wgrad_hook(torch.zeros(1), lambda: None, pre=lambda: None)
+        sched.set_last_wgrad_tail(64, 128)
+        sched.set_graphone_backward_hook(lambda: None)
 
-    for key in ("count", "riders"):  # every key is in the literal that creates its dict: no .get / .setdefault fallbacks
-        assert key in ops._wq
-    assert "handoff" in ops._wgrad and "pre" in ops._last_wgrad
+    # every field is in the literal that creates its structure: no .get / getattr fallbacks
+    assert set(vars(q)) == {"on", "count", "items", "tiles", "hold", "reds", "riders"}
+    assert set(vars(side)) == {"enabled", "streams", "pending", "queued", "exclude", "handoff"}
+    assert set(vars(forks)) == {"items", "busy", "on"}
+    assert set(last) == {"param", "hook", "pre", "inline", "tail", "leaked"}
     idle = settings()
     # 1. chosen settings inside, the previous ones afterwards
-    with ops.step_schedule(True, True, 8, False, True):
+    with sched.step_schedule(True, True, 8, False, True):
         assert settings() == (True, True, 8, False, True)
         assert_clean()
-        with ops.step_schedule(False, True, None, True):  # nested: the outer scope's settings come back
+        with sched.step_schedule(False, True, None, True):  # nested: the outer scope's settings come back
             assert settings() == (False, True, None, True, False)
         assert settings() == (True, True, 8, False, True)
     assert settings() == idle
     assert_clean()
     # 2. left through an exception, with work parked / deferred and hooks installed inside
     with pytest.raises(ValueError):
-        with ops.step_schedule(True, True, 6, True, False):
+        with sched.step_schedule(True, True, 6, True, False):
             litter()
-            assert ops._wq["items"] and ops._wq["riders"] and ops._deferred["items"] and ops._last_wgrad["tail"] == (64, 128)
+            assert q.items and q.reds and q.hold and q.riders and q.tiles == 1 and forks.items and last["tail"] == (64, 128)
             raise ValueError("abandoned")
     assert settings() == idle
     assert_clean()
     # ... and the same litter is dropped on a normal exit, and on the way IN (left by whoever issued outside a scope)
-    with ops.step_schedule(True, False):
+    with sched.step_schedule(True, False):
         litter()
     assert settings() == idle
     assert_clean()
-    ops._wq["items"].append((("args",), {}))
-    ops._deferred["items"].append(((0, 0), None, lambda ev: None))
-    with ops.step_schedule(True, True):
-        assert ops._wq["items"] == [] and ops._deferred["items"] == []
+    litter()
+    with sched.step_schedule(True, True):
+        assert q.items == [] and q.reds == [] and q.riders == [] and q.hold == [] and q.tiles == 0 and forks.items == []
     assert_clean()
+
+
+def _reds(targets):
+    """sched.Reduction records over CPU slots: ``targets`` = (dw, db) pairs."""
+    from egopack_amd import sched
+    return [sched.Reduction(torch.zeros(1), dw, db, 4, 4, 0) for dw, db in targets]
+
+
+def test_reduction_batches_are_greedy_ordered_and_never_repeat_a_target():
+    """sched.reduction_batches: at most 8 reductions per batch, no dw / db address twice in a batch, order kept, and a batch
+    ends ONLY when it is full or at a repeated target."""
+    from egopack_amd import sched
+    buf = torch.zeros(64)
+    slot = lambda i: buf[i:i + 1]
+
+    def batches(reds):
+        got = sched.reduction_batches(reds)
+        flat = [r for b in got for r in b]
+        assert len(flat) == len(reds) and all(r is g for r, g in zip(reds, flat))  # (the concatenation of the batches IS the input)
+        for b in got:
+            ptrs = [t.data_ptr() for r in b for t in (r.dw, r.db)]
+            assert 1 <= len(b) <= 8 and len(set(ptrs)) == len(ptrs)
+        return [len(b) for b in got]
+
+    assert batches([]) == []
+    assert batches(_reds([(slot(2 * i), slot(2 * i + 1)) for i in range(9)])) == [8, 1]  # nine distinct targets
+    targets = [(slot(2 * i), slot(2 * i + 1)) for i in range(11)]
+    targets[4] = (targets[1][0], targets[4][1])  # the fifth shares its dw with the second
+    assert batches(_reds(targets)) == [4, 7]
+    targets = [(slot(2 * i), slot(2 * i + 1)) for i in range(5)]
+    targets[3] = (targets[3][0], targets[0][0])  # a db that repeats an earlier dw
+    assert batches(_reds(targets)) == [3, 2]
+
+
+@pytest.fixture
+def parked_queue(monkeypatch):
+    """The parking queue inside a scope, with the streams stubbed out: nothing excluded, launches recorded instead of issued."""
+    from egopack_amd import sched
+    launched = []
+    monkeypatch.setattr(sched, "_on_excluded_stream", lambda: False)
+    monkeypatch.setattr(sched, "_wgrad_launch", lambda in_place, tensors, launch, in_backward=True: launched.append((in_place, list(tensors))))
+    with sched.step_schedule(True, True):
+        yield sched, launched
+
+
+def _park_at(sched, buf, first, M=128, N=128):
+    """Park an M x N problem whose gradient slot starts at element ``first`` of ``buf``."""
+    op = torch.zeros(8)
+    sched._park((M, N, op, 8, op, 8, 64, buf[first:], N), {"tag": first}, (op,))
+
+
+def test_take_parked_is_all_or_none(parked_queue):
+    sched, _ = parked_queue
+    buf = torch.zeros(256)
+    for first, (M, N) in zip((0, 64, 128), ((128, 128), (129, 128), (256, 300))):
+        _park_at(sched, buf, first, M, N)
+    assert [p.tiles for p in sched._wq.items] == [1, 2, 6] and sched._wq.tiles == 9 == sum(sched.tiles(*p.args[:2]) for p in sched._wq.items)
+    assert sched._take_parked(2) == [] and len(sched._wq.items) == 3 and sched._wq.tiles == 9
+    got = sched._take_parked(3)
+    assert [kw["tag"] for _, kw in got] == [0, 64, 128] and sched._wq.items == [] and sched._wq.tiles == 0
+    assert sched._take_parked(3) == []
+
+
+def test_tail_take_splits_what_is_parked_by_slot_address(parked_queue):
+    sched, _ = parked_queue
+    buf = torch.zeros(256)
+    base = buf.data_ptr()
+
+    def park_all():
+        for first, (M, N) in zip((0, 64, 96, 128), ((128, 128), (129, 128), (128, 257), (256, 300))):
+            _park_at(sched, buf, first, M, N)
+        for dw, db in ((64, 100), (64, 128), (0, 100), (127, 65)):  # (only the first and the last lie inside with BOTH targets)
+            sched.issue_ln_reduce(torch.zeros(1), buf[dw:], buf[db:], 1, 1, 0)
+    park_all()
+    assert sched._take_tail_items() == ([], []) and len(sched._wq.items) == 4 and len(sched._wq.reds) == 4  # no tail set
+    sched.set_last_wgrad_hook(torch.zeros(1), lambda: None)
+    sched.set_last_wgrad_tail(base + 4 * 64, base + 4 * 128)
+    items, reds = sched._take_tail_items()
+    assert [p.kw["tag"] for p in items] == [64, 96] and all(p.out.data_ptr() == base + 4 * p.kw["tag"] for p in items)
+    assert [p.kw["tag"] for p in sched._wq.items] == [0, 128]
+    assert sched._wq.tiles == 1 + 6 == sum(p.tiles for p in sched._wq.items)
+    assert [(r.dw.data_ptr() - base) // 4 for r in reds] == [64, 127]
+    assert [(r.dw.data_ptr() - base) // 4 for r in sched._wq.reds] == [64, 0]
+    assert sched.last_wgrad_tail_on_backward_stream()  # (taken, not flushed: nothing of the range left for the side stream)
+
+
+def test_tail_range_leaks_when_a_flush_issues_one_of_its_gradients(parked_queue):
+    sched, launched = parked_queue
+    last = sched._last_wgrad
+    buf = torch.zeros(256)
+    base = buf.data_ptr()
+
+    def arm():
+        sched.set_last_wgrad_hook(torch.zeros(1), lambda: None)
+        sched.set_last_wgrad_tail(base + 4 * 64, base + 4 * 128)
+        assert last["leaked"] is False and sched.last_wgrad_tail_on_backward_stream()
+    arm()
+    _park_at(sched, buf, 0)
+    sched.issue_ln_reduce(torch.zeros(1), buf[0:], buf[128:], 1, 1, 0)
+    sched.flush_wgrad()  # (nothing of the range among what went out)
+    assert len(launched) == 1 and launched[0][0] is True and len(launched[0][1]) == 2
+    assert sched._wq.items == [] and sched._wq.reds == [] and sched._wq.hold == [] and last["leaked"] is False
+    _park_at(sched, buf, 96)
+    sched.flush_wgrad()  # a problem of the range
+    assert last["leaked"] is True and not sched.last_wgrad_tail_on_backward_stream()
+    arm()  # (set_last_wgrad_tail clears the flag)
+    sched.issue_ln_reduce(torch.zeros(1), buf[0:], buf[100:], 1, 1, 0)
+    sched.flush_wgrad()  # a reduction with ONE target in the range
+    assert last["leaked"] is True and len(launched) == 3
+    sched.flush_wgrad()  # (nothing parked: no launch)
+    assert len(launched) == 3
+    sched.set_last_wgrad_hook(None, None)
+    assert last["tail"] is None and not sched.last_wgrad_tail_on_backward_stream()
+
+
+def test_the_benchmark_switches_reach_the_scheduler(monkeypatch):
+    """bench.py assigns the ``side`` key of ``ops._wgrad_ln`` and the ``inline`` key of ``ops._last_wgrad``: the scheduler's own objects."""
+    import types
+    from egopack_amd import ops, sched
+    assert ops._wgrad_ln is sched._wgrad_ln and ops._last_wgrad is sched._last_wgrad
+    assert "side" in sched._wgrad_ln and "inline" in sched._last_wgrad
+    own = [n for n, v in vars(sched).items() if getattr(v, "__module__", None) == sched.__name__]  # its functions and record types
+    # (ops re-exports nothing else -- but ``join_wgrad``, which whoever calls backward() over these ops needs after it)
+    assert "issue_wgrad" in own and "Problem" in own and [n for n in own if hasattr(ops, n)] == ["join_wgrad"]
+    assert ops.join_wgrad is sched.join_wgrad
+    assert not [n for n in ("_wq", "_wgrad", "_deferred", "_g1_hook") if hasattr(ops, n)]
+
+    def no_stream():
+        raise AssertionError("a stream was asked for")
+    monkeypatch.setattr(sched, "_on_excluded_stream", no_stream)
+    monkeypatch.setattr(sched._wgrad, "enabled", True)
+    slot, x = torch.zeros(4), types.SimpleNamespace(is_cuda=True)
+    with pytest.raises(AssertionError, match="a stream was asked for"):  # (side streams on, in-place slots: the stream decides)
+        sched._ln_reduce_on_side(slot, slot, x)
+    monkeypatch.setitem(sched._wgrad_ln, "side", False)
+    assert sched._ln_reduce_on_side(slot, slot, x) is False  # ... and with the switch off it is never asked
 
 
 def test_fast_key_sees_the_labelled_row_set_of_a_compacted_head():
