@@ -29,6 +29,12 @@ HEADERS = {key: HERE.parent / "include" / f"egopack_{key}.h" for key in (
 EXTRA_HEADERS = {"lamb": HERE.parent / "include" / "egopack_lamb.h"}
 LAMB_PIECE = 4096  # EGK_LAMB_PIECE (include/egopack_lamb.h)
 
+# The OPEN third table: every later header goes here.  The same parser, the same rules, and one ledger for the whole
+# table, tests/test_cabi_addons.py, which reads what it pins per key from tests/cabi_addon_<key>.py -- a new header adds a key here and
+# files there.  Scalars and pointers only (STRUCTS stays as ledgered); a name another header of any table declares is refused.
+ADDON_HEADERS = {"calibrate": HERE.parent / "include" / "egopack_calibrate.h"}
+TEMP_MAX_HEADS, TEMP_MAX_K = 8, 64  # EGK_TEMP_MAX_* (include/egopack_calibrate.h)
+
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
 
@@ -243,6 +249,23 @@ def extra_signatures() -> dict:
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def addon_signatures() -> dict:
+    """header key -> {name: (restype, argtypes)} of the files of ADDON_HEADERS (once); a name that a header of HEADERS, of
+    EXTRA_HEADERS or another add-on declares too is refused."""
+    owner = {name: key for tables in (signatures(), extra_signatures()) for key, table in tables.items() for name in table}
+    out = {}
+    for key, path in ADDON_HEADERS.items():
+        if not path.exists():
+            raise RuntimeError(f"{path} is missing: it is header '{key}' of the C ABI (ADDON_HEADERS)")
+        out[key] = parse_prototypes(path.read_text(), path.name)
+        for name in out[key]:
+            if name in owner:
+                raise RuntimeError(f"{name} is declared in {path.name} and again under the key '{owner[name]}'")
+            owner[name] = key
+    return out
+
+
 _lib = None
 
 
@@ -256,7 +279,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m egopack_amd.build` "
             "(or __graft_entry__.build()).  egopack_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for table in (*signatures().values(), *extra_signatures().values()):  # (raises for a missing header and for a name two headers declare)
+    for table in (*signatures().values(), *extra_signatures().values(), *addon_signatures().values()):  # (raises for a missing header and for a name two headers declare)
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res

@@ -114,6 +114,10 @@ enum KernelId {
     KID_CLASS_REPORT,      // egk_class_report: confusion, top-2 confusion and per-class loss sums of all heads in one launch (metrics.hip)
     KID_TOPK_SOFTMAX,      // egk_topk_softmax: the best k classes of every row of every head, their probabilities and the log-sum-exp (metrics.hip)
     KID_RETRIEVAL_REPORT,  // egk_retrieval_report: per node and auxiliary task the distances of its prototypes and their wins in the first gather-max (graph_ops.hip)
+    KID_TEMP_STATS,        // egk_temp_stats: the q24 sums of F, F' and F'' of one head at a temperature read from device memory (calibrate.hip)
+    KID_TEMP_NEWTON,       // egk_temp_newton: one safeguarded Newton step per head from those sums (calibrate.hip)
+    KID_TEMP_TOPK_PROB,    // egk_temp_topk_prob: the probabilities of a given top-k order at a temperature (calibrate.hip)
+    KID_TEMP_SCALE_ROWS,   // egk_temp_scale_rows: an f32 copy of the logits times 1/T (calibrate.hip)
     KID_LAMB_MOMENTS,      // egk_lamb_moments: LAMB's moments and the per-piece partial sums of p^2 and u^2 (optim_lamb.hip)
     KID_LAMB_TRUST,        // egk_lamb_trust: the trust ratio of every slot from those sums (optim_lamb.hip)
     KID_LAMB_APPLY,        // egk_lamb_apply: p -= (lr * trust) * u, the bf16 copies and the weight average (optim_lamb.hip)

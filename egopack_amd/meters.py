@@ -236,6 +236,16 @@ class _Calibration:
         self.hits += torch.bincount(idx, weights=w * (pred == labels).to(torch.float64), minlength=self.n_bins + 1).to(torch.int64)
         self.conf += torch.bincount(idx, weights=w * conf.double(), minlength=self.n_bins + 1)
 
+    def update_conf(self, conf: torch.Tensor, pred: torch.Tensor, labels: torch.Tensor):
+        """The same bins and sums from a confidence and a prediction formed elsewhere: the calibrated scores (the raw top-1 with its
+        probability at the fitted temperature, ``calibration.cross_scores``)."""
+        conf, labels = conf.detach().float(), labels.to(torch.int64)
+        w = (labels != -1).to(torch.float64)
+        idx = (torch.bucketize(conf, self.bounds, right=True) - 1).clamp_(0, self.n_bins)
+        self.count += torch.bincount(idx, weights=w, minlength=self.n_bins + 1).to(torch.int64)
+        self.hits += torch.bincount(idx, weights=w * (pred == labels).to(torch.float64), minlength=self.n_bins + 1).to(torch.int64)
+        self.conf += torch.bincount(idx, weights=w * conf.double(), minlength=self.n_bins + 1)
+
     def tensors(self) -> List[torch.Tensor]:
         return [self.count, self.hits, self.conf]
 
@@ -259,8 +269,13 @@ class BaseMeter:
     """utils/meters/base.py: running mean of the per-batch loss + sample counter."""
 
     def __init__(self, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
-                 shots=(20, 100), top_confusions: int = 20) -> None:
+                 shots=(20, 100), top_confusions: int = 20, calibration=None) -> None:
         self.device = torch.device(device)
+        # temperature calibration (``calibration``: t_range, iterations, stop, max_rows of the config block; None: no state, no
+        # launch, no key): the meters that have heads fill ``temp_store`` with what they score, ``get_logs`` fits once
+        self.temp_cfg = dict(calibration) if calibration else None
+        self.temp_store, self._temp, self._temp_batches = None, None, 0
+        self.batch_ordinal = None  # the validation loop stamps the batch's ordinal here before ``update`` (the folds follow it)
         self.loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         self.loss_n = 0
         self.counter = 0
@@ -299,6 +314,60 @@ class BaseMeter:
             if tc is not None:
                 out[f"{p}train_counts"] = torch.as_tensor(tc).cpu()
         return out
+
+    # ---- temperature calibration (egopack_amd/calibration.py) -------------------------------------
+    def _add_temperature(self, heads: Dict[str, int]) -> None:
+        """``heads``: key prefix -> class count of every head that takes a temperature."""
+        if self.temp_cfg is None:
+            return
+        from .calibration import LogitStore
+        self.temp_store = LogitStore(heads, self.temp_cfg.get("max_rows", 1048576), self.device)
+
+    def _temperature_append(self, heads) -> None:
+        """``heads``: (key prefix, logits [N, C], labels [N]) of one batch, stored as the meter scores them."""
+        if self.temp_store is None:
+            return
+        ordinal = self.batch_ordinal if self.batch_ordinal is not None else self._temp_batches
+        self._temp_batches += 1
+        for prefix, logits, labels in heads:
+            self.temp_store.append(prefix, logits.detach(), labels.to(torch.int64), ordinal)
+        self._temp = None
+
+    def temperature_fit(self) -> Dict[str, dict]:
+        """``calibration.fit`` over the stored rows (once; the accumulators are summed over the ranks of a process group), with the
+        cross-fitted calibration error and Brier score added per head: {} with calibration off."""
+        if self.temp_store is None:
+            return {}
+        if self._temp is None:
+            from . import calibration as CAL
+            reduce = CAL.all_reduce_sum()
+            res = CAL.fit(self.temp_store, self.temp_cfg, reduce=reduce)
+            for prefix, (in_sample, parts) in CAL.cross_scores(self.temp_store, res).items():
+                ece, brier = _Calibration(15, "l1", self.device), _Calibration(1, "l2", self.device)
+                for conf, pred, y in parts:
+                    ece.update_conf(conf, pred, y)
+                    brier.update_conf(conf, pred, y)
+                if reduce is not None:
+                    for t in (*ece.tensors(), *brier.tensors()):
+                        reduce(t)
+                res[prefix].update(calibration_error_calibrated=ece.compute(), brier_score_calibrated=brier.compute(), in_sample=bool(in_sample))
+            self._temp = res
+        return self._temp
+
+    def _temperature_logs(self) -> dict:
+        out = {}
+        for p, r in self.temperature_fit().items():
+            out.update({f"{p}temperature": r["temperature"], f"{p}nll": r["nll"], f"{p}nll_calibrated": r["nll_calibrated"],
+                        f"{p}calibration_erorr_calibrated": r["calibration_error_calibrated"],  # (the spelling of the raw key)
+                        f"{p}brier_score_calibrated": r["brier_score_calibrated"]})
+            if r["in_sample"]:
+                out[f"{p}calibration_in_sample"] = 1
+        return out
+
+    def _temperature_lines(self) -> List[str]:
+        return [f"{p.rstrip('_') or 'head'} temperature: {r['temperature']:.4f} [{r['status']}, {r['iterations']} iterations, {r['rows']} rows], "
+                f"NLL {r['nll']:.4f} -> {r['nll_calibrated']:.4f}, calibration error (cross-fitted{', IN SAMPLE' if r['in_sample'] else ''}) "
+                f"{r['calibration_error_calibrated']:.4f}" for p, r in self.temperature_fit().items()]
 
     def update(self, labels, loss, *args, **kwargs) -> None:
         loss = loss.detach().double()
@@ -370,10 +439,10 @@ class BaseMeter:
         return torch.float32
 
     def print_logs(self) -> List[str]:
-        return [*self._report_lines(), f"Loss: {self.loss():.4f}"]
+        return [*self._report_lines(), *self._temperature_lines(), f"Loss: {self.loss():.4f}"]
 
     def get_logs(self, *args, **kwargs) -> Dict[str, float]:
-        return {"loss": self.loss(), **self._report_logs()}
+        return {"loss": self.loss(), **self._report_logs(), **self._temperature_logs()}
 
 
 class _VerbNounMeter(BaseMeter):
@@ -387,6 +456,7 @@ class _VerbNounMeter(BaseMeter):
         # (the reference builds its noun table from the VERB matrix, utils/meters/ego4d.py:148; here the nouns get the nouns' matrix)
         self._add_report("verbs_", self.verb_labels, self.idx_verbs)
         self._add_report("nouns_", self.noun_labels, self.idx_nouns)
+        self._add_temperature({"verbs_": len(self.verb_labels), "nouns_": len(self.noun_labels)})
 
     def _sums(self):
         return [*super()._sums(), *self.verbs.tensors(), *self.nouns.tensors()]
@@ -398,6 +468,8 @@ class _VerbNounMeter(BaseMeter):
         if self.class_report:  # both heads in one launch, beside the counting above
             class_report([(logits[self.idx_verbs], labels[:, self.idx_verbs], self.reports["verbs_"][0]),
                           (logits[self.idx_nouns], labels[:, self.idx_nouns], self.reports["nouns_"][0])])
+        self._temperature_append([("verbs_", logits[self.idx_verbs], labels[:, self.idx_verbs]),
+                                  ("nouns_", logits[self.idx_nouns], labels[:, self.idx_nouns])])
 
 
 class RecognitionMeter(_VerbNounMeter):
@@ -467,6 +539,7 @@ class OSCCMeter(BaseMeter):
             if tc is not None and not torch.is_tensor(tc):
                 tc = tc[0]
             self.reports[""] = (_ClassReport(2, self.device), list(getattr(dataset, "oscc_class_labels", ("no_change", "change"))), tc)
+        self._add_temperature({"": 2})
 
     def _sums(self):
         return [*super()._sums(), *self.counts.tensors()]
@@ -477,6 +550,7 @@ class OSCCMeter(BaseMeter):
         self.counts.update(logits.detach(), labels)
         if self.class_report:
             class_report([(logits, labels, self.reports[""][0])])
+        self._temperature_append([("", logits, labels)])
 
     def print_logs(self):
         return [f"Accuracy: {self.counts.accuracy(1) * 100:.2f}", *super().print_logs()]
@@ -599,13 +673,14 @@ class LTAMeter(_VerbNounMeter):
 
 
 def build_meter_for_dataset(dataset, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
-                            shots=(20, 100), top_confusions: int = 20) -> BaseMeter:
+                            shots=(20, 100), top_confusions: int = 20, calibration=None) -> BaseMeter:
     """utils/meters/__init__.py:10-22, keyed on the dataset's ``task`` name (synthetic and Ego4D datasets alike).
     ``class_report``: the per-class report of the verb / noun and OSCC meters (PNR is binary and reports tp / tn already: it
-    takes no report); ``train_counts``: per head the training labels of every class (``train.label_counts``) for the
+    takes no report); ``calibration``: the temperature fit of the same meters (``train.calibration_meter_args``; PNR takes none:
+    a one-logit BCE head whose export is a frame index); ``train_counts``: per head the training labels of every class (``train.label_counts``) for the
     many / medium / few-shot accuracies, ``shots`` their (lo, hi) borders, ``top_confusions`` the length of the confusion list."""
     kind = getattr(dataset, "task", None) or type(dataset).__name__.lower()
-    rep = dict(class_report=class_report, train_counts=train_counts, shots=shots, top_confusions=top_confusions)
+    rep = dict(class_report=class_report, train_counts=train_counts, shots=shots, top_confusions=top_confusions, calibration=calibration)
     if "pnr" in kind:
         return PNRMeter(dataset, device=device)
     if "oscc" in kind:

@@ -3596,13 +3596,24 @@ def categorical_sample_multi(logits_list, K: int, seed: int, ordinal: int, row0:
 
 class FutureSampler:
     """The seeded sampler of the LTA futures (``lta_sampling.mode=philox``): stateless -- nothing to checkpoint, the samples of a
-    batch depend on (seed, the batch's ordinal, row, head, k) alone."""
+    batch depend on (seed, the batch's ordinal, row, head, k) alone.  ``temperature`` T != 1: the draws come from softmax(z / T) --
+    every head is scaled by fl(1 / T) into an f32 copy first (``temp_scale_rows``, one launch per head) and the same sampling launch
+    reads the copies; at exactly 1.0 there is no extra launch and the draws are those of the raw logits."""
 
-    def __init__(self, seed: int = 0):
+    def __init__(self, seed: int = 0, temperature: float = 1.0):
         self.seed = int(seed)
+        self.temperature = float(temperature)
+        if not (self.temperature > 0.0 and self.temperature < float("inf")):
+            raise ValueError(f"FutureSampler: temperature must be a finite positive number (got {temperature!r})")
+        self._beta = None  # the device word fl(1 / T), made at the first call
 
     def __call__(self, logits, K: int, ordinal: int, row0: int = 0):
-        return categorical_sample_multi(list(logits), K, self.seed, ordinal, row0)
+        logits = list(logits)
+        if self.temperature != 1.0:
+            if self._beta is None or self._beta.device != logits[0].device:
+                self._beta = torch.tensor([1.0 / self.temperature], dtype=torch.float32, device=logits[0].device)
+            logits = [temp_scale_rows(l, self._beta) for l in logits]
+        return categorical_sample_multi(logits, K, self.seed, ordinal, row0)
 
 
 # ---- top-k softmax (include/egopack_topk.h, DESIGN 3.14) ---------------------------------------------------------------------------
@@ -3640,6 +3651,89 @@ def topk_softmax(logits_list, k: int, want_prob: bool = True, want_lse: bool = F
             t.lse = _p(lse)
     _ck(_lib.load().egk_topk_softmax(_stream(), tasks, len(logits_list), N, k, _dt(logits_list[0])), "egk_topk_softmax")
     return outs
+
+
+# ---- temperature calibration (include/egopack_calibrate.h) --------------------------------------------------------------
+def _temp_operands(what: str, logits, beta):
+    """The [N, C] logits as a launch reads them (a view with a unit class stride in place, through its row stride) and the checks
+    every temperature launch shares: ``beta`` is an f32 device tensor whose first word is 1 / T."""
+    _need_gpu(logits, beta)
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"{what}: logits of [N, C] with C >= 1 (got {tuple(logits.shape)})")
+    if beta.dtype != torch.float32 or beta.numel() < 1:
+        raise ValueError(f"{what}: beta is an f32 device tensor of at least one word (got {beta.dtype}, {tuple(beta.shape)})")
+    logits = _rm(logits.detach())
+    return logits, max(logits.stride(0), logits.shape[1])  # (a one-row tensor's stride is arbitrary)
+
+
+@torch.no_grad()
+def temp_stats(logits, labels, beta, acc):
+    """ADDS the sums of one head at beta = ``beta[0]`` to ``acc`` (int64 [8], on the device): q24 sums of the NLL of the scaled
+    logits and of its first and second derivative in beta, then the valid / ignored / left-out row counts (``egk_temp_stats``).
+    ``labels``: int64 [N], a column view is read through its stride."""
+    logits, ld = _temp_operands("temp_stats", logits, beta)
+    _need_gpu(labels, acc)
+    if labels.dim() != 1 or labels.shape[0] != logits.shape[0] or labels.dtype != torch.int64:
+        raise ValueError(f"temp_stats: int64 labels of [N] (got {labels.dtype}, {tuple(labels.shape)} for {tuple(logits.shape)})")
+    if acc.dtype != torch.int64 or acc.numel() < 8 or not acc.is_contiguous():
+        raise ValueError(f"temp_stats: acc is a contiguous int64 tensor of 8 words (got {acc.dtype}, {tuple(acc.shape)})")
+    if logits.shape[0] == 0:
+        return acc
+    _ck(_lib.load().egk_temp_stats(_stream(), _p(logits), ld, _p(labels), labels.stride(0), logits.shape[0], logits.shape[1], _p(beta),
+                                   _p(acc), _dt(logits)), "egk_temp_stats")
+    return acc
+
+
+@torch.no_grad()
+def temp_newton(acc, state, beta, beta_min: float, beta_max: float, stop: float):
+    """One safeguarded Newton step for every head (``egk_temp_newton``): ``acc`` int64 [H, 8] (read), ``state`` f64 [H, 8] and
+    ``beta`` f32 [H] (updated in place), H in 1 .. 8."""
+    _need_gpu(acc, state, beta)
+    H = beta.numel()
+    if acc.dtype != torch.int64 or state.dtype != torch.float64 or beta.dtype != torch.float32 or not (
+            acc.is_contiguous() and state.is_contiguous() and beta.is_contiguous()) or acc.numel() != 8 * H or state.numel() != 8 * H:
+        raise ValueError(f"temp_newton: acc int64 [H, 8], state f64 [H, 8], beta f32 [H], contiguous (got {tuple(acc.shape)}, "
+                         f"{tuple(state.shape)}, {tuple(beta.shape)})")
+    _ck(_lib.load().egk_temp_newton(_stream(), _p(acc), H, _p(state), _p(beta), float(beta_min), float(beta_max), float(stop)),
+        "egk_temp_newton")
+    return state
+
+
+@torch.no_grad()
+def temp_topk_prob(logits, idx, beta, want_lse: bool = False):
+    """(prob f32 [N, k], lse f32 [N] | None): the probabilities of the GIVEN order ``idx`` (int64 [N, k], ``topk_softmax``'s, never
+    written or recomputed) under softmax(beta[0] * logits) and the scaled rows' log-sum-exp (``egk_temp_topk_prob``)."""
+    logits, ld = _temp_operands("temp_topk_prob", logits, beta)
+    _need_gpu(idx)
+    if idx.dim() != 2 or idx.shape[0] != logits.shape[0] or idx.dtype != torch.int64 or not 1 <= idx.shape[1] <= _lib.TEMP_MAX_K:
+        raise ValueError(f"temp_topk_prob: int64 idx of [N, k], k in 1 .. {_lib.TEMP_MAX_K} (got {idx.dtype}, {tuple(idx.shape)})")
+    if idx.stride(1) != 1 or (idx.shape[0] > 1 and idx.stride(0) < idx.shape[1]):
+        idx = idx.contiguous()
+    N, k = idx.shape
+    prob = torch.empty((N, k), dtype=torch.float32, device=logits.device)
+    lse = torch.empty((N,), dtype=torch.float32, device=logits.device) if want_lse else None
+    if N == 0:
+        return prob, lse
+    _ck(_lib.load().egk_temp_topk_prob(_stream(), _p(logits), ld, N, logits.shape[1], _p(beta), _p(idx), max(idx.stride(0), k), k,
+                                       _p(prob), k, _p(lse), _dt(logits)), "egk_temp_topk_prob")
+    return prob, lse
+
+
+@torch.no_grad()
+def temp_scale_rows(logits, beta, out=None):
+    """f32 [N, C]: fl(beta[0] * logits), one product per element (``egk_temp_scale_rows``).  ``out``: an f32 [N, >= C] row-major
+    tensor to write the first C columns of."""
+    logits, ld = _temp_operands("temp_scale_rows", logits, beta)
+    N, Cn = logits.shape
+    if out is None:
+        out = torch.empty((N, Cn), dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != N or out.shape[1] < Cn or out.stride(1) != 1 or not out.is_cuda:
+        raise ValueError(f"temp_scale_rows: out is an f32 device tensor of [N, >= C] with a unit column stride (got {tuple(out.shape)})")
+    if N == 0:
+        return out
+    _ck(_lib.load().egk_temp_scale_rows(_stream(), _p(logits), ld, N, Cn, _p(beta), _p(out), max(out.stride(0), out.shape[1]),
+                                        _dt(logits)), "egk_temp_scale_rows")
+    return out[:, :Cn] if out.shape[1] != Cn else out
 
 
 # ---- retrieval report (include/egopack_retrieval.h, DESIGN 3.15) -------------------------------------------------------------------

@@ -90,11 +90,30 @@ class _Fields:
         return {k: torch.cat(v) for k, v in self.parts.items()}
 
 
+# ---- the fitted temperatures of a calibration file (train.load_calibration) ------------------------------------------
+def beta_words(calibration: Optional[dict], prefixes, device):
+    """Per head of ``prefixes`` (the meters' key prefixes: "verbs_", "nouns_", "" for OSCC) the device word fl(1 / T) the
+    temperature launches read; None without a calibration file."""
+    if not calibration:
+        return None
+    return [torch.tensor([1.0 / float(calibration["heads"][p]["temperature"])], dtype=torch.float32, device=device) for p in prefixes]
+
+
+def temperatures(calibration: Optional[dict]) -> dict:
+    """What a prediction file records of the calibration it was written with: {} without one (the file is then today's)."""
+    if not calibration:
+        return {}
+    return {"temperature": {(p.rstrip("_") or "oscc"): float(v["temperature"]) for p, v in calibration["heads"].items()}}
+
+
 # ---- AR and LTA: the verb / noun heads, per node ------------------------------------------------------------------------------------
-def _heads_batch(out: _Fields, data, logits, k: int, bs: int, head_index):
+def _heads_batch(out: _Fields, data, logits, k: int, bs: int, head_index, betas=None):
     from .meters import label_rank
     heads = [logits[i] for i in head_index]
     (vi, vp, vl), (ni, np_, nl) = ops.topk_softmax(heads, k, want_prob=True, want_lse=True)  # both heads, one launch
+    if betas is not None:  # calibrated: the probabilities of the SAME order at the fitted temperatures (the order is never recomputed)
+        vp, vl = ops.temp_topk_prob(heads[0], vi, betas[0], want_lse=True)
+        np_, nl = ops.temp_topk_prob(heads[1], ni, betas[1], want_lse=True)
     y = getattr(data, "y", None)
     label = rank = None
     if y is not None:
@@ -106,25 +125,27 @@ def _heads_batch(out: _Fields, data, logits, k: int, bs: int, head_index):
 
 @torch.no_grad()
 def predict_heads(temporal_graph_model, dataloader, primary_task, k: int = 5, other_tasks: Optional[List] = None, graphone=None,
-                  late_fusion: bool = True, device: str = "cuda", head_index=(0, 1)) -> dict:
+                  late_fusion: bool = True, device: str = "cuda", head_index=(0, 1), calibration=None) -> dict:
     """The verb / noun heads of the AR task (or of any multi-head task), per node: ``sample``, ``pos``, ``verb_topk``, ``verb_prob``,
     ``noun_topk``, ``noun_prob`` [rows, k], ``verb_lse``, ``noun_lse`` [rows] and, when the split has labels, ``label`` [rows, 2] and
-    ``rank`` int32 [rows, 2] (``egk_label_rank``; -1 for an ignored row).  ``late_fusion``: as ``validate.validate``."""
+    ``rank`` int32 [rows, 2] (``egk_label_rank``; -1 for an ignored row).  ``late_fusion``: as ``validate.validate``.
+    ``calibration`` (``train.load_calibration``): ``*_prob`` and ``*_lse`` at the fitted temperatures, over the raw order."""
     other_tasks = other_tasks or []
     bs = _batch_size(dataloader)
+    betas = beta_words(calibration, ("verbs_", "nouns_"), device)
     _eval_mode(temporal_graph_model, primary_task, other_tasks, graphone)
     out = _Fields()
     for data in dataloader:
         data = data.to(device)
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
-        _heads_batch(out, data, logits, k, bs, head_index)
+        _heads_batch(out, data, logits, k, bs, head_index, betas)
     return out.result()
 
 
 @torch.no_grad()
 def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed: int = 0, n_nodes: int = 22, n_futures: int = 5,
                 other_tasks: Optional[List] = None, graphone=None, late_fusion: bool = False, device: str = "cuda",
-                head_index=(0, 1)) -> dict:
+                head_index=(0, 1), calibration=None) -> dict:
     """The LTA task: the per-node fields of ``predict_heads`` and the sampled futures ``verb_futures`` / ``noun_futures``, int64
     [sequences, Z, K] (``futures_sample`` [sequences]: their samples), after dropping the observed nodes as ``meters.LTAMeter``
     does (sequences of ``n_nodes`` nodes -- the dataset's ``lta_nodes`` --, the first ``LTAMeter.SKIP`` dropped).  The futures come
@@ -134,6 +155,7 @@ def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed
     other_tasks = other_tasks or []
     bs = _batch_size(dataloader)
     sampler = ops.FutureSampler(seed)
+    betas = beta_words(calibration, ("verbs_", "nouns_"), device)  # (the per-node probabilities; the futures are the raw logits')
     _eval_mode(temporal_graph_model, primary_task, other_tasks, graphone)
     out = _Fields()
     for data in dataloader:
@@ -141,7 +163,7 @@ def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
         predictions, logits = primary_task.generate_from_logits(logits, K=n_futures, sampler=sampler,
                                                                 ordinal=getattr(data, "ordinal", None))
-        _heads_batch(out, data, logits, k, bs, head_index)
+        _heads_batch(out, data, logits, k, bs, head_index, betas)
         fut = [predictions[i].reshape(-1, n_nodes, n_futures)[:, LTAMeter.SKIP:] for i in head_index]
         out.add(verb_futures=fut[0], noun_futures=fut[1], futures_sample=_seq_samples(data, bs, fut[0].shape[0], fut[0].device))
     return out.result()
@@ -150,17 +172,21 @@ def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed
 # ---- OSCC: one state-change probability per sequence --------------------------------------------------------------------------------
 @torch.no_grad()
 def predict_oscc(temporal_graph_model, dataloader, primary_task, other_tasks: Optional[List] = None, graphone=None,
-                 late_fusion: bool = True, device: str = "cuda") -> dict:
+                 late_fusion: bool = True, device: str = "cuda", calibration=None) -> dict:
     """Per sequence: ``sample``, ``pred`` (the first class of the order), ``prob_change`` (the probability of class 1), ``lse`` and,
-    when the split has labels, ``label``.  One ``topk_softmax`` launch with k = 2 per batch."""
+    when the split has labels, ``label``.  One ``topk_softmax`` launch with k = 2 per batch.  ``calibration``: ``prob_change`` and
+    ``lse`` at the fitted temperature, over the raw order."""
     other_tasks = other_tasks or []
     bs = _batch_size(dataloader)
+    betas = beta_words(calibration, ("",), device)
     _eval_mode(temporal_graph_model, primary_task, other_tasks, graphone)
     out = _Fields()
     for data in dataloader:
         data = data.to(device)
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
         (idx, prob, lse), = ops.topk_softmax([logits], 2, want_prob=True, want_lse=True)
+        if betas is not None:
+            prob, lse = ops.temp_topk_prob(logits, idx, betas[0], want_lse=True)
         change = torch.where(idx[:, 0] == 1, prob[:, 0], prob[:, 1])
         y = getattr(data, "y", None)
         out.add(sample=_seq_samples(data, bs, idx.shape[0], idx.device), pred=idx[:, 0], prob_change=change, lse=lse,
@@ -255,11 +281,14 @@ def _class_names(task: str, dataset):
     return None
 
 
-def predict_task(t: str, model, dataloader, dataset, task, pc: dict, ls: dict, device, **fusion) -> dict:
+def predict_task(t: str, model, dataloader, dataset, task, pc: dict, ls: dict, device, calibration=None, **fusion) -> dict:
     """The loop of task ``t`` with the entry points' arguments (``pc``: ``predict_config``, ``ls``: ``train.lta_sampling_config``).
-    ``fusion``: ``other_tasks`` / ``graphone`` / ``late_fusion`` of the loops, for a model with a GraphONE."""
+    ``calibration``: the task's calibration file (``train.load_calibration``; PNR takes none).  ``fusion``: ``other_tasks`` /
+    ``graphone`` / ``late_fusion`` of the loops, for a model with a GraphONE."""
     names = getattr(dataset, "label_names", None)
     heads = (names.index("verbs"), names.index("nouns")) if names else (0, 1)
+    if t != "pnr" and calibration:
+        fusion = {**fusion, "calibration": calibration}
     if t == "ar":
         return predict_heads(model, dataloader, task, k=pc["topk"], device=device, head_index=heads, **fusion)
     if t == "lta":
@@ -339,10 +368,12 @@ def main(argv=None):
     results, paths, seconds = {}, {}, {}
     for t in enabled:
         t0 = time.perf_counter()
-        pred = predict_task(t, model, loaders[t], dsets[t], tasks[t], pc, ls, device)
+        # calibration.predict: the file calibrate.py (or a validation with calibration.mode=temperature) wrote beside the checkpoint
+        cal = T.load_calibration(cfg, Path(cfg.resume_from).resolve().parent, t) if t != "pnr" else None
+        pred = predict_task(t, model, loaders[t], dsets[t], tasks[t], pc, ls, device, calibration=cal)
         torch.cuda.synchronize()
         seconds[t] = time.perf_counter() - t0
-        results[t], paths[t] = write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t])
+        results[t], paths[t] = write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t], **temperatures(cal))
     return {"predictions": results, "paths": paths, "out": out_dir, "seconds": seconds, "model": model, "tasks": tasks,
             "datasets": dsets, "loaders": loaders}
 

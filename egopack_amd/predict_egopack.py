@@ -170,14 +170,17 @@ def main(argv=None):
         others = [tasks[o] for o in AUX_ORDER[t] if o in graphone.task_labels]  # (main_egopack.validate_metrics)
         tap = RetrievalTap(graphone, loaders[t]) if ec["retrieval"] and others else None
         t0 = time.perf_counter()
-        pred = P.predict_task(t, model, loaders[t] if tap is None else tap, dsets[t], tasks[t], pc, ls, device, other_tasks=others,
-                              graphone=graphone if tap is None else tap, late_fusion=cfg.late_fusion)
+        # calibration.predict: the file calibrate.py enable_graphone=True wrote beside the checkpoint (PNR takes none)
+        cal = T.load_calibration(cfg, Path(cfg.resume_from).resolve().parent, t) if t != "pnr" else None
+        pred = P.predict_task(t, model, loaders[t] if tap is None else tap, dsets[t], tasks[t], pc, ls, device, calibration=cal,
+                              other_tasks=others, graphone=graphone if tap is None else tap, late_fusion=cfg.late_fusion)
         if tap is not None:
             pred.update(tap.result(labels, n_nouns))
         torch.cuda.synchronize()
         seconds[t] = time.perf_counter() - t0
         extra = {"retrieval_tasks": [o.name for o in others], "retrieval_k": int(graphone.k),
                  "retrieval_distance": graphone.distance_func} if tap is not None else {}
+        extra.update(P.temperatures(cal))
         results[t], paths[t] = P.write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t], **extra)
     return {"predictions": results, "paths": paths, "out": out_dir, "seconds": seconds, "model": model, "tasks": tasks,
             "graphone": graphone, "datasets": dsets, "loaders": loaders, "bank_labels": labels}

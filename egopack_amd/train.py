@@ -631,6 +631,97 @@ def save_class_reports(logger, cfg, directory: Path, reports: dict) -> list:
     return paths
 
 
+# ---- post-hoc temperature calibration of the heads (``calibration:`` of the config; include/egopack_calibrate.h) ---------
+def calibration_config(cfg) -> dict:
+    """The ``calibration:`` block with its defaults filled in and checked; an unknown key, mode, task or ``predict`` value is a
+    ValueError that names it.  ``enabled`` = (mode == "temperature")."""
+    from .calibration import DEFAULTS, MODES, TASKS as CAL_TASKS
+    raw = cfg.get("calibration") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(DEFAULTS)
+    if unknown:
+        raise ValueError(f"calibration: unknown key(s) {sorted(unknown)} ({', '.join(DEFAULTS)})")
+    cal = {**DEFAULTS, **raw}
+    cal["mode"] = str(cal["mode"]).lower()
+    if cal["mode"] not in MODES:
+        raise ValueError(f"calibration.mode: unknown mode '{cal['mode']}' ({' | '.join(MODES)})")
+    tasks = [str(t) for t in (cal["tasks"] if not isinstance(cal["tasks"], str) else [cal["tasks"]])]
+    bad = [t for t in tasks if t not in CAL_TASKS]
+    if bad:
+        raise ValueError(f"calibration.tasks: {bad} take no temperature ({', '.join(CAL_TASKS)}; PNR is a one-logit head)")
+    cal["tasks"] = tasks
+    tr = list(cal["t_range"]) if hasattr(cal["t_range"], "__iter__") else [cal["t_range"]]
+    if len(tr) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in tr) or not 0.0 < tr[0] <= 1.0 <= tr[1] < float("inf"):
+        raise ValueError(f"calibration.t_range: {tr!r} is not [T_min, T_max] with 0 < T_min <= 1 <= T_max")
+    cal["t_range"] = [float(tr[0]), float(tr[1])]
+    for key, least in (("iterations", 1), ("max_rows", 1)):
+        if isinstance(cal[key], bool) or not isinstance(cal[key], int) or cal[key] < least:
+            raise ValueError(f"calibration.{key}: {cal[key]!r} is not an integer >= {least}")
+    if isinstance(cal["stop"], bool) or not isinstance(cal["stop"], (int, float)) or not cal["stop"] >= 0:
+        raise ValueError(f"calibration.stop: {cal['stop']!r} is not a number >= 0")
+    cal["stop"], cal["save"] = float(cal["stop"]), bool(cal["save"])
+    pred = cal["predict"]
+    pred = "true" if pred is True else "false" if pred is False else str(pred).lower()
+    if pred not in ("auto", "true", "false"):
+        raise ValueError(f"calibration.predict: unknown value '{cal['predict']}' (auto | true | false)")
+    cal["predict"] = pred
+    cal["enabled"] = cal["mode"] == "temperature"
+    return cal
+
+
+def calibration_meter_args(cfg, task: str) -> dict:
+    """The keyword arguments of ``build_meter_for_dataset`` for ``task``: {} with calibration off (or a task that takes none)."""
+    cal = calibration_config(cfg)
+    if not cal["enabled"] or task not in cal["tasks"]:
+        return {}
+    return dict(calibration={k: cal[k] for k in ("t_range", "iterations", "stop", "max_rows")})
+
+
+def calibration_path(directory, task: str) -> Path:
+    return Path(directory) / f"calibration_{task}.pt"
+
+
+def save_calibration(logger, cfg, directory: Path, fits: dict) -> list:
+    """``calibration.save``: one ``calibration_<task>.pt`` per task under ``directory`` (beside the checkpoint, like
+    ``class_report_<task>.pt``) with the per-head temperatures, status and row counts of the fit on all rows, the fold fits,
+    ``t_range`` and the split it was fitted on.  ``fits``: task -> ``calibration.fit``'s result.  Returns the paths written."""
+    cal = calibration_config(cfg)
+    if not (cal["enabled"] and cal["save"]):
+        return []
+    paths = []
+    for t, heads in (fits or {}).items():
+        if not heads:
+            continue
+        Path(directory).mkdir(parents=True, exist_ok=True)
+        path = calibration_path(directory, t)
+        torch.save({"task": t, "heads": heads, "t_range": cal["t_range"], "split": str(cfg.get("validation_split", "")),
+                    "iterations": cal["iterations"], "stop": cal["stop"]}, path)
+        logger.info("calibration of %s -> %s (%s)", t, path, ", ".join(f"{h} T={v['temperature']:.4f} [{v['status']}]" for h, v in heads.items()))
+        paths.append(path)
+    return paths
+
+
+def load_calibration(cfg, directory, task: str) -> Optional[dict]:
+    """The calibration file of ``task`` under ``directory`` as ``calibration.predict`` asks for it: None with ``false`` and, with
+    ``auto``, when there is no file; with ``true`` a missing file is a FileNotFoundError.  A file of another task or with a
+    temperature that is not a finite positive number is a ValueError."""
+    cal = calibration_config(cfg)
+    if cal["predict"] == "false":
+        return None
+    path = calibration_path(directory, task)
+    if not path.exists():
+        if cal["predict"] == "true":
+            raise FileNotFoundError(f"calibration.predict=true: {path} is missing (python calibrate.py resume_from=<checkpoint> writes it)")
+        return None
+    blob = torch.load(path, map_location="cpu", weights_only=False)
+    if blob.get("task") != task or not blob.get("heads"):
+        raise ValueError(f"{path}: not a calibration file of task {task}")
+    for h, v in blob["heads"].items():
+        if not 0.0 < float(v["temperature"]) < float("inf"):
+            raise ValueError(f"{path}: head {h} holds the temperature {v['temperature']!r}")
+    return blob
+
+
 def build_lta_sampler(cfg):
     """The ``ops.FutureSampler`` of ``lta_sampling.mode=philox`` (stateless: nothing of it goes into a checkpoint); None with
     ``mode: torch`` -- the validation loop then samples with torch's generator, as the reference does."""

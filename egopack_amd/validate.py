@@ -82,6 +82,7 @@ def validate(epoch, temporal_graph_model, dataloader, meter, primary_task, other
         logits, feat = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
         pre = data.x.mean(1) if data.x.dim() == 3 else data.x
         loss = primary_task.compute_loss(logits, data.y).mean()
+        meter.batch_ordinal = getattr(data, "ordinal", None)  # (the folds of the temperature fit follow the batch order, not the rank)
         meter.update(logits, data.y, loss, pre, feat)
 
 
@@ -101,6 +102,7 @@ def validate_lta(temporal_graph_model, dataloader, meter, primary_task, other_ta
         else:
             predictions, logits = primary_task.generate_from_logits(logits)
         loss = primary_task.compute_loss(logits, data.y).mean()
+        meter.batch_ordinal = getattr(data, "ordinal", None)
         meter.update(logits, data.y, predictions, loss)
 
 

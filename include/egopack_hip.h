@@ -800,5 +800,9 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* LAMB, the layer-wise adaptive rule: per-slot norms of the parameters and of the update in a reduce launch, a trust ratio per slot,
  * and the apply launch (egk_lamb_moments, egk_lamb_trust, egk_lamb_apply) */
 #include "egopack_lamb.h"
+/* post-hoc temperature calibration of a head, fitted on the device: integer sums of the scaled logits' NLL and its two derivatives,
+ * a safeguarded Newton step per head, and the calibrated probabilities of a given top-k order (egk_temp_stats, egk_temp_newton,
+ * egk_temp_topk_prob, egk_temp_scale_rows) */
+#include "egopack_calibrate.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -35,11 +35,12 @@ AUX_ORDER = {"ar": ("lta", "oscc", "pnr"), "oscc": ("ar", "lta", "pnr"), "lta": 
 
 
 def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders, late_fusion=True, validate_all=False,
-                     device="cuda", sampler=None, report=None, reports=None):
+                     device="cuda", sampler=None, report=None, reports=None, calibrations=None):
     """Task metrics with the GraphONE interaction for the novel task(s) (reference main_egopack.py:374-448).  ``sampler``: the
     seeded sampler of the LTA futures (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``:
-    task -> the meter's per-class report arguments (``T.class_report_meter_args``, log_confusion_matrices); ``reports``: a dict
-    that receives every task's tables."""
+    task -> the meter's per-class report arguments (``T.class_report_meter_args``, log_confusion_matrices) and its temperature-fit
+    arguments (``T.calibration_meter_args``, calibration.mode); ``reports``: a dict that receives every task's tables;
+    ``calibrations``: a dict that receives every task's fitted temperatures (``BaseMeter.temperature_fit``)."""
     out = {}
     for t in ("ar", "oscc", "lta", "pnr"):
         if not (validate_all or weights.get(t, 0) > 0):
@@ -60,6 +61,8 @@ def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders,
         out[t] = {k: v for k, v in meter.get_logs().items() if isinstance(v, (int, float))}
         if reports is not None and meter.reports:
             reports[t] = meter.report_tables()
+        if calibrations is not None and meter.temp_store is not None:
+            calibrations[t] = meter.temperature_fit()
     return out
 
 
@@ -180,7 +183,8 @@ def main(argv=None):
     # log_confusion_matrices: the per-class report of the validation meters; the training labels are counted once, here
     validated = [t for t in ("ar", "oscc", "lta", "pnr") if cfg.validate_all_tasks or weights.get(t, 0) > 0]
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=validated)
-    report, reports = (lambda t: T.class_report_meter_args(cfg, train_counts, t)), {}
+    report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t)}), {}
+    calibrations = {}  # (calibration.mode=temperature: task -> the temperatures fitted in the last validation)
     for epoch in range(1, cfg.num_epochs + 1):
         T.apply_reweight(logger, cfg, balance, tasks, epoch)  # (in place: a captured step keeps its pointers)
         train(epoch, step, dl_train, weights, device, store=store)
@@ -189,10 +193,12 @@ def main(argv=None):
         with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
             validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, dl_val, late_fusion=cfg.late_fusion,
                              validate_all=cfg.validate_all_tasks, device=device, sampler=sampler, report=report,
-                             reports=reports)  # all ranks: the split is sharded by batch
+                             reports=reports, calibrations=calibrations)  # all ranks: the split is sharded by batch
     if rank == 0:  # (class_report.save: the tables of the last validation, beside the checkpoint)
         T.save_class_reports(logger, cfg, Path(cfg.checkpoint_dir) / (f"{cfg.artifact_prefix}_egopack_" + "-".join(
             sorted(t for t, w in weights.items() if w > 0))), reports)
+        T.save_calibration(logger, cfg, Path(cfg.checkpoint_dir) / (f"{cfg.artifact_prefix}_egopack_" + "-".join(
+            sorted(t for t, w in weights.items() if w > 0))), calibrations)
     if cfg.save_model and step.sync is not None:
         step.sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
     if cfg.save_model and rank == 0:

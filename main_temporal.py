@@ -94,10 +94,13 @@ def validate_losses(step: engine.MTLStep, loaders, device="cuda"):
     return out
 
 
-def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="cuda", sampler=None, report=None, reports=None):
+def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="cuda", sampler=None, report=None, reports=None,
+                     calibrations=None):
     """Task metrics of every enabled task (reference main_temporal.py:340-400).  ``sampler``: the seeded sampler of the LTA futures
     (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``: task -> the meter's per-class report
-    arguments (``T.class_report_meter_args``, log_confusion_matrices); ``reports``: a dict that receives every task's tables."""
+    arguments (``T.class_report_meter_args``, log_confusion_matrices) and its temperature-fit arguments
+    (``T.calibration_meter_args``, calibration.mode); ``reports``: a dict that receives every task's tables; ``calibrations``: a dict
+    that receives every task's fitted temperatures (``BaseMeter.temperature_fit``)."""
     out = {}
     for t in enabled:
         meter = build_meter_for_dataset(dsets_val[t], device=device, **(report(t) if report else {}))
@@ -113,6 +116,8 @@ def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="c
         out[t] = {k: v for k, v in meter.get_logs().items() if isinstance(v, (int, float))}
         if reports is not None and meter.reports:
             reports[t] = meter.report_tables()
+        if calibrations is not None and meter.temp_store is not None:
+            calibrations[t] = meter.temperature_fit()
     return out
 
 
@@ -204,7 +209,8 @@ def main(argv=None):
     sampler = T.build_lta_sampler(cfg)  # (lta_sampling.mode=philox: the LTA futures from the seeded launch; None: torch's generator)
     # log_confusion_matrices: the per-class report of the validation meters; the training labels are counted once, here
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=step.enabled)
-    report, reports = (lambda t: T.class_report_meter_args(cfg, train_counts, t)), {}
+    report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t)}), {}
+    calibrations = {}  # (calibration.mode=temperature: task -> the temperatures fitted in the last validation)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
         # (ce_shape.reweight_after: the class-weight buffers are rewritten in place -- a captured step keeps its pointers; after a
@@ -224,14 +230,15 @@ def main(argv=None):
             with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
                 logger.info("validation losses: %s", validate_losses(step, dl_val, device))
                 metrics = validate_metrics(epoch, model, tasks, step.enabled, dsets_val, dl_val, device, sampler=sampler,
-                                           report=report, reports=reports)
+                                           report=report, reports=reports, calibrations=calibrations)
     if cfg.num_epochs < first_epoch and cfg.get("validate_untrained", False):  # (num_epochs=0: metrics of the initial state)
         T.log_validation_weights(logger, cfg, optimizer, 0)
         with T.ema_scope(cfg, optimizer):
             metrics = validate_metrics(0, model, tasks, step.enabled, dsets_val, dl_val, device, sampler=sampler, report=report,
-                                       reports=reports)
+                                       reports=reports, calibrations=calibrations)
     if rank == 0:
         T.save_class_reports(logger, cfg, ckpt_path.parent, reports)  # (class_report.save: the tables of the last validation)
+        T.save_calibration(logger, cfg, ckpt_path.parent, calibrations)  # (calibration.save: the temperatures of the last validation)
     if cfg.save_model and sync is not None:
         sync.gather_moments(optimizer)
     if cfg.save_model and rank == 0:
