@@ -32,8 +32,9 @@ LAMB_PIECE = 4096  # EGK_LAMB_PIECE (include/egopack_lamb.h)
 # The OPEN third table: every later header goes here.  The same parser, the same rules, and one ledger for the whole
 # table, tests/test_cabi_addons.py, which reads what it pins per key from tests/cabi_addon_<key>.py -- a new header adds a key here and
 # files there.  Scalars and pointers only (STRUCTS stays as ledgered); a name another header of any table declares is refused.
-ADDON_HEADERS = {"calibrate": HERE.parent / "include" / "egopack_calibrate.h"}
+ADDON_HEADERS = {"calibrate": HERE.parent / "include" / "egopack_calibrate.h", "action": HERE.parent / "include" / "egopack_action.h"}
 TEMP_MAX_HEADS, TEMP_MAX_K = 8, 64  # EGK_TEMP_MAX_* (include/egopack_calibrate.h)
+ACTION_MAX_K, ACTION_MAX_C = 32, 1024  # EGK_ACTION_MAX_* (include/egopack_action.h)
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 

@@ -10,6 +10,7 @@
 //                     row's log-sum-exp, in one launch (include/egopack_topk.h: what a prediction file holds)
 #include "ce_row.h"
 #include "common.h"
+#include "rank_key.h"
 
 namespace egk {
 
@@ -64,19 +65,8 @@ __global__ __launch_bounds__(64) void edit_distance_kernel(const long long* __re
 }
 
 // ---- the per-class report: one wave per (task, row) ---------------------------------------------------------------------------
-// The order of label_rank_kernel as ONE integer per class: the f32 value as a monotone 32-bit key (NaN -> 0, below the key of -inf;
-// -0 and +0 share a key) above the complemented class index, so that the larger integer is the better class, no two classes of a
-// row share one, and 0 means "no class".  top1 / top2 are the largest and the second largest of the row.
-__device__ __forceinline__ unsigned long long rank_key(float v, int c) {
-    unsigned k;
-    if (v != v) {
-        k = 0u;
-    } else {
-        const unsigned b = __float_as_uint(v == 0.f ? 0.f : v);
-        k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    return ((unsigned long long)k << 32) | (unsigned long long)(0xffffffffu - (unsigned)c);
-}
+// (the order of label_rank_kernel as ONE integer per class: rank_key of rank_key.h.)  top1 / top2 are the largest and the second
+// largest key of the row.
 __device__ __forceinline__ void add_i64(long long* p, long long v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 
 struct ClassReportTasks {
@@ -144,15 +134,6 @@ constexpr int TOPK_RES = WAVE * TOPK_SLOTS;
 struct TopkTasks {
     egk_topk_task t[EGK_TOPK_MAX_TASKS];
 };
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long b = __shfl_xor(v, o, 64);
-        v = v > b ? v : b;
-    }
-    return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void topk_softmax_kernel(const TopkTasks P, int count, int rows, int k) {

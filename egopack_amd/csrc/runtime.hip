@@ -58,7 +58,8 @@ static const char* const kNames[KID_COUNT] = {
     "row_inv_norm", "topk", "scatter_add_f64", "ce_fwd", "ce_bwd", "bce_fwd", "bce_bwd",
     "dropout_fwd", "dropout_bwd", "relu_gate", "cast", "axpby", "sum_scale", "adam", "optim", "optim_groups", "optim_ema", "ema_swap",
     "ce_balanced", "bce_balanced", "task_scale", "categorical_sample", "class_report", "topk_softmax",
-    "retrieval_report", "temp_stats", "temp_newton", "temp_topk_prob", "temp_scale_rows",  // (the LAMB ids stay last: tests/test_lamb_cpu.py)
+    "retrieval_report", "temp_stats", "temp_newton", "temp_topk_prob", "temp_scale_rows",
+    "action_topk", "edit_distance_pairs",  // (the LAMB ids stay last: tests/test_lamb_cpu.py)
     "lamb_moments", "lamb_trust", "lamb_apply"};
 
 struct Pending {

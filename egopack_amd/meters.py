@@ -15,6 +15,8 @@ it kept in small device tensors -- nothing is copied to the host before ``comput
     utils/confusion.py + ego4d.py:125-170   class_report=True   per head: *_confusion, *_top2_confusion, *_class_loss,
                                                            *_class_precision / _recall / _f1, *_top_confusions,
                                                            *_macro_precision / _recall / _f1, *_acc_many / _medium / _few
+    action_scores (config block)   action_scores=  actions_top{1,2,3,5} (AR, anticipation), actions_top1 + actions_ed
+                                                           (LTA), actions_seen_top1 / actions_unseen_top1 with their supports
 Dropped: feature dumps, W&B tables and plots (reporting only).
 
 The per-class report (``class_report=True``; ``log_confusion_matrices`` of the config) is one ``egk_class_report`` launch per
@@ -67,6 +69,29 @@ def edit_distances(pred: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
     ops._ck(_lib.load().egk_edit_distance(ops._stream(), ops._p(pred), pred.stride(0), pred.stride(1), pred.stride(2),
                                           ops._p(label), label.stride(0), label.stride(1), ops._p(out), n, z, k),
             "egk_edit_distance")
+    return out
+
+
+def action_edit_distances(pred_v: torch.Tensor, pred_n: torch.Tensor, label_v: torch.Tensor, label_n: torch.Tensor) -> torch.Tensor:
+    """int32 [N, K, 3]: the Levenshtein distances between the futures pred[n, :, k] and label[n, :] of the verbs ([., ., 0]), of the
+    nouns ([., ., 1]: both the integers of ``edit_distances``) and of the actions ([., ., 2]: a position matches only if verb AND
+    noun do), in one launch -- ``egk_edit_distance_pairs``."""
+    ops._need_gpu(pred_v, pred_n, label_v, label_n)
+    if pred_v.shape != pred_n.shape or label_v.shape != label_n.shape or pred_v.dim() != 3 or label_v.shape != pred_v.shape[:2]:
+        raise ValueError(f"action_edit_distances: pred [N, Z, K] and label [N, Z] of both heads (got {tuple(pred_v.shape)}, "
+                         f"{tuple(pred_n.shape)}, {tuple(label_v.shape)}, {tuple(label_n.shape)})")
+    pred_v, pred_n, label_v, label_n = (t.to(torch.int64) for t in (pred_v, pred_n, label_v, label_n))
+    if pred_n.stride() != pred_v.stride():  # (the launch reads both heads through one set of strides)
+        pred_v, pred_n = pred_v.contiguous(), pred_n.contiguous()
+    if label_n.stride() != label_v.stride():
+        label_v, label_n = label_v.contiguous(), label_n.contiguous()
+    n, z, k = pred_v.shape
+    out = torch.zeros((n, k, 3), dtype=torch.int32, device=pred_v.device)
+    if n == 0 or z == 0 or k == 0:  # empty sequences are at distance 0
+        return out
+    ops._ck(_lib.load().egk_edit_distance_pairs(ops._stream(), ops._p(pred_v), ops._p(pred_n), pred_v.stride(0), pred_v.stride(1),
+                                                pred_v.stride(2), ops._p(label_v), ops._p(label_n), label_v.stride(0),
+                                                label_v.stride(1), ops._p(out), n, z, k), "egk_edit_distance_pairs")
     return out
 
 
@@ -208,6 +233,54 @@ class _HeadCounts:
         return float(self.class_accuracy(k)[seen].mean()) if bool(seen.any()) else 0.0
 
 
+class _ActionCounts:
+    """hits@k and the valid count of the ACTION, the (verb, noun) pair, of a meter with both heads, on the device: integer counts
+    of the exact rank of the labelled pair among all Cv * Cn pairs (``ops.action_topk``: one launch per batch, k = the largest of
+    ``ks``, ranks only).  A row counts when both labels lie inside their heads.  ``seen`` (a sorted int64 vector of
+    the codes v * Cn + n of the training split's pairs, on the device; None: off) splits the top-1 counts into pairs that occur in
+    the training split and pairs that do not: ``split`` = [seen hits, seen rows, unseen hits, unseen rows]."""
+
+    def __init__(self, n_verbs: int, n_nouns: int, device, ks: Sequence[int] = KS, seen=None):
+        self.ks, self.Cv, self.Cn = tuple(ks), int(n_verbs), int(n_nouns)
+        self.hits = torch.zeros(len(self.ks), dtype=torch.int64, device=device)
+        self.valid = torch.zeros((), dtype=torch.int64, device=device)
+        self.seen = None if seen is None else torch.as_tensor(seen, dtype=torch.int64).to(device)
+        self.split = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def update(self, verb_logits, noun_logits, verb_labels, noun_labels):
+        yv, yn = verb_labels.to(torch.int64), noun_labels.to(torch.int64)
+        rank = ops.action_topk(verb_logits, noun_logits, max(self.ks), labels=(yv, yn), want_prob=False, want_logp=False)["rank"]
+        self.count(rank, yv, yn)
+
+    def count(self, rank: torch.Tensor, yv: torch.Tensor, yn: torch.Tensor):
+        """The integer arithmetic on a rank vector (-1: the row does not count)."""
+        ok = rank >= 0
+        self.valid += ok.sum()
+        for i, k in enumerate(self.ks):
+            self.hits[i] += (ok & (rank < k)).sum()
+        if self.seen is not None:
+            code = torch.where(ok, yv.to(torch.int64) * self.Cn + yn.to(torch.int64), torch.full_like(yv, -1, dtype=torch.int64))
+            known = torch.zeros_like(ok)
+            if self.seen.numel():
+                at = torch.searchsorted(self.seen, code).clamp(max=self.seen.numel() - 1)
+                known = ok & (self.seen[at] == code)
+            hit = ok & (rank < 1)
+            self.split += torch.stack([(hit & known).sum(), known.sum(), (hit & ~known).sum(), (ok & ~known).sum()])
+
+    def tensors(self) -> List[torch.Tensor]:
+        return [self.hits, self.valid, self.split]
+
+    def accuracy(self, k: int) -> float:
+        return float(self.hits[self.ks.index(k)]) / max(int(self.valid), 1)
+
+    def split_logs(self) -> dict:
+        if self.seen is None:
+            return {}
+        sh, sn, uh, un = (int(v) for v in self.split)
+        return {"actions_seen_top1": sh / max(sn, 1), "actions_seen_support": sn, "actions_unseen_top1": uh / max(un, 1),
+                "actions_unseen_support": un}
+
+
 class _Calibration:
     """torchmetrics MulticlassCalibrationError(num_classes, n_bins, norm, ignore_index=-1) as the reference builds it
     (utils/meters/ego4d.py:52-53, :66-67: 15 bins / l1 = the expected calibration error; 1 bin / l2 = its "Brier score") as
@@ -269,8 +342,11 @@ class BaseMeter:
     """utils/meters/base.py: running mean of the per-batch loss + sample counter."""
 
     def __init__(self, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
-                 shots=(20, 100), top_confusions: int = 20, calibration=None) -> None:
+                 shots=(20, 100), top_confusions: int = 20, calibration=None, action_scores=None) -> None:
         self.device = torch.device(device)
+        # action-level scores (``action_scores``: topk and the seen pairs of the config block; None: no state, no launch, no key):
+        # the verb / noun meters build an ``_ActionCounts`` from it
+        self.action_cfg = dict(action_scores) if action_scores else None
         # temperature calibration (``calibration``: t_range, iterations, stop, max_rows of the config block; None: no state, no
         # launch, no key): the meters that have heads fill ``temp_store`` with what they score, ``get_logs`` fits once
         self.temp_cfg = dict(calibration) if calibration else None
@@ -457,9 +533,28 @@ class _VerbNounMeter(BaseMeter):
         self._add_report("verbs_", self.verb_labels, self.idx_verbs)
         self._add_report("nouns_", self.noun_labels, self.idx_nouns)
         self._add_temperature({"verbs_": len(self.verb_labels), "nouns_": len(self.noun_labels)})
+        self.actions = None  # (action_scores off: no state, no launch, no key)
+        if self.action_cfg is not None:
+            self.actions = _ActionCounts(len(self.verb_labels), len(self.noun_labels), self.device, seen=self.action_cfg.get("seen"))
 
     def _sums(self):
-        return [*super()._sums(), *self.verbs.tensors(), *self.nouns.tensors()]
+        return [*super()._sums(), *self.verbs.tensors(), *self.nouns.tensors(), *(self.actions.tensors() if self.actions else ())]
+
+    def _action_logs(self, ks=KS, fmt: str = "actions_top{k}") -> dict:
+        if self.actions is None:
+            return {}
+        return {**{fmt.format(k=k): self.actions.accuracy(k) for k in ks}, **self.actions.split_logs()}
+
+    def _action_lines(self, ks=KS) -> List[str]:
+        if self.actions is None:
+            return []
+        a = self.actions
+        line = "Actions " + ", ".join(f"Top-{k}: {a.accuracy(k) * 100:.2f}" for k in ks)
+        sp = a.split_logs()
+        if sp:
+            line += (f"; seen pairs Top-1: {sp['actions_seen_top1'] * 100:.2f} (n={sp['actions_seen_support']}), "
+                     f"unseen Top-1: {sp['actions_unseen_top1'] * 100:.2f} (n={sp['actions_unseen_support']})")
+        return [line]
 
     @torch.no_grad()
     def _count(self, logits, labels):
@@ -470,6 +565,8 @@ class _VerbNounMeter(BaseMeter):
                           (logits[self.idx_nouns], labels[:, self.idx_nouns], self.reports["nouns_"][0])])
         self._temperature_append([("verbs_", logits[self.idx_verbs], labels[:, self.idx_verbs]),
                                   ("nouns_", logits[self.idx_nouns], labels[:, self.idx_nouns])])
+        if self.actions is not None:  # the joint of both heads: one launch, ranks only
+            self.actions.update(logits[self.idx_verbs], logits[self.idx_nouns], labels[:, self.idx_verbs], labels[:, self.idx_nouns])
 
 
 class RecognitionMeter(_VerbNounMeter):
@@ -496,7 +593,7 @@ class RecognitionMeter(_VerbNounMeter):
                 f"Verbs Mean class: {v.mean_class() * 100:.2f}", f"Nouns Mean class: {n.mean_class() * 100:.2f}",
                 f"Verbs Brier score: {self.calibration['verbs'][1].compute():.4f}",
                 f"Nouns Brier score: {self.calibration['nouns'][1].compute():.4f}",
-                *super().print_logs()]
+                *self._action_lines(), *super().print_logs()]
 
     def get_logs(self, *args, **kwargs):
         out = {}
@@ -507,7 +604,7 @@ class RecognitionMeter(_VerbNounMeter):
                                         "top-5": h.class_accuracy(5).cpu(), "support": h.support.cpu()}
             out[f"{name}_calibration_erorr"] = self.calibration[name][0].compute()  # (sic: the reference's key, ego4d.py:174)
             out[f"{name}_brier_score"] = self.calibration[name][1].compute()
-        return {**out, **super().get_logs()}
+        return {**out, **self._action_logs(), **super().get_logs()}
 
 
 class AnticipationMeter(_VerbNounMeter):
@@ -521,12 +618,12 @@ class AnticipationMeter(_VerbNounMeter):
         for name, h in (("verbs", self.verbs), ("nouns", self.nouns)):
             out.update({f"{name}_accuracy_top{k}": h.accuracy(k) for k in KS})
             out.update({f"{name}_recall_top{k}": h.mean_class(k) for k in KS})  # topk_recall_fast: classes that occur
-        return {**out, **super().get_logs()}
+        return {**out, **self._action_logs(), **super().get_logs()}
 
     def print_logs(self):
         logs = self.get_logs()
         mine = [k for k in logs if k.startswith(("verbs_accuracy_top", "verbs_recall_top", "nouns_accuracy_top", "nouns_recall_top"))]
-        return [", ".join(f"{k}: {logs[k] * 100:.2f}" for k in mine), *super().print_logs()]
+        return [", ".join(f"{k}: {logs[k] * 100:.2f}" for k in mine), *self._action_lines(), *super().print_logs()]
 
 
 class OSCCMeter(BaseMeter):
@@ -640,11 +737,22 @@ class LTAMeter(_VerbNounMeter):
         self.N_NODES = int(getattr(dataset, "lta_nodes", self.N_NODES))  # synthetic datasets use their own T
         self.ed_sum = torch.zeros(2, dtype=torch.float64, device=self.device)
         self.ed_n = 0
+        self.action_ed_sum = torch.zeros((), dtype=torch.float64, device=self.device) if self.actions is not None else None
 
     _INTS = (*BaseMeter._INTS, "ed_n")
 
     def _sums(self):
-        return [*super()._sums(), self.ed_sum]
+        return [*super()._sums(), self.ed_sum, *([self.action_ed_sum] if self.action_ed_sum is not None else ())]
+
+    def _pair_distances(self, preds, labels):
+        """(verb, noun, action) distances per sequence -- the minimum over the futures of each column, divided by Z -- from ONE
+        ``egk_edit_distance_pairs`` launch; ``last_pair_distances``: its int32 [N, K, 3] result."""
+        pv, pn = (preds[i].reshape(-1, self.N_NODES, self.N_SAMPLES)[:, self.SKIP:] for i in (self.idx_verbs, self.idx_nouns))
+        lv, ln = (labels[:, i].reshape(-1, self.N_NODES)[:, self.SKIP:] for i in (self.idx_verbs, self.idx_nouns))
+        d = action_edit_distances(pv, pn, lv, ln)
+        self.last_pair_distances = d
+        best = d.min(dim=1).values.double() / pv.shape[1]
+        return best[:, 0], best[:, 1], best[:, 2]
 
     def _edit_distance(self, preds: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         p = preds.reshape(-1, self.N_NODES, self.N_SAMPLES)[:, self.SKIP:]
@@ -655,30 +763,41 @@ class LTAMeter(_VerbNounMeter):
     def update(self, logits, labels, predictions, *args, **kwargs) -> None:
         super().update(labels, *args, **kwargs)
         self._count(logits, labels)  # rows with negative labels are skipped by the rank kernel (labels >= 0 filter)
-        dv = self._edit_distance(predictions[self.idx_verbs], labels[:, self.idx_verbs])
-        dn = self._edit_distance(predictions[self.idx_nouns], labels[:, self.idx_nouns])
+        if self.actions is not None:  # all three distances from the pair launch (the verb / noun columns are egk_edit_distance's integers)
+            dv, dn, da = self._pair_distances(predictions, labels)
+            self.action_ed_sum += da.sum()
+        else:
+            dv = self._edit_distance(predictions[self.idx_verbs], labels[:, self.idx_verbs])
+            dn = self._edit_distance(predictions[self.idx_nouns], labels[:, self.idx_nouns])
         self.ed_sum += torch.stack([dv.sum(), dn.sum()])
         self.ed_n += dv.numel()
         self.last_distances = (dv, dn)
 
     def get_logs(self, *args, **kwargs):
         v, n = (float(x) / max(self.ed_n, 1) for x in self.ed_sum)
-        return {"verbs_ed": v, "nouns_ed": n, "verbs_top1": self.verbs.accuracy(1), "nouns_top1": self.nouns.accuracy(1),
+        act = {}
+        if self.actions is not None:
+            act = {"actions_ed": float(self.action_ed_sum) / max(self.ed_n, 1), **self._action_logs(ks=(1,))}
+        return {"verbs_ed": v, "nouns_ed": n, "verbs_top1": self.verbs.accuracy(1), "nouns_top1": self.nouns.accuracy(1), **act,
                 **super().get_logs()}
 
     def print_logs(self):
         l = self.get_logs()
         return [f"verbs_ed: {l['verbs_ed']:.4f}", f"nouns_ed: {l['nouns_ed']:.4f}", f"verbs_top1: {l['verbs_top1']:.4f}",
-                f"nouns_top1: {l['nouns_top1']:.4f}", *super().print_logs()]
+                f"nouns_top1: {l['nouns_top1']:.4f}",
+                *([f"actions_ed: {l['actions_ed']:.4f}", *self._action_lines(ks=(1,))] if self.actions is not None else []),
+                *super().print_logs()]
 
 
 def build_meter_for_dataset(dataset, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
-                            shots=(20, 100), top_confusions: int = 20, calibration=None) -> BaseMeter:
+                            shots=(20, 100), top_confusions: int = 20, calibration=None, action_scores=None) -> BaseMeter:
     """utils/meters/__init__.py:10-22, keyed on the dataset's ``task`` name (synthetic and Ego4D datasets alike).
     ``class_report``: the per-class report of the verb / noun and OSCC meters (PNR is binary and reports tp / tn already: it
     takes no report); ``calibration``: the temperature fit of the same meters (``train.calibration_meter_args``; PNR takes none:
     a one-logit BCE head whose export is a frame index); ``train_counts``: per head the training labels of every class (``train.label_counts``) for the
-    many / medium / few-shot accuracies, ``shots`` their (lo, hi) borders, ``top_confusions`` the length of the confusion list."""
+    many / medium / few-shot accuracies, ``shots`` their (lo, hi) borders, ``top_confusions`` the length of the confusion list;
+    ``action_scores``: the action-level scores of the verb / noun meters (``train.action_scores_meter_args``; OSCC and PNR have no
+    pair and take none)."""
     kind = getattr(dataset, "task", None) or type(dataset).__name__.lower()
     rep = dict(class_report=class_report, train_counts=train_counts, shots=shots, top_confusions=top_confusions, calibration=calibration)
     if "pnr" in kind:
@@ -686,9 +805,9 @@ def build_meter_for_dataset(dataset, save_features: bool = False, device="cuda",
     if "oscc" in kind:
         return OSCCMeter(dataset, device=device, **rep)
     if "lta" in kind:
-        return LTAMeter(dataset, device=device, **rep)
+        return LTAMeter(dataset, device=device, action_scores=action_scores, **rep)
     if "anticipation" in kind:
-        return AnticipationMeter(dataset, device=device, **rep)
+        return AnticipationMeter(dataset, device=device, action_scores=action_scores, **rep)
     if "ar" in kind or "recognition" in kind:
-        return RecognitionMeter(dataset, save_features=save_features, device=device, **rep)
+        return RecognitionMeter(dataset, save_features=save_features, device=device, action_scores=action_scores, **rep)
     raise NotImplementedError(f"no meter for dataset {type(dataset).__name__}")

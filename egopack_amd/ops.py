@@ -3736,6 +3736,56 @@ def temp_scale_rows(logits, beta, out=None):
     return out[:, :Cn] if out.shape[1] != Cn else out
 
 
+# ---- action-level scores (include/egopack_action.h) -------------------------------------------------------------------
+@torch.no_grad()
+def action_topk(verb_logits, noun_logits, k: int, labels=None, beta=None, want_prob: bool = True, want_lse: bool = False,
+                want_rank: Optional[bool] = None, want_logp: bool = True):
+    """The best ``k`` (verb, noun) pairs of every row under the product of the two heads' softmaxes, in ONE launch
+    (``egk_action_topk``): a dict with ``pair`` int64 [N, k, 2] ((-1, -1) beyond Cv * Cn), ``logp`` / ``prob`` f32 [N, k] | None,
+    ``lse`` f32 [N, 2] | None and ``rank`` int32 [N] | None -- the exact number of pairs that outrank the labelled one, -1 for a row
+    with a label outside its head; ``rank < k`` <=> the labelled pair is exported.  ``labels``: (verb labels [N], noun labels [N]),
+    int64, column views are read through their stride; ``want_rank`` defaults to "labels are given".  ``beta``: f32 device tensor
+    of two words, 1 / T of the verbs and of the nouns (None: the raw logits).  The logits are [N, C] f32 or bf16 of one type (mixed:
+    widened to f32); views with a unit class stride are read in place through their row stride."""
+    _need_gpu(verb_logits, noun_logits, beta)
+    if verb_logits.dim() != 2 or noun_logits.dim() != 2 or verb_logits.shape[0] != noun_logits.shape[0]:
+        raise ValueError(f"action_topk: heads of [N, Cv] and [N, Cn] with one N (got {tuple(verb_logits.shape)}, {tuple(noun_logits.shape)})")
+    if not 1 <= int(k) <= _lib.ACTION_MAX_K:
+        raise RuntimeError(f"action_topk: k in 1 .. {_lib.ACTION_MAX_K} (got {k})")
+    k = int(k)
+    if not (1 <= verb_logits.shape[1] <= _lib.ACTION_MAX_C and 1 <= noun_logits.shape[1] <= _lib.ACTION_MAX_C):
+        raise RuntimeError(f"action_topk: 1 .. {_lib.ACTION_MAX_C} classes per head (got {verb_logits.shape[1]}, {noun_logits.shape[1]})")
+    zv, zn = verb_logits.detach(), noun_logits.detach()
+    if zv.dtype != zn.dtype:  # (one element type per launch; a bf16 head and its widening give the same scores)
+        zv, zn = cast_raw(_c(zv), torch.float32), cast_raw(_c(zn), torch.float32)
+    zv, zn = _rm(zv), _rm(zn)
+    if beta is not None and (beta.dtype != torch.float32 or beta.numel() < 2 or not beta.is_contiguous()):
+        raise ValueError(f"action_topk: beta is a contiguous f32 device tensor of two words (got {beta.dtype}, {tuple(beta.shape)})")
+    want_rank = labels is not None if want_rank is None else bool(want_rank)
+    if want_rank and labels is None:
+        raise ValueError("action_topk: want_rank needs the labels")
+    N, dev = zv.shape[0], zv.device
+    yv = yn = None
+    if want_rank:
+        yv, yn = labels
+        _need_gpu(yv, yn)
+        if any(y.dim() != 1 or y.shape[0] != N or y.dtype != torch.int64 for y in (yv, yn)):
+            raise ValueError(f"action_topk: int64 labels of [N] per head (got {[(y.dtype, tuple(y.shape)) for y in (yv, yn)]})")
+    out = {"pair": torch.empty((N, k, 2), dtype=torch.int64, device=dev),
+           "logp": torch.empty((N, k), dtype=torch.float32, device=dev) if want_logp else None,
+           "prob": torch.empty((N, k), dtype=torch.float32, device=dev) if want_prob else None,
+           "lse": torch.empty((N, 2), dtype=torch.float32, device=dev) if want_lse else None,
+           "rank": torch.empty((N,), dtype=torch.int32, device=dev) if want_rank else None}
+    if N == 0:  # (no rows: nothing to launch, and an empty tensor has no pointer to hand over)
+        return out
+    ld = lambda m: max(m.stride(0), m.shape[1])  # (a one-row tensor's stride is arbitrary)
+    _ck(_lib.load().egk_action_topk(_stream(), _p(zv), ld(zv), zv.shape[1], _p(zn), ld(zn), zn.shape[1], _p(beta),
+                                    _p(yv), yv.stride(0) if want_rank else 0, _p(yn), yn.stride(0) if want_rank else 0, N, k,
+                                    _p(out["pair"]), 2 * k, _p(out["logp"]), _p(out["prob"]), k, _p(out["lse"]), _p(out["rank"]),
+                                    _dt(zv)), "egk_action_topk")
+    return out
+
+
 # ---- retrieval report (include/egopack_retrieval.h, DESIGN 3.15) -------------------------------------------------------------------
 @torch.no_grad()
 def retrieval_report(feats, feats_act, banks, nns, distance_func: str = "cosine", want_dist: bool = True, want_wins: bool = True):

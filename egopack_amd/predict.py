@@ -107,7 +107,16 @@ def temperatures(calibration: Optional[dict]) -> dict:
 
 
 # ---- AR and LTA: the verb / noun heads, per node ------------------------------------------------------------------------------------
-def _heads_batch(out: _Fields, data, logits, k: int, bs: int, head_index, betas=None):
+def action_args(action: Optional[dict], device):
+    """``action`` ({"topk": k, "betas": [1 / T verbs, 1 / T nouns] | None}; None: the export is off) as the loops use it: (k, the
+    two-word device tensor ``ops.action_topk`` reads, or None)."""
+    if not action:
+        return None
+    betas = action.get("betas")
+    return int(action["topk"]), None if betas is None else torch.tensor([float(b) for b in betas], dtype=torch.float32, device=device)
+
+
+def _heads_batch(out: _Fields, data, logits, k: int, bs: int, head_index, betas=None, action=None):
     from .meters import label_rank
     heads = [logits[i] for i in head_index]
     (vi, vp, vl), (ni, np_, nl) = ops.topk_softmax(heads, k, want_prob=True, want_lse=True)  # both heads, one launch
@@ -121,31 +130,38 @@ def _heads_batch(out: _Fields, data, logits, k: int, bs: int, head_index, betas=
         rank = torch.stack([label_rank(h.detach(), y[:, i]) for h, i in zip(heads, head_index)], 1)
     out.add(sample=_node_samples(data, bs), pos=data.pos, verb_topk=vi, verb_prob=vp, noun_topk=ni, noun_prob=np_, verb_lse=vl,
             noun_lse=nl, label=label, rank=rank)
+    if action is not None:  # the best pairs under the product of both heads' softmaxes, one launch (action_scores)
+        a = ops.action_topk(heads[0], heads[1], action[0], beta=action[1], want_prob=True)
+        out.add(action_topk=a["pair"], action_logp=a["logp"], action_prob=a["prob"])
 
 
 @torch.no_grad()
 def predict_heads(temporal_graph_model, dataloader, primary_task, k: int = 5, other_tasks: Optional[List] = None, graphone=None,
-                  late_fusion: bool = True, device: str = "cuda", head_index=(0, 1), calibration=None) -> dict:
+                  late_fusion: bool = True, device: str = "cuda", head_index=(0, 1), calibration=None, action=None) -> dict:
     """The verb / noun heads of the AR task (or of any multi-head task), per node: ``sample``, ``pos``, ``verb_topk``, ``verb_prob``,
     ``noun_topk``, ``noun_prob`` [rows, k], ``verb_lse``, ``noun_lse`` [rows] and, when the split has labels, ``label`` [rows, 2] and
     ``rank`` int32 [rows, 2] (``egk_label_rank``; -1 for an ignored row).  ``late_fusion``: as ``validate.validate``.
-    ``calibration`` (``train.load_calibration``): ``*_prob`` and ``*_lse`` at the fitted temperatures, over the raw order."""
+    ``calibration`` (``train.load_calibration``): ``*_prob`` and ``*_lse`` at the fitted temperatures, over the raw order.
+    ``action`` ({"topk": k, "betas": [1 / T verbs, 1 / T nouns] | None}): also ``action_topk`` int64 [rows, k, 2], ``action_logp`` and
+    ``action_prob`` [rows, k], the best (verb, noun) pairs of ``ops.action_topk``; with betas the joint is SCORED AND ORDERED at
+    them, so its order may differ from the raw one (two temperatures make another product distribution)."""
     other_tasks = other_tasks or []
     bs = _batch_size(dataloader)
     betas = beta_words(calibration, ("verbs_", "nouns_"), device)
+    action = action_args(action, device)
     _eval_mode(temporal_graph_model, primary_task, other_tasks, graphone)
     out = _Fields()
     for data in dataloader:
         data = data.to(device)
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
-        _heads_batch(out, data, logits, k, bs, head_index, betas)
+        _heads_batch(out, data, logits, k, bs, head_index, betas, action)
     return out.result()
 
 
 @torch.no_grad()
 def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed: int = 0, n_nodes: int = 22, n_futures: int = 5,
                 other_tasks: Optional[List] = None, graphone=None, late_fusion: bool = False, device: str = "cuda",
-                head_index=(0, 1), calibration=None) -> dict:
+                head_index=(0, 1), calibration=None, action=None) -> dict:
     """The LTA task: the per-node fields of ``predict_heads`` and the sampled futures ``verb_futures`` / ``noun_futures``, int64
     [sequences, Z, K] (``futures_sample`` [sequences]: their samples), after dropping the observed nodes as ``meters.LTAMeter``
     does (sequences of ``n_nodes`` nodes -- the dataset's ``lta_nodes`` --, the first ``LTAMeter.SKIP`` dropped).  The futures come
@@ -156,6 +172,7 @@ def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed
     bs = _batch_size(dataloader)
     sampler = ops.FutureSampler(seed)
     betas = beta_words(calibration, ("verbs_", "nouns_"), device)  # (the per-node probabilities; the futures are the raw logits')
+    action = action_args(action, device)  # (``action``: as ``predict_heads``)
     _eval_mode(temporal_graph_model, primary_task, other_tasks, graphone)
     out = _Fields()
     for data in dataloader:
@@ -163,7 +180,7 @@ def predict_lta(temporal_graph_model, dataloader, primary_task, k: int = 5, seed
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=True)
         predictions, logits = primary_task.generate_from_logits(logits, K=n_futures, sampler=sampler,
                                                                 ordinal=getattr(data, "ordinal", None))
-        _heads_batch(out, data, logits, k, bs, head_index, betas)
+        _heads_batch(out, data, logits, k, bs, head_index, betas, action)
         fut = [predictions[i].reshape(-1, n_nodes, n_futures)[:, LTAMeter.SKIP:] for i in head_index]
         out.add(verb_futures=fut[0], noun_futures=fut[1], futures_sample=_seq_samples(data, bs, fut[0].shape[0], fut[0].device))
     return out.result()
@@ -246,13 +263,17 @@ def to_json(task: str, pred: dict, dataset) -> dict:
     OSCC: {"state_change", "prob"}; PNR: {"pnr_frame", "node", "prob"}.  A file with retrieval fields (predict_egopack.py) also gets
     ``"retrieval"`` per sample: {"pos": its nodes, <aux task>: {"index", "dist", "wins"[, "label"]} per node}."""
     doc = {}
+    act = [f for f in ("action_topk", "action_logp", "action_prob") if f in pred]  # (action_scores.enabled: per node of the sample)
     if task == "lta":
         for s, v, n in zip(pred["futures_sample"].tolist(), pred["verb_futures"], pred["noun_futures"]):
             doc[_key(dataset, s)] = {"verb": v.t().tolist(), "noun": n.t().tolist()}
+        if act:
+            for s, rows in _by_sample(pred["sample"]).items():
+                doc.setdefault(_key(dataset, s), {}).update({f: pred[f][rows].tolist() for f in act})
     elif task == "ar":
         for s, rows in _by_sample(pred["sample"]).items():
             doc[_key(dataset, s)] = {"pos": pred["pos"][rows].tolist(),
-                                     **{f: pred[f][rows].tolist() for f in ("verb_topk", "verb_prob", "noun_topk", "noun_prob")}}
+                                     **{f: pred[f][rows].tolist() for f in ("verb_topk", "verb_prob", "noun_topk", "noun_prob", *act)}}
     elif task == "oscc":
         for s, p, c in zip(pred["sample"].tolist(), pred["pred"].tolist(), pred["prob_change"].tolist()):
             doc[_key(dataset, s)] = {"state_change": bool(p == 1), "prob": float(c)}
@@ -281,7 +302,20 @@ def _class_names(task: str, dataset):
     return None
 
 
-def predict_task(t: str, model, dataloader, dataset, task, pc: dict, ls: dict, device, calibration=None, **fusion) -> dict:
+def action_export(cfg, directory, t: str, calibration=None):
+    """(``action`` of the loops, what the document records) for task ``t`` as the ``action_scores:`` block asks: (None, {}) with the
+    block off -- the file is then today's.  The record: ``action_topk_k`` and ``action_betas`` ({"verb", "noun"}: the 1 / T the
+    joint was scored at, or None: the raw logits)."""
+    from . import train as T
+    ac = T.action_scores_config(cfg)
+    if not ac["enabled"] or t not in ac["tasks"]:
+        return None, {}
+    _, betas = T.action_scores_betas(cfg, directory, t, calibration=calibration)
+    return ({"topk": ac["topk"], "betas": betas},
+            {"action_topk_k": ac["topk"], "action_betas": None if betas is None else {"verb": betas[0], "noun": betas[1]}})
+
+
+def predict_task(t: str, model, dataloader, dataset, task, pc: dict, ls: dict, device, calibration=None, action=None, **fusion) -> dict:
     """The loop of task ``t`` with the entry points' arguments (``pc``: ``predict_config``, ``ls``: ``train.lta_sampling_config``).
     ``calibration``: the task's calibration file (``train.load_calibration``; PNR takes none).  ``fusion``: ``other_tasks`` /
     ``graphone`` / ``late_fusion`` of the loops, for a model with a GraphONE."""
@@ -289,6 +323,8 @@ def predict_task(t: str, model, dataloader, dataset, task, pc: dict, ls: dict, d
     heads = (names.index("verbs"), names.index("nouns")) if names else (0, 1)
     if t != "pnr" and calibration:
         fusion = {**fusion, "calibration": calibration}
+    if t in ("ar", "lta") and action:  # (``action``: ``action_export``'s first entry)
+        fusion = {**fusion, "action": action}
     if t == "ar":
         return predict_heads(model, dataloader, task, k=pc["topk"], device=device, head_index=heads, **fusion)
     if t == "lta":
@@ -370,10 +406,11 @@ def main(argv=None):
         t0 = time.perf_counter()
         # calibration.predict: the file calibrate.py (or a validation with calibration.mode=temperature) wrote beside the checkpoint
         cal = T.load_calibration(cfg, Path(cfg.resume_from).resolve().parent, t) if t != "pnr" else None
-        pred = predict_task(t, model, loaders[t], dsets[t], tasks[t], pc, ls, device, calibration=cal)
+        action, action_doc = action_export(cfg, Path(cfg.resume_from).resolve().parent, t, calibration=cal)
+        pred = predict_task(t, model, loaders[t], dsets[t], tasks[t], pc, ls, device, calibration=cal, action=action)
         torch.cuda.synchronize()
         seconds[t] = time.perf_counter() - t0
-        results[t], paths[t] = write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t], **temperatures(cal))
+        results[t], paths[t] = write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t], **temperatures(cal), **action_doc)
     return {"predictions": results, "paths": paths, "out": out_dir, "seconds": seconds, "model": model, "tasks": tasks,
             "datasets": dsets, "loaders": loaders}
 

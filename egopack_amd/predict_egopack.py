@@ -172,8 +172,9 @@ def main(argv=None):
         t0 = time.perf_counter()
         # calibration.predict: the file calibrate.py enable_graphone=True wrote beside the checkpoint (PNR takes none)
         cal = T.load_calibration(cfg, Path(cfg.resume_from).resolve().parent, t) if t != "pnr" else None
+        action, action_doc = P.action_export(cfg, Path(cfg.resume_from).resolve().parent, t, calibration=cal)  # (action_scores)
         pred = P.predict_task(t, model, loaders[t] if tap is None else tap, dsets[t], tasks[t], pc, ls, device, calibration=cal,
-                              other_tasks=others, graphone=graphone if tap is None else tap, late_fusion=cfg.late_fusion)
+                              action=action, other_tasks=others, graphone=graphone if tap is None else tap, late_fusion=cfg.late_fusion)
         if tap is not None:
             pred.update(tap.result(labels, n_nouns))
         torch.cuda.synchronize()
@@ -181,6 +182,7 @@ def main(argv=None):
         extra = {"retrieval_tasks": [o.name for o in others], "retrieval_k": int(graphone.k),
                  "retrieval_distance": graphone.distance_func} if tap is not None else {}
         extra.update(P.temperatures(cal))
+        extra.update(action_doc)
         results[t], paths[t] = P.write_predictions(t, pred, dsets[t], pc, ls, ck, out_dir, seconds[t], **extra)
     return {"predictions": results, "paths": paths, "out": out_dir, "seconds": seconds, "model": model, "tasks": tasks,
             "graphone": graphone, "datasets": dsets, "loaders": loaders, "bank_labels": labels}

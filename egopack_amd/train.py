@@ -722,6 +722,101 @@ def load_calibration(cfg, directory, task: str) -> Optional[dict]:
     return blob
 
 
+# ---- action-level scores (``action_scores:`` of the config; include/egopack_action.h) ---------------------------------
+ACTION_SCORES_DEFAULTS = {"enabled": False, "tasks": ["ar", "lta"], "topk": 5, "calibrated": "auto", "seen_split": False}
+ACTION_SCORES_TASKS = ("ar", "lta")  # (the tasks with a verb and a noun head)
+
+
+def action_scores_config(cfg) -> dict:
+    """The ``action_scores:`` block with its defaults filled in and checked (a config without the block: the defaults, off); an
+    unknown key, task or ``calibrated`` value and a ``topk`` outside 1 .. 32 are ValueErrors that name it."""
+    from ._lib import ACTION_MAX_K
+    raw = cfg.get("action_scores") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(ACTION_SCORES_DEFAULTS)
+    if unknown:
+        raise ValueError(f"action_scores: unknown key(s) {sorted(unknown)} ({', '.join(ACTION_SCORES_DEFAULTS)})")
+    ac = {**ACTION_SCORES_DEFAULTS, **raw}
+    ac["enabled"], ac["seen_split"] = bool(ac["enabled"]), bool(ac["seen_split"])
+    tasks = [str(t) for t in (ac["tasks"] if not isinstance(ac["tasks"], str) else [ac["tasks"]])]
+    bad = [t for t in tasks if t not in ACTION_SCORES_TASKS]
+    if bad:
+        raise ValueError(f"action_scores.tasks: {bad} have no (verb, noun) pair ({', '.join(ACTION_SCORES_TASKS)})")
+    ac["tasks"] = tasks
+    if isinstance(ac["topk"], bool) or not isinstance(ac["topk"], int) or not 1 <= ac["topk"] <= ACTION_MAX_K:
+        raise ValueError(f"action_scores.topk: an integer in 1 .. {ACTION_MAX_K} (got {ac['topk']!r})")
+    cal = ac["calibrated"]
+    cal = "true" if cal is True else "false" if cal is False else str(cal).lower()
+    if cal not in ("auto", "true", "false"):
+        raise ValueError(f"action_scores.calibrated: unknown value '{ac['calibrated']}' (auto | true | false)")
+    ac["calibrated"] = cal
+    return ac
+
+
+def action_pair_codes(dataset) -> torch.Tensor:
+    """The sorted distinct codes v * Cn + n (int64) of the (verb, noun) pairs the labels of ``dataset`` hold, over all nodes of all
+    samples with both labels inside their heads: one pass over the split, like ``label_counts`` (from the label table where the
+    dataset holds one)."""
+    names = list(dataset.label_names)
+    iv, inn = names.index("verbs"), names.index("nouns")
+    Cv, Cn = dataset.num_class_labels[iv], dataset.num_class_labels[inn]
+    if hasattr(dataset, "_tables"):
+        y = torch.as_tensor(dataset._tables()["y"])
+        ys = [y.reshape(-1, y.shape[-1])]
+    else:
+        ys = [torch.as_tensor(dataset[i].y).reshape(-1, len(names)) for i in range(len(dataset))]
+    y = torch.cat(ys).to(torch.int64) if ys else torch.zeros((0, len(names)), dtype=torch.int64)
+    v, n = y[:, iv], y[:, inn]
+    ok = (v >= 0) & (v < Cv) & (n >= 0) & (n < Cn)
+    return torch.unique(v[ok] * Cn + n[ok])  # (sorted)
+
+
+def action_scores_seen(cfg, dsets_train, tasks=None) -> dict:
+    """{task: ``action_pair_codes`` of its training split} with ``action_scores.seen_split`` on -- {} otherwise (nothing is read).
+    Built once per run."""
+    ac = action_scores_config(cfg)
+    if not (ac["enabled"] and ac["seen_split"]):
+        return {}
+    return {t: action_pair_codes(dsets_train[t]) for t in ac["tasks"] if t in dsets_train and (tasks is None or t in tasks)}
+
+
+def action_scores_meter_args(cfg, task: str, seen=None) -> dict:
+    """The keyword arguments of ``build_meter_for_dataset`` for ``task``: {} with the block off (or a task without a pair).
+    ``seen``: ``action_scores_seen``'s dict."""
+    ac = action_scores_config(cfg)
+    if not ac["enabled"] or task not in ac["tasks"]:
+        return {}
+    args = {"topk": ac["topk"]}
+    if ac["seen_split"] and seen is not None and task in seen:
+        args["seen"] = seen[task]
+    return dict(action_scores=args)
+
+
+def action_scores_betas(cfg, directory, task: str, calibration=None):
+    """What the export scores the joint at: (the task's calibration file or None, [1 / T of the verbs, 1 / T of the nouns] or None)
+    as ``action_scores.calibrated`` asks.  ``calibration``: the file the caller loaded (``load_calibration``: what
+    ``calibration.predict`` allows).  ``auto``: that file when it is loaded, else the raw logits; ``true``: the file is required --
+    the one under ``directory`` is read when the caller loaded none, and a missing file is a FileNotFoundError; ``false`` (or the
+    block off for ``task``): (None, None)."""
+    ac = action_scores_config(cfg)
+    if not ac["enabled"] or task not in ac["tasks"] or ac["calibrated"] == "false":
+        return None, None
+    blob = calibration
+    if blob is None and ac["calibrated"] == "true":
+        path = calibration_path(directory, task)
+        if not path.exists():
+            raise FileNotFoundError(f"action_scores.calibrated=true: {path} is missing (python calibrate.py resume_from=<checkpoint> writes it)")
+        blob = torch.load(path, map_location="cpu", weights_only=False)
+        if blob.get("task") != task or not blob.get("heads"):
+            raise ValueError(f"{path}: not a calibration file of task {task}")
+    if blob is None:
+        return None, None
+    betas = [1.0 / float(blob["heads"][p]["temperature"]) for p in ("verbs_", "nouns_")]
+    if not all(0.0 < b < float("inf") for b in betas):
+        raise ValueError(f"action_scores: the calibration file of task {task} holds the temperatures {[1 / b for b in betas]}")
+    return blob, betas
+
+
 def build_lta_sampler(cfg):
     """The ``ops.FutureSampler`` of ``lta_sampling.mode=philox`` (stateless: nothing of it goes into a checkpoint); None with
     ``mode: torch`` -- the validation loop then samples with torch's generator, as the reference does."""

@@ -804,5 +804,9 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
  * a safeguarded Newton step per head, and the calibrated probabilities of a given top-k order (egk_temp_stats, egk_temp_newton,
  * egk_temp_topk_prob, egk_temp_scale_rows) */
 #include "egopack_calibrate.h"
+/* action-level scores: the best k (verb, noun) pairs of every row under the product of the two heads' softmaxes with the exact rank
+ * of the labelled pair, and the edit distances of the sampled futures per head and per action (egk_action_topk,
+ * egk_edit_distance_pairs) */
+#include "egopack_action.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -39,7 +39,7 @@ def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders,
     """Task metrics with the GraphONE interaction for the novel task(s) (reference main_egopack.py:374-448).  ``sampler``: the
     seeded sampler of the LTA futures (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``:
     task -> the meter's per-class report arguments (``T.class_report_meter_args``, log_confusion_matrices) and its temperature-fit
-    arguments (``T.calibration_meter_args``, calibration.mode); ``reports``: a dict that receives every task's tables;
+    arguments (``T.calibration_meter_args``, calibration.mode) and its action-score arguments (``T.action_scores_meter_args``); ``reports``: a dict that receives every task's tables;
     ``calibrations``: a dict that receives every task's fitted temperatures (``BaseMeter.temperature_fit``)."""
     out = {}
     for t in ("ar", "oscc", "lta", "pnr"):
@@ -183,7 +183,9 @@ def main(argv=None):
     # log_confusion_matrices: the per-class report of the validation meters; the training labels are counted once, here
     validated = [t for t in ("ar", "oscc", "lta", "pnr") if cfg.validate_all_tasks or weights.get(t, 0) > 0]
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=validated)
-    report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t)}), {}
+    seen_pairs = T.action_scores_seen(cfg, dsets_train, tasks=validated)  # (action_scores.seen_split: the training split's pairs, once)
+    report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t),
+                                  **T.action_scores_meter_args(cfg, t, seen_pairs)}), {}
     calibrations = {}  # (calibration.mode=temperature: task -> the temperatures fitted in the last validation)
     for epoch in range(1, cfg.num_epochs + 1):
         T.apply_reweight(logger, cfg, balance, tasks, epoch)  # (in place: a captured step keeps its pointers)

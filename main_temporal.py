@@ -99,7 +99,7 @@ def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="c
     """Task metrics of every enabled task (reference main_temporal.py:340-400).  ``sampler``: the seeded sampler of the LTA futures
     (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``: task -> the meter's per-class report
     arguments (``T.class_report_meter_args``, log_confusion_matrices) and its temperature-fit arguments
-    (``T.calibration_meter_args``, calibration.mode); ``reports``: a dict that receives every task's tables; ``calibrations``: a dict
+    (``T.calibration_meter_args``, calibration.mode) and its action-score arguments (``T.action_scores_meter_args``); ``reports``: a dict that receives every task's tables; ``calibrations``: a dict
     that receives every task's fitted temperatures (``BaseMeter.temperature_fit``)."""
     out = {}
     for t in enabled:
@@ -209,7 +209,9 @@ def main(argv=None):
     sampler = T.build_lta_sampler(cfg)  # (lta_sampling.mode=philox: the LTA futures from the seeded launch; None: torch's generator)
     # log_confusion_matrices: the per-class report of the validation meters; the training labels are counted once, here
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=step.enabled)
-    report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t)}), {}
+    seen_pairs = T.action_scores_seen(cfg, dsets_train, tasks=step.enabled)  # (action_scores.seen_split: the training split's pairs, once)
+    report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t),
+                                  **T.action_scores_meter_args(cfg, t, seen_pairs)}), {}
     calibrations = {}  # (calibration.mode=temperature: task -> the temperatures fitted in the last validation)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
