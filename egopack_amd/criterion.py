@@ -141,9 +141,24 @@ class MetricSelectorWrapper(torch.nn.Module):
             return tuple(logits), ground_truths, smoothing  # all heads: the common case on the path
         return tuple(logits[h] for h in heads), ground_truths[:, heads].contiguous(), smoothing
 
-    def forward(self, logits: Tuple[torch.Tensor, ...], ground_truths: torch.Tensor) -> torch.Tensor:
+    def select_mix(self, logits: Tuple[torch.Tensor, ...], mix):
+        """The two-target argument of ``ops.cross_entropy(mix=)`` for the heads ``select`` chooses: (the partner labels' columns,
+        lam) -- or None without one or in ``eval()`` mode (mixup shapes the training loss only)."""
+        if mix is None or not self.training:
+            return None
+        y_b, lam = mix
+        heads = self._heads(len(logits))
+        if heads == list(range(y_b.shape[1])):
+            return y_b, lam
+        return y_b[:, heads].contiguous(), lam
+
+    def forward(self, logits: Tuple[torch.Tensor, ...], ground_truths: torch.Tensor, mix=None) -> torch.Tensor:
+        """``mix``: None, or (partner labels of ground_truths' shape, f32 lam per row) -- sequence mixup, training mode only."""
         sel, gt, smoothing = self.select(logits, ground_truths)
         weights, offsets = self.select_balance(logits)
         margins, gamma = self.select_shape(logits)
+        mix = self.select_mix(logits, mix)
+        if mix is not None:
+            return ops.cross_entropy(sel, gt, smoothing, weight=weights, offset=offsets, margin=margins, gamma=gamma, mix=mix)
         # one fused per-row sum over the heads
         return ops.cross_entropy(sel, gt, smoothing, weight=weights, offset=offsets, margin=margins, gamma=gamma)

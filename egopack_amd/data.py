@@ -290,6 +290,51 @@ def live_rows_progression(live_idx):
     return int(idx[0]), step, n
 
 
+# ---- sequence mixup: pairing and coefficients, drawn on the host (include/egopack_mixup.h reads them on the device) -----------------
+MIX_TASKS = ("ar", "lta")
+MIX_TASK_IDS = {"ar": 1, "lta": 2}
+
+
+def mixup_key(seed: int, epoch: int, ordinal: int, task: str):
+    """(key [2], counter [4]) of the Philox stream of one batch's mixup draw: a function of (seed, epoch, batch ordinal, task) and of
+    nothing else -- not of the process, the rank, the worker that collated the batch or the batches drawn before it."""
+    if task not in MIX_TASK_IDS:
+        raise ValueError(f"mixup: task '{task}' is not one of {MIX_TASKS}")
+    key = np.array([int(seed) & 0xFFFFFFFFFFFFFFFF, ((int(epoch) & 0xFFFFFFFF) << 32) | (int(ordinal) & 0xFFFFFFFF)], dtype=np.uint64)
+    return key, np.array([MIX_TASK_IDS[task], 0x6D697875, 0, 0], dtype=np.uint64)
+
+
+def mixup_fields(ptr, y, seed: int, epoch: int, ordinal: int, task: str, alpha: float, per_sequence: bool = True, prob: float = 1.0):
+    """The three fields a mixed training batch carries -- (mix_src int32 [N], mix_lam float32 [N], mix_y = y[mix_src]) -- for a batch
+    whose sequence s owns the rows ptr[s] .. ptr[s + 1]:
+      mix_src  the partner ROW of every node.  Partners are whole sequences of the same node count, node i onto node i; the pairing
+               is a random permutation inside each group of equal-length sequences (of the whole batch when all are equally long);
+               a sequence without an equal-length partner maps to itself.  A permutation of the rows, so every entry is in [0, N).
+      mix_lam  Beta(alpha, alpha), clipped to [0, 1], one draw per sequence (``per_sequence``) or one for the batch, constant over a
+               sequence; with probability 1 - ``prob`` the batch is not mixed: 1 everywhere.
+    The order of the draws is fixed: the batch's coin, the permutations in ascending sequence length, the coefficients."""
+    if not (alpha > 0.0 and math.isfinite(alpha)):
+        raise ValueError(f"mixup_fields: alpha must be finite and > 0, got {alpha}")
+    rng = np.random.Generator(np.random.Philox(**dict(zip(("key", "counter"), mixup_key(seed, epoch, ordinal, task)))))
+    ptr = np.asarray(ptr, dtype=np.int64)
+    lengths = np.diff(ptr)
+    B = int(lengths.shape[0])
+    mixed = bool(rng.random() < prob)
+    partner = np.arange(B, dtype=np.int64)
+    for L in np.unique(lengths):
+        members = np.flatnonzero(lengths == L)
+        partner[members] = members[rng.permutation(members.shape[0])]
+    lam_seq = np.clip(rng.beta(alpha, alpha, size=B if per_sequence else 1), 0.0, 1.0).astype(np.float32)
+    lam_seq = np.broadcast_to(lam_seq, (B,)) if not per_sequence else lam_seq
+    if not mixed:
+        lam_seq = np.ones(B, dtype=np.float32)
+    seq = np.repeat(np.arange(B, dtype=np.int64), lengths)          # the sequence of every node
+    node = np.arange(int(lengths.sum()), dtype=np.int64) - ptr[seq]  # its place inside the sequence
+    src = torch.from_numpy((ptr[partner[seq]] + node).astype(np.int32))
+    y = torch.as_tensor(y)
+    return src, torch.from_numpy(np.ascontiguousarray(lam_seq[seq])), y[src.long()]
+
+
 def _attach_live_rows(out: "Data") -> None:
     lr = live_label_rows(out.y, int(out.pos.shape[0]))
     if lr is not None:
@@ -911,12 +956,43 @@ class BatchLoader:
         batch.ordinal = int(ordinal)
         return batch
 
+    # -- sequence mixup (``mixup:`` of the config): set on the TRAINING loader of a mixed task, never on a validation one
+    mixup = None     # None, or dict(task, alpha, per_sequence, prob, seed): every batch then carries mix_src / mix_lam / mix_y
+    mix_epoch = 0    # the epoch of the draws' key: the entry point sets it before an epoch (so that a resumed run draws what the
+                     # uninterrupted one draws); it also moves on by one with every pass over the loader
+    mix_lam_sum, mix_lam_count = 0.0, 0  # running sum of mix_lam over the nodes of the batches built (``mix_lam_mean``)
+
+    def mix_lam_mean(self, reset: bool = True) -> Optional[float]:
+        """Mean lambda over the nodes of the batches built since the last reset (None without one)."""
+        out = self.mix_lam_sum / self.mix_lam_count if self.mix_lam_count else None
+        if reset:
+            self.mix_lam_sum, self.mix_lam_count = 0.0, 0
+        return out
+
+    def _finish(self, batch, ordinal: int, epoch: int):
+        """Stamp the batch and, on a mixed loader, attach the three mixup fields -- in the loading process, from the batch's ``ptr``
+        and ``y`` alone, so they are the same through the plain loader, the collation processes and the native builder.  A batch
+        that lives in an arena is handed on as plain tensors: the arena's layout has no room for fields it did not plan."""
+        batch = self._stamp(batch, ordinal)
+        m = self.mixup
+        if not m:
+            return batch
+        if batch.__dict__.get("_arena") is not None:
+            batch = Data(**{k: v for k, v in batch.materialise().__dict__.items() if k not in ("_arena", "_struct_key")})
+        src, lam, my = mixup_fields(batch.ptr, batch.y, m["seed"], epoch, ordinal, m["task"], m["alpha"], m["per_sequence"], m["prob"])
+        batch.mix_src, batch.mix_lam, batch.mix_y = src, lam, my
+        self.mix_lam_sum += float(lam.double().sum())
+        self.mix_lam_count += int(lam.numel())
+        return batch
+
     def __iter__(self):
+        epoch = self.mix_epoch
+        self.mix_epoch = epoch + 1
         if self.workers > 0:
-            yield from self._iter_workers()
+            yield from self._iter_workers(epoch)
             return
         for ordinal, chunk in self._numbered_chunks():
-            b = self._stamp(collate_chunk(self.dataset, chunk), ordinal)
+            b = self._finish(collate_chunk(self.dataset, chunk), ordinal, epoch)
             yield b.pin_memory() if self.pin_memory else b
 
     # -- worker processes (opt-in: ``workers`` > 0) ------------------------------------------------------------------
@@ -942,7 +1018,7 @@ class BatchLoader:
             self._pool = ctx.Pool(self.workers, initializer=_worker_init, initargs=(self.dataset,))
         return self
 
-    def _iter_workers(self):
+    def _iter_workers(self, mix_epoch: int = 0):
         import collections
         self.start_workers()
         self._epoch = getattr(self, "_epoch", -1) + 1
@@ -954,11 +1030,11 @@ class BatchLoader:
                 pending.append((ordinal, self._pool.apply_async(_worker_collate, (chunk, (self.seed, self._epoch, n)))))
                 if len(pending) >= 2 * self.workers:
                     ordinal_, res = pending.popleft()
-                    b = self._stamp(unpack_data(*res.get(timeout=300)), ordinal_)
+                    b = self._finish(unpack_data(*res.get(timeout=300)), ordinal_, mix_epoch)
                     yield b.pin_memory() if self.pin_memory else b
             while pending:
                 ordinal_, res = pending.popleft()
-                b = self._stamp(unpack_data(*res.get(timeout=300)), ordinal_)
+                b = self._finish(unpack_data(*res.get(timeout=300)), ordinal_, mix_epoch)
                 yield b.pin_memory() if self.pin_memory else b
         finally:
             if pending:  # the consumer stopped early: drop the in-flight work with its processes (a new pool next time)

@@ -1626,6 +1626,68 @@ class MTLStep(StepBase):
             ops.fill_scaled_from(g, coef, scale)
         return g
 
+    # ---- sequence mixup (include/egopack_mixup.h) -------------------------------------------------------------------------
+    # A training batch of a mixed task carries mix_src / mix_lam / mix_y (data.BatchLoader); batches without them run exactly the
+    # launches they ran before.  ONE launch in front of the backbone writes the mixed rows of all task batches into a second input
+    # buffer (out of place: the staged input stays as it was, so a replay over it mixes the same rows again, not the mix), an
+    # unmixed task's rows are copied by the same launch; the heads hand both labels and lambda to their cross entropy.
+    def _mix_of(self, d):
+        """(mix_y, mix_lam) of a batch that carries the fields while the model trains, else None."""
+        if d is None or not self.model.training or getattr(d, "mix_src", None) is None:
+            return None
+        return d.mix_y, d.mix_lam
+
+    @staticmethod
+    def _mix_rows_of(xs, ds):
+        """The mixed copies of the input blocks ``xs`` ([N, ...] each) of the batches ``ds``: one launch over all of them."""
+        outs = [torch.empty_like(x) for x in xs]
+        flat = lambda x: x.reshape(x.shape[0], -1)
+        mixed = [getattr(d, "mix_src", None) is not None for d in ds]
+        ops.mix_rows([flat(x) for x in xs], [flat(o) for o in outs], [d.mix_src if m else None for d, m in zip(ds, mixed)],
+                     [d.mix_lam if m else None for d, m in zip(ds, mixed)])
+        return outs
+
+    def features(self, batches, merged=None):
+        live = self._live(batches)
+        if not any(self._mix_of(batches[t]) is not None for t in live):
+            return super().features(batches, merged)
+        if self.fused and len(live) > 1:
+            if merged is None:
+                merged = merge_batches([batches[t] for t in live])
+                merged = merged.to(batches[live[0]].pos.device)
+            x = merged.x
+            if isinstance(x, (list, tuple)):
+                x = torch.cat(list(x))
+            rows = [batches[t].pos.shape[0] for t in live]
+            offs = [sum(rows[:i]) for i in range(len(rows) + 1)]
+            out = torch.empty_like(x)
+            flat = lambda v: v.reshape(v.shape[0], -1)
+            ds = [batches[t] for t in live]
+            mixed = [self._mix_of(d) is not None for d in ds]
+            ops.mix_rows([flat(x[a:b]) for a, b in zip(offs, offs[1:])], [flat(out[a:b]) for a, b in zip(offs, offs[1:])],
+                         [d.mix_src if m else None for d, m in zip(ds, mixed)], [d.mix_lam if m else None for d, m in zip(ds, mixed)])
+            keep = (merged.__dict__.get("x"), merged.__dict__.get("x_base"))
+            merged.x = merged.x_base = out
+            try:
+                feat = self.model(merged)
+            finally:
+                merged.x, merged.x_base = keep
+            return dict(zip(live, ops.split_rows(feat, rows)))
+        feats = {}
+        for t in live:
+            d = batches[t]
+            if self._mix_of(d) is None:
+                feats[t] = self.model(d)
+                continue
+            keep = (d.__dict__.get("x"), d.__dict__.get("x_base"))
+            d.x, = self._mix_rows_of([d.x], [d])
+            d.x_base = None
+            try:
+                feats[t] = self.model(d)
+            finally:
+                d.x, d.x_base = keep
+        return feats
+
     def _head(self, t: str, feat, d):
         task = self.tasks[t]
         f = task.forward_features(feat)
@@ -1752,7 +1814,8 @@ class MTLStep(StepBase):
                     n_loss = 0
                 else:
                     logits = task.forward_logits(f, d) if t == "oscc" else task.forward_logits(f)
-                    v = self.criteria[t](logits, labels[t])
+                    mix = self._mix_of(d) if isinstance(self.criteria[t], MetricSelectorWrapper) else None
+                    v = self.criteria[t](logits, labels[t]) if mix is None else self.criteria[t](logits, labels[t], mix=mix)
             n_out = v.numel() if t not in live else n_full[t]  # elements of the loss vector the objective averages over
             if n_loss and n_out != n_loss:
                 raise RuntimeError(f"head {t}: {n_out} loss elements where {n_loss} were announced to the fused loss")
@@ -1780,16 +1843,19 @@ class MTLStep(StepBase):
                 #  launch it always was)
                 bal = [self.criteria[t].select_balance(logits) for t, logits in zip(banked, all_logits)]
                 shp = [self.criteria[t].select_shape(logits) for t, logits in zip(banked, all_logits)]
+                mixes = [self.criteria[t].select_mix(logits, self._mix_of(batches[t])) for t, logits in zip(banked, all_logits)]
                 multi = ops.cross_entropy_multi([(s_[0], s_[1]) for s_ in sel], [self.weights[t] / n_loss[t] for t in banked],
                                                 sel[0][2], weights=[w for w, _ in bal], offsets=[a for _, a in bal],
                                                 scales=None if sc_vec is None else [sc[t] for t in banked],
-                                                margins=[m for m, _ in shp], gammas=[g for _, g in shp])
+                                                margins=[m for m, _ in shp], gammas=[g for _, g in shp],
+                                                mixes=mixes if any(m is not None for m in mixes) else None)
             for i, (t, logits) in enumerate(zip(banked, all_logits)):
                 if multi is not None:
                     v = multi[i]
                 else:
                     with ops.loss_seed(self.weights[t] / n_loss[t], scale=sc[t]):
-                        v = self.criteria[t](logits, labels[t])
+                        mix = self._mix_of(batches[t])
+                        v = self.criteria[t](logits, labels[t]) if mix is None else self.criteria[t](logits, labels[t], mix=mix)
                 if v.numel() != proj_leaves[t].shape[0]:
                     raise RuntimeError(f"head {t}: {v.numel()} loss elements for {proj_leaves[t].shape[0]} rows")
                 g = self._seed_grad((t, v.numel(), n_loss[t], v.dtype, v.device), v, t, self.weights[t] / n_loss[t], sc[t])
@@ -1853,6 +1919,8 @@ class MTLStep(StepBase):
         no active dropout in the head (its masks are drawn by row position), the batch built by data.collate with its
         ``live_*`` index arrays on the features' device."""
         if not self.compact_heads or t not in ("ar", "lta"):
+            return False
+        if self._mix_of(d) is not None:  # (mixup: a row is live if EITHER label is; the live_* arrays know the first only)
             return False
         idx = getattr(d, "live_idx", None)
         if idx is None or getattr(d, "live_inv", None) is None or getattr(d, "live_y", None) is None:

@@ -2684,7 +2684,8 @@ class _CEMulti(torch.autograd.Function):
         return tuple(out)
 
 
-def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None, scales=None, margins=None, gammas=None):
+def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offsets=None, scales=None, margins=None, gammas=None,
+                        mixes=None):
     """[loss_t] of ``cross_entropy(logits_t, y_t, smoothing)`` for several tasks whose backward seeds ``coefs`` are known, in ONE
     launch that also writes every task's gradient operand -- or None when some task does not qualify for the fused form
     (the caller then takes them one by one).  ``tasks``: [(logits tuple, y [N, heads] int64)].
@@ -2693,12 +2694,19 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
     ``scales``: None, or one one-element f32 device tensor per task: task i's seed is fl32(coefs[i] * scales[i][0]), formed inside
     the launch (include/egopack_task_scale.h).  None: exactly the launch without the argument.
     ``margins`` / ``gammas``: None, or one entry per task, each what ``cross_entropy`` takes as ``margin`` / ``gamma`` (the tail of
-    ``egk_ce_task``, include/egopack_hip.h); with every margin None and every gamma 0 the launch is the one without them."""
+    ``egk_ce_task``, include/egopack_hip.h); with every margin None and every gamma 0 the launch is the one without them.
+    ``mixes``: None, or one entry per task -- None or the (y_b, lam) of ``cross_entropy(mix=)``.  With some task mixed the ONE launch
+    is the two-target one (egk_ce_mix_fused_multi, include/egopack_mixup.h) and an unmixed task rides in it with lam == 1, which has
+    the plain launch's bits; a task with class-balance vectors, margins or a focal exponent beside a mixed one: None (no such
+    two-target form).  All None: exactly the launch without the argument."""
+    if mixes is not None and all(m is None for m in mixes):
+        mixes = None
     if scales is not None:
         if any(sc is None for sc in scales):
             raise ValueError("cross_entropy_multi: scales has a None entry (every task needs its scale, or pass scales=None)")
         scales = [_scale_arg(sc, f"cross_entropy_multi (task {i})") for i, sc in enumerate(scales)]
-    for name, arg in (("weights", weights), ("offsets", offsets), ("scales", scales), ("margins", margins), ("gammas", gammas)):
+    for name, arg in (("weights", weights), ("offsets", offsets), ("scales", scales), ("margins", margins), ("gammas", gammas),
+                      ("mixes", mixes)):
         if arg is not None and len(arg) != len(tasks):
             raise ValueError(f"cross_entropy_multi: {name} has {len(arg)} entries for {len(tasks)} tasks")
     if not (2 <= len(tasks) <= 4) or not torch.is_grad_enabled():
@@ -2724,10 +2732,156 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
         bal = None
     if all(sh is None for sh in shape):
         shape = None
+    if mixes is not None:
+        if bal is not None or shape is not None:
+            return None
+        flat = []
+        for i, (logits, y) in enumerate(tasks):
+            logits = (logits,) if torch.is_tensor(logits) else tuple(logits)
+            y = y.contiguous()
+            y_b, lam = _mix_arg(mixes[i], y, f"cross_entropy_multi (task {i})") if mixes[i] is not None else (y, torch.ones(y.shape[0], dtype=torch.float32, device=y.device))  # (a fill on this stream, no cached state)
+            flat += [y, y_b, lam, *logits]
+        return list(_CEMixMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, scales, *flat))
     return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, scales, shape, *flat))
 
 
-def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None, margin=None, gamma=0.0):
+# ---- two targets per row: sequence mixup (include/egopack_mixup.h) ------------------------------------------------------------------
+def _mix_arg(mix, y, where):
+    """The ``mix=(y_b, lam)`` argument of the cross entropies as the launch reads it: y_b int64 with y's shape, lam f32 [rows], both
+    contiguous on y's device.  Constants of the loss: no gradient reaches them."""
+    try:
+        y_b, lam = mix
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: mix is a pair (y_b, lam)") from None
+    if not torch.is_tensor(y_b) or y_b.dtype != torch.int64 or y_b.shape != y.shape or y_b.device != y.device:
+        raise ValueError(f"{where}: mix y_b must be an int64 tensor of y's shape {tuple(y.shape)} on {y.device}, got "
+                         f"{(y_b.dtype, tuple(y_b.shape), str(y_b.device)) if torch.is_tensor(y_b) else type(y_b).__name__}")
+    if not torch.is_tensor(lam) or lam.dtype != torch.float32 or lam.dim() != 1 or lam.shape[0] != y.shape[0] or lam.device != y.device:
+        raise ValueError(f"{where}: mix lam must be a float32 tensor of [{y.shape[0]}] on {y.device}, got "
+                         f"{(lam.dtype, tuple(lam.shape), str(lam.device)) if torch.is_tensor(lam) else type(lam).__name__}")
+    return y_b.detach().contiguous(), lam.detach().contiguous()
+
+
+def _ce_mix_launch(tasks, smoothing, scales=None):
+    """ONE two-target launch (egk_ce_mix_fused_multi) for the loss vectors AND the gradient operands of ``tasks`` =
+    [(plan, logits, y, y_b, lam, coef)]; ``scales``: None, or one task scale (``_scale_arg``) per task.  Returns the loss vectors."""
+    n = len(tasks)
+    lg, ld, Cs = (C.c_void_p * (4 * n))(), (C.c_int64 * (4 * n))(), (C.c_int32 * (4 * n))()
+    pad, dcol = (C.c_int32 * (4 * n))(), (C.c_int64 * (4 * n))()
+    losses = []
+    for i, ((gbuf, state, starts, pads), logits, y, y_b, lam, coef) in enumerate(tasks):
+        for h, l in enumerate(logits):
+            k = 4 * i + h
+            lg[k], ld[k], Cs[k], pad[k], dcol[k] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
+        losses.append(torch.empty(logits[0].shape[0], dtype=torch.float32, device=gbuf.device))
+        state["filled"].update(starts)
+        state["pads"] = True
+    vp = lambda xs: (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+    _ck(_lib.load().egk_ce_mix_fused_multi(
+        _stream(), n, lg, ld, Cs, pad, dcol, (C.c_int32 * n)(*[len(t[1]) for t in tasks]), vp([t[2] for t in tasks]),
+        vp([t[3] for t in tasks]), (C.c_int64 * n)(*[1 if t[2].dim() == 1 else t[2].shape[1] for t in tasks]), vp([t[4] for t in tasks]),
+        vp(losses), vp([t[0][0] for t in tasks]), (C.c_int64 * n)(*[t[0][0].stride(0) for t in tasks]),
+        (C.c_int32 * n)(*[t[1][0].shape[0] for t in tasks]), (C.c_float * n)(*[float(t[5]) for t in tasks]),
+        None if scales is None else vp(scales), float(smoothing), _dt(tasks[0][0][0])), "egk_ce_mix_fused_multi")
+    return losses
+
+
+class _CEMix(torch.autograd.Function):
+    """``cross_entropy(mix=)``: lam CE(z, y) + (1 - lam) CE(z, y_b) per row, summed over the heads.  Under an announced seed on bank
+    logits the launch writes the gradient operand itself (the step's path); elsewhere it runs with seed 1 into an f32 scratch and the
+    backward scales its rows by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, smoothing, y, y_b, lam, *logits):
+        _need_gpu(y, *logits)
+        if any(l.dtype != torch.float32 for l in logits):
+            raise TypeError("cross_entropy expects f32 logits")
+        if len(logits) > 4:
+            raise ValueError(f"cross_entropy: mix takes at most 4 heads, got {len(logits)}")
+        seed = _loss_seed["coef"]
+        plan = None if seed is None else _ce_fused_plan(y, logits, from_col0=False)
+        ctx.fused = plan is not None
+        ctx.shapes = [tuple(l.shape) for l in logits]
+        if plan is not None:
+            scale = _loss_seed["scale"]
+            loss, = _ce_mix_launch([(plan, logits, y, y_b, lam, seed)], smoothing, None if scale is None else [scale])
+            if plan[2][0] > 0:
+                plan[0][:, :plan[2][0]].zero_()
+            return loss
+        ls = [_rm(l) for l in logits]
+        widths = [l.shape[1] for l in ls]
+        starts = [sum(widths[:h]) for h in range(len(ls))]
+        d = torch.empty((ls[0].shape[0], sum(widths)), dtype=torch.float32, device=ls[0].device)
+        loss, = _ce_mix_launch([((d, {"filled": set()}, starts, widths), ls, y, y_b, lam, 1.0)], smoothing)
+        ctx.starts = starts
+        ctx.save_for_backward(d)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if ctx.fused:  # the gradient is already in the bank's operand buffer: placeholders for autograd
+            return (None, None, None, None, *[torch.empty(s_, dtype=torch.float32, device=gloss.device) for s_ in ctx.shapes])
+        d, = ctx.saved_tensors
+        d = d * _f32c(gloss)[:, None]
+        return (None, None, None, None, *[d[:, c0:c0 + shp[1]] for c0, shp in zip(ctx.starts, ctx.shapes)])
+
+
+class _CEMixMulti(torch.autograd.Function):
+    """``_CEMulti`` with two targets per row: ONE launch of egk_ce_mix_fused_multi for several tasks."""
+
+    @staticmethod
+    def forward(ctx, smoothing, coefs, heads_per_task, plans, scales, *tensors):
+        tasks, shapes, k = [], [], 0
+        for i, coef in enumerate(coefs):
+            y, y_b, lam = tensors[k:k + 3]
+            logits = tensors[k + 3:k + 3 + heads_per_task[i]]
+            k += 3 + heads_per_task[i]
+            tasks.append((plans[i], logits, y, y_b, lam, coef))
+            shapes.append([tuple(l.shape) for l in logits])
+        losses = _ce_mix_launch(tasks, smoothing, scales)
+        ctx.shapes, ctx.fused = shapes, True
+        ctx.set_materialize_grads(False)
+        return tuple(losses)
+
+    @staticmethod
+    def backward(ctx, *glosses):
+        out = [None, None, None, None, None]
+        dev = next(g.device for g in glosses if g is not None)
+        for shp in ctx.shapes:  # placeholders: the gradients are already in the banks' operand buffers
+            out.extend([None, None, None])  # y, y_b, lam
+            out.extend(torch.empty(s_, dtype=torch.float32, device=dev) for s_ in shp)
+        return tuple(out)
+
+
+def mix_rows(xs, outs, srcs, lams):
+    """outs[i][r] = lams[i][r] * xs[i][r] + (1 - lams[i][r]) * xs[i][srcs[i][r]] for up to 4 SEGMENTS in ONE launch
+    (egk_mix_rows_multi, include/egopack_mixup.h): f32 arithmetic, one rounding to the element type; rows with lam 1 / 0 or their
+    own partner are copied bit for bit.  ``xs`` / ``outs``: 2-D device tensors of one float32 / bfloat16 dtype and one width with
+    unit column stride; ``srcs`` (int32 [rows], the partner row INSIDE the segment -- the caller guarantees the range) and ``lams``
+    (float32 [rows]) per segment, or None for both: the segment is copied.  Out of place: an output that overlaps an input is
+    refused.  Not differentiable (inputs carry no gradient).  Returns ``outs``."""
+    n = len(xs)
+    if not (len(outs) == len(srcs) == len(lams) == n):
+        raise ValueError(f"mix_rows: {n} inputs, {len(outs)} outputs, {len(srcs)} srcs, {len(lams)} lams")
+    _need_gpu(*xs, *outs)
+    for i, (x, o, sr, lm) in enumerate(zip(xs, outs, srcs, lams)):
+        if x.dim() != 2 or o.shape != x.shape or o.dtype != x.dtype or x.dtype != xs[0].dtype or x.shape[1] != xs[0].shape[1]:
+            raise ValueError(f"mix_rows: segment {i}: input {tuple(x.shape)} {x.dtype}, output {tuple(o.shape)} {o.dtype} (one dtype, one width)")
+        if x.shape[0] and (x.stride(1) != 1 or o.stride(1) != 1):
+            raise ValueError(f"mix_rows: segment {i}: rows must have a unit column stride")
+        if (sr is None) != (lm is None):
+            raise ValueError(f"mix_rows: segment {i}: src and lam are both given or both None")
+        if sr is not None and (sr.dtype != torch.int32 or lm.dtype != torch.float32 or sr.shape != (x.shape[0],) or lm.shape != (x.shape[0],)
+                               or not sr.is_contiguous() or not lm.is_contiguous() or sr.device != x.device or lm.device != x.device):
+            raise ValueError(f"mix_rows: segment {i}: src is int32 [{x.shape[0]}] and lam float32 [{x.shape[0]}], contiguous, on {x.device}")
+    vp = lambda ts: (C.c_void_p * max(n, 1))(*[None if t is None else t.data_ptr() for t in ts])
+    ld = lambda ts: (C.c_int64 * max(n, 1))(*[max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1] for t in ts])
+    _ck(_lib.load().egk_mix_rows_multi(_stream(), n, vp(xs), vp(outs), ld(xs), ld(outs), (C.c_int32 * max(n, 1))(*[x.shape[0] for x in xs]),
+                                       vp(srcs), vp(lams), xs[0].shape[1] if n else 0, _dt(xs[0]) if n else 0), "egk_mix_rows_multi")
+    return outs
+
+
+def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None, margin=None, gamma=0.0, mix=None):
     """Per-row CrossEntropy(reduction='none', ignore_index=-1), summed over heads when ``logits`` is
     a tuple and y is [N, heads].  Logits are f32; their gradient is emitted in the element type the
     producing contraction wants (bf16 in 'bf16' mode).
@@ -2738,9 +2892,17 @@ def cross_entropy(logits, y, smoothing: float = 0.0, weight=None, offset=None, m
     target's logit only, and the focal exponent -- loss = (1 - q)^gamma * CE(z), z = x + offset - onehot(y) * margin, q =
     softmax(z)[y] (the tail of ``egk_ce_task``, include/egopack_hip.h; at most 4 heads).  Under an announced seed on bank logits the
     step's one fused launch carries them; elsewhere the same launch runs forward-only and, in backward, with the incoming gradient
-    as row seeds.  Constants.  All None / 0: exactly the launches without the arguments."""
+    as row seeds.  Constants.  All None / 0: exactly the launches without the arguments.
+    ``mix``: None, or (y_b, lam) -- a second label tensor of y's shape and an f32 coefficient per row: the loss becomes
+    lam * CE(z, y) + (1 - lam) * CE(z, y_b), one launch with one log-sum-exp per row and head (include/egopack_mixup.h); a row with
+    lam == 1 has the plain launch's bits.  Not together with weight / offset / margin / gamma (no such two-target form)."""
     if torch.is_tensor(logits):
         logits = (logits,)
+    if mix is not None:
+        if _class_balance(weight, offset, logits) is not None or _ce_shape(margin, gamma, logits) is not None:
+            raise ValueError("cross_entropy: mix does not combine with weight / offset / margin / gamma (the two-target launch is the plain one)")
+        y = y.contiguous()
+        return _CEMix.apply(float(smoothing), y, *_mix_arg(mix, y, "cross_entropy"), *logits)
     return _CE.apply(float(smoothing), y, _state["act"], _class_balance(weight, offset, logits),
                      _ce_shape(margin, gamma, logits), *logits)
 

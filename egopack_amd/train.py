@@ -118,10 +118,77 @@ def build_loaders(cfg, dsets, train: bool, rank: int, world: int, batch_size: Op
     """Training loaders shard by sample (equal steps per rank); evaluation loaders shard by batch, so that every batch
     -- and with it every graph-LayerNorm statistic -- is the one the single-process pass sees."""
     bs = batch_size or cfg.batch_size
-    return {t: D.build_dataloader(ds, bs, train, cfg.num_workers, train, seed=cfg.seed, rank=rank, world_size=world,
-                                  shard="samples" if train else "batches",
-                                  workers=int(cfg.get("loader_workers", 0)) if train else 0)
-            for t, ds in dsets.items()}
+    out = {t: D.build_dataloader(ds, bs, train, cfg.num_workers, train, seed=cfg.seed, rank=rank, world_size=world,
+                                 shard="samples" if train else "batches",
+                                 workers=int(cfg.get("loader_workers", 0)) if train else 0)
+           for t, ds in dsets.items()}
+    mx = mixup_config(cfg)
+    if train and mx["alpha"] > 0:  # (validation batches carry none of the fields)
+        for t in mx["tasks"]:
+            if t in out:
+                out[t].mixup = dict(task=t, alpha=mx["alpha"], per_sequence=mx["per_sequence"], prob=mx["prob"],
+                                    seed=int(cfg.seed if mx["seed"] is None else mx["seed"]))
+    return out
+
+
+# ---- sequence mixup of the AR / LTA heads (``mixup:`` of the config; include/egopack_mixup.h, DESIGN 3.21) ---------------------------
+MIXUP_DEFAULTS = {"alpha": 0.0, "tasks": ["ar", "lta"], "per_sequence": True, "prob": 1.0, "seed": None}
+
+
+def mixup_config(cfg) -> dict:
+    """The ``mixup:`` block with its defaults filled in.  A ValueError names the key: an unknown key, alpha < 0 or not finite, prob
+    outside [0, 1], a task outside [ar, lta]."""
+    raw = cfg.get("mixup") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(MIXUP_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mixup: unknown key(s) {sorted(unknown)} ({', '.join(MIXUP_DEFAULTS)})")
+    mx = {**MIXUP_DEFAULTS, **raw}
+    mx["alpha"], mx["prob"] = float(mx["alpha"]), float(mx["prob"])
+    if not (mx["alpha"] >= 0.0 and mx["alpha"] < float("inf")):
+        raise ValueError(f"mixup.alpha: {mx['alpha']} is not a finite value >= 0")
+    if not (0.0 <= mx["prob"] <= 1.0):
+        raise ValueError(f"mixup.prob: {mx['prob']} is outside [0, 1]")
+    mx["tasks"] = [str(t) for t in (mx["tasks"] or [])]
+    bad = [t for t in mx["tasks"] if t not in D.MIX_TASKS]
+    if bad:
+        raise ValueError(f"mixup.tasks: {bad} outside {list(D.MIX_TASKS)}")
+    mx["per_sequence"] = bool(mx["per_sequence"])
+    mx["seed"] = None if mx["seed"] is None else int(mx["seed"])
+    return mx
+
+
+def check_mixup(cfg, enable_graphone: bool = False, entry: str = "main_temporal.py") -> dict:
+    """The ``mixup:`` block checked against the rest of the configuration at build time; returns it.  With alpha > 0 refused, each
+    ValueError naming both keys: a mixed task with class_balance.mode != none or with ce_shape margins / gamma (the weighted and shaped
+    two-target losses do not exist), and the EgoPack step (enable_graphone / main_egopack.py: MTLStep only, like task weighting)."""
+    mx = mixup_config(cfg)
+    if mx["alpha"] <= 0 or not mx["tasks"]:
+        return mx
+    if enable_graphone:
+        raise ValueError(f"mixup.alpha = {mx['alpha']} with enable_graphone=True ({entry}): the EgoPack step trains one primary task "
+                         "through GraphONE and has no mixed input -- mixup is for main_temporal.py (MTLStep)")
+    cb = class_balance_config(cfg)
+    if cb["mode"] != "none":
+        both = [t for t in mx["tasks"] if t in cb["tasks"]]
+        if both:
+            raise ValueError(f"mixup.tasks {both} with class_balance.mode = {cb['mode']}: there is no class-balanced two-target cross "
+                             "entropy -- take the task out of mixup.tasks or of class_balance.tasks")
+    sh = ce_shape_config(cfg)
+    if sh["margin"] != "none" or sh["gamma"] > 0:
+        both = [t for t in mx["tasks"] if t in sh["tasks"]]
+        if both:
+            raise ValueError(f"mixup.tasks {both} with ce_shape.margin = {sh['margin']} / ce_shape.gamma = {sh['gamma']}: there is no "
+                             "shaped two-target cross entropy -- take the task out of mixup.tasks or of ce_shape.tasks")
+    return mx
+
+
+def log_mixup(logger, epoch: int, loaders) -> None:
+    """The mean lambda per mixed task over the batches of the epoch; nothing with the feature off."""
+    means = {t: l.mix_lam_mean() for t, l in loaders.items() if getattr(l, "mixup", None)}
+    means = {t: round(m, 4) for t, m in means.items() if m is not None}
+    if means:
+        logger.info("epoch %d: mixup mean lambda %s", epoch, means)
 
 
 def env_ranks() -> tuple:

@@ -808,5 +808,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
  * of the labelled pair, and the edit distances of the sampled futures per head and per action (egk_action_topk,
  * egk_edit_distance_pairs) */
 #include "egopack_action.h"
+/* sequence mixup for the verb / noun heads: the convex combination of paired rows of up to 4 segments in one out-of-place launch,
+ * and the fused cross entropy against two labels per row (egk_mix_rows_multi, egk_ce_mix_fused_multi) */
+#include "egopack_mixup.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -43,6 +43,9 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
     step.loss_sums()  # (clears the per-task loss sums: they accumulate inside the step, on the device, until the epoch ends)
     if step.optimizer.clipping:
         step.grad_norm_stats()  # (and the gradient-norm statistics of grad_clip_norm)
+    for l in loaders.values():
+        if getattr(l, "mixup", None):
+            l.mix_epoch = epoch  # (mixup: the draws are keyed by the epoch -- a resumed run draws what the uninterrupted one draws)
     hosts = (dict(zip(order, batch)) for batch in multiloader([loaders[t] for t in order], [weights[t] for t in order]))
     # batch i + 1 is built and copied to the device (staging thread, copy stream) while step i runs
     mark = None  # (iteration, wall clock, sequences so far) once the eager steps and the capture are behind: steady-state rate
@@ -64,6 +67,7 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
                 {t: round(s_ / max(n_, 1), 4) for t, (s_, n_) in step.loss_sums().items() if n_})
     T.log_grad_norms(logger, epoch, step)
     T.log_trust_ratios(logger, epoch, step)  # (LAMB: min / median / max trust ratio)
+    T.log_mixup(logger, epoch, loaders)  # (the mean lambda per mixed task; nothing with the feature off)
     T.log_task_weighting(logger, epoch, step)  # (s_t and w_t exp(-s_t), or the manual scales; nothing with the feature off)
     lc = getattr(step, "loop_counts", None)
     if lc is not None:  # how many steps replayed the captured graph and how many ran eagerly (shape changes, warm-up)
@@ -134,6 +138,7 @@ def main(argv=None):
 
     # datasets, loaders and their collation processes come first: nothing has touched the GPU yet, so the workers are a
     # plain fork of a process without HIP state (data.BatchLoader.start_workers)
+    T.check_mixup(cfg, enable_graphone=bool(cfg.get("enable_graphone", False)))  # (mixup with class_balance / ce_shape / GraphONE: refused here)
     dsets_train, dsets_val = T.build_datasets(cfg, "train"), T.build_datasets(cfg, cfg.validation_split)
     assert len({d.features_size for d in dsets_train.values()}) == 1, "all tasks must share the input feature size"
     dl_train = T.build_loaders(cfg, dsets_train, True, rank, world)
