@@ -72,6 +72,9 @@ struct GemmArgs {
     // rows epilogue: 1 = the descriptor-once, mode-specialised store loop (gemm_epilogue_rows_fast), which implies
     // epilogue_rows_ok(g) -- set on the host; 0 = the branch-ladder loop (egk_gemm_set_pipeline(890 / 891))
     int epi;
+    // bf16 pipelined kernels: the K tiles (64 deep) of all sources together, total_tiles(g, 64) done on the host -- the entry of
+    // gemm_pipe_body takes it with the rest of its descriptor fields in one batch (PipeEntry)
+    int nkt;
 };
 
 // Workgroup -> (slab z, tile row, tile column) for a 1-D launch of tiles_m * tiles_n * splitk workgroups.
@@ -999,30 +1002,33 @@ typedef const __attribute__((address_space(1))) void glb_void_t;
 // Per-wave cursor over the 4 pieces (1 KiB each) a wave fetches of one operand image per K tile.  The per-lane
 // source addresses are computed ONCE; a K-tile step is a uniform pointer increment (the address arithmetic of 8
 // DMA instructions per tile would otherwise cost as many VALU cycles as the tile's MFMAs at one wave per SIMD).
+// this lane's source address of piece ``idx`` of an operand image made of 16-KiB sub-images of 128 rows (16 pieces each)
+template <bool TR>
+__device__ __forceinline__ const bf16_t* cursor_piece(const bf16_t* __restrict__ base, long long ld, int rows_total, int row0, int k0,
+                                                      int idx, int lane) {
+    const int piece = idx & 15, sub_row0 = row0 + (idx >> 4) * 128;
+    if constexpr (TR) {  // piece = 4 k-rows of 256 B; lane -> (k = 4*piece + lane/16, slot = lane%16)
+        const int k = piece * 4 + (lane >> 4);
+        const int c = (lane & 15) ^ (2 * (k & 3) + 8 * ((k >> 3) & 1));
+        // a chunk is fetched whenever it lies inside the ALLOCATED row (ld): with a padded row stride the last
+        // valid rows (e.g. 112..114 of 115) sit in a chunk that extends into the padding.  Chunks beyond the
+        // row are redirected to the row's first chunk: they only feed output rows that are never stored.
+        int col = sub_row0 + c * 8;
+        if (col + 8 > ld) col = 0;
+        return base + (long long)(k0 + k) * ld + col;
+    } else {  // piece = 8 rows of 128 B; lane -> (row = 8*piece + lane/8, slot = lane%8)
+        const int r = piece * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        return base + (long long)min(sub_row0 + r, rows_total - 1) * ld + k0 + c * 8;
+    }
+}
 template <bool TR, int NP, int OFF = 0, int TOT = NP>
 __device__ __forceinline__ void cursor_init(const bf16_t* (&pp)[TOT], long long& step, const bf16_t* __restrict__ base, long long ld,
                                             int rows_total, int row0, int k0, int first, int lane, int tiles_per_step) {
-    // pieces first .. first + NP - 1 of an operand image made of 16-KiB sub-images of 128 rows (16 pieces each), kept in
-    // slots OFF .. OFF + NP - 1 of the pointer array
+    // pieces first .. first + NP - 1, kept in slots OFF .. OFF + NP - 1 of the pointer array
     const bf16_t** p = pp + OFF;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int piece = (first + i) & 15, sub_row0 = row0 + ((first + i) >> 4) * 128;
-        if constexpr (TR) {  // piece = 4 k-rows of 256 B; lane -> (k = 4*piece + lane/16, slot = lane%16)
-            const int k = piece * 4 + (lane >> 4);
-            const int c = (lane & 15) ^ (2 * (k & 3) + 8 * ((k >> 3) & 1));
-            // a chunk is fetched whenever it lies inside the ALLOCATED row (ld): with a padded row stride the last
-            // valid rows (e.g. 112..114 of 115) sit in a chunk that extends into the padding.  Chunks beyond the
-            // row are redirected to the row's first chunk: they only feed output rows that are never stored.
-            int col = sub_row0 + c * 8;
-            if (col + 8 > ld) col = 0;
-            p[i] = base + (long long)(k0 + k) * ld + col;
-        } else {  // piece = 8 rows of 128 B; lane -> (row = 8*piece + lane/8, slot = lane%8)
-            const int r = piece * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            p[i] = base + (long long)min(sub_row0 + r, rows_total - 1) * ld + k0 + c * 8;
-        }
-    }
+    for (int i = 0; i < NP; ++i) p[i] = cursor_piece<TR>(base, ld, rows_total, row0, k0, first + i, lane);
     step = (TR ? 64 * ld : 64) * tiles_per_step;
 }
 template <int NP, int OFF = 0, int TOT = NP>
@@ -1043,7 +1049,76 @@ struct OperandCursor {
         cursor_init<TR, NP, 0, NP>(p, step, base, ld, rows_total, row0, k0, first, lane, tiles_per_step);
     }
     __device__ __forceinline__ void issue(unsigned char* img, int first) { cursor_issue<NP, 0, NP>(p, step, img, first); }
+    // init + issue of one tile, piece by piece: a piece is requested as soon as its own address exists, not behind the address
+    // arithmetic of all the pieces (two 32-bit multiplies and a 64-bit multiply-add each)
+    __device__ __forceinline__ void init_issue(const bf16_t* __restrict__ base, long long ld, int rows_total, int row0, int k0, int first,
+                                               int lane, int tiles_per_step, unsigned char* img, unsigned long long* stamp = nullptr) {
+        step = (TR ? 64 * ld : 64) * tiles_per_step;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            p[i] = cursor_piece<TR>(base, ld, rows_total, row0, k0, first + i, lane);
+#ifdef EGK_GEMM_STAMPS
+            if (i == 0 && stamp) *stamp = __builtin_amdgcn_s_memtime();  // (diagnostic build: the first request goes out here)
+#endif
+            __builtin_amdgcn_global_load_lds((glb_void_t*)p[i], (lds_void_t*)(img + (first + i) * 1024), 16, 0, 0);
+            p[i] += step;
+            __builtin_amdgcn_sched_barrier(0);  // (or the scheduler moves every piece's arithmetic in front of the first request again)
+        }
+    }
 };
+
+// The descriptor fields that stand between kernel entry and the first LDS-DMA piece, each in scalar registers of its own: read as
+// ONE batch of scalar loads behind one wait.  (Kernel arguments are rematerialisable: left alone, the compiler loads each field
+// where it is first used, and the entry becomes a chain of dependent round trips to a cold scalar cache -- four on the loader
+// waves of the 192-row tile: tile grid + split, group_m + nsrc, K[0], then the operand pointers and strides.)  Source 0 only: a
+// workgroup whose first K tile lies in a later source (slab z > 0 of a split multi-source contraction) goes back for that source.
+struct PipeEntry {
+    int M, N, nsrc, K0, splitk, tiles_m, tiles_n, group_m, nkt;
+    const bf16_t* A0;
+    const bf16_t* B0;
+    long long lda0, ldb0;
+};
+__device__ __forceinline__ void entry_fetch(const GemmArgs& g, PipeEntry& E) {
+    int M = g.M, N = g.N, nsrc = g.nsrc, K0 = g.K[0], splitk = g.splitk, tiles_m = g.tiles_m, tiles_n = g.tiles_n, group_m = g.group_m;
+    int nkt = g.nkt;
+    const bf16_t* A0 = (const bf16_t*)g.A[0];
+    const bf16_t* B0 = (const bf16_t*)g.B[0];
+    long long lda0 = g.lda[0], ldb0 = g.ldb[0];
+    asm volatile("" : "+s"(M), "+s"(N), "+s"(nsrc), "+s"(K0), "+s"(splitk), "+s"(tiles_m), "+s"(tiles_n), "+s"(group_m), "+s"(nkt),
+                      "+s"(A0), "+s"(B0), "+s"(lda0), "+s"(ldb0));
+    E.M = M; E.N = N; E.nsrc = nsrc; E.K0 = K0; E.splitk = splitk; E.tiles_m = tiles_m; E.tiles_n = tiles_n; E.group_m = group_m;
+    E.nkt = nkt; E.A0 = A0; E.B0 = B0; E.lda0 = lda0; E.ldb0 = ldb0;
+}
+// tile_of / tile_of_virtual on the pinned fields: the same walk; an unsplit launch (every grouped one is) has one slab and skips the
+// division that finds it (a scalar division is ~40 dependent instructions through the reciprocal unit)
+template <bool VIRT>
+__device__ __forceinline__ void entry_tile_of(const PipeEntry& E, int bid, int& z, int& tm, int& tn) {
+    const int tiles = E.tiles_m * E.tiles_n;
+    int v = bid;
+    if constexpr (!VIRT) {
+        const int nwg = tiles * E.splitk;
+        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    }
+    z = 0;
+    int t = v;
+    if (E.splitk > 1) {
+        z = v / tiles;
+        t = v - z * tiles;
+    }
+    const int gsz = E.group_m * E.tiles_n;
+    const int grp = t / gsz, first = grp * E.group_m;
+    const int rows = min(E.group_m, E.tiles_m - first);
+    const int rr = t - grp * gsz;
+    tm = first + rr % rows;
+    tn = rr / rows;
+}
+// source_of on the pinned fields: one source, or a tile inside source 0, needs no further descriptor read
+template <int KT>
+__device__ __forceinline__ void entry_source_of(const GemmArgs& g, const PipeEntry& E, int t, int& src, int& tt) {
+    if (E.nsrc <= 1 || t < (E.K0 + KT - 1) / KT) { src = 0; tt = t; }
+    else source_of<KT>(g, t, src, tt);
+}
 
 // (128 * MB) x 128 output tile, NSTAGE-deep ring of (A image | B image) = (16 * MB + 16) KiB per stage; every wave
 // owns a 64 x 64 patch of the tile (4 x 4 MFMA accumulators).
@@ -1065,7 +1140,9 @@ __device__ __forceinline__ f32x4 mfma16(const uint4& b, const uint4& a, const f3
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
 }
 
-template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool VIRT = false, bool F16 = false, int LW = 0>
+// FE: the entry described at PipeEntry (one descriptor batch, tile 0 requested piece by piece); false: the entry it replaces, kept
+// as kernels of their own (gemm_pipe_kernel_e0, egk_gemm_set_pipeline(880 / 881)) -- the same K loop, epilogue and bits.
+template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool VIRT = false, bool F16 = false, int LW = 0, bool FE = true>
 __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid) {
     // LW > 0: LW extra LOADER waves issue every LDS-DMA piece of the workgroup; the WG * KG compute waves only read fragments and
     // feed the matrix pipe.  A piece holds the wave that issues it until the CU's vector-memory path accepts it (100 - 185 cycles
@@ -1088,19 +1165,27 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
     constexpr int KT = 64;
 #ifdef EGK_GEMM_STAMPS  // diagnostic build only (tools/gemm_stamps.py --phases): entry, first tile landed, loop end, exit
     const unsigned long long ps_entry = __builtin_amdgcn_s_memtime(), ps_rentry = __builtin_amdgcn_s_memrealtime();
-    unsigned long long ps_first = 0;
+    unsigned long long ps_first = 0, ps_arrive = 0, ps_iss0 = 0, ps_iss1 = 0;  // (ps_iss*: the first / last piece of tile 0 issued)
 #endif
-
-    int z, tm, tn;
-    if constexpr (VIRT) tile_of_virtual(g, bid, z, tm, tn);  // (the caller did the XCD placement: grouped launches)
-    else tile_of(g, bid, z, tm, tn);
-    const int m0 = tm * (32 * NI * MB), n0 = tn * BN;
-    const int nkt = total_tiles(g, KT);
-    const int per = (nkt + g.splitk - 1) / g.splitk;
-    const int t_begin = z * per, t_end = min(nkt, t_begin + per);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wall = __builtin_amdgcn_readfirstlane(tid >> 6);
+    PipeEntry E;
+    int z, tm, tn, nkt, splitk;
+    if constexpr (FE) {
+        entry_fetch(g, E);
+        entry_tile_of<VIRT>(E, bid, z, tm, tn);
+        nkt = E.nkt;
+        splitk = E.splitk;
+    } else {
+        if constexpr (VIRT) tile_of_virtual(g, bid, z, tm, tn);  // (the caller did the XCD placement: grouped launches)
+        else tile_of(g, bid, z, tm, tn);
+        nkt = total_tiles(g, KT);
+        splitk = g.splitk;
+    }
+    const int m0 = tm * (32 * NI * MB), n0 = tn * BN;
+    const int per = (FE && splitk == 1) ? nkt : (nkt + splitk - 1) / splitk;
+    const int t_begin = z * per, t_end = min(nkt, t_begin + per);
     const int grp = KG == 1 ? 0 : (wall / WG);  // wave group (K-tile parity)
     const int w = wall % WG;
     const int wm = w >> 1, wn = w & 1;  // wm: 64-row band of the tile, 0 .. 2 * MB - 1
@@ -1118,21 +1203,48 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
     auto issue = [&](int i, int stage) {  // i-th tile of this group
         const int t = t_begin + grp + KG * i;
         int src, tt;
-        source_of<KT>(g, t, src, tt);
+        unsigned char* sbase = ring + stage * STAGE;
+        if constexpr (FE) {
+            entry_source_of<KT>(g, E, t, src, tt);
+            if (src != cur_src) {  // (uniform) as below, each operand's pieces requested as their addresses are formed
+                const int k0 = tt * KT;
+                const bool s0 = src == 0;
+                unsigned long long* st0 = nullptr;
+#ifdef EGK_GEMM_STAMPS
+                if (i == 0) st0 = &ps_iss0;
+#endif
+                ca.init_issue(s0 ? E.A0 : (const bf16_t*)g.A[src], s0 ? E.lda0 : g.lda[src], E.M, m0, k0, w * NI, lane, KG, sbase, st0);
+                cb.init_issue(s0 ? E.B0 : (const bf16_t*)g.B[src], s0 ? E.ldb0 : g.ldb[src], E.N, n0, k0, w * NPB, lane, KG, sbase + IMG_A);
+                cur_src = src;
+#ifdef EGK_GEMM_STAMPS
+                if (i == 0) ps_iss1 = __builtin_amdgcn_s_memtime();
+#endif
+                return;
+            }
+        } else {
+            source_of<KT>(g, t, src, tt);
+        }
         if (src != cur_src) {  // (uniform) first tile, or the walk crossed from one K source into the next
             const int k0 = tt * KT;
             ca.init((const bf16_t*)g.A[src], g.lda[src], g.M, m0, k0, w * NI, lane, KG);
             cb.init((const bf16_t*)g.B[src], g.ldb[src], g.N, n0, k0, w * NPB, lane, KG);
             cur_src = src;
         }
-        unsigned char* sbase = ring + stage * STAGE;
+#ifdef EGK_GEMM_STAMPS
+        if (i == 0) ps_iss0 = __builtin_amdgcn_s_memtime();
+#endif
         ca.issue(sbase, w * NI);
         cb.issue(sbase + IMG_A, w * NPB);
+#ifdef EGK_GEMM_STAMPS
+        if (i == 0) ps_iss1 = __builtin_amdgcn_s_memtime();
+#endif
     };
 
     if constexpr (LW > 0) {
         static_assert(KG == 1 && (WG * NI) % LW == 0 && (WG * NPB) % LW == 0, "loader waves: one wave group, pieces divisible among the loaders");
-        if (wall >= WG) {  // (wave-uniform) a loader wave: pieces [L * PA, (L + 1) * PA) of the A image, [L * PB, ..) of the B image
+        // (FE: the loader path laid out as the fall-through of the entry code, which the instruction prefetch already has; placed behind the
+        //  epilogue, as it is without the hint, its first instruction is a cold miss in front of the workgroup's first request)
+        if (FE ? __builtin_expect(wall >= WG, 1) : (wall >= WG)) {  // (wave-uniform) a loader wave: pieces [L * PA, (L + 1) * PA) of the A image, [L * PB, ..) of the B image
             constexpr int PA = WG * NI / LW, PB = WG * NPB / LW;
             const int L = wall - WG;
             OperandCursor<TRA, PA> la;
@@ -1141,16 +1253,41 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
             auto lissue = [&](int i, int stage) {
                 const int t = t_begin + i;
                 int src, tt;
-                source_of<KT>(g, t, src, tt);
+                unsigned char* sbase = ring + stage * STAGE;
+                if constexpr (FE) {
+                    entry_source_of<KT>(g, E, t, src, tt);
+                    if (src != lsrc) {
+                        const int k0 = tt * KT;
+                        const bool s0 = src == 0;
+                        unsigned long long* st0 = nullptr;
+#ifdef EGK_GEMM_STAMPS
+                        if (i == 0) st0 = &ps_iss0;
+#endif
+                        la.init_issue(s0 ? E.A0 : (const bf16_t*)g.A[src], s0 ? E.lda0 : g.lda[src], E.M, m0, k0, L * PA, lane, 1, sbase, st0);
+                        lb.init_issue(s0 ? E.B0 : (const bf16_t*)g.B[src], s0 ? E.ldb0 : g.ldb[src], E.N, n0, k0, L * PB, lane, 1, sbase + IMG_A);
+                        lsrc = src;
+#ifdef EGK_GEMM_STAMPS
+                        if (i == 0) ps_iss1 = __builtin_amdgcn_s_memtime();
+#endif
+                        return;
+                    }
+                } else {
+                    source_of<KT>(g, t, src, tt);
+                }
                 if (src != lsrc) {
                     const int k0 = tt * KT;
                     la.init((const bf16_t*)g.A[src], g.lda[src], g.M, m0, k0, L * PA, lane, 1);
                     lb.init((const bf16_t*)g.B[src], g.ldb[src], g.N, n0, k0, L * PB, lane, 1);
                     lsrc = src;
                 }
-                unsigned char* sbase = ring + stage * STAGE;
+#ifdef EGK_GEMM_STAMPS
+                if (i == 0) ps_iss0 = __builtin_amdgcn_s_memtime();
+#endif
                 la.issue(sbase, L * PA);
                 lb.issue(sbase + IMG_A, L * PB);
+#ifdef EGK_GEMM_STAMPS
+                if (i == 0) ps_iss1 = __builtin_amdgcn_s_memtime();
+#endif
             };
 #pragma unroll
             for (int p = 0; p < NSTAGE - 1; ++p)
@@ -1161,8 +1298,17 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
                 else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();  // tile ``it`` is in LDS for everybody; the stage read at it - 1 is free
+#ifdef EGK_GEMM_STAMPS
+                if (it == 0) ps_first = __builtin_amdgcn_s_memtime();
+#endif
                 if (it + NSTAGE - 1 < nt) lissue(it + NSTAGE - 1, (it + NSTAGE - 1) % NSTAGE);
             }
+#ifdef EGK_GEMM_STAMPS
+            if (g.ws_bias != nullptr && g.dbias == nullptr && tid == WG * 64) {  // the first loader wave's own entry phases
+                unsigned long long* o = reinterpret_cast<unsigned long long*>(g.ws_bias) + (long long)bid * 16;
+                o[9] = ps_iss0 - ps_entry; o[10] = ps_iss1 - ps_entry; o[11] = ps_first - ps_entry;
+            }
+#endif
             return;  // (the epilogue's barriers count the surviving waves only)
         }
     }
@@ -1224,6 +1370,9 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
             else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
+#ifdef EGK_GEMM_STAMPS
+        if (it == 0) ps_arrive = __builtin_amdgcn_s_memtime();
+#endif
         __builtin_amdgcn_s_barrier();  // every wave's pieces of tile ``it`` landed; the stage read at it-1 is free
 #ifdef EGK_GEMM_STAMPS
         if (it == 0) ps_first = __builtin_amdgcn_s_memtime();
@@ -1406,9 +1555,11 @@ __device__ __forceinline__ void gemm_pipe_body(const GemmArgs& g, const int bid)
     if (g.ws_bias != nullptr && g.dbias == nullptr && tid == 0) {  // (the host points ws_bias behind the slabs in this build)
         const unsigned long long ps_issued = __builtin_amdgcn_s_memtime();  // the output stores are issued ...
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // ... and acknowledged
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(g.ws_bias) + (long long)bid * 8;
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(g.ws_bias) + (long long)bid * 16;
         const unsigned long long ps_end = __builtin_amdgcn_s_memtime();
         o[7] = ps_issued - ps_loop;
+        o[8] = ps_arrive - ps_entry;  // this compute wave reached the barrier of tile 0
+        if constexpr (LW == 0) { o[9] = ps_iss0 - ps_entry; o[10] = ps_iss1 - ps_entry; o[11] = ps_first - ps_entry; }
         o[0] = ps_first - ps_entry; o[1] = ps_loop - ps_first; o[2] = ps_end - ps_loop; o[3] = ps_end - ps_entry;
         o[4] = __builtin_amdgcn_s_memrealtime() - ps_rentry; o[5] = ps_rentry; o[6] = nt;
     }
@@ -1466,6 +1617,12 @@ template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 =
 __global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB, NI, LW)) void gemm_pipe_kernel(const GemmArgs g) {
     gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, false, F16, LW>(g, blockIdx.x);
 }
+// ... and with the entry it had before PipeEntry (egk_gemm_set_pipeline(880)): a kernel of its own, so that reading the descriptor
+// batch cannot warm the scalar cache for the field-by-field reads it is compared with
+template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 = false, int LW = 0>
+__global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB, NI, LW)) void gemm_pipe_kernel_e0(const GemmArgs g) {
+    gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, false, F16, LW, false>(g, blockIdx.x);
+}
 
 // Grouped launch: up to MAX_GROUPS independent contractions of the SAME layout / element types / tile variant in one
 // launch (the projection heads of the task batches: same shapes, different rows of the backbone output, different
@@ -1479,9 +1636,37 @@ constexpr int MAX_GROUPS = 8;
 struct GemmGroup {
     GemmArgs p[MAX_GROUPS];
     int packed, count, total;  // packed placement (always 1): number of problems, total tile count
+    int start[MAX_GROUPS];     // packed placement: the tiles in front of problem i (``total`` for i >= count), one 32-byte read
 };
 template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 = false, int LW = 0>
 __global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB, NI, LW)) void gemm_pipe_group_kernel(const GemmGroup gg) {
+    if (gg.packed) {
+        // problem and virtual tile from one read (total + the start table) instead of a walk over the problems' tile grids, one
+        // round trip each; the problem's own fields are then gemm_pipe_body's one batch
+        int total = gg.total, s1 = gg.start[1], s2 = gg.start[2], s3 = gg.start[3], s4 = gg.start[4], s5 = gg.start[5], s6 = gg.start[6];
+        int s7 = gg.start[7];
+        asm volatile("" : "+s"(total), "+s"(s1), "+s"(s2), "+s"(s3), "+s"(s4), "+s"(s5), "+s"(s6), "+s"(s7));
+        const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
+        const int q = total >> 3, r = total & 7;
+        if (slot >= q + (xcd < r ? 1 : 0)) return;
+        int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+        int pi = 0, first = 0;  // (the starts do not decrease: the last one at or below v is the problem's)
+        if (v >= s1) { pi = 1; first = s1; }
+        if (v >= s2) { pi = 2; first = s2; }
+        if (v >= s3) { pi = 3; first = s3; }
+        if (v >= s4) { pi = 4; first = s4; }
+        if (v >= s5) { pi = 5; first = s5; }
+        if (v >= s6) { pi = 6; first = s6; }
+        if (v >= s7) { pi = 7; first = s7; }
+        gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, true, F16, LW>(gg.p[pi], v - first);
+        return;
+    }
+    const GemmArgs& g = gg.p[blockIdx.y];
+    if ((int)blockIdx.x >= g.tiles_m * g.tiles_n * g.splitk) return;
+    gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, false, F16, LW>(g, blockIdx.x);
+}
+template <int NSTAGE, bool TRA, bool TRB, int KG, int MB, int NI = 4, bool F16 = false, int LW = 0>
+__global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB, NI, LW)) void gemm_pipe_group_kernel_e0(const GemmGroup gg) {
     if (gg.packed) {
         const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
         const int q = gg.total >> 3, r = gg.total & 7;
@@ -1493,12 +1678,12 @@ __global__ __launch_bounds__(NTHREADS * KG * MB + 64 * LW, pipe_min_waves(KG, MB
             if (v < t) break;
             v -= t;
         }
-        gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, true, F16, LW>(gg.p[pi], v);
+        gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, true, F16, LW, false>(gg.p[pi], v);
         return;
     }
     const GemmArgs& g = gg.p[blockIdx.y];
     if ((int)blockIdx.x >= g.tiles_m * g.tiles_n * g.splitk) return;
-    gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, false, F16, LW>(g, blockIdx.x);
+    gemm_pipe_body<NSTAGE, TRA, TRB, KG, MB, NI, false, F16, LW, false>(g, blockIdx.x);
 }
 
 
@@ -2002,11 +2187,20 @@ static int g_use_pipe = 1;
 static constexpr double REDUCE_FIXED_US = 3.5;
 static int g_r192_loaders = 1;  // egk_gemm_set_pipeline(870 / 871): the 192 x 128 tile with four loader waves (variant 19) off / on
 static int g_rows_fast = 1;     // egk_gemm_set_pipeline(890 / 891): the rows epilogue's descriptor-once, mode-specialised store loop (GemmArgs::epi) off / on
+static int g_entry_fast = 1;    // egk_gemm_set_pipeline(880 / 881): the pipelined kernels' entry, field by field (gemm_pipe_kernel_e0) / one descriptor batch, tile 0 requested piece by piece (PipeEntry)
 static int g_tt_tall = 1;       // egk_gemm_set_pipeline(850 / 851): 256 x 128 tiles for weight-gradient groups that leave the second workgroup slot of many CUs empty, off / on
 static bool g_lds_attr_set = false;
+// a bf16 pipelined launch: the kernel, or its twin with the earlier entry (g_entry_fast)
+#define EGK_LAUNCH_E(KERNEL, GRID, BLOCK, LDS, S, ARG, ...)                                              \
+    do {                                                                                                 \
+        if (g_entry_fast) hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), GRID, BLOCK, LDS, S, ARG);           \
+        else hipLaunchKernelGGL((KERNEL##_e0<__VA_ARGS__>), GRID, BLOCK, LDS, S, ARG);                   \
+    } while (0)
 template <int NS, bool TA, bool TB, int KG, int MB = 1>
 static void set_lds_attr() {
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<NS, TA, TB, KG, MB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              NS * KG * (MB + 1) * 16384);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<NS, TA, TB, KG, MB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               NS * KG * (MB + 1) * 16384);
 }
 static void ensure_lds_attr() {
@@ -2014,9 +2208,13 @@ static void ensure_lds_attr() {
     set_lds_attr<2, false, false, 1>(); set_lds_attr<2, false, true, 1>(); set_lds_attr<2, true, true, 1>(); set_lds_attr<2, true, false, 1>();
     set_lds_attr<2, false, false, 2>(); set_lds_attr<2, false, true, 2>(); set_lds_attr<2, true, true, 2>(); set_lds_attr<2, true, false, 2>();
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
@@ -2024,19 +2222,33 @@ static void ensure_lds_attr() {
     (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, false, 8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, true, 8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, true, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, true, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, true, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, true, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<3, true, true, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 49152);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<3, true, true, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 49152);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
@@ -2047,20 +2259,29 @@ static void ensure_lds_attr() {
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, false, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, false, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, true, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, true, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, false, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, false, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
     (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
+    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, true, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
     g_lds_attr_set = true;
 }
 // A/B runs in one process and the tests' forced variants: 0 routes every contraction through the generic kernel; 850 / 851 and
 // 870 / 871 switch one policy choice (g_tt_tall, g_r192_loaders); 890 / 891 switch the store loop of the rows epilogue: 890 the
 // branch ladder that reads the descriptor in every iteration (gemm_epilogue_rows), 891 (default) the descriptor-once, mode-specialised
-// two-phase loop (gemm_epilogue_rows_fast) -- the same bits either way.  Any other code outside 0 .. 19 changes nothing and returns -1.
+// two-phase loop (gemm_epilogue_rows_fast) -- the same bits either way; 880 / 881 switch the entry of the bf16 pipelined kernels: 880 the
+// kernels that read each descriptor field where it is first used, 881 (default) one batch at entry and tile 0 requested piece by piece
+// (PipeEntry) -- the same bits again.  Any other code outside 0 .. 19 changes nothing and returns -1.
 extern "C" int egk_gemm_set_pipeline(int32_t on) {
     const int prev = g_use_pipe;
     if (on == 890 || on == 891) { g_rows_fast = on - 890; return prev; }
+    if (on == 880 || on == 881) { g_entry_fast = on - 880; return 0; }
     if (on == 870 || on == 871) { g_r192_loaders = on - 870; return prev; }
     if (on == 850 || on == 851) { g_tt_tall = on - 850; return prev; }
     if (on < 0 || on >= 20) return -1;
@@ -2226,6 +2447,8 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
         EGK_REQUIRE(d->st_mode == 1 || (d->st_x && d->st_stats && d->st_w && d->st_b), "egk_gemm: st_mode 2 needs x, stats, w, b");
     }
     g.epi = g_rows_fast && epilogue_rows_ok(g);
+    g.nkt = 0;
+    for (int i = 0; i < g.nsrc; ++i) g.nkt += (g.K[i] + 63) / 64;
     if (query_blocks) *query_blocks = 0;
     const long long K = src.k_total;
     const double flops = 2.0 * d->M * d->N * K;
@@ -2330,7 +2553,7 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
 #ifdef EGK_GEMM_STAMPS
         if (variant != 7 && !g.dbias && d->ws) {
             const int64_t slab = g.splitk > 1 ? (int64_t)g.splitk * d->M * d->N * 4 : 0;
-            if (d->ws_bytes >= slab + (int64_t)g.tiles_m * g.tiles_n * g.splitk * 64) g.ws_bias = (float*)((char*)d->ws + slab);
+            if (d->ws_bytes >= slab + (int64_t)g.tiles_m * g.tiles_n * g.splitk * 128) g.ws_bias = (float*)((char*)d->ws + slab);
         }
         if (variant == 7 && g.splitk == 1 && !g.dbias && d->ws && d->ws_bytes >= (int64_t)g.tiles_m * g.tiles_n * 8 * 64)
             g.ws_bias = (float*)d->ws;  // per-wave cycle stamps land in the caller's workspace
@@ -2369,22 +2592,22 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
 #define EGK_PIPE(TA, TB)                                                                                                  \
     do {                                                                                                                  \
         if (variant == 16 && g_r192_loaders && nkt_slab >= 4) {                                                           \
-            hipLaunchKernelGGL((gemm_pipe_kernel<3, false, TB, 1, 2, 3, false, 4>), pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, g); \
+            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, g, 3, false, TB, 1, 2, 3, false, 4); \
         } else if (variant == 16) {                                                                                       \
-            hipLaunchKernelGGL((gemm_pipe_kernel<3, false, TB, 1, 2, 3>), pgrid, dim3(2 * NTHREADS), 3 * 40960, s, g);    \
+            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS), 3 * 40960, s, g, 3, false, TB, 1, 2, 3);    \
         } else if (variant == 15) {                                                                                       \
             hipLaunchKernelGGL((gemm_big_kernel<false, TB, 8, 6>), pgrid, dim3(512), 131072, s, g);                       \
         } else if (variant == 7) {                                                                                        \
             hipLaunchKernelGGL((gemm_big_kernel<TA, TB>), pgrid, dim3(512), 131072, s, g);                                \
         } else if (variant == 12) {                                                                                       \
-            hipLaunchKernelGGL((gemm_pipe_kernel<2, false, TB, 2, 1, 2>), pgrid, dim3(2 * NTHREADS), 4 * 24576, s, g);    \
+            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS), 4 * 24576, s, g, 2, false, TB, 2, 1, 2);    \
         } else if (variant == 11) {                                                                                       \
-            hipLaunchKernelGGL((gemm_pipe_kernel<2, false, TB, 1, 1, 2>), pgrid, pblock, 2 * 24576, s, g);                \
+            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, pblock, 2 * 24576, s, g, 2, false, TB, 1, 1, 2);                \
         } else if (variant == 8) {                                                                                        \
-            hipLaunchKernelGGL((gemm_pipe_kernel<2, false, TB, 1, 1, 3>), pgrid, pblock, 2 * 28672, s, g);                \
+            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, pblock, 2 * 28672, s, g, 2, false, TB, 1, 1, 3);                \
         } else if (variant == 5)                                                                                          \
-            hipLaunchKernelGGL((gemm_pipe_kernel<2, TA, TB, 2, 1>), pgrid, dim3(2 * NTHREADS), 4 * 32768, s, g);          \
-        else hipLaunchKernelGGL((gemm_pipe_kernel<2, TA, TB, 1, 1>), pgrid, pblock, 2 * 32768, s, g);                     \
+            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS), 4 * 32768, s, g, 2, TA, TB, 2, 1);          \
+        else EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, pblock, 2 * 32768, s, g, 2, TA, TB, 1, 1);                     \
     } while (0)
         {
             ProfScope prof((variant == 7 || variant == 15) ? KID_GEMM_BF16_NN_T256 + layout : variant == 8 ? KID_GEMM_BF16_NN_R96 + layout : variant == 11 ? KID_GEMM_BF16_NN_R64 + layout
@@ -2541,6 +2764,8 @@ static int fill_group_args(const egk_gemm_desc* d, GemmArgs& g) {
     g.st_stats = nullptr; g.st_w = nullptr; g.st_b = nullptr; g.st_slope = 0.f;
     EGK_REQUIRE(d->st_mode == 0, "egk_gemm_grouped: no segment statistics in a grouped launch");
     g.epi = g_rows_fast && epilogue_rows_ok(g);
+    g.nkt = 0;
+    for (int i = 0; i < g.nsrc; ++i) g.nkt += (g.K[i] + 63) / 64;
     return 0;
 }
 
@@ -2594,6 +2819,10 @@ extern "C" int egk_gemm_grouped(egk_stream_t stream, const egk_gemm_desc* descs,
         }
         for (int i = count; i < MAX_GROUPS; ++i) gg.p[i] = gg.p[0];
         gg.packed = 1; gg.count = count; gg.total = total;
+    for (int i = 0, t = 0; i < MAX_GROUPS; ++i) {
+        gg.start[i] = i < count ? t : total;
+        t += gg.p[i].tiles_m * gg.p[i].tiles_n;
+    }
         const dim3 pgrid((total + 7) / 8 * 8), pblock(NTHREADS);
         const int layout = ta ? (tb ? 2 : 3) : (tb ? 1 : 0);
         EGK_REQUIRE(!(ta && !tb), "egk_gemm_grouped: the tn layout is not instantiated");
@@ -2643,34 +2872,47 @@ extern "C" int egk_gemm_grouped(egk_stream_t stream, const egk_gemm_desc* descs,
         while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
         g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
     }
+#ifdef EGK_GEMM_STAMPS
+    if (descs[0].ws && descs[0].ws_bytes >= (int64_t)total * 128) {  // 128 bytes of stamps per workgroup, problem after problem
+        int64_t off = 0;
+        for (int i = 0; i < count; ++i) {
+            if (!gg.p[i].dbias) gg.p[i].ws_bias = (float*)((char*)descs[0].ws + off);
+            off += (int64_t)gg.p[i].tiles_m * gg.p[i].tiles_n * 128;
+        }
+    }
+#endif
     for (int i = count; i < MAX_GROUPS; ++i) gg.p[i] = gg.p[0];
     gg.packed = 1; gg.count = count; gg.total = total;
+    for (int i = 0, t = 0; i < MAX_GROUPS; ++i) {
+        gg.start[i] = i < count ? t : total;
+        t += gg.p[i].tiles_m * gg.p[i].tiles_n;
+    }
     const dim3 pgrid((total + 7) / 8 * 8);
     const dim3 pblock(NTHREADS);
     const int layout = ta ? (tb ? 2 : 3) : (tb ? 1 : 0);
     EGK_REQUIRE(!(ta && !tb), "egk_gemm_grouped: the tn layout is not instantiated");
 #define EGK_PIPE_G(TA, TB)                                                                                                  \
     do {                                                                                                                    \
-        if (variant == 5) hipLaunchKernelGGL((gemm_pipe_group_kernel<2, TA, TB, 2, 1>), pgrid, dim3(2 * NTHREADS), 4 * 32768, s, gg); \
-        else hipLaunchKernelGGL((gemm_pipe_group_kernel<2, TA, TB, 1, 1>), pgrid, pblock, 2 * 32768, s, gg);                \
+        if (variant == 5) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS), 4 * 32768, s, gg, 2, TA, TB, 2, 1); \
+        else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 32768, s, gg, 2, TA, TB, 1, 1);                \
     } while (0)
     {
         ProfScope prof(KID_GEMM_BF16_GROUP_NN + layout, s, flops, bytes);  // (layout 0 nn, 1 nt, 2 tt; the tall weight-gradient tile included)
         if (f16) {
             ensure_lds_attr();
-            hipLaunchKernelGGL((gemm_pipe_group_kernel<2, false, false, 1, 1, 4, true>), pgrid, pblock, 2 * 32768, s, gg);
+            EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 32768, s, gg, 2, false, false, 1, 1, 4, true);
         } else if (!ta && variant == 16) {
-            if (!tb) hipLaunchKernelGGL((gemm_pipe_group_kernel<3, false, false, 1, 2, 3, false, 4>), pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, gg);
-            else hipLaunchKernelGGL((gemm_pipe_group_kernel<3, false, true, 1, 2, 3, false, 4>), pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, gg);
+            if (!tb) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, gg, 3, false, false, 1, 2, 3, false, 4);
+            else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, gg, 3, false, true, 1, 2, 3, false, 4);
         } else if (!ta && variant == 11) {
-            if (!tb) hipLaunchKernelGGL((gemm_pipe_group_kernel<2, false, false, 1, 1, 2>), pgrid, pblock, 2 * 24576, s, gg);
-            else hipLaunchKernelGGL((gemm_pipe_group_kernel<2, false, true, 1, 1, 2>), pgrid, pblock, 2 * 24576, s, gg);
+            if (!tb) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 24576, s, gg, 2, false, false, 1, 1, 2);
+            else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 24576, s, gg, 2, false, true, 1, 1, 2);
         } else if (!ta && variant == 8) {
-            if (!tb) hipLaunchKernelGGL((gemm_pipe_group_kernel<2, false, false, 1, 1, 3>), pgrid, pblock, 2 * 28672, s, gg);
-            else hipLaunchKernelGGL((gemm_pipe_group_kernel<2, false, true, 1, 1, 3>), pgrid, pblock, 2 * 28672, s, gg);
+            if (!tb) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 28672, s, gg, 2, false, false, 1, 1, 3);
+            else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 28672, s, gg, 2, false, true, 1, 1, 3);
         } else if (!ta && !tb) EGK_PIPE_G(false, false);
         else if (!ta && tb) EGK_PIPE_G(false, true);
-        else if (variant == 13) hipLaunchKernelGGL((gemm_pipe_group_kernel<3, true, true, 1, 2>), pgrid, dim3(2 * NTHREADS), 3 * 49152, s, gg);
+        else if (variant == 13) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS), 3 * 49152, s, gg, 3, true, true, 1, 2);
         else EGK_PIPE_G(true, true);
     }
 #undef EGK_PIPE_G
