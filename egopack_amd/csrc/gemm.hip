@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_policy.h"
 
 namespace egk {
 
@@ -2167,13 +2168,52 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(const GemmArgs g) {
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <bool BF16C, typename AT, typename BT>
-static void launch_layout(const egk_gemm_desc* d, dim3 grid, hipStream_t s, const GemmArgs& g) {
-    dim3 block(NTHREADS);
-    if (!d->transA && !d->transB) hipLaunchKernelGGL((gemm_kernel<BF16C, false, false, AT, BT>), grid, block, 0, s, g);
-    else if (!d->transA && d->transB) hipLaunchKernelGGL((gemm_kernel<BF16C, false, true, AT, BT>), grid, block, 0, s, g);
-    else if (d->transA && d->transB) hipLaunchKernelGGL((gemm_kernel<BF16C, true, true, AT, BT>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<BF16C, true, false, AT, BT>), grid, block, 0, s, g);
+// ---- launch table ---------------------------------------------------------------------------------------------------------
+// One row per launched instantiation (the list of gemm_policy.h): the kernel's host address -- [0] the twin with the earlier entry
+// (g_entry_fast off) where the family has one, [1] the kernel -- and its block size and LDS bytes, from the variant's geometry record.
+struct LaunchRow {
+    const void* fn[2];
+    int family, variant, layout, flavour;
+    int threads, lds;
+};
+static_assert(policy::MAX_PROBLEMS == MAX_GROUPS && NTHREADS == 256 && BM == 128 && BN == 128, "gemm_policy.h restates these");
+static_assert(policy::PROF_NN == KID_GEMM_BF16_NN && policy::PROF_G2 == KID_GEMM_BF16_NN_G2 && policy::PROF_R96 == KID_GEMM_BF16_NN_R96 &&
+                  policy::PROF_R64 == KID_GEMM_BF16_NN_R64 && policy::PROF_R192 == KID_GEMM_BF16_NN_R192 &&
+                  policy::PROF_T256 == KID_GEMM_BF16_NN_T256,
+              "gemm_policy.h restates the profile ids");
+#define EGK_SHAPE(V) policy::shape(policy::V)
+#define EGK_PIPE_ARGS(V, TA, TB, FL) \
+    EGK_SHAPE(V).stages, TA, TB, EGK_SHAPE(V).kg, EGK_SHAPE(V).mb, EGK_SHAPE(V).ni, policy::FL == policy::F16, (policy::FL == policy::LOADERS ? EGK_SHAPE(V).lw : 0)
+#define EGK_FN_PIPE(V, TA, TB, FL) {(const void*)gemm_pipe_kernel_e0<EGK_PIPE_ARGS(V, TA, TB, FL)>, (const void*)gemm_pipe_kernel<EGK_PIPE_ARGS(V, TA, TB, FL)>}
+#define EGK_FN_GROUP(V, TA, TB, FL) {(const void*)gemm_pipe_group_kernel_e0<EGK_PIPE_ARGS(V, TA, TB, FL)>, (const void*)gemm_pipe_group_kernel<EGK_PIPE_ARGS(V, TA, TB, FL)>}
+#define EGK_FN_ONE(...) {(const void*)__VA_ARGS__, (const void*)__VA_ARGS__}
+#define EGK_FN_BIG(V, TA, TB, FL) EGK_FN_ONE(gemm_big_kernel<TA, TB, 8, EGK_SHAPE(V).ni>)
+#define EGK_FN_F32(V, TA, TB, FL) EGK_FN_ONE(gemm_pipe_f32_kernel<TA, TB, EGK_SHAPE(V).ni>)
+#define EGK_FN_F32_GROUP(V, TA, TB, FL) EGK_FN_ONE(gemm_pipe_f32_group_kernel<TA, TB>)
+#define EGK_FN_GEN_F32(V, TA, TB, FL) EGK_FN_ONE(gemm_kernel<false, TA, TB, float, float>)
+#define EGK_FN_GEN_BF16(V, TA, TB, FL) EGK_FN_ONE(gemm_kernel<true, TA, TB, bf16_t, bf16_t>)
+#define EGK_FN_GEN_MIXED(V, TA, TB, FL) EGK_FN_ONE(gemm_kernel<true, TA, TB, float, float>)
+#define EGK_ROW(FAM, V, TA, TB, FL)                                                                        \
+    {EGK_FN_##FAM(V, TA, TB, FL), policy::FAM, policy::V, policy::layout_of(TA, TB), policy::FL,           \
+     policy::row_threads(policy::FAM, policy::V, policy::FL), policy::row_lds_bytes(policy::FAM, policy::V)},
+static const LaunchRow LAUNCH_TABLE[] = {EGK_GEMM_LAUNCH_ROWS(EGK_ROW)};
+#undef EGK_ROW
+#undef EGK_FN_PIPE
+#undef EGK_FN_GROUP
+#undef EGK_FN_BIG
+#undef EGK_FN_F32
+#undef EGK_FN_F32_GROUP
+#undef EGK_FN_GEN_F32
+#undef EGK_FN_GEN_BF16
+#undef EGK_FN_GEN_MIXED
+#undef EGK_FN_ONE
+#undef EGK_PIPE_ARGS
+#undef EGK_SHAPE
+
+static const LaunchRow* find_row(int family, int variant, int layout, int flavour) {
+    for (const LaunchRow& r : LAUNCH_TABLE)
+        if (r.family == family && r.variant == variant && r.layout == layout && r.flavour == flavour) return &r;
+    return nullptr;
 }
 
 }  // namespace egk
@@ -2185,92 +2225,33 @@ static int g_use_pipe = 1;
 // stand-alone fit; inside a captured step every extra launch also pays a boundary on its queue (a one-lane kernel lasts ~4.7 us
 // in a replay).
 static constexpr double REDUCE_FIXED_US = 3.5;
-static int g_r192_loaders = 1;  // egk_gemm_set_pipeline(870 / 871): the 192 x 128 tile with four loader waves (variant 19) off / on
+static int g_r192_loaders = 1;  // egk_gemm_set_pipeline(870 / 871): the 192 x 128 tile with four loader waves (variant 16) off / on
 static int g_rows_fast = 1;     // egk_gemm_set_pipeline(890 / 891): the rows epilogue's descriptor-once, mode-specialised store loop (GemmArgs::epi) off / on
 static int g_entry_fast = 1;    // egk_gemm_set_pipeline(880 / 881): the pipelined kernels' entry, field by field (gemm_pipe_kernel_e0) / one descriptor batch, tile 0 requested piece by piece (PipeEntry)
 static int g_tt_tall = 1;       // egk_gemm_set_pipeline(850 / 851): 256 x 128 tiles for weight-gradient groups that leave the second workgroup slot of many CUs empty, off / on
-static bool g_lds_attr_set = false;
-// a bf16 pipelined launch: the kernel, or its twin with the earlier entry (g_entry_fast)
-#define EGK_LAUNCH_E(KERNEL, GRID, BLOCK, LDS, S, ARG, ...)                                              \
-    do {                                                                                                 \
-        if (g_entry_fast) hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), GRID, BLOCK, LDS, S, ARG);           \
-        else hipLaunchKernelGGL((KERNEL##_e0<__VA_ARGS__>), GRID, BLOCK, LDS, S, ARG);                   \
-    } while (0)
-template <int NS, bool TA, bool TB, int KG, int MB = 1>
-static void set_lds_attr() {
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<NS, TA, TB, KG, MB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              NS * KG * (MB + 1) * 16384);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<NS, TA, TB, KG, MB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              NS * KG * (MB + 1) * 16384);
-}
+static policy::Knobs policy_knobs() { return {g_use_pipe, g_tt_tall, g_r192_loaders}; }
+
+// Every row's dynamic LDS size, registered on the first contraction call of the process (never at a row's first launch: that one
+// may fall inside a graph capture).
 static void ensure_lds_attr() {
-    if (g_lds_attr_set) return;
-    set_lds_attr<2, false, false, 1>(); set_lds_attr<2, false, true, 1>(); set_lds_attr<2, true, true, 1>(); set_lds_attr<2, true, false, 1>();
-    set_lds_attr<2, false, false, 2>(); set_lds_attr<2, false, true, 2>(); set_lds_attr<2, true, true, 2>(); set_lds_attr<2, true, false, 2>();
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, false, 8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_big_kernel<false, true, 8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 1, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 1, 1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 1, 1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, true, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, true, true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, true, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, true, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<3, true, true, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 49152);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<3, true, true, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 49152);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel<2, false, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_group_kernel_e0<2, false, true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_group_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_group_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_group_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_f32_kernel<false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, false, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, false, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, true, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, true, 1, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, false, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<3, false, true, 1, 2, 3, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 40960);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, false, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, false, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel<2, false, true, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
-    (void)hipFuncSetAttribute((const void*)egk::gemm_pipe_kernel_e0<2, false, true, 2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 24576);
-    g_lds_attr_set = true;
+    static bool done = false;
+    if (done) return;
+    for (const LaunchRow& r : LAUNCH_TABLE)
+        for (const void* fn : r.fn)
+            if (r.lds > 0) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds);
+    done = true;
+}
+// Launch a row on ``grid`` with the row's block and LDS size (errors: check_launch).
+template <typename Args>
+static void launch_row(const LaunchRow& r, dim3 grid, hipStream_t s, const Args& args) {
+    void* argv[] = {const_cast<Args*>(&args)};
+    (void)hipLaunchKernel(r.fn[g_entry_fast ? 1 : 0], grid, dim3(r.threads), argv, r.lds, s);
+}
+// The reduce launch behind a split contraction.  ``work``: the items a thread takes one of -- element groups of 4 (the vector path;
+// the scalar path strides), or the elements themselves behind the generic kernel.
+static void launch_splitk_reduce(const GemmArgs& g, long long work, double slab_bytes, hipStream_t s) {
+    ProfScope prof(KID_GEMM_SPLITK_REDUCE, s, 0, slab_bytes);
+    hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048)), dim3(256), 0, s, g);
 }
 // A/B runs in one process and the tests' forced variants: 0 routes every contraction through the generic kernel; 850 / 851 and
 // 870 / 871 switch one policy choice (g_tt_tall, g_r192_loaders); 890 / 891 switch the store loop of the rows epilogue: 890 the
@@ -2285,10 +2266,7 @@ extern "C" int egk_gemm_set_pipeline(int32_t on) {
     if (on == 870 || on == 871) { g_r192_loaders = on - 870; return prev; }
     if (on == 850 || on == 851) { g_tt_tall = on - 850; return prev; }
     if (on < 0 || on >= 20) return -1;
-    // 0 generic kernel only; 1 default policy; 2 always 3-stage; 3 always 2-stage; 4 always 4-stage (all 128 x 128,
-    // one wave group); 5 always two wave groups; 6 always the 256 x 128 tile (2-stage); 7 always the 256 x 256 tile (no fused
-    // bias gradient: falls back to 3 with one); 8 / 11 the 96 x 128 / 64 x 128 tile where legal (row-major A); 16 the 192 x 128
-    // tile (8 waves, 3-stage ring) where legal (row-major A, no split-K)
+    // 0 generic kernel only; 1 the policy; else a policy::Variant forced where it is legal (gemm_policy.h: pick_single, pick_group)
     g_use_pipe = on;
     return prev;
 }
@@ -2385,6 +2363,47 @@ static int fill_sources(const egk_gemm_desc* d, GemmArgs& g, int ea, int eb, Sou
     return 0;
 }
 
+// Output, epilogue operands and their alignment flags of a descriptor into g, for a launch of ``splitk`` slabs in ``ws``; no bias
+// gradient and no segment statistics (the caller sets those).  After fill_sources.
+static void fill_output(const egk_gemm_desc* d, GemmArgs& g, int splitk, float* ws) {
+    g.C = d->C; g.ldc = d->ldc;
+    g.c_bf16 = d->c_dtype == EGK_BF16;
+    g.c_vec = g.c_bf16 ? ((reinterpret_cast<uintptr_t>(g.C) & 7) == 0 && g.ldc % 4 == 0) : (aligned16(g.C) && g.ldc % 4 == 0);
+    g.accumulate = d->accumulate; g.act = d->act; g.alpha = d->alpha;
+    g.bias = d->bias; g.residual = d->residual; g.ldr = d->ldr;
+    g.r_bf16 = d->r_dtype == EGK_BF16;
+    g.r_vec = g.residual && (g.r_bf16 ? ((reinterpret_cast<uintptr_t>(g.residual) & 7) == 0 && g.ldr % 4 == 0)
+                                      : (aligned16(g.residual) && g.ldr % 4 == 0));
+    g.splitk = splitk;
+    g.ws = ws;
+    g.dbias = nullptr; g.ws_bias = nullptr;
+    g.rows_epilogue = 1;
+    g.st_mode = 0; g.st_nseg = 0; g.st_seg_ptr = nullptr; g.st_ws = nullptr; g.st_x = nullptr; g.st_ldx = 0;
+    g.st_stats = nullptr; g.st_w = nullptr; g.st_b = nullptr; g.st_slope = 0.f;
+    g.epi = g_rows_fast && epilogue_rows_ok(g);
+    g.nkt = 0;
+    for (int i = 0; i < g.nsrc; ++i) g.nkt += (g.K[i] + 63) / 64;
+}
+
+// Segment statistics in the epilogue: variants that write their tile out through LDS in whole rows (``capable``), unsplit, and tiles
+// of ``tile_rows`` rows that span at most two row segments; st_mode 2 reads x in vectors of ``x_vec`` elements.  Answers the query of
+// egk_gemm_stats_blocks, or refuses a launch that asks for statistics it cannot have.  Returns true when gemm_core is done, with *rc.
+static bool stats_epilogue_gate(const egk_gemm_desc* d, const GemmArgs& g, bool capable, int tile_rows, int x_vec, int* query_blocks, int* rc) {
+    const bool st_ok = capable && g.splitk == 1 && epilogue_rows_ok(g) && d->st_min_seg_rows >= tile_rows &&
+                       (d->st_mode != 2 || (aligned16(d->st_x) && d->st_ldx % x_vec == 0 && aligned16(d->st_w) && aligned16(d->st_b)));
+    *rc = 0;
+    if (query_blocks) {
+        *query_blocks = (d->st_mode && st_ok) ? g.tiles_m * g.tiles_n : 0;
+        return true;
+    }
+    if (d->st_mode && !st_ok) {
+        set_error("egk_gemm: st_mode %d is not available for this launch (ask egk_gemm_stats_blocks first)", d->st_mode);
+        *rc = EGK_EUNSUPPORTED;
+        return true;
+    }
+    return false;
+}
+
 static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blocks);
 
 extern "C" int egk_gemm(egk_stream_t stream, const egk_gemm_desc* d) { return gemm_core(stream, d, nullptr); }
@@ -2423,22 +2442,11 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
         const int rc = fill_sources(d, g, ea, eb, src, "egk_gemm");
         if (rc) return rc;
     }
-    g.C = d->C; g.ldc = d->ldc;
-    g.c_bf16 = d->c_dtype == EGK_BF16;
-    g.c_vec = g.c_bf16 ? ((reinterpret_cast<uintptr_t>(g.C) & 7) == 0 && g.ldc % 4 == 0) : (aligned16(g.C) && g.ldc % 4 == 0);
-    g.accumulate = d->accumulate; g.act = d->act; g.alpha = d->alpha;
-    g.bias = d->bias; g.residual = d->residual; g.ldr = d->ldr;
-    g.r_bf16 = d->r_dtype == EGK_BF16;
-    g.r_vec = g.residual && (g.r_bf16 ? ((reinterpret_cast<uintptr_t>(g.residual) & 7) == 0 && g.ldr % 4 == 0)
-                                      : (aligned16(g.residual) && g.ldr % 4 == 0));
-    g.splitk = d->splitk > 1 ? d->splitk : 1;
-    g.ws = (float*)d->ws;
-    if (g.splitk > 1)
-        EGK_REQUIRE(g.ws && d->ws_bytes >= (int64_t)g.splitk * d->M * d->N * 4, "egk_gemm: split-K workspace too small");
+    if (d->splitk > 1)
+        EGK_REQUIRE(d->ws && d->ws_bytes >= (int64_t)d->splitk * d->M * d->N * 4, "egk_gemm: split-K workspace too small");
+    fill_output(d, g, d->splitk > 1 ? d->splitk : 1, (float*)d->ws);
     g.tiles_m = cdiv(g.M, BM); g.tiles_n = cdiv(g.N, BN);
-    g.dbias = nullptr; g.ws_bias = nullptr;
     g.group_m = 1;
-    g.rows_epilogue = 1;
     g.st_mode = d->st_mode; g.st_nseg = d->st_nseg; g.st_seg_ptr = d->st_seg_ptr; g.st_ws = (double*)d->st_ws;
     g.st_x = d->st_x; g.st_ldx = d->st_ldx; g.st_stats = d->st_stats; g.st_w = d->st_w; g.st_b = d->st_b; g.st_slope = d->st_slope;
     if (d->st_mode) {
@@ -2446,9 +2454,6 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
         EGK_REQUIRE(d->st_nseg >= 1 && d->st_nseg <= 16 && d->st_seg_ptr && (query_blocks || d->st_ws), "egk_gemm: st_* segments / workspace");
         EGK_REQUIRE(d->st_mode == 1 || (d->st_x && d->st_stats && d->st_w && d->st_b), "egk_gemm: st_mode 2 needs x, stats, w, b");
     }
-    g.epi = g_rows_fast && epilogue_rows_ok(g);
-    g.nkt = 0;
-    for (int i = 0; i < g.nsrc; ++i) g.nkt += (g.K[i] + 63) / 64;
     if (query_blocks) *query_blocks = 0;
     const long long K = src.k_total;
     const double flops = 2.0 * d->M * d->N * K;
@@ -2480,226 +2485,60 @@ static int gemm_core(egk_stream_t stream, const egk_gemm_desc* d, int* query_blo
             if (rc) return rc;
         }
     }
+    // ask the policy (gemm_policy.h), then look the launch up: family, row and profile id
+    int family, prof_id, flavour = policy::PLAIN;
+    policy::Choice c;
     if (pipe_ok) {
+        c = policy::pick_single(d->M, d->N, K, cdiv(K / 64, g.splitk), layout, g.splitk, g.dbias != nullptr, d->st_mode != 0, policy_knobs());
+        const policy::Shape shape = policy::shape(c.variant);
+        family = shape.big ? policy::BIG : policy::PIPE;
+        flavour = c.loaders ? policy::LOADERS : policy::PLAIN;
+        prof_id = shape.prof + layout;
+    } else if (pipe32_ok) {  // exact-f32 pipelined kernel: f32 operands, 16-byte aligned rows, every K source a multiple of 32
+        c = policy::pick_single_f32(d->M, d->N, layout, g.splitk, policy_knobs());
+        family = policy::F32;
+        prof_id = KID_GEMM_F32_NN + layout;
+    } else {  // the generic kernel: 128 x 128 tiles on a (tiles, slabs) grid
+        c = {policy::V_128, false, g.tiles_m, g.tiles_n, 1};
+        family = !bf ? policy::GEN_F32 : a16 ? policy::GEN_BF16 : policy::GEN_MIXED;
+        prof_id = bf ? KID_GEMM_BF16_GENERIC : KID_GEMM_F32_NN + layout;
+    }
+    const bool pipelined = pipe_ok || pipe32_ok;
+    g.tiles_m = c.tiles_m; g.tiles_n = c.tiles_n; g.group_m = c.group_m;
+    if (pipelined) {
         ensure_lds_attr();
-        dim3 pblock(NTHREADS);
-        // Variant policy (g_use_pipe == 1), by the number of 128 x 128 workgroups the launch would have:
-        //   <= 256 : one workgroup (one wave per SIMD) per CU would walk K at a fifth of the MFMA rate (DMA issue, LDS
-        //            reads and MFMAs of the lone wave serialise): two wave groups per workgroup instead (5);
-        //   >  256 : 128 x 128 tiles, two 4-wave workgroups per CU (3).
-        // The 256 x 128 tile (6) is kept as a measured alternative: it fetches a third fewer bytes per flop, but the
-        // rate of this loop is set by LDS fragment reads + MFMA issue per 64 x 64 wave patch, not by the bytes a CU
-        // takes in -- it is 3-10 % slower than (3) up to 4096^3 and 5 % faster at 8192^3 (tools/gemm_bench.py --layouts).
-        const int nwg128 = g.tiles_m * g.tiles_n * g.splitk;
-        const int nkt_slab = cdiv(K / 64, g.splitk);
-        int variant = g_use_pipe;
-        if (variant == 1) {
-            variant = nwg128 > 256 ? 3 : (nkt_slab >= 4 ? 5 : 3);
-            if (!d->transA && g.splitk == 1) {  // row-major A: the tile height is free (MFMA row fragments per wave)
-                const long long t128 = (long long)cdiv(g.M, 128) * g.tiles_n, t96 = (long long)cdiv(g.M, 96) * g.tiles_n;
-                const long long t64 = (long long)cdiv(g.M, 64) * g.tiles_n;
-                if (nwg128 > 256) {
-                    // a CU runs its share of the tiles two at a time at a fixed intake: the launch ends after
-                    // ceil(tiles / 256) tiles' worth of bytes on the fullest CU (6144 x 1024: 2 x 32 KiB per K tile with
-                    // 384 tiles of 128 rows, 2 x 28 KiB with 512 tiles of 96 rows)
-                    if (((t96 + 255) / 256) * 28 < ((t128 + 255) / 256) * 32) variant = 8;
-                    // ... or ONE 8-wave workgroup per CU on 192 x 128 tiles with a 3-stage ring (two K tiles = 80 KiB in flight
-                    // per CU): 40 KiB per K tile and round of 256 tiles -- 6144 x 1024 is exactly one round (256 tiles) where the
-                    // 96-row tiles are two co-resident workgroups of 28 KiB each
-                    const long long t192 = (long long)cdiv(g.M, 192) * g.tiles_n;
-                    const long long cur = variant == 8 ? ((t96 + 255) / 256) * 28 : ((t128 + 255) / 256) * 32;
-                    // (ONE round only: 8192 x 1024 -- 344 tiles, two rounds of which the second is a third full -- measured 32.6 us
-                    //  against 22.3 on 128-row tiles; BASELINE config 5's 16384 rows 3.08 against 2.92 ms per step)
-                    if (t192 > 192 && t192 <= 256 && 40 < cur) variant = 16;
-                    // (several rounds of this tile with its loader waves -- 16384 x 1024: 688 tiles, 2.7 rounds -- measured 2.938 -> 2.901 ms
-                    //  for BASELINE config 5 on one box and 2.93 -> 3.03 on two others: one round only)
-                } else if (t64 <= 256 && t64 > t128) {
-                    // at most 128 tiles: 64-row tiles put one 4-wave workgroup on twice as many CUs instead of one
-                    // 8-wave (two wave groups) workgroup on half of them (2048 x 1024 x 1024: 10.6 vs 12.4 us)
-                    variant = 11;
-                }
-            }
-            // large outputs with a long K walk: 256 x 256 tiles, one 8-wave workgroup per CU, when whole tiles fill at least
-            // 90 % of the CU slots of the rounds they take.  Measured against the 128 x 128 kernel (tools/gemm_big.py):
-            // 16384 x 1024 x 4608: 126 vs 145 us; 4096^3: 113 vs 128; 8192^3: 836 vs 1178; but 16384 x 1024 x 2048: 76 vs 74
-            // and x 1024: 45 vs 45 (16 K tiles: prologue and epilogue of the big tile weigh as much as its loop saves),
-            // 24576 x 1024 (384 tiles, 1.5 rounds): 78 vs 65.  6144 x 1024 (96 tiles) never qualifies.
-            const long long t256 = (long long)cdiv(g.M, 256) * cdiv(g.N, 256);
-            if (g.splitk == 1 && !g.dbias && g.M % 256 == 0 && g.N % 256 == 0 && t256 >= 192 && K >= 3072 &&
-                10 * t256 >= 9 * 256 * ((t256 + 255) / 256))
-                variant = 7;
-            // ... and 192 x 256 tiles (row-major A) where THEY fill their rounds and the 256-row tiles do not: 6144 x 4096 is 384
-            // tiles of 256 rows (1.5 rounds: the makespan of two) but 512 of 192 rows (two whole rounds of 3/4 the height)
-            const long long t192 = (long long)cdiv(g.M, 192) * cdiv(g.N, 256);
-            // (round 5, HISTORY.md; us: 6144 x 4096 x 4608 199 vs 211-263 on 128-row tiles, x 4096 180 vs 190, the dX form 185 vs
-            //  190, 6144 x 4096 x 1024 63.3 vs 66.7; 6144 x 1024 outputs are 128 such tiles and stay on 96-row tiles)
-            if (variant != 7 && !d->transA && g.splitk == 1 && !g.dbias && g.M % 192 == 0 && g.N % 256 == 0 && t192 >= 192 && K >= 1024 &&
-                10 * t192 >= 9 * 256 * ((t192 + 255) / 256))
-                variant = 15;
-        } else if ((variant == 8 || variant == 11 || variant == 12 || variant == 16) &&
-                   (d->transA || (variant == 16 && g.splitk > 1))) {
-            variant = 3;  // the forced variants exist for row-major A only (16: unsplit)
-        } else if (variant == 7 && (g.dbias || g.M % 256 != 0 || g.N % 256 != 0)) {
-            variant = 3;  // whole 256 x 256 tiles only, no fused bias gradient
-        } else if (variant == 15 && (d->transA || g.dbias || g.M % 192 != 0 || g.N % 256 != 0)) {
-            variant = 3;  // whole 192 x 256 tiles of a row-major A only
-        }
-        if (variant != 3 && variant != 5 && variant != 7 && variant != 8 && variant != 11 && variant != 12 && variant != 15 && variant != 16)
-            variant = 3;  // (a forced value that names no tile variant: the 2-stage 128 x 128 kernel)
-        if (variant == 12 && d->st_mode) variant = 11;  // (forced by the knob: the epilogue statistics win)
-        g.tiles_m = variant == 8 ? cdiv(g.M, 96) : (variant == 11 || variant == 12) ? cdiv(g.M, 64) : variant == 7 ? cdiv(g.M, 256)
-                    : (variant == 15 || variant == 16) ? cdiv(g.M, 192) : cdiv(g.M, BM);
-        if (variant == 7 || variant == 15) g.tiles_n = cdiv(g.N, 256);
 #ifdef EGK_GEMM_STAMPS
-        if (variant != 7 && !g.dbias && d->ws) {
+        if (pipe_ok && c.variant != policy::V_T256 && !g.dbias && d->ws) {
             const int64_t slab = g.splitk > 1 ? (int64_t)g.splitk * d->M * d->N * 4 : 0;
             if (d->ws_bytes >= slab + (int64_t)g.tiles_m * g.tiles_n * g.splitk * 128) g.ws_bias = (float*)((char*)d->ws + slab);
         }
-        if (variant == 7 && g.splitk == 1 && !g.dbias && d->ws && d->ws_bytes >= (int64_t)g.tiles_m * g.tiles_n * 8 * 64)
+        if (pipe_ok && c.variant == policy::V_T256 && g.splitk == 1 && !g.dbias && d->ws && d->ws_bytes >= (int64_t)g.tiles_m * g.tiles_n * 8 * 64)
             g.ws_bias = (float*)d->ws;  // per-wave cycle stamps land in the caller's workspace
 #endif
-        {  // near-square XCD patches: group_m ~ sqrt(workgroups per XCD), inside one slab
-            const int tiles = g.tiles_m * g.tiles_n;
-            int per_xcd = cdiv(tiles * g.splitk, 8);
-            if (per_xcd > tiles) per_xcd = tiles;
-            int gm = 1;
-            while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
-            g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
-            // Row-major A (forward / dX forms: the output rows ARE the rows of the chain's activations): XCD x takes the tile rows
-            // [x * tiles_m / 8, (x + 1) * tiles_m / 8) with ALL their tile columns -- the contiguous eighth of the rows that the row
-            // kernels in front of and behind this launch give to XCD x (common.h, row_walk): its A strips were written, and its output
-            // rows will be read, by workgroups of the SAME XCD, i.e. through that XCD's own L2 instead of across the fabric
-            // (tools/exp/xcd_affinity.hip: 4.0-4.4 us against 8.3-11.2 us for a 12.6 MB hand-off).  Every XCD then streams the whole
-            // B operand (weights: 2-9 MB, shared by its 32 workgroups K tile by K tile).
-            if (!d->transA && g.splitk == 1 && g.tiles_m % 8 == 0) g.group_m = g.tiles_m / 8;
-        }
-
-        // segment statistics in the epilogue: the 4-wave variants that write their tile out through LDS in whole rows, unsplit,
-        // and tiles that span at most two row segments
-        const int tile_rows = variant == 8 ? 96 : (variant == 11 || variant == 12) ? 64 : variant == 16 ? 192 : 128;
-        const bool st_ok = (variant == 3 || variant == 8 || variant == 11 || variant == 16) && g.splitk == 1 &&
-                           epilogue_rows_ok(g) && d->st_min_seg_rows >= tile_rows &&
-                           (d->st_mode != 2 || (aligned16(d->st_x) && d->st_ldx % (g.c_bf16 ? 8 : 4) == 0 && aligned16(d->st_w) && aligned16(d->st_b)));
-        if (query_blocks) {
-            *query_blocks = (d->st_mode && st_ok) ? g.tiles_m * g.tiles_n : 0;
-            return 0;
-        }
-        if (d->st_mode && !st_ok) {
-            set_error("egk_gemm: st_mode %d is not available for this launch (ask egk_gemm_stats_blocks first)", d->st_mode);
+        int rc;
+        const policy::Shape shape = policy::shape(c.variant);
+        if (stats_epilogue_gate(d, g, pipe32_ok || shape.stats, shape.rows, (pipe_ok && g.c_bf16) ? 8 : 4, query_blocks, &rc)) return rc;
+    } else {
+        if (query_blocks) return 0;  // (the generic kernel has no statistics epilogue: 0 blocks, not ok)
+        if (d->st_mode) {
+            set_error("egk_gemm: st_mode %d is not available on the generic kernel (ask egk_gemm_stats_blocks first)", d->st_mode);
             return EGK_EUNSUPPORTED;
         }
-        dim3 pgrid(g.tiles_m * g.tiles_n * g.splitk);
-#define EGK_PIPE(TA, TB)                                                                                                  \
-    do {                                                                                                                  \
-        if (variant == 16 && g_r192_loaders && nkt_slab >= 4) {                                                           \
-            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, g, 3, false, TB, 1, 2, 3, false, 4); \
-        } else if (variant == 16) {                                                                                       \
-            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS), 3 * 40960, s, g, 3, false, TB, 1, 2, 3);    \
-        } else if (variant == 15) {                                                                                       \
-            hipLaunchKernelGGL((gemm_big_kernel<false, TB, 8, 6>), pgrid, dim3(512), 131072, s, g);                       \
-        } else if (variant == 7) {                                                                                        \
-            hipLaunchKernelGGL((gemm_big_kernel<TA, TB>), pgrid, dim3(512), 131072, s, g);                                \
-        } else if (variant == 12) {                                                                                       \
-            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS), 4 * 24576, s, g, 2, false, TB, 2, 1, 2);    \
-        } else if (variant == 11) {                                                                                       \
-            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, pblock, 2 * 24576, s, g, 2, false, TB, 1, 1, 2);                \
-        } else if (variant == 8) {                                                                                        \
-            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, pblock, 2 * 28672, s, g, 2, false, TB, 1, 1, 3);                \
-        } else if (variant == 5)                                                                                          \
-            EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, dim3(2 * NTHREADS), 4 * 32768, s, g, 2, TA, TB, 2, 1);          \
-        else EGK_LAUNCH_E(gemm_pipe_kernel, pgrid, pblock, 2 * 32768, s, g, 2, TA, TB, 1, 1);                     \
-    } while (0)
-        {
-            ProfScope prof((variant == 7 || variant == 15) ? KID_GEMM_BF16_NN_T256 + layout : variant == 8 ? KID_GEMM_BF16_NN_R96 + layout : variant == 11 ? KID_GEMM_BF16_NN_R64 + layout
-                                       : variant == 16 ? KID_GEMM_BF16_NN_R192 + layout
-                                       : ((variant == 5 || variant == 12) ? KID_GEMM_BF16_NN_G2 : KID_GEMM_BF16_NN) + layout, s, flops, bytes);
-            if (!d->transA && !d->transB) EGK_PIPE(false, false);
-            else if (!d->transA && d->transB) EGK_PIPE(false, true);
-            else if (d->transA && d->transB) EGK_PIPE(true, true);
-            else EGK_PIPE(true, false);
-        }
-#undef EGK_PIPE
-        const bool defer = take_defer_reduce();
-        if (defer)
-            EGK_REQUIRE(g.splitk > 1 && !g.accumulate && g.act == 0 && !g.residual && g.alpha == 1.f && !g.c_bf16 && !g.dbias,
-                        "egk_gemm_defer_reduce_next: a split launch with a plain f32 result (bias only)");
-        if (g.splitk > 1 && !defer) {
-            ProfScope prof(KID_GEMM_SPLITK_REDUCE, s, 0, slab_bytes);
-            const long long total = (long long)g.M * g.N;
-            const long long work = (total + 3) / 4;  // element groups of 4 (the vector path; the scalar path strides)
-            hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048)),
-                               dim3(256), 0, s, g);
-        }
-        return check_launch("egk_gemm");
     }
-    // exact-f32 pipelined kernel: f32 operands, 16-byte aligned rows, every K source a multiple of 32
-    if (pipe32_ok) {
-        ensure_lds_attr();
-        // 96-row tiles (row-major A) when they load the CUs more evenly: the matrix pipes of a CU are shared by its co-resident
-        // workgroups, so a launch lasts as long as the ROWS on its fullest CU
-        bool r96 = false;
-        if (!d->transA && g_use_pipe != 3) {
-            const long long t128 = (long long)cdiv(g.M, 128) * g.tiles_n * g.splitk, t96 = (long long)cdiv(g.M, 96) * g.tiles_n * g.splitk;
-            r96 = g_use_pipe == 8 || ((t96 + 255) / 256) * 96 < ((t128 + 255) / 256) * 128;
-        }
-        if (r96) g.tiles_m = cdiv(g.M, 96);
-        {  // near-square XCD patches, as for the bf16 kernel
-            const int tiles = g.tiles_m * g.tiles_n;
-            int per_xcd = cdiv(tiles * g.splitk, 8);
-            if (per_xcd > tiles) per_xcd = tiles;
-            int gm = 1;
-            while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
-            g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
-            if (!d->transA && g.splitk == 1 && g.tiles_m % 8 == 0) g.group_m = g.tiles_m / 8;  // (as for the bf16 kernel)
-        }
-        const bool st_ok = g.splitk == 1 && epilogue_rows_ok(g) && d->st_min_seg_rows >= (r96 ? 96 : 128) &&
-                           (d->st_mode != 2 || (aligned16(d->st_x) && d->st_ldx % 4 == 0 && aligned16(d->st_w) && aligned16(d->st_b)));
-        if (query_blocks) {
-            *query_blocks = (d->st_mode && st_ok) ? g.tiles_m * g.tiles_n : 0;
-            return 0;
-        }
-        if (d->st_mode && !st_ok) {
-            set_error("egk_gemm: st_mode %d is not available for this launch (ask egk_gemm_stats_blocks first)", d->st_mode);
-            return EGK_EUNSUPPORTED;
-        }
-        const dim3 pgrid(g.tiles_m * g.tiles_n * g.splitk), pblock(NTHREADS);
-        {
-            ProfScope prof(KID_GEMM_F32_NN + layout, s, flops, bytes);
-            if (r96 && !d->transB) hipLaunchKernelGGL((gemm_pipe_f32_kernel<false, false, 3>), pgrid, pblock, 2 * 28672, s, g);
-            else if (r96) hipLaunchKernelGGL((gemm_pipe_f32_kernel<false, true, 3>), pgrid, pblock, 2 * 28672, s, g);
-            else if (!d->transA && !d->transB) hipLaunchKernelGGL((gemm_pipe_f32_kernel<false, false>), pgrid, pblock, 65536, s, g);
-            else if (!d->transA && d->transB) hipLaunchKernelGGL((gemm_pipe_f32_kernel<false, true>), pgrid, pblock, 65536, s, g);
-            else if (d->transA && d->transB) hipLaunchKernelGGL((gemm_pipe_f32_kernel<true, true>), pgrid, pblock, 65536, s, g);
-            else hipLaunchKernelGGL((gemm_pipe_f32_kernel<true, false>), pgrid, pblock, 65536, s, g);
-        }
-        EGK_REQUIRE(!take_defer_reduce(), "egk_gemm_defer_reduce_next: only the bf16-operand pipelined launches leave their slabs");
-        if (g.splitk > 1) {
-            ProfScope prof(KID_GEMM_SPLITK_REDUCE, s, 0, slab_bytes);
-            const long long total = (long long)g.M * g.N;
-            const long long work = (total + 3) / 4;
-            hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048)),
-                               dim3(256), 0, s, g);
-        }
-        return check_launch("egk_gemm");
-    }
-    if (query_blocks) return 0;  // (the generic kernel has no statistics epilogue: 0 blocks, not ok)
-    if (d->st_mode) {
-        set_error("egk_gemm: st_mode %d is not available on the generic kernel (ask egk_gemm_stats_blocks first)", d->st_mode);
-        return EGK_EUNSUPPORTED;
-    }
-    dim3 grid(g.tiles_m * g.tiles_n, g.splitk);
+    const LaunchRow* row = find_row(family, c.variant, layout, flavour);
+    EGK_REQUIRE(row != nullptr, "egk_gemm: tile variant %d is not instantiated for this layout", c.variant);
     {
-        ProfScope prof(bf ? KID_GEMM_BF16_GENERIC : KID_GEMM_F32_NN + layout, s, flops, bytes);
-        if (!bf) launch_layout<false, float, float>(d, grid, s, g);
-        else if (a16) launch_layout<true, bf16_t, bf16_t>(d, grid, s, g);
-        else launch_layout<true, float, float>(d, grid, s, g);
+        ProfScope prof(prof_id, s, flops, bytes);
+        launch_row(*row, pipelined ? dim3(g.tiles_m * g.tiles_n * g.splitk) : dim3(g.tiles_m * g.tiles_n, g.splitk), s, g);
     }
-    EGK_REQUIRE(!take_defer_reduce(), "egk_gemm_defer_reduce_next: only the bf16-operand pipelined launches leave their slabs");
-    if (g.splitk > 1) {
-        ProfScope prof(KID_GEMM_SPLITK_REDUCE, s, 0, slab_bytes);
+    const bool defer = take_defer_reduce();
+    EGK_REQUIRE(!defer || pipe_ok, "egk_gemm_defer_reduce_next: only the bf16-operand pipelined launches leave their slabs");
+    if (defer)
+        EGK_REQUIRE(g.splitk > 1 && !g.accumulate && g.act == 0 && !g.residual && g.alpha == 1.f && !g.c_bf16 && !g.dbias,
+                    "egk_gemm_defer_reduce_next: a split launch with a plain f32 result (bias only)");
+    if (g.splitk > 1 && !defer) {
         const long long total = (long long)g.M * g.N;
-        hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)),
-                           dim3(256), 0, s, g);
+        launch_splitk_reduce(g, pipelined ? (total + 3) / 4 : total, slab_bytes, s);
     }
     return check_launch("egk_gemm");
 }
@@ -2718,10 +2557,7 @@ extern "C" int egk_gemm_reduce_slabs(egk_stream_t stream, const float* ws, int32
     g.bias = bias;
     g.splitk = splitk;
     g.ws = const_cast<float*>(ws);
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_GEMM_SPLITK_REDUCE, s, 0, 4.0 * (splitk + 1) * M * N);
-    const long long work = ((long long)M * N + 3) / 4;
-    hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048)), dim3(256), 0, s, g);
+    launch_splitk_reduce(g, ((long long)M * N + 3) / 4, 4.0 * (splitk + 1) * M * N, (hipStream_t)stream);
     return check_launch("egk_gemm_reduce_slabs");
 }
 
@@ -2748,24 +2584,9 @@ static int fill_group_args(const egk_gemm_desc* d, GemmArgs& g) {
         EGK_REQUIRE(src.all_k64, "egk_gemm_grouped: K sources must be multiples of 64");
     }
     EGK_REQUIRE(src.all_vec, "egk_gemm_grouped: operand rows must be 16-byte aligned");
-    g.C = d->C; g.ldc = d->ldc;
-    g.c_bf16 = d->c_dtype == EGK_BF16;
-    g.c_vec = g.c_bf16 ? ((reinterpret_cast<uintptr_t>(g.C) & 7) == 0 && g.ldc % 4 == 0) : (aligned16(g.C) && g.ldc % 4 == 0);
-    g.accumulate = d->accumulate; g.act = d->act; g.alpha = d->alpha;
-    g.bias = d->bias; g.residual = d->residual; g.ldr = d->ldr;
-    g.r_bf16 = d->r_dtype == EGK_BF16;
-    g.r_vec = g.residual && (g.r_bf16 ? ((reinterpret_cast<uintptr_t>(g.residual) & 7) == 0 && g.ldr % 4 == 0)
-                                      : (aligned16(g.residual) && g.ldr % 4 == 0));
-    g.splitk = 1;
-    g.ws = nullptr;
-    g.dbias = d->dbias; g.ws_bias = nullptr;
-    g.rows_epilogue = 1;
-    g.st_mode = 0; g.st_nseg = 0; g.st_seg_ptr = nullptr; g.st_ws = nullptr; g.st_x = nullptr; g.st_ldx = 0;
-    g.st_stats = nullptr; g.st_w = nullptr; g.st_b = nullptr; g.st_slope = 0.f;
     EGK_REQUIRE(d->st_mode == 0, "egk_gemm_grouped: no segment statistics in a grouped launch");
-    g.epi = g_rows_fast && epilogue_rows_ok(g);
-    g.nkt = 0;
-    for (int i = 0; i < g.nsrc; ++i) g.nkt += (g.K[i] + 63) / 64;
+    fill_output(d, g, 1, nullptr);
+    g.dbias = d->dbias;
     return 0;
 }
 
@@ -2779,7 +2600,7 @@ extern "C" int egk_gemm_grouped(egk_stream_t stream, const egk_gemm_desc* descs,
     const bool f16 = descs[0].op_f16 != 0;
     EGK_REQUIRE(!f16 || (!ta && !tb && !f32g), "egk_gemm_grouped: op_f16 takes row-major 16-bit operands");
     double flops = 0, bytes = 0;
-    long long t128 = 0, t96 = 0, t64 = 0, t256 = 0, t192 = 0;
+    int Ms[MAX_GROUPS], Ns[MAX_GROUPS];
     int min_nkt = 1 << 30, any_extra = 0;
     for (int i = 0; i < count; ++i) {
         const egk_gemm_desc* d = descs + i;
@@ -2793,87 +2614,21 @@ extern "C" int egk_gemm_grouped(egk_stream_t stream, const egk_gemm_desc* descs,
         for (int x = 0; x < d->n_extra; ++x) K += d->xK[x];
         flops += 2.0 * d->M * d->N * K;
         bytes += 2.0 * ((double)d->M * K + (double)d->N * K) + (gg.p[i].c_bf16 ? 2.0 : 4.0) * d->M * d->N;
-        const int tn = cdiv(d->N, BN);
-        t128 += (long long)cdiv(d->M, 128) * tn; t96 += (long long)cdiv(d->M, 96) * tn; t64 += (long long)cdiv(d->M, 64) * tn;
-        t256 += (long long)cdiv(d->M, 256) * tn;
-        t192 += (long long)cdiv(d->M, 192) * tn;
+        Ms[i] = d->M; Ns[i] = d->N;
         any_extra |= d->n_extra > 0;
         min_nkt = K / 64 < min_nkt ? K / 64 : min_nkt;
     }
     ensure_lds_attr();
-    if (f32g) {  // exact-f32 problems: 128 x 128 tiles, XCD-packed placement
-        int total = 0;
-        for (int i = 0; i < count; ++i) {
-            GemmArgs& g = gg.p[i];
-            g.tiles_m = cdiv(g.M, BM);
-            g.tiles_n = cdiv(g.N, BN);
-            total += g.tiles_m * g.tiles_n;
-        }
-        for (int i = 0; i < count; ++i) {
-            GemmArgs& g = gg.p[i];
-            const int tiles = g.tiles_m * g.tiles_n;
-            int per_xcd = cdiv(total, 8), gm = 1;
-            if (per_xcd > tiles) per_xcd = tiles;
-            while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
-            g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
-        }
-        for (int i = count; i < MAX_GROUPS; ++i) gg.p[i] = gg.p[0];
-        gg.packed = 1; gg.count = count; gg.total = total;
-    for (int i = 0, t = 0; i < MAX_GROUPS; ++i) {
-        gg.start[i] = i < count ? t : total;
-        t += gg.p[i].tiles_m * gg.p[i].tiles_n;
-    }
-        const dim3 pgrid((total + 7) / 8 * 8), pblock(NTHREADS);
-        const int layout = ta ? (tb ? 2 : 3) : (tb ? 1 : 0);
-        EGK_REQUIRE(!(ta && !tb), "egk_gemm_grouped: the tn layout is not instantiated");
-        ProfScope prof(KID_GEMM_F32_NN + layout, s, flops, 2.0 * bytes);  // (bytes above count 2 per operand element)
-        if (!ta && !tb) hipLaunchKernelGGL((gemm_pipe_f32_group_kernel<false, false>), pgrid, pblock, 65536, s, gg);
-        else if (!ta) hipLaunchKernelGGL((gemm_pipe_f32_group_kernel<false, true>), pgrid, pblock, 65536, s, gg);
-        else hipLaunchKernelGGL((gemm_pipe_f32_group_kernel<true, true>), pgrid, pblock, 65536, s, gg);
-        return check_launch("egk_gemm_grouped");
-    }
-    // one tile variant for the whole launch, by the policy of egk_gemm applied to the TOTAL tile count
-    int variant = t128 > 256 ? 3 : (min_nkt >= 4 ? 5 : 3);
-    if (!ta) {
-        if (t128 > 256) {
-            if (((t96 + 255) / 256) * 28 < ((t128 + 255) / 256) * 32) variant = 8;
-        } else if (t64 <= 256 && t64 > t128) {
-            variant = 11;
-        }
-    }
-    // weight-gradient groups (A^T B): a CU works on one 128 x 128 workgroup at a time (272 registers per lane), so a launch of 257 ..
-    // 512 tiles takes two rounds whatever its tile count; when that count leaves many CUs idle in the second round (the pooling's
-    // three weight gradients: 416 tiles) and the 256 x 128 tiling fits one workgroup per CU, the tall tile (8 waves, 3-stage ring,
-    // 48 KiB per K tile for twice the flops) is one round instead.  Long K walks only: same box, alternating, 6144 rows 1.291 -> 1.284 ms, 16384 rows
-    // 2.947 -> 2.934, 2048 rows 0.842 -> 0.863 (its 3-stage fill and 256-row epilogue outweigh 32 K tiles).
-    if (ta && tb && g_tt_tall && t128 > 256 && t128 <= 448 && t256 <= 256 && min_nkt >= 64) variant = 13;
-    // row-major A: the 192 x 128 tile with loader waves (egk_gemm's variant 16) when the group is ONE round of such tiles that more
-    // than half fills the chip and 128- / 96-row tiles would take more than one (the projection heads of three task batches:
-    // 64 + 2048 + 2048 rows = 184 tiles against 264 / 360)
-    // (not for the three-product groups of the precise pass: BASELINE config 4 2.113 -> 2.124 ms with them)
-    if (!ta && !f16 && !any_extra && g_r192_loaders && t192 > 128 && t192 <= 256 && t128 > 256 && min_nkt >= 8) variant = 16;
-    if (g_use_pipe == 3 || g_use_pipe == 5) variant = g_use_pipe;
-    if (g_use_pipe == 13 && ta && tb) variant = 13;
-    if ((g_use_pipe == 8 || g_use_pipe == 11) && !ta) variant = g_use_pipe;
-    if (f16) variant = 3;  // (one instantiation: 128 x 128 tiles, one wave group)
-    int total = 0;
+    // one tile variant for the whole launch (gemm_policy.h), then the group's finish: tiles and XCD patches of every problem, padding
+    // problems, the start table
+    const int layout = policy::layout_of(ta, tb);
+    const policy::GroupChoice c = policy::pick_group(Ms, Ns, count, layout, min_nkt, any_extra != 0, f16, f32g, policy_knobs());
     for (int i = 0; i < count; ++i) {
-        GemmArgs& g = gg.p[i];
-        g.tiles_m = variant == 8 ? cdiv(g.M, 96) : variant == 11 ? cdiv(g.M, 64) : variant == 13 ? cdiv(g.M, 256) : variant == 16 ? cdiv(g.M, 192) : cdiv(g.M, BM);
-        g.tiles_n = cdiv(g.N, BN);
-        total += g.tiles_m * g.tiles_n;
+        gg.p[i].tiles_m = c.tiles_m[i]; gg.p[i].tiles_n = c.tiles_n[i]; gg.p[i].group_m = c.group_m[i];
     }
-    for (int i = 0; i < count; ++i) {
-        GemmArgs& g = gg.p[i];
-        const int tiles = g.tiles_m * g.tiles_n;
-        // near-square patches of what ONE XCD works on: its share of the whole launch
-        int per_xcd = cdiv(total, 8), gm = 1;
-        if (per_xcd > tiles) per_xcd = tiles;
-        while ((gm + 1) * (gm + 1) <= per_xcd) ++gm;
-        g.group_m = gm < g.tiles_m ? gm : g.tiles_m;
-    }
+    const int total = c.total;
 #ifdef EGK_GEMM_STAMPS
-    if (descs[0].ws && descs[0].ws_bytes >= (int64_t)total * 128) {  // 128 bytes of stamps per workgroup, problem after problem
+    if (!f32g && descs[0].ws && descs[0].ws_bytes >= (int64_t)total * 128) {  // 128 bytes of stamps per workgroup, problem after problem
         int64_t off = 0;
         for (int i = 0; i < count; ++i) {
             if (!gg.p[i].dbias) gg.p[i].ws_bias = (float*)((char*)descs[0].ws + off);
@@ -2887,34 +2642,11 @@ extern "C" int egk_gemm_grouped(egk_stream_t stream, const egk_gemm_desc* descs,
         gg.start[i] = i < count ? t : total;
         t += gg.p[i].tiles_m * gg.p[i].tiles_n;
     }
-    const dim3 pgrid((total + 7) / 8 * 8);
-    const dim3 pblock(NTHREADS);
-    const int layout = ta ? (tb ? 2 : 3) : (tb ? 1 : 0);
-    EGK_REQUIRE(!(ta && !tb), "egk_gemm_grouped: the tn layout is not instantiated");
-#define EGK_PIPE_G(TA, TB)                                                                                                  \
-    do {                                                                                                                    \
-        if (variant == 5) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS), 4 * 32768, s, gg, 2, TA, TB, 2, 1); \
-        else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 32768, s, gg, 2, TA, TB, 1, 1);                \
-    } while (0)
-    {
-        ProfScope prof(KID_GEMM_BF16_GROUP_NN + layout, s, flops, bytes);  // (layout 0 nn, 1 nt, 2 tt; the tall weight-gradient tile included)
-        if (f16) {
-            ensure_lds_attr();
-            EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 32768, s, gg, 2, false, false, 1, 1, 4, true);
-        } else if (!ta && variant == 16) {
-            if (!tb) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, gg, 3, false, false, 1, 2, 3, false, 4);
-            else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS + 256), 3 * 40960, s, gg, 3, false, true, 1, 2, 3, false, 4);
-        } else if (!ta && variant == 11) {
-            if (!tb) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 24576, s, gg, 2, false, false, 1, 1, 2);
-            else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 24576, s, gg, 2, false, true, 1, 1, 2);
-        } else if (!ta && variant == 8) {
-            if (!tb) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 28672, s, gg, 2, false, false, 1, 1, 3);
-            else EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, pblock, 2 * 28672, s, gg, 2, false, true, 1, 1, 3);
-        } else if (!ta && !tb) EGK_PIPE_G(false, false);
-        else if (!ta && tb) EGK_PIPE_G(false, true);
-        else if (variant == 13) EGK_LAUNCH_E(gemm_pipe_group_kernel, pgrid, dim3(2 * NTHREADS), 3 * 49152, s, gg, 3, true, true, 1, 2);
-        else EGK_PIPE_G(true, true);
-    }
-#undef EGK_PIPE_G
+    const LaunchRow* row = find_row(f32g ? policy::F32_GROUP : policy::GROUP, c.variant, layout,
+                                    f16 ? policy::F16 : c.loaders ? policy::LOADERS : policy::PLAIN);
+    EGK_REQUIRE(row != nullptr, "egk_gemm_grouped: the tn layout is not instantiated");
+    // (profile ids: layout 0 nn, 1 nt, 2 tt; the tall weight-gradient tile included.  ``bytes`` counts 2 per operand element)
+    ProfScope prof(f32g ? KID_GEMM_F32_NN + layout : KID_GEMM_BF16_GROUP_NN + layout, s, flops, f32g ? 2.0 * bytes : bytes);
+    launch_row(*row, dim3((total + 7) / 8 * 8), s, gg);
     return check_launch("egk_gemm_grouped");
 }

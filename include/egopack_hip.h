@@ -306,13 +306,26 @@ int egk_gemm_grouped(egk_stream_t s, const egk_gemm_desc* descs, int32_t count);
 int egk_gemm_splitk(int32_t M, int32_t N, int32_t K, int32_t compute);
 /* development knob of the row kernels (launch geometry only, results unchanged): returns the previous value */
 int egk_tune(int32_t key, int32_t value);
-/* development knob for A/B measurements in one process (results unchanged up to the summation order of variant 5):
- * 0 routes every contraction through the generic register-staged kernel; 1 (default) lets eligible ones (bf16
- * operands, 16-byte aligned rows, K % 64 == 0) use the LDS-DMA pipelined kernels, variant chosen per launch; a value
- * 2..11 forces one variant where it is legal (2 / 3 / 4: 3- / 2- / 4-stage ring on 128 x 128 tiles, 5: two wave groups,
- * 6: 256 x 128 tile, 7: 256 x 256 tile, 8 / 11: 96- / 64-row tiles); 100 + g overrides the XCD tile-group height
- * (100 = policy); 200 / 201 selects the direct / row-contiguous (default) epilogue of the 4-wave variants; 300 / 301 the
- * spread / XCD-packed (default) workgroup placement of grouped launches.  Returns the previous variant setting. */
+/* development knob for A/B measurements in one process and the tests' forced variants (results unchanged up to the summation
+ * order of the two-wave-group variants 5 and 12).  Accepted codes:
+ *   0 .. 19   the variant setting; returns the previous one.
+ *             0  every contraction runs on the generic register-staged kernel;
+ *             1  (default) eligible ones (bf16 operands, 16-byte aligned rows, every K source a multiple of 64; f32 operands
+ *                with K sources multiples of 32) run on the LDS-DMA pipelined kernels, tile variant chosen per launch;
+ *             a tile variant, forced where it is legal, else 128 x 128 tiles:
+ *             3  128 x 128, one wave group;  5  128 x 128, two wave groups;
+ *             7  256 x 256 (whole tiles, no fused bias gradient);  8 / 11  96- / 64-row tiles (row-major A);
+ *             12  64-row tiles with two wave groups (row-major A; 11 when the launch carries segment statistics);
+ *             15  192 x 256 (whole tiles, row-major A, no fused bias gradient);  16  192 x 128 (row-major A, no split-K);
+ *             13  256 x 128 for grouped launches of the tt layout (single launches: 128 x 128).
+ *             Grouped launches follow 3, 5, 8, 11 and 13 only.  Exact-f32 launches follow 3 (128-row tiles) and 8 (96-row tiles).
+ *             Every other value in 2 .. 19 names no variant: 128 x 128 tiles for single launches, the policy for grouped ones.
+ *   850 / 851 the 256 x 128 tile (13) in the policy of tt groups off / on (default);   returns the variant setting.
+ *   870 / 871 the loader waves of the 192 x 128 tile (16) off / on (default; off, the policy of grouped launches does not pick
+ *             the tile at all);   returns the variant setting.
+ *   880 / 881 entry of the bf16 pipelined kernels: field by field / one descriptor batch (default), same bits;   returns 0.
+ *   890 / 891 store loop of the rows epilogue: branch ladder / descriptor-once (default), same bits;   returns the variant setting.
+ * Any other code changes nothing and returns -1. */
 int egk_gemm_set_pipeline(int32_t on);
 
 /* out[n] (+)= sum_m x[m, n] : bias gradients of every Linear above.  Two launches (row-chunk
