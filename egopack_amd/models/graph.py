@@ -42,6 +42,10 @@ class Graph(torch.nn.Module):
         self.temporal_pooling = (_instantiate(temporal_pooling, input_size, hidden_size, num_segments)
                                  if temporal_pooling else None)
         self.positional_encoding = PositionalEncoding(hidden_size)
+        # DropEdge of the SAGE means (ops.EdgeDrop or None): plain attributes set by the training entry point after
+        # construction -- no constructor argument and no state-dict entry, so checkpoints keep the reference's layout.
+        # ``edge_drop_per_layer`` False: one mask per forward pass, shared by all layers.
+        self.edge_drop, self.edge_drop_per_layer = None, True
         if depth > 0:
             self.net = nn.Module()  # children named as PyG's gnn.Sequential names them
             for d in range(depth):
@@ -103,13 +107,17 @@ class Graph(torch.nn.Module):
         # the two gradients of x in a pass of its own, the final Linear hands the residual's gradient to the FIRST SAGE layer,
         # which adds it in the epilogue of its dX contraction (both are gradients of the same [N, H] tensor)
         res = {} if (self.depth > 0 and x.requires_grad and h.dtype == x.dtype) else None
+        drop = self.edge_drop if (self.training and self.edge_drop and torch.is_grad_enabled()) else None
+        if drop is not None and not self.edge_drop_per_layer:
+            drop = drop.with_rng(ops.edge_drop_rng(x.shape[0]))  # one (seed, offset) for every layer of this pass
         for d in range(self.depth):
             conv = getattr(self.net, f"module_{3 * d}")
             norm = getattr(self.net, f"module_{3 * d + 1}")
             slope = getattr(self.net, f"module_{3 * d + 2}").negative_slope
             req = ({"seg_ptr": seg_ptr, "n_seg": n_seg, "min_rows": min_rows}
                    if min_rows > 0 and not ops.graph_ln_exchange_on() else None)
-            c = ops.sage_mean_layer(h, conv, graph, ln_out=req, ln_in=ln_prev, res_src=res if d == 0 else None)
+            c = ops.sage_mean_layer(h, conv, graph, ln_out=req, ln_in=ln_prev, res_src=res if d == 0 else None,
+                                    drop=drop)
             h, ln_prev = norm(c, seg_ptr, slope, partials=req.get("partials") if req else None, min_seg_rows=min_rows,
                               return_ctx=True)                # SAGEConv -> graph-LN -> LeakyReLU
             ops.stamp("fwd_sage", seq=True)

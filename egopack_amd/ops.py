@@ -1719,7 +1719,8 @@ class tap_dropout_masks:
     active dropout can be compared element by element.  ``tap.launches`` (``tap = ops.tap_dropout_masks()``; ``with tap as
     masks:``) records what every dropout launch issued inside was given, one tuple per launch in issue order:
     ``("rows", seed, host offset, rows, cols)`` for a fused LayerNorm + dropout launch (``launches`` filtered by ``"rows"`` lines up
-    with ``masks``), ``("flat", seed, host offset, 1, n)`` for a ``dropout`` launch.  Read-only: nothing reads it back."""
+    with ``masks``), ``("flat", seed, host offset, 1, n)`` for a ``dropout`` launch, ``("edge", seed, host offset, rows, E)`` for
+    the forward launch of an ``EdgeDrop`` (E = edges of the graph).  Read-only: nothing reads it back."""
 
     def __enter__(self):
         self.prev = (_mask_tap["on"], _mask_tap["masks"], _mask_tap["launches"])
@@ -2010,6 +2011,115 @@ def _csr_gather(x, rowptr, col, wgt, gate, out, heavy=None, heavy_mode=0, band=N
 
 
 
+class EdgeDrop:
+    """DropEdge (Rong et al. 2020) of a mean aggregation: every edge is kept with probability 1 - p, seeded (include/
+    egopack_edge_drop.h).  ``symmetric``: i -> j and j -> i share one decision; ``keep_self``: an edge i -> i is
+    always kept.  ``rng`` = a pre-drawn ``(seed, offset)`` (``ops.edge_drop_rng(rows)``): several launches then share ONE mask --
+    without it every forward launch draws its own.  A value: nothing of it is trained or saved."""
+    __slots__ = ("p", "symmetric", "keep_self", "rng")
+
+    def __init__(self, p: float, symmetric: bool = True, keep_self: bool = True, rng=None):
+        p = float(p)
+        if not 0.0 <= p <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"EdgeDrop: p must lie in [0, 1], got {p}")
+        self.p, self.symmetric, self.keep_self = p, bool(symmetric), bool(keep_self)
+        self.rng = None if rng is None else (int(rng[0]), int(rng[1]))
+
+    def __bool__(self):
+        return self.p > 0.0
+
+    def __repr__(self):
+        return f"EdgeDrop(p={self.p}, symmetric={self.symmetric}, keep_self={self.keep_self}" + (f", rng={self.rng})" if self.rng else ")")
+
+    @property
+    def flags(self) -> int:
+        return (_lib.EDGE_DROP_SYMMETRIC if self.symmetric else 0) | (_lib.EDGE_DROP_KEEP_SELF if self.keep_self else 0)
+
+    def with_rng(self, rng) -> "EdgeDrop":
+        return EdgeDrop(self.p, self.symmetric, self.keep_self, rng)
+
+
+def edge_drop_rng(rows: int):
+    """``(seed, offset)`` of one edge-drop launch over ``rows`` nodes: rows + 64 counters of the dropout streams are reserved."""
+    return _next_rng(4 * int(rows))
+
+
+def _active_drop(drop) -> Optional["EdgeDrop"]:
+    """``drop`` where it applies: given, p > 0, and in training use (gradients enabled); None otherwise -- today's code path."""
+    if drop is None or not drop or not torch.is_grad_enabled():
+        return None
+    if not isinstance(drop, EdgeDrop):
+        raise TypeError(f"drop must be an ops.EdgeDrop, got {type(drop).__name__}")
+    return drop
+
+
+_edge_keep_tap = {"on": False, "fwd": [], "bwd": []}
+
+
+class tap_edge_keep:
+    """``with ops.tap_edge_keep() as tap:`` -- test only: every edge-drop launch issued inside also writes its keep bits (uint8 [E],
+    1 = kept); ``tap.fwd`` holds those of the forward launches in the order of ``graph.col``, ``tap.bwd`` those of the backward
+    launches in the order of ``graph.t_col``, both in issue order."""
+
+    def __enter__(self):
+        self.prev = dict(_edge_keep_tap)
+        _edge_keep_tap.update(on=True, fwd=[], bwd=[])
+        self.fwd, self.bwd = _edge_keep_tap["fwd"], _edge_keep_tap["bwd"]
+        return self
+
+    def __exit__(self, *a):
+        _edge_keep_tap.update(self.prev)
+
+
+def _edge_keep_buffer(which: str, col: torch.Tensor):
+    if not _edge_keep_tap["on"]:
+        return None
+    keep = torch.empty(col.numel(), dtype=torch.uint8, device=col.device)
+    _edge_keep_tap[which].append(keep)
+    return keep
+
+
+def _csr_mean_drop_fwd(x, rowptr, col, out, drop: "EdgeDrop"):
+    """The forward launch of ``drop``: returns (inv_deg, (seed, offset)) for the backward launch."""
+    rows, cols = x.shape
+    seed, off = drop.rng if drop.rng is not None else edge_drop_rng(rows)
+    inv_deg = torch.empty(rows, dtype=torch.float32, device=x.device)
+    keep = _edge_keep_buffer("fwd", col)
+    _ck(_lib.load().egk_csr_mean_drop_fwd(_stream(), _p(x), _p(rowptr), _p(col), _p(out), _p(inv_deg), _p(keep), rows, cols, _dt(x),
+                                          drop.p, drop.flags, seed, off, _p(rng_device_offset(x.device))), "egk_csr_mean_drop_fwd")
+    if _mask_tap["on"]:
+        _mask_tap["launches"].append(("edge", seed, off, rows, int(col.numel())))
+    return inv_deg, (seed, off)
+
+
+def _csr_mean_drop_bwd(dout, t_rowptr, t_col, inv_deg, gate, dx, drop: "EdgeDrop", rng):
+    rows, cols = dout.shape
+    keep = _edge_keep_buffer("bwd", t_col)
+    _ck(_lib.load().egk_csr_mean_drop_bwd(_stream(), _p(dout), _p(t_rowptr), _p(t_col), _p(inv_deg), _p(gate), _p(dx), _p(keep), rows,
+                                          cols, _dt(dout), drop.p, drop.flags, rng[0], rng[1], _p(rng_device_offset(dout.device))),
+        "egk_csr_mean_drop_bwd")
+
+
+class _CSRMeanDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rowptr, col, t_rowptr, t_col, drop):
+        _need_gpu(x, rowptr, col)
+        x = _c(x)
+        out = torch.empty_like(x)
+        inv_deg, ctx.rng = _csr_mean_drop_fwd(x, rowptr, col, out, drop)
+        ctx.drop = drop
+        ctx.save_for_backward(t_rowptr, t_col, inv_deg)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        t_rowptr, t_col, inv_deg = ctx.saved_tensors
+        dout = _c(dout)
+        dx = torch.empty_like(dout)
+        _csr_mean_drop_bwd(dout, t_rowptr, t_col, inv_deg, None, dx, ctx.drop, ctx.rng)
+        return dx, None, None, None, None, None
+
+
 class _CSRMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rowptr, col, t_rowptr, t_col, t_wgt, heavy, t_heavy, heavy_mode=0, t_heavy_mode=0, band=None):
@@ -2030,8 +2140,12 @@ class _CSRMean(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None, None, None, None
 
 
-def csr_mean_aggregate(x, graph):
-    """agg[i] = mean_{j->i} x[j] (0 without in-edges); ``graph`` = egopack_amd.data.CSRGraph."""
+def csr_mean_aggregate(x, graph, drop=None):
+    """agg[i] = mean_{j->i} x[j] (0 without in-edges); ``graph`` = egopack_amd.data.CSRGraph.  ``drop`` = ``ops.EdgeDrop``: the mean
+    over a seeded subset of the edges, in training use (gradients enabled, p > 0); otherwise the call of before."""
+    drop = _active_drop(drop)
+    if drop is not None:
+        return _CSRMeanDrop.apply(x, graph.rowptr, graph.col, graph.t_rowptr, graph.t_col, drop)
     return _CSRMean.apply(x, graph.rowptr, graph.col, graph.t_rowptr, graph.t_col, graph.t_wgt,
                           getattr(graph, "heavy", None), getattr(graph, "t_heavy", None), getattr(graph, "heavy_mode", 0),
                           getattr(graph, "t_heavy_mode", 0), getattr(graph, "band", None))
@@ -2045,7 +2159,7 @@ class _SageMean(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, Wp, bp, Wl, bl, Wr, rowptr, col, t_rowptr, t_col, t_wgt, compute, heavy=None, t_heavy=None,
-                heavy_mode=0, t_heavy_mode=0, ln_out=None, ln_in=None, res_src=None, band=None):
+                heavy_mode=0, t_heavy_mode=0, ln_out=None, ln_in=None, res_src=None, band=None, drop=None):
         _need_gpu(h, Wp, Wl, Wr)
         lib = _lib.load()
         h = _c(h)
@@ -2055,8 +2169,11 @@ class _SageMean(torch.autograd.Function):
         xp = torch.empty_like(h)
         agg = torch.empty_like(h)
         p_args, p_kw = (N, H, h, H, Wp_o, H, H, xp, H), dict(bias=_f32c(bp), act=1, compute=compute)
+        if drop is not None and (_dual["tape"] is not None or _dual["replay"] is not None):
+            raise RuntimeError("sage_mean_layer: drop= inside dual_record / dual_replay -- the tape knows nothing of dropped edges")
         taped = _tape_take("sage_mean", h)
         Ho = Wl.shape[0]
+        ctx.drop, inv_deg = drop, None
         if taped is not None:
             xp, agg, out = _r16(taped, "xp"), _r16(taped, "agg"), _r16(taped, "out")
             if tuple(out.shape) != (N, Ho):
@@ -2066,7 +2183,10 @@ class _SageMean(torch.autograd.Function):
             ctx.t_heavy_mode = t_heavy_mode
         else:
             gemm(*p_args, **p_kw)
-            _csr_gather(xp, rowptr, col, None, None, agg, heavy, heavy_mode, band)
+            if drop is not None:  # (no tee is armed: that exists only inside a precise scope, which does not train)
+                inv_deg, ctx.drop_rng = _csr_mean_drop_fwd(xp, rowptr, col, agg, drop)
+            else:
+                _csr_gather(xp, rowptr, col, None, None, agg, heavy, heavy_mode, band)
             ctx.t_heavy_mode = t_heavy_mode
             out = torch.empty((N, Ho), dtype=dt, device=h.device)
             c_args = (N, Ho, agg, H, Wl_o, H, H, out, Ho)
@@ -2080,14 +2200,14 @@ class _SageMean(torch.autograd.Function):
             _tape_put("sage_mean", xp=xp, agg=agg, out=out)
         ctx.ln_in, ctx.res_src = ln_in, res_src
         ctx.compute, ctx.params = compute, (Wp, bp, Wl, bl, Wr)
-        ctx.save_for_backward(h, xp, agg, Wp_o, Wl_o, Wr_o, t_rowptr, t_col, t_wgt, t_heavy)
+        ctx.save_for_backward(h, xp, agg, Wp_o, Wl_o, Wr_o, t_rowptr, t_col, t_wgt, t_heavy, inv_deg)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         lib = _lib.load()
         stamp("bwd_sage", seq=True)
-        h, xp, agg, Wp_o, Wl_o, Wr_o, t_rowptr, t_col, t_wgt, t_heavy = ctx.saved_tensors
+        h, xp, agg, Wp_o, Wl_o, Wr_o, t_rowptr, t_col, t_wgt, t_heavy, inv_deg = ctx.saved_tensors
         Wp, bp, Wl, bl, Wr = ctx.params
         g = _operand_rows(d_out, h.dtype)
         N, H = h.shape
@@ -2129,7 +2249,10 @@ class _SageMean(torch.autograd.Function):
         d_pre = torch.empty_like(h)  # gradient at the projection's pre-activation: transposed gather gated by xp > 0
         a_args, a_kw = (N, H, g, g.stride(0), Wl_o, H, Ho, d_agg, H), dict(transB=True, compute=ctx.compute)
         gemm(*a_args, **a_kw)
-        _csr_gather(d_agg, t_rowptr, t_col, t_wgt, xp, d_pre, t_heavy, ctx.t_heavy_mode)
+        if ctx.drop is not None:  # the forward launch's subset, regenerated from its (seed, offset); graph.t_wgt is not read
+            _csr_mean_drop_bwd(d_agg, t_rowptr, t_col, inv_deg, xp, d_pre, ctx.drop, ctx.drop_rng)
+        else:
+            _csr_gather(d_agg, t_rowptr, t_col, t_wgt, xp, d_pre, t_heavy, ctx.t_heavy_mode)
         d_h = None
         if ctx.needs_input_grad[0]:
             d_h = torch.empty_like(h)
@@ -2152,21 +2275,23 @@ class _SageMean(torch.autograd.Function):
             # the FIRST layer of the stack (its backward is the stack's last): what is parked goes out now, beside the temporal
             # pooling's backward chain -- the step's tail launch then holds the temporal pooling's weight gradients only
             sched.flush_wgrad(before_tail=True)
-        return (d_h, rWp, rbp, rWl, rbl, rWr, None, None, None, None, None, None, None, None, None, None, None, None, None, None)
+        return (d_h, rWp, rbp, rWl, rbl, rWr, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
-def sage_mean_layer(h, conv, graph, compute=None, ln_out=None, ln_in=None, res_src=None):
+def sage_mean_layer(h, conv, graph, compute=None, ln_out=None, ln_in=None, res_src=None, drop=None):
     """SAGEConv(project=True, mean) of ``conv`` (models.layers.SAGEConv parameters) on CSR ``graph``.
     ``ln_out`` = dict(seg_ptr, n_seg, min_rows): a graph LayerNorm over those row segments follows -- its forward sums are
     taken in the last contraction's epilogue and left in ``ln_out['partials']`` (None if that launch could not).
     ``ln_in``: context of the graph LayerNorm that produced ``h`` (see ``graph_layernorm_lrelu``).
     ``res_src``: a dict in which a later node of the forward graph leaves, in backward, a gradient that belongs to ``h``
-    as well (``linear(..., res_sink=)``): it is added in this layer's dX epilogue."""
+    as well (``linear(..., res_sink=)``): it is added in this layer's dX epilogue.
+    ``drop`` = ``ops.EdgeDrop``: the mean runs over a seeded subset of the edges (egk_csr_mean_drop_fwd / _bwd) in
+    training use -- gradients enabled and p > 0; otherwise every launch is the one of before."""
     return _SageMean.apply(h, conv.lin.weight, conv.lin.bias, conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight,
                            graph.rowptr, graph.col, graph.t_rowptr, graph.t_col, graph.t_wgt,
                            _compute_for(h) if compute is None else compute, getattr(graph, "heavy", None),
                            getattr(graph, "t_heavy", None), getattr(graph, "heavy_mode", 0), getattr(graph, "t_heavy_mode", 0),
-                           ln_out, ln_in, res_src, getattr(graph, "band", None))
+                           ln_out, ln_in, res_src, getattr(graph, "band", None), _active_drop(drop))
 
 
 # ---- labelled rows only (the heads' row compaction) --------------------------------------------------------------------------

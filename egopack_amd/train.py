@@ -191,6 +191,53 @@ def log_mixup(logger, epoch: int, loaders) -> None:
         logger.info("epoch %d: mixup mean lambda %s", epoch, means)
 
 
+# ---- DropEdge of the backbone's SAGE means (``edge_drop:`` of the config) ------------------------------------------
+EDGE_DROP_DEFAULTS = {"p": 0.0, "symmetric": True, "keep_self": True, "per_layer": True}
+
+
+def edge_drop_config(cfg) -> dict:
+    """The ``edge_drop:`` block with its defaults filled in.  A ValueError names the key: an unknown key, p outside [0, 1) or NaN."""
+    raw = cfg.get("edge_drop") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(EDGE_DROP_DEFAULTS)
+    if unknown:
+        raise ValueError(f"edge_drop: unknown key(s) {sorted(unknown)} ({', '.join(EDGE_DROP_DEFAULTS)})")
+    ed = {**EDGE_DROP_DEFAULTS, **raw}
+    ed["p"] = float(ed["p"])
+    if not (0.0 <= ed["p"] < 1.0):
+        raise ValueError(f"edge_drop.p: {ed['p']} is outside [0, 1)")
+    for k in ("symmetric", "keep_self", "per_layer"):
+        ed[k] = bool(ed[k])
+    return ed
+
+
+def check_edge_drop(cfg, enable_graphone: bool = False, entry: str = "main_temporal.py") -> dict:
+    """The ``edge_drop:`` block checked against the rest of the configuration at build time; returns it.  With p > 0 the EgoPack step
+    is refused (enable_graphone / main_egopack.py): the dual-replay tape of its SAGE layers knows nothing of dropped edges -- MTLStep
+    only, like mixup and task weighting."""
+    ed = edge_drop_config(cfg)
+    if ed["p"] > 0 and enable_graphone:
+        raise ValueError(f"edge_drop.p = {ed['p']} with enable_graphone=True ({entry}): the EgoPack step replays its SAGE layers from a "
+                         "tape that knows nothing of dropped edges -- edge_drop is for main_temporal.py (MTLStep)")
+    return ed
+
+
+def apply_edge_drop(model, ed: dict) -> None:
+    """Set ``model.edge_drop`` / ``model.edge_drop_per_layer`` (models.graph.Graph) from a checked ``edge_drop:`` block; p == 0 leaves
+    the attribute None -- every launch is the one of before."""
+    from . import ops
+    model.edge_drop = ops.EdgeDrop(ed["p"], ed["symmetric"], ed["keep_self"]) if ed["p"] > 0 else None
+    model.edge_drop_per_layer = ed["per_layer"]
+
+
+def log_edge_drop(logger, epoch: int, model) -> None:
+    """One line with the configured p and flags; nothing with the feature off.  (No device statistic: the masks are never stored.)"""
+    ed = getattr(model, "edge_drop", None)
+    if ed:
+        logger.info("epoch %d: edge_drop p %s symmetric %s keep_self %s per_layer %s", epoch, ed.p, ed.symmetric, ed.keep_self,
+                    bool(getattr(model, "edge_drop_per_layer", True)))
+
+
 def env_ranks() -> tuple:
     """(rank, local_rank, world) of the launcher environment, without initialising anything."""
     import os

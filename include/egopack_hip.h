@@ -824,5 +824,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* sequence mixup for the verb / noun heads: the convex combination of paired rows of up to 4 segments in one out-of-place launch,
  * and the fused cross entropy against two labels per row (egk_mix_rows_multi, egk_ce_mix_fused_multi) */
 #include "egopack_mixup.h"
+/* DropEdge for the SAGE mean: the CSR neighbour mean over a seeded subset of every row's edges and its backward over the transposed
+ * CSR with the regenerated subset (egk_csr_mean_drop_fwd, egk_csr_mean_drop_bwd) */
+#include "egopack_edge_drop.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -109,6 +109,7 @@ def main(argv=None):
 
     # (before anything touches the GPU: collation workers are then a plain fork, data.BatchLoader.start_workers)
     T.check_mixup(cfg, enable_graphone=True, entry="main_egopack.py")  # (mixup.alpha > 0: a ValueError -- MTLStep only, like task weighting)
+    T.check_edge_drop(cfg, enable_graphone=True, entry="main_egopack.py")  # (edge_drop.p > 0: a ValueError -- the tape of the SAGE layers)
     dsets_train, dsets_val = T.build_datasets(cfg, "train"), T.build_datasets(cfg, cfg.validation_split)
     dl_train = T.build_loaders(cfg, dsets_train, True, rank, world)
     dl_val = T.build_loaders(cfg, dsets_val, False, rank, world)  # batch-sharded; meters are summed across ranks

@@ -68,6 +68,7 @@ def train(epoch, step: engine.MTLStep, loaders, weights, device="cuda", store=No
     T.log_grad_norms(logger, epoch, step)
     T.log_trust_ratios(logger, epoch, step)  # (LAMB: min / median / max trust ratio)
     T.log_mixup(logger, epoch, loaders)  # (the mean lambda per mixed task; nothing with the feature off)
+    T.log_edge_drop(logger, epoch, step.model)  # (the configured p and flags; nothing with the feature off)
     T.log_task_weighting(logger, epoch, step)  # (s_t and w_t exp(-s_t), or the manual scales; nothing with the feature off)
     lc = getattr(step, "loop_counts", None)
     if lc is not None:  # how many steps replayed the captured graph and how many ran eagerly (shape changes, warm-up)
@@ -139,6 +140,7 @@ def main(argv=None):
     # datasets, loaders and their collation processes come first: nothing has touched the GPU yet, so the workers are a
     # plain fork of a process without HIP state (data.BatchLoader.start_workers)
     T.check_mixup(cfg, enable_graphone=bool(cfg.get("enable_graphone", False)))  # (mixup with class_balance / ce_shape / GraphONE: refused here)
+    edge_drop = T.check_edge_drop(cfg, enable_graphone=bool(cfg.get("enable_graphone", False)))  # (edge_drop.p > 0 with GraphONE: refused here)
     dsets_train, dsets_val = T.build_datasets(cfg, "train"), T.build_datasets(cfg, cfg.validation_split)
     assert len({d.features_size for d in dsets_train.values()}) == 1, "all tasks must share the input feature size"
     dl_train = T.build_loaders(cfg, dsets_train, True, rank, world)
@@ -157,6 +159,7 @@ def main(argv=None):
     H = cfg.model.hidden_size
     model = instantiate(cfg.model, input_size=dsets_train["ar"].features_size,
                         num_segments=cfg.dataset_recognition.num_segments, _recursive_=False).to(device)
+    T.apply_edge_drop(model, edge_drop)  # (DropEdge of the SAGE means in training mode; p = 0: the attribute stays None)
     tasks = {
         "ar": RecognitionTask(H, H, heads=dsets_train["ar"].num_class_labels, dropout=cfg.task_dropout, head_dropout=cfg.task_head_dropout),
         "oscc": OSCCTask(H, cfg.oscc_feat_size, dropout=cfg.task_dropout, head_dropout=cfg.task_head_dropout, loss_func=cfg.oscc_loss),
