@@ -121,7 +121,7 @@ enum KernelId {
     KID_ACTION_TOPK,       // egk_action_topk: the best k (verb, noun) pairs of every row, their scores and the exact rank of the labelled pair (action.hip)
     KID_EDIT_DISTANCE_PAIRS, // egk_edit_distance_pairs: verb, noun and action edit distances of the sampled futures in one launch (action.hip)
     KID_MIX_ROWS,          // egk_mix_rows_multi: the convex combination of paired rows of up to 4 segments, out of place (mixup.hip)
-    KID_CE_MIX,            // egk_ce_mix_fused_multi: the fused cross entropy against two labels per row (mixup.hip)
+    KID_CE_MIX,            // egk_ce_mix_fused_multi: the fused cross entropy against two labels per row (loss.hip)
     KID_CSR_MEAN_DROP,     // egk_csr_mean_drop_fwd / _bwd: the neighbour mean over a seeded subset of the edges and its backward (graph_drop.hip)
     KID_LAMB_MOMENTS,      // egk_lamb_moments: LAMB's moments and the per-piece partial sums of p^2 and u^2 (optim_lamb.hip)
     KID_LAMB_TRUST,        // egk_lamb_trust: the trust ratio of every slot from those sums (optim_lamb.hip)

@@ -1,14 +1,12 @@
-// Sequence mixup (include/egopack_mixup.h):
+// Sequence mixup (include/egopack_mixup.h), the row mix:
 //   egk_mix_rows_multi       out[r] = lam[r] in[r] + (1 - lam[r]) in[src[r]] for the rows of up to 4 segments, out of place, one launch
-//   egk_ce_mix_fused_multi   the fused cross entropy of up to 4 tasks x 4 heads against two labels per row: loss and dlogits
+// (the header's other entry point, the two-target cross entropy egk_ce_mix_fused_multi, is a mode of the fused cross entropy: loss.hip).
 // Plain C++: one wave per row, four waves per workgroup, at most 2048 workgroups, the row walk of the other row kernels (common.h:
 // XCD x owns a contiguous eighth of the rows); no LDS, no workspace, no atomics.  The mix is HBM-bound: 16-byte accesses along the
-// row, ordinary stores (the first contraction reads the output next, from the L2 of the XCD that wrote it).  The forward pass of
-// the loss is the plain row function's (ce_row.h), operation by operation, so that a row with lam == 1 has the plain launch's bits.
-// Every launcher refuses its argument errors on the host before it launches.
+// row, ordinary stores (the first contraction reads the output next, from the L2 of the XCD that wrote it).
+// The launcher refuses its argument errors on the host before it launches.
 #include <math.h>
 
-#include "ce_row.h"
 #include "common.h"
 
 namespace egk {
@@ -110,104 +108,6 @@ __global__ __launch_bounds__(256) void mix_rows_kernel(const MixArgs A) {
     }
 }
 
-// ---- the two-target cross entropy ---------------------------------------------------------------------------------------------------
-struct CEMixTasks {
-    const float* logits[EGK_CE_MIX_MAX_TASKS][EGK_CE_MIX_MAX_HEADS];
-    long long ld[EGK_CE_MIX_MAX_TASKS][EGK_CE_MIX_MAX_HEADS];
-    long long dcol[EGK_CE_MIX_MAX_TASKS][EGK_CE_MIX_MAX_HEADS];
-    int C[EGK_CE_MIX_MAX_TASKS][EGK_CE_MIX_MAX_HEADS];
-    int pad[EGK_CE_MIX_MAX_TASKS][EGK_CE_MIX_MAX_HEADS];
-    const long long* y[EGK_CE_MIX_MAX_TASKS];
-    const long long* yb[EGK_CE_MIX_MAX_TASKS];
-    const float* lam[EGK_CE_MIX_MAX_TASKS];
-    float* loss[EGK_CE_MIX_MAX_TASKS];
-    void* dlogits[EGK_CE_MIX_MAX_TASKS];
-    const float* scale[EGK_CE_MIX_MAX_TASKS];
-    long long ys[EGK_CE_MIX_MAX_TASKS], ldd[EGK_CE_MIX_MAX_TASKS];
-    int n_heads[EGK_CE_MIX_MAX_TASKS], rows[EGK_CE_MIX_MAX_TASKS];
-    float gscale[EGK_CE_MIX_MAX_TASKS];
-};
-
-// The plain launch's loss of a live label, WRITTEN AS ce_row_plain WRITES IT (ce_row.h) and compiled like it: no pragma here.
-// The lam == 1 identity of the LOSS rests on the compiler contracting (or not) the multiply-adds of this expression here as it
-// does there -- two inlinings of the same text under the same flags.  Nothing in the language promises that: it is pinned by
-// tests/test_gpu_mixup.py::test_ce_mix_lam_one_is_the_plain_launch_bit_for_bit, which a compiler upgrade has to pass.  (The
-// gradient needs no such luck: the plain form has no multiply-add to contract.)
-__device__ __forceinline__ float ce_plain_loss(const float* __restrict__ lr, float l, long long t, float sx, float smoothing, int C) {
-    return l - (1.f - smoothing) * ld1t(lr + t) - (smoothing > 0.f ? smoothing / C * sx : 0.f);
-}
-
-// What the two labels add to the plain row: every operation rounded separately (the header's order).  With la == 1, lb == 0 every
-// extra factor is an exact 1 and every extra term an exact 0.
-template <typename T>
-__device__ __forceinline__ float ce_mix_tail(const float* __restrict__ lr, int C, int pad, long long a, long long b, bool alive,
-                                             bool blive, float lam, float ca, float cb, float l, float smoothing, float g,
-                                             T* __restrict__ dr, int lane) {
-#pragma clang fp contract(off)  // (the f32 and the bf16 instantiation form the same f32 value: no fusing that depends on the code around)
-    const float la = alive ? lam : 0.f, lb = blive ? 1.f - lam : 0.f, W = la + lb;
-    float loss = la > 0.f ? la * ca : 0.f;
-    if (lb > 0.f) loss = loss + lb * cb;
-    const float sm = smoothing > 0.f ? smoothing / C : 0.f;
-    const float hs = 1.f - smoothing, Wsm = W * sm;
-    for (int c = lane; c < pad; c += 64) {
-        float d = 0.f;
-        if (W > 0.f && c < C) {
-            const float p = expf(ld1t(lr + c) - l);
-            const float oh = (c == a ? la : 0.f) + (c == b ? lb : 0.f);
-            d = g * (W * p - hs * oh - Wsm);
-        }
-        st1t(dr + c, d);
-    }
-    return loss;
-}
-
-// One row of one head: the log-sum-exp and the sum of the logits ONCE, as ce_row_plain<FWD> forms them (the same lane striding, the
-// same wave reductions, the same operations in the same order), then both labels' losses and the gradient.
-template <typename T>
-__device__ __forceinline__ float ce_row_mix(const float* __restrict__ lr, int C, int pad, long long a, long long b, float lam,
-                                            float smoothing, float g, T* __restrict__ dr, int lane) {
-    float mx = -INFINITY;
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, ld1t(lr + c));
-    mx = wave_max(mx);
-    float se = 0.f, sx = 0.f;
-    for (int c = lane; c < C; c += 64) {
-        const float v = ld1t(lr + c);
-        se += expf(v - mx);
-        sx += v;
-    }
-    se = wave_sum(se);
-    sx = wave_sum(sx);
-    const float l = mx + logf(se);
-    const bool alive = a >= 0 && a < C, blive = b >= 0 && b < C;
-    float ca = 0.f, cb = 0.f;
-    if (alive) ca = ce_plain_loss(lr, l, a, sx, smoothing, C);
-    if (blive) cb = ce_plain_loss(lr, l, b, sx, smoothing, C);
-    return ce_mix_tail<T>(lr, C, pad, a, b, alive, blive, lam, ca, cb, l, smoothing, g, dr, lane);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void ce_mix_fused_multi_kernel(const CEMixTasks P, float smoothing) {
-    const int k = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n_heads = P.n_heads[k], rows = P.rows[k];
-    const long long* __restrict__ y = P.y[k];
-    const long long* __restrict__ yb = P.yb[k];
-    const float* __restrict__ lamp = P.lam[k];
-    const long long ys = P.ys[k], ldd = P.ldd[k];
-    float* __restrict__ loss = P.loss[k];
-    T* __restrict__ dlogits = (T*)P.dlogits[k];
-    const float g = scaled_seed(P.gscale[k], P.scale[k]);  // (common.h: one rounded product, the seed itself without a scale)
-    const RowWalk rw = row_walk(blockIdx.x, gridDim.x, 0, rows, wave, MIX_WPB);  // (XCD x owns a contiguous eighth of the rows: common.h)
-    for (int row = rw.first; row < rw.end; row += rw.step) {
-        const float lam = lamp[row];
-        float total = 0.f;
-        for (int h = 0; h < n_heads; ++h)
-            total += ce_row_mix<T>(P.logits[k][h] + (long long)row * P.ld[k][h], P.C[k][h], P.pad[k][h], y[(long long)row * ys + h],
-                                   yb[(long long)row * ys + h], lam, smoothing, g, dlogits + (long long)row * ldd + P.dcol[k][h], lane);
-        if (lane == 0) loss[row] = total;
-    }
-}
-
 // [lo, hi) in bytes of a [rows, cols] matrix with rows ``ld`` elements apart.  A matrix without rows counts as one row (an in-place
 // call is refused whatever its size); a null pointer names nothing.
 struct ByteRange {
@@ -276,53 +176,6 @@ int egk_mix_rows_multi(egk_stream_t stream, int32_t n_seg, const void* const* x_
     if (vec) EGK_DISPATCH_T(dtype, hipLaunchKernelGGL((mix_rows_kernel<T, true>), dim3(mix_row_grid((int)total)), dim3(256), 0, s, A));
     else EGK_DISPATCH_T(dtype, hipLaunchKernelGGL((mix_rows_kernel<T, false>), dim3(mix_row_grid((int)total)), dim3(256), 0, s, A));
     return check_launch("egk_mix_rows_multi");
-}
-
-int egk_ce_mix_fused_multi(egk_stream_t stream, int32_t count, const float* const* logits, const int64_t* ld, const int32_t* C,
-                           const int32_t* pad, const int64_t* dcol, const int32_t* n_heads, const int64_t* const* y,
-                           const int64_t* const* y_b, const int64_t* y_stride, const float* const* lam, float* const* loss,
-                           void* const* dlogits, const int64_t* ldd, const int32_t* rows, const float* gscale,
-                           const float* const* scales, float smoothing, int32_t dtype) {
-    EGK_REQUIRE(logits && ld && C && pad && dcol && n_heads && y && y_b && y_stride && lam && loss && dlogits && ldd && rows && gscale,
-                "egk_ce_mix_fused_multi: null pointer (a host array)");
-    EGK_REQUIRE(count >= 1 && count <= EGK_CE_MIX_MAX_TASKS, "egk_ce_mix_fused_multi: 1 .. %d tasks (got %d)", EGK_CE_MIX_MAX_TASKS, count);
-    EGK_REQUIRE(dtype == EGK_F32 || dtype == EGK_BF16, "egk_ce_mix_fused_multi: unknown activation dtype %d", dtype);
-    CEMixTasks P;
-    double bytes = 0;
-    int max_rows = 0;
-    for (int i = 0; i < EGK_CE_MIX_MAX_TASKS; ++i) {
-        const int j = i < count ? i : count - 1;  // (the slots behind count repeat the last task with no rows: no wild pointers)
-        EGK_REQUIRE(n_heads[j] >= 1 && n_heads[j] <= EGK_CE_MIX_MAX_HEADS, "egk_ce_mix_fused_multi: 1 .. %d heads (task %d)",
-                    EGK_CE_MIX_MAX_HEADS, j);
-        EGK_REQUIRE(rows[j] >= 0, "egk_ce_mix_fused_multi: rows must be >= 0 (task %d)", j);
-        EGK_REQUIRE(y[j] && y_b[j], "egk_ce_mix_fused_multi: null pointer (y or y_b of task %d)", j);
-        EGK_REQUIRE(lam[j], "egk_ce_mix_fused_multi: null pointer (lam of task %d)", j);
-        EGK_REQUIRE(loss[j] && dlogits[j], "egk_ce_mix_fused_multi: null pointer (loss or dlogits of task %d)", j);
-        EGK_REQUIRE(aligned_to(8u, {y[j], y_b[j]}), "egk_ce_mix_fused_multi: y / y_b of task %d are not 8-byte aligned", j);
-        EGK_REQUIRE(aligned_to(4u, {lam[j], loss[j]}), "egk_ce_mix_fused_multi: lam / loss of task %d are not 4-byte aligned", j);
-        EGK_REQUIRE(aligned_to(dtype == EGK_BF16 ? 2u : 4u, {dlogits[j]}), "egk_ce_mix_fused_multi: dlogits of task %d is not aligned to its element", j);
-        P.scale[i] = scales ? scales[j] : nullptr;
-        EGK_REQUIRE(aligned_to(4u, {P.scale[i]}), "egk_ce_mix_fused_multi: the scale of task %d is not 4-byte aligned", j);
-        for (int h = 0; h < EGK_CE_MIX_MAX_HEADS; ++h) {
-            const int k = EGK_CE_MIX_MAX_HEADS * j + (h < n_heads[j] ? h : n_heads[j] - 1);
-            EGK_REQUIRE(logits[k], "egk_ce_mix_fused_multi: null pointer (logits of head %d of task %d)", k % EGK_CE_MIX_MAX_HEADS, j);
-            EGK_REQUIRE(aligned_to(4u, {logits[k]}), "egk_ce_mix_fused_multi: the logits of head %d of task %d are not 4-byte aligned",
-                        k % EGK_CE_MIX_MAX_HEADS, j);
-            EGK_REQUIRE(C[k] >= 1, "egk_ce_mix_fused_multi: C must be >= 1 (head %d of task %d)", k % EGK_CE_MIX_MAX_HEADS, j);
-            EGK_REQUIRE(pad[k] >= C[k], "egk_ce_mix_fused_multi: pad must be >= C (head %d of task %d)", k % EGK_CE_MIX_MAX_HEADS, j);
-            P.logits[i][h] = logits[k]; P.ld[i][h] = ld[k]; P.dcol[i][h] = dcol[k]; P.C[i][h] = C[k]; P.pad[i][h] = pad[k];
-            if (i < count && h < n_heads[j]) bytes += 6.0 * rows[j] * C[k];
-        }
-        P.y[i] = (const long long*)y[j]; P.yb[i] = (const long long*)y_b[j]; P.lam[i] = lam[j]; P.loss[i] = loss[j];
-        P.dlogits[i] = dlogits[j]; P.ys[i] = y_stride[j]; P.ldd[i] = ldd[j]; P.n_heads[i] = n_heads[j];
-        P.rows[i] = i < count ? rows[j] : 0; P.gscale[i] = gscale[j];
-        if (i < count && rows[j] > max_rows) max_rows = rows[j];
-    }
-    if (max_rows == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(KID_CE_MIX, s, 0, bytes);
-    EGK_DISPATCH_T(dtype, hipLaunchKernelGGL((ce_mix_fused_multi_kernel<T>), dim3(mix_row_grid(max_rows), count), dim3(256), 0, s, P, smoothing));
-    return check_launch("egk_ce_mix_fused_multi");
 }
 
 }  // extern "C"

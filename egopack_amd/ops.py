@@ -2609,46 +2609,56 @@ def _ce_fused_plan(y, logits, from_col0):
     return gbuf, state, starts, [e - s0 for s0, e in zip(starts, ends)]
 
 
-def _ce_fused_launch(tasks, smoothing, bal, scales=None, shape=None):
+def _ce_fused_launch(tasks, smoothing, bal, scales=None, shape=None, mix=None):
     """ONE launch for the loss vectors AND the gradient operands of ``tasks`` = [(plan, logits, y, coef)]; ``bal``: None (the
     plain launch), or per task None / the (weights, offsets) of ``_class_balance``; ``scales``: None, or one task scale
     (``_scale_arg``) per task -- the _s launches of include/egopack_task_scale.h; ``shape``: None, or per task None / the
-    (margins, gamma) of ``_ce_shape`` -- the tail of ``egk_ce_task``, in whichever of those launches.  Returns the loss vectors."""
+    (margins, gamma) of ``_ce_shape`` -- the tail of ``egk_ce_task``, in whichever of those launches; ``mix``: None, or per task the
+    (y_b, lam) of ``_mix_arg`` -- the two-target launch (egk_ce_mix_fused_multi, include/egopack_mixup.h), which takes ``scales`` but
+    neither ``bal`` nor ``shape``.  Returns the loss vectors."""
     lib = _lib.load()
-    arr = ((_lib.CETask if bal is None else _lib.CEWTask) * len(tasks))()
+    n = len(tasks)
     losses = []
-    for i, ((gbuf, state, starts, pads), logits, y, coef) in enumerate(tasks):
-        rows = logits[0].shape[0]
-        loss = torch.empty(rows, dtype=torch.float32, device=gbuf.device)
-        if bal is None:
-            _ce_task(arr[i], logits, pads, starts, y, loss, gbuf, rows, coef)
-        else:
-            _ce_w_task(arr[i], logits, pads, starts, y, loss, gbuf, rows, coef, bal[i])
-        if shape is not None:
-            _ce_tail(arr[i] if bal is None else arr[i].base, shape[i], len(logits))
-        losses.append(loss)
+    for (gbuf, state, starts, pads), logits, y, coef in tasks:
+        losses.append(torch.empty(logits[0].shape[0], dtype=torch.float32, device=gbuf.device))
         state["filled"].update(starts)
         state["pads"] = True
     dt = _dt(tasks[0][0][0])
-    if scales is not None:
-        sc = (C.c_void_p * len(tasks))(*[t.data_ptr() for t in scales])
+    vp = lambda xs: (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+    sc = None if scales is None else vp(scales)
+    if mix is not None:  # the array form: entry [4 * task + head]
+        lg, ld, Cs = (C.c_void_p * (4 * n))(), (C.c_int64 * (4 * n))(), (C.c_int32 * (4 * n))()
+        pad, dcol = (C.c_int32 * (4 * n))(), (C.c_int64 * (4 * n))()
+        for i, ((gbuf, state, starts, pads), logits, y, coef) in enumerate(tasks):
+            for h, l in enumerate(logits):
+                k = 4 * i + h
+                lg[k], ld[k], Cs[k], pad[k], dcol[k] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
+        _ck(lib.egk_ce_mix_fused_multi(
+            _stream(), n, lg, ld, Cs, pad, dcol, (C.c_int32 * n)(*[len(t[1]) for t in tasks]), vp([t[2] for t in tasks]),
+            vp([m[0] for m in mix]), (C.c_int64 * n)(*[1 if t[2].dim() == 1 else t[2].shape[1] for t in tasks]), vp([m[1] for m in mix]),
+            vp(losses), vp([t[0][0] for t in tasks]), (C.c_int64 * n)(*[t[0][0].stride(0) for t in tasks]),
+            (C.c_int32 * n)(*[t[1][0].shape[0] for t in tasks]), (C.c_float * n)(*[float(t[3]) for t in tasks]), sc,
+            float(smoothing), dt), "egk_ce_mix_fused_multi")
+        return losses
+    arr = ((_lib.CETask if bal is None else _lib.CEWTask) * n)()
+    for i, ((gbuf, state, starts, pads), logits, y, coef) in enumerate(tasks):
         if bal is None:
-            _ck(lib.egk_ce_fused_multi_s(_stream(), arr, sc, len(tasks), float(smoothing), dt), "egk_ce_fused_multi_s")
+            _ce_task(arr[i], logits, pads, starts, y, losses[i], gbuf, logits[0].shape[0], coef)
         else:
-            _ck(lib.egk_ce_w_fused_multi_s(_stream(), arr, sc, len(tasks), float(smoothing), dt), "egk_ce_w_fused_multi_s")
-    elif bal is None:
-        _ck(lib.egk_ce_fused_multi(_stream(), arr, len(tasks), float(smoothing), dt), "egk_ce_fused_multi")
-    else:
-        _ck(lib.egk_ce_w_fused_multi(_stream(), arr, len(tasks), float(smoothing), dt), "egk_ce_w_fused_multi")
+            _ce_w_task(arr[i], logits, pads, starts, y, losses[i], gbuf, logits[0].shape[0], coef, bal[i])
+        if shape is not None:
+            _ce_tail(arr[i] if bal is None else arr[i].base, shape[i], len(logits))
+    name = ("egk_ce_fused_multi" if bal is None else "egk_ce_w_fused_multi") + ("" if sc is None else "_s")
+    _ck(getattr(lib, name)(_stream(), arr, *(() if sc is None else (sc,)), n, float(smoothing), dt), name)
     return losses
 
 
 class _CE(torch.autograd.Function):
     @staticmethod
-    def _fused(ctx, smoothing, y, logits, bal=None, shape=None):
+    def _fused(ctx, smoothing, y, logits, bal=None, shape=None, mix=None):
         """One launch for loss and gradient when the seed is known and every head's logits are blocks of ONE bank buffer
         (``_ce_fused_plan``): the fused launch with one task.  ``bal``: the per-class vectors (``_class_balance``); ``shape``: the
-        margins and the focal exponent (``_ce_shape``)."""
+        margins and the focal exponent (``_ce_shape``); ``mix``: the second labels and the coefficients (``_mix_arg``)."""
         seed = _loss_seed["coef"]
         plan = None if seed is None else _ce_fused_plan(y, logits, from_col0=False)
         if plan is None:
@@ -2656,7 +2666,8 @@ class _CE(torch.autograd.Function):
         gbuf, starts = plan[0], plan[2]
         scale = _loss_seed["scale"]
         loss, = _ce_fused_launch([(plan, logits, y, seed)], smoothing, None if bal is None else [bal],
-                                 None if scale is None else [scale], None if shape is None else [shape])
+                                 None if scale is None else [scale], None if shape is None else [shape],
+                                 None if mix is None else [mix])
         if starts[0] > 0:
             gbuf[:, :starts[0]].zero_()
         ctx.fused, ctx.shapes, ctx.seed = True, [tuple(l.shape) for l in logits], float(seed)
@@ -2783,7 +2794,8 @@ class _CEMulti(torch.autograd.Function):
     as ONE launch, ``egk_ce_fused_multi``."""
 
     @staticmethod
-    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, scales, shape, *tensors):
+    def forward(ctx, smoothing, coefs, heads_per_task, plans, bal, scales, shape, mix, *tensors):
+        # mix: None, or one (y_b, lam) of ``_mix_arg`` per task -- the two-target launch (egk_ce_mix_fused_multi)
         # shape: None, or one entry per task -- None or the (margins, gamma) of ``_ce_shape`` -- the tail of egk_ce_task
         # bal: None, or one entry per task -- None or the (weights, offsets) of ``_class_balance`` -- the launch with the vectors
         # scales: None, or one task scale per task -- the launch that multiplies each coef by its scale inside (egk_ce_*_fused_multi_s)
@@ -2794,14 +2806,14 @@ class _CEMulti(torch.autograd.Function):
             k += 1 + heads_per_task[i]
             tasks.append((plans[i], logits, y, coef))
             shapes.append([tuple(l.shape) for l in logits])
-        losses = _ce_fused_launch(tasks, smoothing, bal, scales, shape)
+        losses = _ce_fused_launch(tasks, smoothing, bal, scales, shape, mix)
         ctx.shapes, ctx.heads, ctx.fused = shapes, heads_per_task, True
         ctx.set_materialize_grads(False)
         return tuple(losses)
 
     @staticmethod
     def backward(ctx, *glosses):
-        out = [None, None, None, None, None, None, None]
+        out = [None, None, None, None, None, None, None, None]
         dev = next(g.device for g in glosses if g is not None)
         for shp in ctx.shapes:  # placeholders: the gradients are already in the banks' operand buffers
             out.append(None)  # y
@@ -2836,7 +2848,7 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
             raise ValueError(f"cross_entropy_multi: {name} has {len(arg)} entries for {len(tasks)} tasks")
     if not (2 <= len(tasks) <= 4) or not torch.is_grad_enabled():
         return None
-    plans, flat, heads, bal, shape = [], [], [], [], []
+    plans, flat, ys, heads, bal, shape = [], [], [], [], [], []
     dt = None
     for i, (logits, y) in enumerate(tasks):
         if torch.is_tensor(logits):
@@ -2852,22 +2864,20 @@ def cross_entropy_multi(tasks, coefs, smoothing: float = 0.0, weights=None, offs
         dt = plan[0].dtype
         plans.append(plan)
         heads.append(len(logits))
+        ys.append(y)
         flat += [y, *logits]
     if all(b is None for b in bal):
         bal = None
     if all(sh is None for sh in shape):
         shape = None
+    mix = None
     if mixes is not None:
         if bal is not None or shape is not None:
             return None
-        flat = []
-        for i, (logits, y) in enumerate(tasks):
-            logits = (logits,) if torch.is_tensor(logits) else tuple(logits)
-            y = y.contiguous()
-            y_b, lam = _mix_arg(mixes[i], y, f"cross_entropy_multi (task {i})") if mixes[i] is not None else (y, torch.ones(y.shape[0], dtype=torch.float32, device=y.device))  # (a fill on this stream, no cached state)
-            flat += [y, y_b, lam, *logits]
-        return list(_CEMixMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, scales, *flat))
-    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, scales, shape, *flat))
+        # an unmixed task rides with lam == 1 (a fill on this stream, no cached state)
+        mix = [(y, torch.ones(y.shape[0], dtype=torch.float32, device=y.device)) if m is None
+               else _mix_arg(m, y, f"cross_entropy_multi (task {i})") for i, (m, y) in enumerate(zip(mixes, ys))]
+    return list(_CEMulti.apply(float(smoothing), [float(c) for c in coefs], heads, plans, bal, scales, shape, mix, *flat))
 
 
 # ---- two targets per row: sequence mixup (include/egopack_mixup.h) ------------------------------------------------------------------
@@ -2887,34 +2897,10 @@ def _mix_arg(mix, y, where):
     return y_b.detach().contiguous(), lam.detach().contiguous()
 
 
-def _ce_mix_launch(tasks, smoothing, scales=None):
-    """ONE two-target launch (egk_ce_mix_fused_multi) for the loss vectors AND the gradient operands of ``tasks`` =
-    [(plan, logits, y, y_b, lam, coef)]; ``scales``: None, or one task scale (``_scale_arg``) per task.  Returns the loss vectors."""
-    n = len(tasks)
-    lg, ld, Cs = (C.c_void_p * (4 * n))(), (C.c_int64 * (4 * n))(), (C.c_int32 * (4 * n))()
-    pad, dcol = (C.c_int32 * (4 * n))(), (C.c_int64 * (4 * n))()
-    losses = []
-    for i, ((gbuf, state, starts, pads), logits, y, y_b, lam, coef) in enumerate(tasks):
-        for h, l in enumerate(logits):
-            k = 4 * i + h
-            lg[k], ld[k], Cs[k], pad[k], dcol[k] = l.data_ptr(), l.stride(0), l.shape[1], pads[h], starts[h]
-        losses.append(torch.empty(logits[0].shape[0], dtype=torch.float32, device=gbuf.device))
-        state["filled"].update(starts)
-        state["pads"] = True
-    vp = lambda xs: (C.c_void_p * n)(*[x.data_ptr() for x in xs])
-    _ck(_lib.load().egk_ce_mix_fused_multi(
-        _stream(), n, lg, ld, Cs, pad, dcol, (C.c_int32 * n)(*[len(t[1]) for t in tasks]), vp([t[2] for t in tasks]),
-        vp([t[3] for t in tasks]), (C.c_int64 * n)(*[1 if t[2].dim() == 1 else t[2].shape[1] for t in tasks]), vp([t[4] for t in tasks]),
-        vp(losses), vp([t[0][0] for t in tasks]), (C.c_int64 * n)(*[t[0][0].stride(0) for t in tasks]),
-        (C.c_int32 * n)(*[t[1][0].shape[0] for t in tasks]), (C.c_float * n)(*[float(t[5]) for t in tasks]),
-        None if scales is None else vp(scales), float(smoothing), _dt(tasks[0][0][0])), "egk_ce_mix_fused_multi")
-    return losses
-
-
 class _CEMix(torch.autograd.Function):
     """``cross_entropy(mix=)``: lam CE(z, y) + (1 - lam) CE(z, y_b) per row, summed over the heads.  Under an announced seed on bank
-    logits the launch writes the gradient operand itself (the step's path); elsewhere it runs with seed 1 into an f32 scratch and the
-    backward scales its rows by the incoming gradient."""
+    logits the launch writes the gradient operand itself (``_CE._fused``, the step's path); elsewhere it runs with seed 1 into an
+    f32 scratch and the backward scales its rows by the incoming gradient."""
 
     @staticmethod
     def forward(ctx, smoothing, y, y_b, lam, *logits):
@@ -2923,21 +2909,15 @@ class _CEMix(torch.autograd.Function):
             raise TypeError("cross_entropy expects f32 logits")
         if len(logits) > 4:
             raise ValueError(f"cross_entropy: mix takes at most 4 heads, got {len(logits)}")
-        seed = _loss_seed["coef"]
-        plan = None if seed is None else _ce_fused_plan(y, logits, from_col0=False)
-        ctx.fused = plan is not None
-        ctx.shapes = [tuple(l.shape) for l in logits]
-        if plan is not None:
-            scale = _loss_seed["scale"]
-            loss, = _ce_mix_launch([(plan, logits, y, y_b, lam, seed)], smoothing, None if scale is None else [scale])
-            if plan[2][0] > 0:
-                plan[0][:, :plan[2][0]].zero_()
-            return loss
+        ctx.fused, ctx.shapes = False, [tuple(l.shape) for l in logits]
+        fused = _CE._fused(ctx, smoothing, y, logits, mix=(y_b, lam))
+        if fused is not None:
+            return fused
         ls = [_rm(l) for l in logits]
         widths = [l.shape[1] for l in ls]
         starts = [sum(widths[:h]) for h in range(len(ls))]
         d = torch.empty((ls[0].shape[0], sum(widths)), dtype=torch.float32, device=ls[0].device)
-        loss, = _ce_mix_launch([((d, {"filled": set()}, starts, widths), ls, y, y_b, lam, 1.0)], smoothing)
+        loss, = _ce_fused_launch([((d, {"filled": set()}, starts, widths), ls, y, 1.0)], smoothing, None, mix=[(y_b, lam)])
         ctx.starts = starts
         ctx.save_for_backward(d)
         return loss
@@ -2949,33 +2929,6 @@ class _CEMix(torch.autograd.Function):
         d, = ctx.saved_tensors
         d = d * _f32c(gloss)[:, None]
         return (None, None, None, None, *[d[:, c0:c0 + shp[1]] for c0, shp in zip(ctx.starts, ctx.shapes)])
-
-
-class _CEMixMulti(torch.autograd.Function):
-    """``_CEMulti`` with two targets per row: ONE launch of egk_ce_mix_fused_multi for several tasks."""
-
-    @staticmethod
-    def forward(ctx, smoothing, coefs, heads_per_task, plans, scales, *tensors):
-        tasks, shapes, k = [], [], 0
-        for i, coef in enumerate(coefs):
-            y, y_b, lam = tensors[k:k + 3]
-            logits = tensors[k + 3:k + 3 + heads_per_task[i]]
-            k += 3 + heads_per_task[i]
-            tasks.append((plans[i], logits, y, y_b, lam, coef))
-            shapes.append([tuple(l.shape) for l in logits])
-        losses = _ce_mix_launch(tasks, smoothing, scales)
-        ctx.shapes, ctx.fused = shapes, True
-        ctx.set_materialize_grads(False)
-        return tuple(losses)
-
-    @staticmethod
-    def backward(ctx, *glosses):
-        out = [None, None, None, None, None]
-        dev = next(g.device for g in glosses if g is not None)
-        for shp in ctx.shapes:  # placeholders: the gradients are already in the banks' operand buffers
-            out.extend([None, None, None])  # y, y_b, lam
-            out.extend(torch.empty(s_, dtype=torch.float32, device=dev) for s_ in shp)
-        return tuple(out)
 
 
 def mix_rows(xs, outs, srcs, lams):

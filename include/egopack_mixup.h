@@ -19,8 +19,8 @@
  * a = y[n, h], b = y_b[n, h] (live when in [0, C), ignored otherwise), eps = smoothing, g = fl(gscale * scale[0]) (gscale without a
  * scale: egopack_task_scale.h):
  *     la = lam[n] if a is live else 0,   lb = fl(1 - lam[n]) if b is live else 0,   W = fl(la + lb)
- *     lse, sum_c z_c                             formed ONCE per row and head, operation by operation as the plain launch forms them
- *     CE(t) = lse - (1 - eps) z_t - eps / C * sum_c z_c        the plain launch's expression (csrc/ce_row.h), 0 for an ignored t
+ *     lse, sum_c z_c                             formed ONCE per row and head, by the function the plain launch forms them with
+ *     CE(t) = lse - (1 - eps) z_t - eps / C * sum_c z_c        the plain launch's own function (csrc/ce_row.h), 0 for an ignored t
  *     loss[n] = sum over the heads of  [la > 0] fl(la * CE(a))  +  [lb > 0] fl(lb * CE(b))
  *     p = expf(z_c - lse)
  *     dz_c = fl(g * fl(fl(fl(W * p) - fl((1 - eps) * fl(fl(la * [c == a]) + fl(lb * [c == b])))) - fl(W * fl(eps / C))))
@@ -29,6 +29,9 @@
  * THE lam == 1 IDENTITY: with lam[n] == 1, la = 1, lb = 0, W = 1 (a live), every extra factor is an exact multiplication by 1 and
  * every extra term an exact 0: the row's loss and gradient are BIT FOR BIT those of egk_ce_fused_multi_s on (z, y), f32 and bf16,
  * whatever y_b holds.  With lam[n] == 0 they are those of the plain launch on (z, y_b).
+ *
+ * The row mix is csrc/mixup.hip; the two-target cross entropy is a mode of the fused cross-entropy kernel and shares its packer
+ * (csrc/loss.hip, the row arithmetic in csrc/ce_row.h).
  *
  * Part of the C ABI of libegopack_hip.so: egopack_hip.h includes this file, a C user includes that one.  The boundary rules of
  * egopack_hip.h hold here word for word (stream-ordered, no allocation, no workspace, no synchronisation, capturable; 0 = ok,

@@ -95,7 +95,7 @@ def reference(x, y, w=None, a=None, m=None, eps=0.0, gamma=0.0, gloss=None):
 
 
 def restate_f32(x, y, w=None, a=None, m=None, eps=0.0, gamma=0.0, gloss=None):
-    """The arithmetic of ce_row_shaped (csrc/loss.hip) in numpy float32, operation by operation, one row at a time (the sums
+    """The arithmetic of ce_row_weighted<SHAPED> (csrc/loss.hip) in numpy float32, operation by operation, one row at a time (the sums
     in numpy's order, not the wave's).  Returns (loss [N] f32, dx [N, C] f32)."""
     f = np.float32
     x = x.detach().cpu().numpy().astype(f)

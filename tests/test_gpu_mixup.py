@@ -293,3 +293,42 @@ def test_ce_mix_two_tasks_in_one_launch_and_refusals(lib):
         refused(call(lam=t["lam"] + 2), "not 4-byte aligned")
         refused(MC.call_ce_mix(lib, [base] * 5, 0.0, MC.F32, S()), "1 .. 4 tasks")
         refused(MC.call_ce_mix(lib, [base], 0.0, 9, S()), "unknown activation dtype")
+
+
+@pytest.mark.parametrize("dt", [F32T, BF])
+def test_ce_mix_scale_beside_null_scale_in_one_launch(lib, dt):
+    """Two tasks in ONE two-target launch, the first with a scale word, the second with NULL in ``scales`` (the _s launches refuse
+    such an entry; this one takes it as "no scale"): each task has the bits of its own single-task launch."""
+    g = MC.gen(11)
+    cases = (ce_case(67, (115, 478), g, "random"), ce_case(5, (20,), g, 0.3))
+    sc = torch.tensor([0.7], device=DEV)
+    keep, tasks, outs = [sc], [], []
+    for i, (logits, y, yb, lam) in enumerate(cases):
+        rows = y.shape[0]
+        L = [l.to(DEV).contiguous() for l in logits]
+        yd, ybd, lamd = y.to(DEV), yb.to(DEV), lam.to(DEV)
+        loss = torch.empty(rows, device=DEV)
+        width = sum(l.shape[1] for l in L)
+        D = torch.empty(rows, width, dtype=dt, device=DEV)
+        dcol = [sum(l.shape[1] for l in L[:h]) for h in range(len(L))]
+        keep += [L, yd, ybd, lamd]
+        tasks.append(dict(logits=[(l.data_ptr(), l.stride(0), l.shape[1], l.shape[1], dcol[h]) for h, l in enumerate(L)], y=yd.data_ptr(),
+                          y_b=ybd.data_ptr(), y_stride=y.shape[1], lam=lamd.data_ptr(), loss=loss.data_ptr(), dlogits=D.data_ptr(), ldd=width,
+                          rows=rows, gscale=0.37, scale=sc.data_ptr() if i == 0 else None))
+        outs.append((loss, D))
+    ok(MC.call_ce_mix(lib, tasks, 0.1, edt(dt), S()))
+    torch.cuda.synchronize()
+    both = [(bits(l).clone(), bits(d).clone()) for l, d in outs]
+    for i in range(2):
+        outs[i][0].fill_(9.0)
+        outs[i][1].fill_(9.0)
+        ok(MC.call_ce_mix(lib, [tasks[i]], 0.1, edt(dt), S()))
+        torch.cuda.synchronize()
+        assert torch.equal(bits(outs[i][0]), both[i][0]) and torch.equal(bits(outs[i][1]), both[i][1]), f"task {i}"
+    # the scale reached the first task and only it: the second task's loss-independent gradient is the unscaled launch's
+    geff = float(torch.tensor(0.37) * torch.tensor(0.7))
+    for i, gs in enumerate((geff, 0.37)):
+        _, ref_grad = MC.ce_mix_model(cases[i][0], cases[i][1], cases[i][2], cases[i][3], 0.1, gs)
+        # f32: the bar of test_ce_mix_against_float64; bf16: that plus one rounding to 8 significant bits, 1e-4 + 2^-9 < 2^-8
+        tol = dict(rtol=1e-4, atol=1e-6) if dt == F32T else dict(rtol=2.0 ** -8, atol=1e-6)
+        torch.testing.assert_close(outs[i][1].cpu().double(), torch.cat(ref_grad, 1), **tol)
