@@ -33,7 +33,9 @@ LAMB_PIECE = 4096  # EGK_LAMB_PIECE (include/egopack_lamb.h)
 # table, tests/test_cabi_addons.py, which reads what it pins per key from tests/cabi_addon_<key>.py -- a new header adds a key here and
 # files there.  Scalars and pointers only (STRUCTS stays as ledgered); a name another header of any table declares is refused.
 ADDON_HEADERS = {"calibrate": HERE.parent / "include" / "egopack_calibrate.h", "action": HERE.parent / "include" / "egopack_action.h",
-                 "mixup": HERE.parent / "include" / "egopack_mixup.h", "edge_drop": HERE.parent / "include" / "egopack_edge_drop.h"}
+                 "mixup": HERE.parent / "include" / "egopack_mixup.h", "edge_drop": HERE.parent / "include" / "egopack_edge_drop.h",
+                 "bootstrap": HERE.parent / "include" / "egopack_bootstrap.h"}
+BOOT_MAX_R, BOOT_MAX_M, BOOT_MAX_C = 65536, 8, 1024  # EGK_BOOT_MAX_* (include/egopack_bootstrap.h)
 EDGE_DROP_SYMMETRIC, EDGE_DROP_KEEP_SELF = 1, 2  # EGK_EDGE_DROP_* (include/egopack_edge_drop.h)
 MIX_MAX_SEGMENTS, CE_MIX_MAX_TASKS, CE_MIX_MAX_HEADS = 4, 4, 4  # EGK_MIX_MAX_SEGMENTS, EGK_CE_MIX_MAX_* (include/egopack_mixup.h)
 TEMP_MAX_HEADS, TEMP_MAX_K = 8, 64  # EGK_TEMP_MAX_* (include/egopack_calibrate.h)

@@ -123,6 +123,7 @@ enum KernelId {
     KID_MIX_ROWS,          // egk_mix_rows_multi: the convex combination of paired rows of up to 4 segments, out of place (mixup.hip)
     KID_CE_MIX,            // egk_ce_mix_fused_multi: the fused cross entropy against two labels per row (loss.hip)
     KID_CSR_MEAN_DROP,     // egk_csr_mean_drop_fwd / _bwd: the neighbour mean over a seeded subset of the edges and its backward (graph_drop.hip)
+    KID_BOOTSTRAP,         // egk_bootstrap_accumulate / _weights: the Poisson cluster bootstrap of the validation metrics (bootstrap.hip)
     KID_LAMB_MOMENTS,      // egk_lamb_moments: LAMB's moments and the per-piece partial sums of p^2 and u^2 (optim_lamb.hip)
     KID_LAMB_TRUST,        // egk_lamb_trust: the trust ratio of every slot from those sums (optim_lamb.hip)
     KID_LAMB_APPLY,        // egk_lamb_apply: p -= (lr * trust) * u, the bf16 copies and the weight average (optim_lamb.hip)

@@ -59,7 +59,7 @@ static const char* const kNames[KID_COUNT] = {
     "dropout_fwd", "dropout_bwd", "relu_gate", "cast", "axpby", "sum_scale", "adam", "optim", "optim_groups", "optim_ema", "ema_swap",
     "ce_balanced", "bce_balanced", "task_scale", "categorical_sample", "class_report", "topk_softmax",
     "retrieval_report", "temp_stats", "temp_newton", "temp_topk_prob", "temp_scale_rows",
-    "action_topk", "edit_distance_pairs", "mix_rows", "ce_mix", "csr_mean_drop",  // (the LAMB ids stay last: tests/test_lamb_cpu.py)
+    "action_topk", "edit_distance_pairs", "mix_rows", "ce_mix", "csr_mean_drop", "bootstrap",  // (the LAMB ids stay last: tests/test_lamb_cpu.py)
     "lamb_moments", "lamb_trust", "lamb_apply"};
 
 struct Pending {

@@ -17,6 +17,8 @@ it kept in small device tensors -- nothing is copied to the host before ``comput
                                                            *_macro_precision / _recall / _f1, *_acc_many / _medium / _few
     action_scores (config block)   action_scores=  actions_top{1,2,3,5} (AR, anticipation), actions_top1 + actions_ed
                                                            (LTA), actions_seen_top1 / actions_unseen_top1 with their supports
+    bootstrap (config block)       bootstrap=       <key>_ci_lo / _ci_hi / _se beside every ratio key: top-k, mean-class
+                                                           top-1, action top-k, edit distances, OSCC accuracy, PNR localization_error
 Dropped: feature dumps, W&B tables and plots (reporting only).
 
 The per-class report (``class_report=True``; ``log_confusion_matrices`` of the config) is one ``egk_class_report`` launch per
@@ -32,12 +34,17 @@ batch (data.BatchLoader ``shard="batches"``) reports exactly the numbers of the 
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+import logging
+import math
+from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib, ops
+
+logger = logging.getLogger(__name__)
 
 KS = (1, 2, 3, 5)
 
@@ -217,6 +224,7 @@ class _HeadCounts:
             hit = ok & (rank < k)
             self.hits[i] += hit.sum()
             self.class_hits[i] += torch.bincount(lab, weights=hit.to(torch.float64), minlength=self.C).to(torch.int64)
+        return rank  # (what was counted: the bootstrap's columns are built from it)
 
     def tensors(self) -> List[torch.Tensor]:
         return [self.hits, self.valid, self.class_hits, self.support]
@@ -251,6 +259,7 @@ class _ActionCounts:
         yv, yn = verb_labels.to(torch.int64), noun_labels.to(torch.int64)
         rank = ops.action_topk(verb_logits, noun_logits, max(self.ks), labels=(yv, yn), want_prob=False, want_logp=False)["rank"]
         self.count(rank, yv, yn)
+        return rank
 
     def count(self, rank: torch.Tensor, yv: torch.Tensor, yn: torch.Tensor):
         """The integer arithmetic on a rank vector (-1: the row does not count)."""
@@ -338,12 +347,164 @@ class _Calibration:
         return ce ** 0.5 if ce > 0 else 0.0
 
 
+# ---- the cluster bootstrap of the ratio metrics (include/egopack_bootstrap.h) -----------------------------------------
+def bootstrap_ratio(acc_num: torch.Tensor, acc_den: torch.Tensor):
+    """float64 [R]: ``acc_num / acc_den`` per replicate, NaN where the denominator is 0 (the replicate is dropped)."""
+    num, den = torch.as_tensor(acc_num).cpu().to(torch.int64), torch.as_tensor(acc_den).cpu().to(torch.int64)
+    ok = den != 0
+    nan = torch.full((), float("nan"), dtype=torch.float64)
+    return torch.where(ok, num.double() / torch.where(ok, den, torch.ones_like(den)).double(), nan)
+
+
+def bootstrap_mean_class(cls_num: torch.Tensor, cls_den: torch.Tensor):
+    """float64 [R]: per replicate the mean over the classes it drew (``cls_den > 0``) of ``cls_num / cls_den`` -- what
+    ``_HeadCounts.mean_class`` divides; NaN for a replicate that drew no class (it is dropped)."""
+    num, den = torch.as_tensor(cls_num).cpu().to(torch.int64), torch.as_tensor(cls_den).cpu().to(torch.int64)
+    seen = den > 0
+    acc = torch.where(seen, num.double() / den.clamp(min=1).double(), torch.zeros((), dtype=torch.float64))
+    n = seen.sum(1)
+    nan = torch.full((), float("nan"), dtype=torch.float64)
+    return torch.where(n > 0, acc.sum(1) / n.clamp(min=1).double(), nan)
+
+
+def bootstrap_interval(values: torch.Tensor, level: float, replicates: int):
+    """{"lo", "hi", "se", "valid", "dropped"} of the valid (not NaN) replicate values, or None with fewer than ``replicates`` / 2 of
+    them: the values sorted, j = floor((1 - level) / 2 * n) (1e-9 is added before the floor, so that a product that is an integer in decimal is not
+    rounded below it), lo = v[j], hi = v[n - 1 - j]; se = the standard deviation with divisor n - 1 (0 for n = 1)."""
+    v = torch.as_tensor(values, dtype=torch.float64).reshape(-1)
+    total = int(v.numel())
+    v = torch.sort(v[~torch.isnan(v)]).values
+    n = int(v.numel())
+    if n == 0 or 2 * n < int(replicates):
+        return None
+    j = int(math.floor((1.0 - float(level)) / 2.0 * n + 1e-9))
+    se = float(np.std(v.numpy(), ddof=1)) if n > 1 else 0.0
+    return {"lo": float(v[j]), "hi": float(v[n - 1 - j]), "se": se, "valid": n, "dropped": total - n}
+
+
+class _BootGroup:
+    """The accumulators of ONE launch per batch: M columns of (numerator, denominator) sums per replicate and, optionally, the
+    per-class (hit, support) pair of one column.  ``keys``: the log key of every column -- column 0 is the row count (num = den = 1
+    on every row, key None): its ``acc_den`` is the sum of the weights, the same for every run that saw the same samples."""
+
+    def __init__(self, R: int, keys, device, class_key=None, class_col: int = -1, n_classes: int = 0):
+        self.keys, self.class_key, self.class_col = list(keys), class_key, int(class_col)
+        self.acc_num = torch.zeros((R, len(self.keys)), dtype=torch.int64, device=device)
+        self.acc_den = torch.zeros_like(self.acc_num)
+        self.cls_num = self.cls_den = None
+        if class_key is not None:
+            self.cls_num = torch.zeros((R, int(n_classes)), dtype=torch.int64, device=device)
+            self.cls_den = torch.zeros_like(self.cls_num)
+
+    def tensors(self) -> List[torch.Tensor]:
+        return [self.acc_num, self.acc_den, *([self.cls_num, self.cls_den] if self.cls_num is not None else ())]
+
+    def values(self) -> Dict[str, torch.Tensor]:
+        """log key -> the replicate values, float64 [R] (NaN: dropped)."""
+        out = {k: bootstrap_ratio(self.acc_num[:, m], self.acc_den[:, m]) for m, k in enumerate(self.keys) if k is not None}
+        if self.class_key is not None:
+            out[self.class_key] = bootstrap_mean_class(self.cls_num, self.cls_den)
+        return out
+
+
+class _Bootstrap:
+    """The seeded Poisson cluster bootstrap of a meter (``bootstrap:`` of the config with replicates > 0), in the manner of
+    ``_ClassReport``: int64 accumulators on the device that join ``_sums()`` -- integers with one writer per word, so shards merge
+    to the bits of the single pass -- added to by ONE ``ops.bootstrap_accumulate`` launch per group and batch.  The validation loop
+    stamps the batch's cluster ids (``stamp``) before ``update``: cluster = batch ordinal * loader batch size + the row's sequence in
+    the batch, ``predict.py``'s ``sample``.  ``trace`` (a list, for tests): every launch's (group, cluster, num, den, label)."""
+
+    def __init__(self, cfg: dict, device):
+        self.R, self.level, self.seed = int(cfg["replicates"]), float(cfg.get("level", 0.95)), int(cfg.get("seed", 0))
+        if not 1 <= self.R <= _lib.BOOT_MAX_R:
+            raise ValueError(f"bootstrap.replicates: an integer in 1 .. {_lib.BOOT_MAX_R} (got {self.R})")
+        self.key, self.device = ops.bootstrap_key(self.seed), device
+        self.groups: Dict[str, _BootGroup] = {}
+        self.clusters = torch.zeros((), dtype=torch.int64, device=device)  # clusters seen (a sum: it merges like the rest)
+        self.first = self.bound = self.nodes = None
+        self.trace = None
+
+    def add(self, name: str, keys, class_key=None, n_classes: int = 0) -> None:
+        """A group with the row-count column and one column per key; ``class_key``: the mean-class key of the FIRST keyed column."""
+        self.groups[name] = _BootGroup(self.R, [None, *keys], self.device, class_key, 1 if class_key is not None else -1, n_classes)
+
+    def tensors(self) -> List[torch.Tensor]:
+        return [self.clusters, *(t for g in self.groups.values() for t in g.tensors())]
+
+    def stamp(self, first: int, batch_size: int, n_clusters: int, nodes=None) -> None:
+        """The cluster ids of the next ``update``: ``first`` = ordinal * batch size, ``nodes`` = the sequence of every node."""
+        self.first, self.bound = int(first), int(first) + max(int(batch_size), int(n_clusters), 1) - 1
+        self.nodes = None if nodes is None else nodes.to(self.device, torch.int64) + self.first
+        self.clusters += int(n_clusters)
+
+    def node_clusters(self, rows: int) -> torch.Tensor:
+        if self.nodes is None or self.nodes.shape[0] != rows:
+            raise ValueError("bootstrap: the meter has no cluster id per node of this batch (the validation loops stamp them: "
+                             f"{None if self.nodes is None else self.nodes.shape[0]} ids, {rows} rows)")
+        return self.nodes
+
+    def sequence_clusters(self, rows: int) -> torch.Tensor:
+        if self.first is None:
+            raise ValueError("bootstrap: the meter has no cluster ids of this batch (the validation loops stamp them)")
+        return torch.arange(rows, dtype=torch.int64, device=self.device) + self.first
+
+    def accumulate(self, name: str, cluster: torch.Tensor, num: torch.Tensor, den: torch.Tensor, label=None) -> None:
+        g = self.groups[name]
+        if self.trace is not None:
+            self.trace.append((name, cluster.cpu(), num.cpu().to(torch.int64), den.cpu().to(torch.int64),
+                               None if label is None or g.class_key is None else label.cpu().to(torch.int64)))
+        ops.bootstrap_accumulate(cluster, num, den, g.acc_num, g.acc_den, self.key, max_cluster=self.bound,
+                                 label=label if g.class_key is not None else None, class_col=g.class_col, cls_num=g.cls_num,
+                                 cls_den=g.cls_den)
+
+    def ranks(self, name: str, rank: torch.Tensor, ks, cluster: torch.Tensor, label=None) -> None:
+        """Columns from a rank vector (-1: the row does not count): num = rank < k, den = rank >= 0."""
+        ok = rank >= 0
+        one = torch.ones_like(ok)
+        num = torch.stack([one, *(ok & (rank < k) for k in ks)], 1).to(torch.int64)
+        den = torch.stack([one, *(ok for _ in ks)], 1).to(torch.int64)
+        self.accumulate(name, cluster, num, den, label)
+
+    def sums(self, name: str, cluster: torch.Tensor, nums, dens) -> None:
+        """Columns from integer per-row terms: ``nums`` / ``dens`` are lists of int64 [rows] (or Python ints for a constant)."""
+        rows = cluster.shape[0]
+        col = lambda v: v.to(torch.int64) if torch.is_tensor(v) else torch.full((rows,), int(v), dtype=torch.int64, device=self.device)  # noqa: E731
+        self.accumulate(name, cluster, torch.stack([col(1), *(col(v) for v in nums)], 1), torch.stack([col(1), *(col(v) for v in dens)], 1))
+
+    def values(self) -> Dict[str, torch.Tensor]:
+        return {k: v for g in self.groups.values() for k, v in g.values().items()}
+
+    def intervals(self) -> Dict[str, Optional[dict]]:
+        """log key -> ``bootstrap_interval`` (None: fewer than R / 2 valid replicates, which a log line says)."""
+        out = {}
+        for k, v in self.values().items():
+            out[k] = bootstrap_interval(v, self.level, self.R)
+            if out[k] is None:
+                logger.warning("bootstrap: %s has %d valid of %d replicates (fewer than half): no interval", k,
+                               int((~torch.isnan(v)).sum()), self.R)
+        return out
+
+    def tables(self, point: dict, split=None) -> dict:
+        """What ``bootstrap.save`` writes: the accumulators per group, the replicate values and the point estimate per metric,
+        seed, R, level, the split's name and the number of clusters seen."""
+        groups = {n: {"keys": list(g.keys), "class_key": g.class_key, "acc_num": g.acc_num.cpu(), "acc_den": g.acc_den.cpu(),
+                      **({"cls_num": g.cls_num.cpu(), "cls_den": g.cls_den.cpu()} if g.cls_num is not None else {})}
+                  for n, g in self.groups.items()}
+        vals = self.values()
+        return {"seed": self.seed, "replicates": self.R, "level": self.level, "split": split, "clusters": int(self.clusters),
+                "groups": groups, "values": vals,
+                "point": {k: float(point[k]) for k in vals if k in point}}
+
+
 class BaseMeter:
     """utils/meters/base.py: running mean of the per-batch loss + sample counter."""
 
     def __init__(self, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
-                 shots=(20, 100), top_confusions: int = 20, calibration=None, action_scores=None) -> None:
+                 shots=(20, 100), top_confusions: int = 20, calibration=None, action_scores=None, bootstrap=None) -> None:
         self.device = torch.device(device)
+        # the cluster bootstrap of the ratio metrics (``bootstrap``: replicates, level, seed of the config block; None or
+        # replicates = 0: no state, no launch, no key): the meters register their groups of columns on ``boot``
+        self.boot = _Bootstrap(bootstrap, self.device) if bootstrap and int(bootstrap.get("replicates", 0)) > 0 else None
         # action-level scores (``action_scores``: topk and the seen pairs of the config block; None: no state, no launch, no key):
         # the verb / noun meters build an ``_ActionCounts`` from it
         self.action_cfg = dict(action_scores) if action_scores else None
@@ -445,6 +606,30 @@ class BaseMeter:
                 f"NLL {r['nll']:.4f} -> {r['nll_calibrated']:.4f}, calibration error (cross-fitted{', IN SAMPLE' if r['in_sample'] else ''}) "
                 f"{r['calibration_error_calibrated']:.4f}" for p, r in self.temperature_fit().items()]
 
+    # ---- the cluster bootstrap ---------------------------------------------------------------------
+    def _boot_logs(self) -> dict:
+        """<key>_ci_lo / _ci_hi / _se of every covered key that has an interval: {} with the bootstrap off."""
+        if self.boot is None:
+            return {}
+        out = {}
+        for k, ci in self.boot.intervals().items():
+            if ci is not None:
+                out.update({f"{k}_ci_lo": ci["lo"], f"{k}_ci_hi": ci["hi"], f"{k}_se": ci["se"]})
+        return out
+
+    @staticmethod
+    def _ci(logs: dict, key: str, scale: float = 1.0, digits: int = 4) -> str:
+        """" [lo, hi]" of a covered key for a line of ``print_logs`` ("" without an interval)."""
+        if f"{key}_ci_lo" not in logs:
+            return ""
+        return f" [{logs[f'{key}_ci_lo'] * scale:.{digits}f}, {logs[f'{key}_ci_hi'] * scale:.{digits}f}]"
+
+    def bootstrap_tables(self, split=None) -> dict:
+        """What ``bootstrap.save`` writes for this meter (``_Bootstrap.tables``): {} with the bootstrap off."""
+        if self.boot is None:
+            return {}
+        return self.boot.tables({k: v for k, v in self.get_logs().items() if isinstance(v, (int, float))}, split)
+
     def update(self, labels, loss, *args, **kwargs) -> None:
         loss = loss.detach().double()
         if bool(torch.isnan(loss).any()):
@@ -462,7 +647,7 @@ class BaseMeter:
 
     def _sums(self) -> List[torch.Tensor]:
         """Device tensors that add across shards (updated in place)."""
-        return [self.loss_sum, *self._report_sums()]
+        return [self.loss_sum, *self._report_sums(), *(self.boot.tensors() if self.boot is not None else ())]
 
     def merge(self, other: "BaseMeter") -> "BaseMeter":
         """Add the state of a meter that saw another shard of the split."""
@@ -518,10 +703,13 @@ class BaseMeter:
         return [*self._report_lines(), *self._temperature_lines(), f"Loss: {self.loss():.4f}"]
 
     def get_logs(self, *args, **kwargs) -> Dict[str, float]:
-        return {"loss": self.loss(), **self._report_logs(), **self._temperature_logs()}
+        return {"loss": self.loss(), **self._report_logs(), **self._temperature_logs(), **self._boot_logs()}
 
 
 class _VerbNounMeter(BaseMeter):
+    # what the bootstrap covers of a head: the key of top-k per k, the ks, the key of mean-class top-1 (None: not logged here)
+    BOOT_TOPK, BOOT_KS, BOOT_MC, BOOT_ACTION_KS = "{name}_top{k}", KS, "{name}_mc", KS
+
     def __init__(self, dataset, *args, **kwargs) -> None:
         super().__init__(*args, **kwargs)
         self.dataset = dataset
@@ -536,6 +724,12 @@ class _VerbNounMeter(BaseMeter):
         self.actions = None  # (action_scores off: no state, no launch, no key)
         if self.action_cfg is not None:
             self.actions = _ActionCounts(len(self.verb_labels), len(self.noun_labels), self.device, seen=self.action_cfg.get("seen"))
+        if self.boot is not None:  # one group (= one launch per batch) per head, one for the action ranks
+            for name, names in (("verbs", self.verb_labels), ("nouns", self.noun_labels)):
+                self.boot.add(name, [self.BOOT_TOPK.format(name=name, k=k) for k in self.BOOT_KS],
+                              self.BOOT_MC.format(name=name) if self.BOOT_MC else None, len(names))
+            if self.actions is not None:
+                self.boot.add("actions", [f"actions_top{k}" for k in self.BOOT_ACTION_KS])
 
     def _sums(self):
         return [*super()._sums(), *self.verbs.tensors(), *self.nouns.tensors(), *(self.actions.tensors() if self.actions else ())]
@@ -549,7 +743,8 @@ class _VerbNounMeter(BaseMeter):
         if self.actions is None:
             return []
         a = self.actions
-        line = "Actions " + ", ".join(f"Top-{k}: {a.accuracy(k) * 100:.2f}" for k in ks)
+        ci = self._boot_logs()
+        line = "Actions " + ", ".join(f"Top-{k}: {a.accuracy(k) * 100:.2f}{self._ci(ci, f'actions_top{k}', 100, 2)}" for k in ks)
         sp = a.split_logs()
         if sp:
             line += (f"; seen pairs Top-1: {sp['actions_seen_top1'] * 100:.2f} (n={sp['actions_seen_support']}), "
@@ -558,15 +753,21 @@ class _VerbNounMeter(BaseMeter):
 
     @torch.no_grad()
     def _count(self, logits, labels):
-        self.verbs.update(logits[self.idx_verbs].detach(), labels[:, self.idx_verbs])
-        self.nouns.update(logits[self.idx_nouns].detach(), labels[:, self.idx_nouns])
+        rank_v = self.verbs.update(logits[self.idx_verbs].detach(), labels[:, self.idx_verbs])
+        rank_n = self.nouns.update(logits[self.idx_nouns].detach(), labels[:, self.idx_nouns])
+        if self.boot is not None:  # the ranks just counted, weighted per replicate: one launch per head
+            nodes = self.boot.node_clusters(labels.shape[0])
+            self.boot.ranks("verbs", rank_v, self.BOOT_KS, nodes, labels[:, self.idx_verbs])
+            self.boot.ranks("nouns", rank_n, self.BOOT_KS, nodes, labels[:, self.idx_nouns])
         if self.class_report:  # both heads in one launch, beside the counting above
             class_report([(logits[self.idx_verbs], labels[:, self.idx_verbs], self.reports["verbs_"][0]),
                           (logits[self.idx_nouns], labels[:, self.idx_nouns], self.reports["nouns_"][0])])
         self._temperature_append([("verbs_", logits[self.idx_verbs], labels[:, self.idx_verbs]),
                                   ("nouns_", logits[self.idx_nouns], labels[:, self.idx_nouns])])
         if self.actions is not None:  # the joint of both heads: one launch, ranks only
-            self.actions.update(logits[self.idx_verbs], logits[self.idx_nouns], labels[:, self.idx_verbs], labels[:, self.idx_nouns])
+            rank_a = self.actions.update(logits[self.idx_verbs], logits[self.idx_nouns], labels[:, self.idx_verbs], labels[:, self.idx_nouns])
+            if self.boot is not None:
+                self.boot.ranks("actions", rank_a, self.BOOT_ACTION_KS, self.boot.node_clusters(labels.shape[0]))
 
 
 class RecognitionMeter(_VerbNounMeter):
@@ -588,9 +789,11 @@ class RecognitionMeter(_VerbNounMeter):
 
     def print_logs(self):
         v, n = self.verbs, self.nouns
-        return [f"Verbs Top-1: {v.accuracy(1) * 100:.2f}, Top-2: {v.accuracy(2) * 100:.2f}, Top-3: {v.accuracy(3) * 100:.2f}, Top-5: {v.accuracy(5) * 100:.2f}",
-                f"Nouns Top-1: {n.accuracy(1) * 100:.2f}, Top-2: {n.accuracy(2) * 100:.2f}, Top-3: {n.accuracy(3) * 100:.2f}, Top-5: {n.accuracy(5) * 100:.2f}",
-                f"Verbs Mean class: {v.mean_class() * 100:.2f}", f"Nouns Mean class: {n.mean_class() * 100:.2f}",
+        ci = self._boot_logs()
+        top = lambda name, h: ", ".join(f"Top-{k}: {h.accuracy(k) * 100:.2f}{self._ci(ci, f'{name}_top{k}', 100, 2)}" for k in KS)  # noqa: E731
+        return [f"Verbs {top('verbs', v)}", f"Nouns {top('nouns', n)}",
+                f"Verbs Mean class: {v.mean_class() * 100:.2f}{self._ci(ci, 'verbs_mc', 100, 2)}",
+                f"Nouns Mean class: {n.mean_class() * 100:.2f}{self._ci(ci, 'nouns_mc', 100, 2)}",
                 f"Verbs Brier score: {self.calibration['verbs'][1].compute():.4f}",
                 f"Nouns Brier score: {self.calibration['nouns'][1].compute():.4f}",
                 *self._action_lines(), *super().print_logs()]
@@ -608,6 +811,8 @@ class RecognitionMeter(_VerbNounMeter):
 
 
 class AnticipationMeter(_VerbNounMeter):
+    BOOT_TOPK, BOOT_MC = "{name}_accuracy_top{k}", "{name}_recall_top1"
+
     @torch.no_grad()
     def update(self, logits, labels, *args, **kwargs) -> None:
         super().update(labels, *args, **kwargs)
@@ -623,7 +828,7 @@ class AnticipationMeter(_VerbNounMeter):
     def print_logs(self):
         logs = self.get_logs()
         mine = [k for k in logs if k.startswith(("verbs_accuracy_top", "verbs_recall_top", "nouns_accuracy_top", "nouns_recall_top"))]
-        return [", ".join(f"{k}: {logs[k] * 100:.2f}" for k in mine), *self._action_lines(), *super().print_logs()]
+        return [", ".join(f"{k}: {logs[k] * 100:.2f}{self._ci(logs, k, 100, 2)}" for k in mine), *self._action_lines(), *super().print_logs()]
 
 
 class OSCCMeter(BaseMeter):
@@ -637,6 +842,8 @@ class OSCCMeter(BaseMeter):
                 tc = tc[0]
             self.reports[""] = (_ClassReport(2, self.device), list(getattr(dataset, "oscc_class_labels", ("no_change", "change"))), tc)
         self._add_temperature({"": 2})
+        if self.boot is not None:
+            self.boot.add("oscc", ["accuracy"])
 
     def _sums(self):
         return [*super()._sums(), *self.counts.tensors()]
@@ -644,13 +851,15 @@ class OSCCMeter(BaseMeter):
     @torch.no_grad()
     def update(self, logits, labels, *args, **kwargs) -> None:
         super().update(labels, *args, **kwargs)
-        self.counts.update(logits.detach(), labels)
+        rank = self.counts.update(logits.detach(), labels)
+        if self.boot is not None:  # (a row is a sequence)
+            self.boot.ranks("oscc", rank, (1,), self.boot.sequence_clusters(labels.shape[0]))
         if self.class_report:
             class_report([(logits, labels, self.reports[""][0])])
         self._temperature_append([("", logits, labels)])
 
     def print_logs(self):
-        return [f"Accuracy: {self.counts.accuracy(1) * 100:.2f}", *super().print_logs()]
+        return [f"Accuracy: {self.counts.accuracy(1) * 100:.2f}{self._ci(self._boot_logs(), 'accuracy', 100, 2)}", *super().print_logs()]
 
     def get_logs(self, *args, **kwargs):
         return {"accuracy": self.counts.accuracy(1), **super().get_logs()}
@@ -667,6 +876,8 @@ class PNRMeter(BaseMeter):
         self.targets: List[torch.Tensor] = []
         self.loc_err_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         self.loc_n = 0
+        if self.boot is not None:  # (accuracy / recall count nodes and the AUROC is no sum of per-sample terms: no interval)
+            self.boot.add("pnr", ["localization_error"])
 
     _INTS = (*BaseMeter._INTS, "loc_n")
     _LISTS = ("probs", "targets")
@@ -700,6 +911,8 @@ class PNRMeter(BaseMeter):
         err_sec = ((ef - sf) / 16 * loc - (pf - sf)).abs() / 30
         self.loc_err_sum += err_sec.sum()
         self.loc_n += n_seg
+        if self.boot is not None:  # seconds in 2^-24 fixed point, rounded to nearest, over 1 in the same fixed point: a row is a sequence
+            self.boot.sums("pnr", self.boot.sequence_clusters(n_seg), [torch.round(err_sec * Q24).to(torch.int64)], [1 << 24])
 
     def auroc(self) -> float:
         """Exact area under the ROC curve (Mann-Whitney U, ties count 1/2) over everything seen."""
@@ -723,7 +936,7 @@ class PNRMeter(BaseMeter):
     def print_logs(self):
         l = self.get_logs()
         return [f"accuracy: {l['accuracy']:.4f}", f"recall: {l['recall']:.4f}", f"auroc: {l['auroc']:.4f}",
-                f"localization_error: {l['localization_error']:.4f}", *super().print_logs()]
+                f"localization_error: {l['localization_error']:.4f}{self._ci(l, 'localization_error')}", *super().print_logs()]
 
 
 class LTAMeter(_VerbNounMeter):
@@ -731,6 +944,7 @@ class LTAMeter(_VerbNounMeter):
     nodes dropped), plus top-1 accuracy on the labelled nodes."""
 
     N_NODES, N_SAMPLES, SKIP = 22, 5, 2
+    BOOT_KS, BOOT_MC, BOOT_ACTION_KS = (1,), None, (1,)  # (the keys this meter logs: verbs_top1 / nouns_top1, actions_top1)
 
     def __init__(self, dataset, *args, **kwargs) -> None:
         super().__init__(dataset, *args, **kwargs)
@@ -738,6 +952,9 @@ class LTAMeter(_VerbNounMeter):
         self.ed_sum = torch.zeros(2, dtype=torch.float64, device=self.device)
         self.ed_n = 0
         self.action_ed_sum = torch.zeros((), dtype=torch.float64, device=self.device) if self.actions is not None else None
+        self._ed_min = []  # the smallest of the K integer distances per sequence of the current update, per column, with Z
+        if self.boot is not None:
+            self.boot.add("ed", ["verbs_ed", "nouns_ed", *(["actions_ed"] if self.actions is not None else [])])
 
     _INTS = (*BaseMeter._INTS, "ed_n")
 
@@ -751,18 +968,23 @@ class LTAMeter(_VerbNounMeter):
         lv, ln = (labels[:, i].reshape(-1, self.N_NODES)[:, self.SKIP:] for i in (self.idx_verbs, self.idx_nouns))
         d = action_edit_distances(pv, pn, lv, ln)
         self.last_pair_distances = d
-        best = d.min(dim=1).values.double() / pv.shape[1]
+        dmin = d.min(dim=1).values
+        self._ed_min += [(dmin[:, c], pv.shape[1]) for c in range(3)]
+        best = dmin.double() / pv.shape[1]
         return best[:, 0], best[:, 1], best[:, 2]
 
     def _edit_distance(self, preds: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         p = preds.reshape(-1, self.N_NODES, self.N_SAMPLES)[:, self.SKIP:]
         l = labels.reshape(-1, self.N_NODES)[:, self.SKIP:]
-        return edit_distances(p, l).min(dim=1).values.double() / p.shape[1]
+        dmin = edit_distances(p, l).min(dim=1).values
+        self._ed_min.append((dmin, p.shape[1]))
+        return dmin.double() / p.shape[1]
 
     @torch.no_grad()
     def update(self, logits, labels, predictions, *args, **kwargs) -> None:
         super().update(labels, *args, **kwargs)
         self._count(logits, labels)  # rows with negative labels are skipped by the rank kernel (labels >= 0 filter)
+        self._ed_min = []
         if self.actions is not None:  # all three distances from the pair launch (the verb / noun columns are egk_edit_distance's integers)
             dv, dn, da = self._pair_distances(predictions, labels)
             self.action_ed_sum += da.sum()
@@ -772,6 +994,8 @@ class LTAMeter(_VerbNounMeter):
         self.ed_sum += torch.stack([dv.sum(), dn.sum()])
         self.ed_n += dv.numel()
         self.last_distances = (dv, dn)
+        if self.boot is not None:  # the integers behind dv / dn (/ da) over Z: a row is a sequence
+            self.boot.sums("ed", self.boot.sequence_clusters(dv.numel()), [d for d, _ in self._ed_min], [z for _, z in self._ed_min])
 
     def get_logs(self, *args, **kwargs):
         v, n = (float(x) / max(self.ed_n, 1) for x in self.ed_sum)
@@ -783,25 +1007,26 @@ class LTAMeter(_VerbNounMeter):
 
     def print_logs(self):
         l = self.get_logs()
-        return [f"verbs_ed: {l['verbs_ed']:.4f}", f"nouns_ed: {l['nouns_ed']:.4f}", f"verbs_top1: {l['verbs_top1']:.4f}",
-                f"nouns_top1: {l['nouns_top1']:.4f}",
-                *([f"actions_ed: {l['actions_ed']:.4f}", *self._action_lines(ks=(1,))] if self.actions is not None else []),
+        return [*(f"{k}: {l[k]:.4f}{self._ci(l, k)}" for k in ("verbs_ed", "nouns_ed", "verbs_top1", "nouns_top1")),
+                *([f"actions_ed: {l['actions_ed']:.4f}{self._ci(l, 'actions_ed')}", *self._action_lines(ks=(1,))] if self.actions is not None else []),
                 *super().print_logs()]
 
 
 def build_meter_for_dataset(dataset, save_features: bool = False, device="cuda", class_report: bool = False, train_counts=None,
-                            shots=(20, 100), top_confusions: int = 20, calibration=None, action_scores=None) -> BaseMeter:
+                            shots=(20, 100), top_confusions: int = 20, calibration=None, action_scores=None, bootstrap=None) -> BaseMeter:
     """utils/meters/__init__.py:10-22, keyed on the dataset's ``task`` name (synthetic and Ego4D datasets alike).
     ``class_report``: the per-class report of the verb / noun and OSCC meters (PNR is binary and reports tp / tn already: it
     takes no report); ``calibration``: the temperature fit of the same meters (``train.calibration_meter_args``; PNR takes none:
     a one-logit BCE head whose export is a frame index); ``train_counts``: per head the training labels of every class (``train.label_counts``) for the
     many / medium / few-shot accuracies, ``shots`` their (lo, hi) borders, ``top_confusions`` the length of the confusion list;
     ``action_scores``: the action-level scores of the verb / noun meters (``train.action_scores_meter_args``; OSCC and PNR have no
-    pair and take none)."""
+    pair and take none); ``bootstrap``: the cluster bootstrap of every meter's ratio metrics (``train.bootstrap_meter_args``: replicates,
+    level, seed; None or replicates = 0: off)."""
     kind = getattr(dataset, "task", None) or type(dataset).__name__.lower()
-    rep = dict(class_report=class_report, train_counts=train_counts, shots=shots, top_confusions=top_confusions, calibration=calibration)
+    rep = dict(class_report=class_report, train_counts=train_counts, shots=shots, top_confusions=top_confusions, calibration=calibration,
+               bootstrap=bootstrap)
     if "pnr" in kind:
-        return PNRMeter(dataset, device=device)
+        return PNRMeter(dataset, device=device, bootstrap=bootstrap)
     if "oscc" in kind:
         return OSCCMeter(dataset, device=device, **rep)
     if "lta" in kind:

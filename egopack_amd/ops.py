@@ -3801,6 +3801,95 @@ def optim_state_key(seed=None) -> int:
     return (seed ^ OPTIM_STATE_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
 
 
+# ---- the cluster bootstrap of the validation metrics (include/egopack_bootstrap.h) -------------------------------------
+# The Philox KEY of the bootstrap weights is the user's seed XOR this constant ("BOOT_CLU" in ASCII): a fourth consumer of one seed
+# with a fourth key, so it never draws a (key, counter) pair of the dropout kernels, the LTA sampler or the state rounding.
+BOOTSTRAP_KEY_SALT = 0x424F4F545F434C55
+BOOTSTRAP_MAX_CLUSTER = (1 << 40) - 1  # the counter holds the cluster id in 40 bits above the 14 bits of replicate >> 2
+
+
+def bootstrap_key(seed: int) -> int:
+    """The Philox key of ``bootstrap_accumulate`` / ``bootstrap_weights`` for a user seed."""
+    return (int(seed) ^ BOOTSTRAP_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
+
+
+def _bootstrap_cluster(cluster, max_cluster, what: str):
+    """The int64 unit-stride cluster vector of a launch; ``max_cluster`` is the caller's HOST-side bound on its ids (from the batch
+    ordinal and the loader's batch size: nothing is read from the device)."""
+    if int(max_cluster) > BOOTSTRAP_MAX_CLUSTER:
+        raise ValueError(f"{what}: cluster ids up to {int(max_cluster)} do not fit the counter's 40 bits (at most {BOOTSTRAP_MAX_CLUSTER})")
+    _need_gpu(cluster)
+    if cluster.dim() != 1:
+        raise ValueError(f"{what}: cluster is one id per row (got {tuple(cluster.shape)})")
+    cluster = cluster.to(torch.int64)
+    return cluster if cluster.numel() <= 1 or cluster.stride(0) == 1 else cluster.contiguous()
+
+
+@torch.no_grad()
+def bootstrap_weights(cluster: torch.Tensor, R: int, key: int, *, max_cluster: int) -> torch.Tensor:
+    """uint8 [rows, R]: the Poisson(1) weight of every row's cluster in every replicate (0 for a negative id) --
+    ``egk_bootstrap_weights``.  ``key``: ``bootstrap_key(seed)``."""
+    cluster = _bootstrap_cluster(cluster, max_cluster, "bootstrap_weights")
+    if not 1 <= int(R) <= _lib.BOOT_MAX_R:
+        raise ValueError(f"bootstrap_weights: 1 .. {_lib.BOOT_MAX_R} replicates (got {R})")
+    w = torch.empty((cluster.shape[0], int(R)), dtype=torch.uint8, device=cluster.device)
+    if cluster.shape[0] == 0:  # (an empty tensor has no pointer)
+        return w
+    _ck(_lib.load().egk_bootstrap_weights(_stream(), _p(cluster), cluster.shape[0], int(R), int(key) & 0xFFFFFFFFFFFFFFFF, _p(w)),
+        "egk_bootstrap_weights")
+    return w
+
+
+@torch.no_grad()
+def bootstrap_accumulate(cluster: torch.Tensor, num: torch.Tensor, den: torch.Tensor, acc_num: torch.Tensor, acc_den: torch.Tensor,
+                         key: int, *, max_cluster: int, label=None, class_col: int = -1, cls_num=None, cls_den=None) -> None:
+    """One ``egk_bootstrap_accumulate`` launch: ``acc_num`` / ``acc_den`` (int64 [R, M], contiguous) gain, per replicate, the sums of
+    ``num`` / ``den`` ([rows, M], any integer or bool dtype; int64 with a unit column stride is read where it lies) weighted by the
+    Poisson(1) weight of every row's ``cluster`` (int64 [rows]; a negative id counts nowhere).  With ``class_col`` >= 0, ``cls_num`` /
+    ``cls_den`` (int64 [R, C], contiguous) gain the weights of the rows whose ``label`` ([rows]; a column view is read through its
+    stride) lies in [0, C) and whose num / den of that column is non-zero.  ``key``: ``bootstrap_key(seed)``."""
+    what = "bootstrap_accumulate"
+    cluster = _bootstrap_cluster(cluster, max_cluster, what)
+    rows = cluster.shape[0]
+    _need_gpu(num, den, acc_num, acc_den, label, cls_num, cls_den)
+    if num.dim() != 2 or num.shape != den.shape or num.shape[0] != rows or not 1 <= num.shape[1] <= _lib.BOOT_MAX_M:
+        raise ValueError(f"{what}: num and den are [rows = {rows}, M] with M in 1 .. {_lib.BOOT_MAX_M} (got {tuple(num.shape)}, {tuple(den.shape)})")
+    M = num.shape[1]
+    num, den = num.to(torch.int64), den.to(torch.int64)
+    if num.stride() != den.stride() or (M > 1 and num.stride(1) != 1) or (rows > 1 and num.stride(0) < M):  # (one ld for both)
+        num, den = num.contiguous(), den.contiguous()
+    ld = max(num.stride(0), M) if rows > 1 else M
+    for name, t in (("acc_num", acc_num), ("acc_den", acc_den)):
+        if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != M or t.shape != acc_num.shape or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} is a contiguous int64 [R, {M}] (got {t.dtype} {tuple(t.shape)})")
+    R = acc_num.shape[0]
+    if not 1 <= R <= _lib.BOOT_MAX_R:
+        raise ValueError(f"{what}: 1 .. {_lib.BOOT_MAX_R} replicates (got {R})")
+    C_, stride = 0, 0
+    if class_col >= 0:
+        if label is None or cls_num is None or cls_den is None or not class_col < M:
+            raise ValueError(f"{what}: class_col = {class_col} needs label, cls_num and cls_den and a column below M = {M}")
+        for name, t in (("cls_num", cls_num), ("cls_den", cls_den)):
+            if t.dtype != torch.int64 or t.dim() != 2 or t.shape[0] != R or t.shape != cls_num.shape or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} is a contiguous int64 [{R}, C] (got {t.dtype} {tuple(t.shape)})")
+        C_ = cls_num.shape[1]
+        if not 1 <= C_ <= _lib.BOOT_MAX_C:
+            raise ValueError(f"{what}: 1 .. {_lib.BOOT_MAX_C} classes (got {C_})")
+        if label.dim() != 1 or label.shape[0] != rows:
+            raise ValueError(f"{what}: label is one class per row (got {tuple(label.shape)})")
+        label = label.to(torch.int64)
+        stride = label.stride(0) if rows > 1 else 1
+    elif class_col != -1:
+        raise ValueError(f"{what}: class_col is -1 (off) or a column (got {class_col})")
+    else:
+        label = cls_num = cls_den = None
+    if rows == 0:  # (an empty batch adds nothing; an empty tensor has no pointer)
+        return
+    _ck(_lib.load().egk_bootstrap_accumulate(_stream(), _p(cluster), _p(num), _p(den), ld, rows, M, _p(label), stride, int(class_col), C_,
+                                             _p(acc_num), _p(acc_den), _p(cls_num), _p(cls_den), R, int(key) & 0xFFFFFFFFFFFFFFFF),
+        "egk_bootstrap_accumulate")
+
+
 @torch.no_grad()
 def categorical_sample_multi(logits_list, K: int, seed: int, ordinal: int, row0: int = 0, debug: bool = False):
     """K samples per row from softmax(logits[row]) for every head of ``logits_list`` ([N, C_h] f32 or bf16, one N) in ONE launch:

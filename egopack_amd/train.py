@@ -906,6 +906,58 @@ def action_scores_meter_args(cfg, task: str, seen=None) -> dict:
     return dict(action_scores=args)
 
 
+# ---- the cluster bootstrap of the validation metrics (``bootstrap:`` of the config; include/egopack_bootstrap.h) --------
+BOOTSTRAP_DEFAULTS = {"replicates": 0, "level": 0.95, "seed": 0, "save": True}
+
+
+def bootstrap_config(cfg) -> dict:
+    """The ``bootstrap:`` block with its defaults filled in and checked (a config without the block: the defaults, off); an unknown
+    key, ``replicates`` outside 0 .. 65536, a ``level`` outside (0, 1) and a seed that is no integer are ValueErrors that name it."""
+    from ._lib import BOOT_MAX_R
+    raw = cfg.get("bootstrap") if hasattr(cfg, "get") else None
+    raw = dict(raw or {})
+    unknown = set(raw) - set(BOOTSTRAP_DEFAULTS)
+    if unknown:
+        raise ValueError(f"bootstrap: unknown key(s) {sorted(unknown)} ({', '.join(BOOTSTRAP_DEFAULTS)})")
+    bc = {**BOOTSTRAP_DEFAULTS, **raw}
+    if isinstance(bc["replicates"], bool) or not isinstance(bc["replicates"], int) or not 0 <= bc["replicates"] <= BOOT_MAX_R:
+        raise ValueError(f"bootstrap.replicates: an integer in 0 .. {BOOT_MAX_R}, 0 = off (got {bc['replicates']!r})")
+    if isinstance(bc["level"], bool) or not isinstance(bc["level"], (int, float)) or not 0.0 < float(bc["level"]) < 1.0:
+        raise ValueError(f"bootstrap.level: a number inside (0, 1) (got {bc['level']!r})")
+    if isinstance(bc["seed"], bool) or not isinstance(bc["seed"], int):
+        raise ValueError(f"bootstrap.seed: an integer (got {bc['seed']!r})")
+    bc["level"], bc["save"] = float(bc["level"]), bool(bc["save"])
+    return bc
+
+
+def bootstrap_meter_args(cfg, task: str = None) -> dict:
+    """The keyword arguments of ``build_meter_for_dataset``: {} with ``bootstrap.replicates`` = 0 (every task's meter takes it)."""
+    bc = bootstrap_config(cfg)
+    if bc["replicates"] == 0:
+        return {}
+    return dict(bootstrap={"replicates": bc["replicates"], "level": bc["level"], "seed": bc["seed"]})
+
+
+def save_bootstraps(logger, cfg, directory: Path, bootstraps: dict) -> list:
+    """``bootstrap.save``: one ``bootstrap_<task>.pt`` per task under ``directory`` with the accumulators, the replicate values and
+    point estimates per metric, seed, R, level, the split's name and the clusters seen of the last validation
+    (``BaseMeter.bootstrap_tables``; ``compare_runs.py`` pairs two of them).  Returns the paths written."""
+    bc = bootstrap_config(cfg)
+    if not (bc["replicates"] > 0 and bc["save"]):
+        return []
+    paths = []
+    for t, tables in (bootstraps or {}).items():
+        if not tables:
+            continue
+        directory.mkdir(parents=True, exist_ok=True)
+        path = directory / f"bootstrap_{t}.pt"
+        torch.save(tables, path)
+        logger.info("bootstrap of %s (%d replicates, seed %d, %d clusters) -> %s", t, tables["replicates"], tables["seed"],
+                    tables["clusters"], path)
+        paths.append(path)
+    return paths
+
+
 def action_scores_betas(cfg, directory, task: str, calibration=None):
     """What the export scores the joint at: (the task's calibration file or None, [1 / T of the verbs, 1 / T of the nouns] or None)
     as ``action_scores.calibrated`` asks.  ``calibration``: the file the caller loaded (``load_calibration``: what

@@ -72,6 +72,26 @@ def _logits(model, data, primary_task, other_tasks, graphone, late_fusion, needs
     return logits, feat
 
 
+def _stamp_clusters(meter, data, dataloader) -> None:
+    """``bootstrap.replicates`` > 0: the cluster id of every row of the batch on the meter, beside ``batch_ordinal`` -- cluster =
+    batch ordinal * the loader's batch size + the row's sequence in the batch, the ``sample`` of predict.py (its helpers; a batch
+    without an ordinal raises with its message).  A sharded loader is fine: the ordinal is the batch's index in the single-process
+    order.  Without a bootstrap on the meter nothing is read."""
+    boot = getattr(meter, "boot", None)
+    if boot is None:
+        return
+    from .predict import _first_sample
+    dl = dataloader
+    while not hasattr(dl, "batch_size") and hasattr(dl, "loader"):  # (an adapter that wraps a loader: train.ResidentLoader)
+        dl = dl.loader
+    bs = getattr(dl, "batch_size", None)
+    if bs is None:
+        raise ValueError("bootstrap: the loader has no batch_size (cluster = ordinal * batch_size + the row's sequence in the batch)")
+    n = getattr(data, "num_graphs", None)
+    n = int(n) if n is not None else int(data.ptr.numel()) - 1
+    boot.stamp(_first_sample(data, int(bs)), int(bs), n, getattr(data, "batch", None))
+
+
 @torch.no_grad()
 def validate(epoch, temporal_graph_model, dataloader, meter, primary_task, other_tasks: Optional[List] = None, graphone=None,
              late_fusion: bool = True, device: str = "cuda"):
@@ -83,6 +103,7 @@ def validate(epoch, temporal_graph_model, dataloader, meter, primary_task, other
         pre = data.x.mean(1) if data.x.dim() == 3 else data.x
         loss = primary_task.compute_loss(logits, data.y).mean()
         meter.batch_ordinal = getattr(data, "ordinal", None)  # (the folds of the temperature fit follow the batch order, not the rank)
+        _stamp_clusters(meter, data, dataloader)
         meter.update(logits, data.y, loss, pre, feat)
 
 
@@ -103,6 +124,7 @@ def validate_lta(temporal_graph_model, dataloader, meter, primary_task, other_ta
             predictions, logits = primary_task.generate_from_logits(logits)
         loss = primary_task.compute_loss(logits, data.y).mean()
         meter.batch_ordinal = getattr(data, "ordinal", None)
+        _stamp_clusters(meter, data, dataloader)
         meter.update(logits, data.y, predictions, loss)
 
 
@@ -115,6 +137,7 @@ def validate_pnr(temporal_graph_model, dataloader, meter, primary_task, other_ta
         data = data.to(device)
         logits, _ = _logits(temporal_graph_model, data, primary_task, other_tasks, graphone, late_fusion, needs_batch=False)
         loss = primary_task.compute_loss(logits, data.y)  # (the reference passes y.float(); the BCE kernel converts)
+        _stamp_clusters(meter, data, dataloader)
         # (the batch object carries the int32 sequence pointer the collation built; a plain ``batch`` vector works too)
         meter.update(logits, data.y, data if getattr(data, "ptr32", None) is not None else data.batch,
                      data.start_frame, data.end_frame, data.pnr_frame, loss)

@@ -827,5 +827,8 @@ int egk_edit_distance(egk_stream_t s, const int64_t* pred, int64_t p_sn, int64_t
 /* DropEdge for the SAGE mean: the CSR neighbour mean over a seeded subset of every row's edges and its backward over the transposed
  * CSR with the regenerated subset (egk_csr_mean_drop_fwd, egk_csr_mean_drop_bwd) */
 #include "egopack_edge_drop.h"
+/* the seeded cluster bootstrap of the validation metrics: R Poisson(1) replicates of integer ratio sums and per-class counts, one
+ * writer per word (egk_bootstrap_accumulate, egk_bootstrap_weights) */
+#include "egopack_bootstrap.h"
 
 #endif /* EGOPACK_HIP_H */

@@ -35,12 +35,15 @@ AUX_ORDER = {"ar": ("lta", "oscc", "pnr"), "oscc": ("ar", "lta", "pnr"), "lta": 
 
 
 def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders, late_fusion=True, validate_all=False,
-                     device="cuda", sampler=None, report=None, reports=None, calibrations=None):
+                     device="cuda", sampler=None, report=None, reports=None, calibrations=None,
+                     bootstraps=None, split=None):
     """Task metrics with the GraphONE interaction for the novel task(s) (reference main_egopack.py:374-448).  ``sampler``: the
     seeded sampler of the LTA futures (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``:
     task -> the meter's per-class report arguments (``T.class_report_meter_args``, log_confusion_matrices) and its temperature-fit
     arguments (``T.calibration_meter_args``, calibration.mode) and its action-score arguments (``T.action_scores_meter_args``); ``reports``: a dict that receives every task's tables;
-    ``calibrations``: a dict that receives every task's fitted temperatures (``BaseMeter.temperature_fit``)."""
+    ``calibrations``: a dict that receives every task's fitted temperatures (``BaseMeter.temperature_fit``); ``bootstraps``: a dict
+    that receives every task's bootstrap tables (``BaseMeter.bootstrap_tables``, bootstrap.replicates > 0; ``split``: the split's
+    name, stored there)."""
     out = {}
     for t in ("ar", "oscc", "lta", "pnr"):
         if not (validate_all or weights.get(t, 0) > 0):
@@ -63,6 +66,8 @@ def validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, loaders,
             reports[t] = meter.report_tables()
         if calibrations is not None and meter.temp_store is not None:
             calibrations[t] = meter.temperature_fit()
+        if bootstraps is not None and meter.boot is not None:
+            bootstraps[t] = meter.bootstrap_tables(split)
     return out
 
 
@@ -110,6 +115,7 @@ def main(argv=None):
     # (before anything touches the GPU: collation workers are then a plain fork, data.BatchLoader.start_workers)
     T.check_mixup(cfg, enable_graphone=True, entry="main_egopack.py")  # (mixup.alpha > 0: a ValueError -- MTLStep only, like task weighting)
     T.check_edge_drop(cfg, enable_graphone=True, entry="main_egopack.py")  # (edge_drop.p > 0: a ValueError -- the tape of the SAGE layers)
+    T.bootstrap_config(cfg)  # (an unknown key of the bootstrap block is refused here, by name)
     dsets_train, dsets_val = T.build_datasets(cfg, "train"), T.build_datasets(cfg, cfg.validation_split)
     dl_train = T.build_loaders(cfg, dsets_train, True, rank, world)
     dl_val = T.build_loaders(cfg, dsets_val, False, rank, world)  # batch-sharded; meters are summed across ranks
@@ -187,7 +193,8 @@ def main(argv=None):
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=validated)
     seen_pairs = T.action_scores_seen(cfg, dsets_train, tasks=validated)  # (action_scores.seen_split: the training split's pairs, once)
     report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t),
-                                  **T.action_scores_meter_args(cfg, t, seen_pairs)}), {}
+                                  **T.action_scores_meter_args(cfg, t, seen_pairs), **T.bootstrap_meter_args(cfg, t)}), {}
+    bootstraps = {}  # (bootstrap.replicates > 0: task -> the accumulators and replicate values of the last validation)
     calibrations = {}  # (calibration.mode=temperature: task -> the temperatures fitted in the last validation)
     for epoch in range(1, cfg.num_epochs + 1):
         T.apply_reweight(logger, cfg, balance, tasks, epoch)  # (in place: a captured step keeps its pointers)
@@ -197,12 +204,15 @@ def main(argv=None):
         with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
             validate_metrics(epoch, model, tasks, graphone, weights, dsets_val, dl_val, late_fusion=cfg.late_fusion,
                              validate_all=cfg.validate_all_tasks, device=device, sampler=sampler, report=report,
-                             reports=reports, calibrations=calibrations)  # all ranks: the split is sharded by batch
+                             reports=reports, calibrations=calibrations, bootstraps=bootstraps,
+                             split=str(cfg.validation_split))  # all ranks: the split is sharded by batch
     if rank == 0:  # (class_report.save: the tables of the last validation, beside the checkpoint)
         T.save_class_reports(logger, cfg, Path(cfg.checkpoint_dir) / (f"{cfg.artifact_prefix}_egopack_" + "-".join(
             sorted(t for t, w in weights.items() if w > 0))), reports)
         T.save_calibration(logger, cfg, Path(cfg.checkpoint_dir) / (f"{cfg.artifact_prefix}_egopack_" + "-".join(
             sorted(t for t, w in weights.items() if w > 0))), calibrations)
+        T.save_bootstraps(logger, cfg, Path(cfg.checkpoint_dir) / (f"{cfg.artifact_prefix}_egopack_" + "-".join(
+            sorted(t for t, w in weights.items() if w > 0))), bootstraps)
     if cfg.save_model and step.sync is not None:
         step.sync.gather_moments(optimizer)  # (sharded update: a collective, every rank; a no-op otherwise)
     if cfg.save_model and rank == 0:

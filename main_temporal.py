@@ -100,12 +100,13 @@ def validate_losses(step: engine.MTLStep, loaders, device="cuda"):
 
 
 def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="cuda", sampler=None, report=None, reports=None,
-                     calibrations=None):
+                     calibrations=None, bootstraps=None, split=None):
     """Task metrics of every enabled task (reference main_temporal.py:340-400).  ``sampler``: the seeded sampler of the LTA futures
     (``T.build_lta_sampler``, lta_sampling.mode=philox); None: torch's generator.  ``report``: task -> the meter's per-class report
     arguments (``T.class_report_meter_args``, log_confusion_matrices) and its temperature-fit arguments
     (``T.calibration_meter_args``, calibration.mode) and its action-score arguments (``T.action_scores_meter_args``); ``reports``: a dict that receives every task's tables; ``calibrations``: a dict
-    that receives every task's fitted temperatures (``BaseMeter.temperature_fit``)."""
+    that receives every task's fitted temperatures (``BaseMeter.temperature_fit``); ``bootstraps``: a dict that receives every
+    task's bootstrap tables (``BaseMeter.bootstrap_tables``, bootstrap.replicates > 0; ``split``: the split's name, stored there)."""
     out = {}
     for t in enabled:
         meter = build_meter_for_dataset(dsets_val[t], device=device, **(report(t) if report else {}))
@@ -123,6 +124,8 @@ def validate_metrics(epoch, model, tasks, enabled, dsets_val, loaders, device="c
             reports[t] = meter.report_tables()
         if calibrations is not None and meter.temp_store is not None:
             calibrations[t] = meter.temperature_fit()
+        if bootstraps is not None and meter.boot is not None:
+            bootstraps[t] = meter.bootstrap_tables(split)
     return out
 
 
@@ -140,6 +143,7 @@ def main(argv=None):
     # datasets, loaders and their collation processes come first: nothing has touched the GPU yet, so the workers are a
     # plain fork of a process without HIP state (data.BatchLoader.start_workers)
     T.check_mixup(cfg, enable_graphone=bool(cfg.get("enable_graphone", False)))  # (mixup with class_balance / ce_shape / GraphONE: refused here)
+    T.bootstrap_config(cfg)  # (an unknown key of the bootstrap block is refused here, by name)
     edge_drop = T.check_edge_drop(cfg, enable_graphone=bool(cfg.get("enable_graphone", False)))  # (edge_drop.p > 0 with GraphONE: refused here)
     dsets_train, dsets_val = T.build_datasets(cfg, "train"), T.build_datasets(cfg, cfg.validation_split)
     assert len({d.features_size for d in dsets_train.values()}) == 1, "all tasks must share the input feature size"
@@ -219,7 +223,8 @@ def main(argv=None):
     train_counts = T.class_report_train_counts(cfg, dsets_train, tasks=step.enabled)
     seen_pairs = T.action_scores_seen(cfg, dsets_train, tasks=step.enabled)  # (action_scores.seen_split: the training split's pairs, once)
     report, reports = (lambda t: {**T.class_report_meter_args(cfg, train_counts, t), **T.calibration_meter_args(cfg, t),
-                                  **T.action_scores_meter_args(cfg, t, seen_pairs)}), {}
+                                  **T.action_scores_meter_args(cfg, t, seen_pairs), **T.bootstrap_meter_args(cfg, t)}), {}
+    bootstraps = {}  # (bootstrap.replicates > 0: task -> the accumulators and replicate values of the last validation)
     calibrations = {}  # (calibration.mode=temperature: task -> the temperatures fitted in the last validation)
     metrics = None
     for epoch in range(first_epoch, cfg.num_epochs + 1):
@@ -240,15 +245,17 @@ def main(argv=None):
             with T.ema_scope(cfg, optimizer):  # (ema.decay > 0 and ema.validate: the averaged weights are scored)
                 logger.info("validation losses: %s", validate_losses(step, dl_val, device))
                 metrics = validate_metrics(epoch, model, tasks, step.enabled, dsets_val, dl_val, device, sampler=sampler,
-                                           report=report, reports=reports, calibrations=calibrations)
+                                           report=report, reports=reports, calibrations=calibrations, bootstraps=bootstraps,
+                                           split=str(cfg.validation_split))
     if cfg.num_epochs < first_epoch and cfg.get("validate_untrained", False):  # (num_epochs=0: metrics of the initial state)
         T.log_validation_weights(logger, cfg, optimizer, 0)
         with T.ema_scope(cfg, optimizer):
             metrics = validate_metrics(0, model, tasks, step.enabled, dsets_val, dl_val, device, sampler=sampler, report=report,
-                                       reports=reports, calibrations=calibrations)
+                                       reports=reports, calibrations=calibrations, bootstraps=bootstraps, split=str(cfg.validation_split))
     if rank == 0:
         T.save_class_reports(logger, cfg, ckpt_path.parent, reports)  # (class_report.save: the tables of the last validation)
         T.save_calibration(logger, cfg, ckpt_path.parent, calibrations)  # (calibration.save: the temperatures of the last validation)
+        T.save_bootstraps(logger, cfg, ckpt_path.parent, bootstraps)  # (bootstrap.save: the replicates of the last validation)
     if cfg.save_model and sync is not None:
         sync.gather_moments(optimizer)
     if cfg.save_model and rank == 0:
